@@ -3,6 +3,12 @@
 GFLv2 head decode -> batched NMS) at 640x640, fp16 storage, synthetic images already resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model yolo11n-test.yaml] [--batch 32] [--imgsz 640] [--nc 80]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up (incl. the start-up stage-count trial), W warm-up steps, K timed steps,
+the outputs of the last timed step when --dump-outputs is given, and the JSON line.  `--full` adds the measurements that take
+runs of their own: `roofline`, `predict_batches` / `predict_batches_u8` and `cpu_baseline` (each can still be dropped with
+--no-roofline / --no-api / --no-cpu-baseline).
 
 N>1: one process per GPU, images sharded across ranks (weak scaling: 32 images per GPU), one RCCL all_gather of the padded
 (B,300,6) result rows + counts per `--gather-every` steps.  Rank 0 prints ONE JSON line.  Two launch forms:
@@ -51,6 +57,10 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--imgsz", type=int, default=640)
     ap.add_argument("--dtype", default="f16", choices=["f16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-kernel roofline, the predict_batches API rates and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (boxes, count) as DIR/<name>.npy, float32 / float64 (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-api", action="store_true", help="skip the YOLO.predict_batches (host tensors in, Results out) measurement")
@@ -71,7 +81,10 @@ def parse(argv=None):
                          "(the JSON line says so; never a measurement)")
     ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE",
                     help="developer option: set a dispatch tunable (ey_tune_set, csrc/tune.h) before anything is launched; recorded in the JSON line")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.roofline_csv and not (a.full and not a.no_roofline):
+        ap.error("--roofline-csv needs the roofline: add --full (and drop --no-roofline)")
+    return a
 
 
 def sparse_biases(sd, head_index, nc, strides, cls_shift=0.0):
@@ -323,6 +336,16 @@ def make_pipeline(model, images, cuts, head_nms, conf, iou, max_det, streams=Non
     return pipe
 
 
+def dump_outputs(path, **arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, floats as float32 and integers as float64 (exact), so that two builds can be
+    compared output for output on the same seeded inputs.  (B,300,6) boxes + (B,) counts: ~0.23 MB at the default batch of 32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(path, f"{name}.npy"), (t.float() if t.is_floating_point() else t.double()).numpy())
+
+
 @contextlib.contextmanager
 def stdout_to_stderr():
     """File descriptor 1 -> 2 for the duration: the collective backend prints its banner ("RCCL version : ...") to stdout when the first
@@ -439,6 +462,8 @@ def run(a):
         step, drain, post_ctx = pipe_fns(pipe)
 
     dt, (boxes, count) = timed_steps(step, drain, gather, a.steps, a.warmup, post_ctx, torch.cuda.synchronize, barrier, reduce_max)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, boxes=boxes, count=count)
 
     out = None
     if rank == 0:
@@ -460,7 +485,7 @@ def run(a):
                        "regime": a.regime, "global_batch": a.batch * world, "imgsz": a.imgsz, "nc": a.nc, "pipeline": pipe_desc, **({"tunables": a.tune} if a.tune else {}),
                        "sharding": f"images x{world}" + (f", RCCL all_gather of boxes every {gather.every} steps" if world > 1 else "")},
         }
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         from edge_yolo_amd import profiling
         torch.cuda.synchronize()
         model.model[-1].head_streams = False
@@ -470,13 +495,13 @@ def run(a):
     if gather is not None and rank == 0:
         rows = gather.results()
         assert len(rows) % (a.batch * world) == 0 and len(rows) > 0 and all(r.shape[1] == 6 for r in rows)
-    if rank == 0 and world == 1 and not a.no_api and not a.force_gather:
+    if rank == 0 and world == 1 and a.full and not a.no_api and not a.force_gather:
         if not a.no_pipeline:
             del pipe, step, drain
         torch.cuda.empty_cache()
         out["predict_batches"] = api_throughput(a.model, sd, a.nc, a.batch, a.imgsz, a.dtype == "f16", min(a.steps, 40), 8, conf, iou, max_det, dev)
         out["predict_batches_u8"] = api_throughput(a.model, sd, a.nc, a.batch, a.imgsz, a.dtype == "f16", min(a.steps, 40), 8, conf, iou, max_det, dev, u8=True)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.model, sd, a.imgsz, a.cpu_images, conf, iou, nc=a.nc)
     if use_gather:
         dist.destroy_process_group()

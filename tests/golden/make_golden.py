@@ -62,6 +62,17 @@ def structure():
     json.dump(out, open(os.path.join(HERE, "structure.json"), "w"), indent=0)
 
 
+def ref_checkpoint():
+    """What a reference training checkpoint of DetectionModel('yolo11n-test.yaml', nc=10) holds besides the pickled classes
+    (engine/trainer.py:513-546): the module's parsed `yaml` dict and its state_dict keys, shapes and dtypes.  The weight-bridge test
+    (tests/test_host_cpu.py::test_reference_checkpoint_bridge) rebuilds a checkpoint of that layout from it."""
+    m = DetectionModel("yolo11n-test.yaml", ch=3, nc=10, verbose=False)
+    sd = m.state_dict()
+    out = dict(yaml=dict(m.yaml), state_shapes={k: list(v.shape) for k, v in sd.items()},
+               state_dtypes={k: str(v.dtype).replace("torch.", "") for k, v in sd.items()})
+    json.dump(out, open(os.path.join(HERE, "ref_checkpoint_n_nc10.json"), "w"), indent=0)
+
+
 HOOKS = {  # inner modules whose outputs pin the per-op restatements
     "yolo11n-test.yaml": ["model.2.cv1", "model.2.wave.f_ll", "model.2.wave", "model.2.m.0.cv1", "model.2.m.0", "model.6.m.0",
                           "model.10.m.0.attn", "model.10.m.0", "model.23.cv2.0", "model.23.cv3.0.0.0", "model.23.cv3.0", "model.23.reg_conf.0"],
@@ -349,6 +360,9 @@ if __name__ == "__main__":
     if "--validator-only" in sys.argv:
         validator_case()
         sys.exit(0)
+    if "--ref-checkpoint-only" in sys.argv:
+        ref_checkpoint()
+        sys.exit(0)
     if "--large-only" in sys.argv:
         model_small("yolo11l-test.yaml", "edgeline_l_64", b=1, layers=False, gain=LARGE_GAIN)
         model_small("yolo11x.yaml", "yolo11x_64", b=1, layers=False, gain=LARGE_GAIN)
@@ -357,6 +371,7 @@ if __name__ == "__main__":
     if "--metrics-only" in sys.argv:
         sys.exit(0)
     structure()
+    ref_checkpoint()
     ops_small()
     nms_cases()
     metrics_cases()

@@ -185,3 +185,13 @@ def test_bench_rejects_mismatched_world_size():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-cpu"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_bench_roofline_csv_needs_full():
+    """The roofline (and so its CSV) is a --full measurement: asking for the CSV without it is an error, not a silently missing file."""
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse(["--roofline-csv", "t.csv"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--full", "--no-roofline", "--roofline-csv", "t.csv"])
+    assert bench.parse(["--full", "--roofline-csv", "t.csv"]).full and not bench.parse([]).full

@@ -205,28 +205,41 @@ def test_tunables_are_api_not_environment():
                 assert "getenv" not in src and "os.environ" not in src, f"{f} reads the environment"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ultralytics"), reason="needs the reference package (build container only)")
-def test_reference_checkpoint_bridge(tmp_path):
+class _RefCheckpointModel(torch.nn.Module):
+    """Stand-in for the pickled reference DetectionModel inside a training checkpoint: the reference's `yaml` dict and its state_dict
+    (the dotted keys through nested modules).  The export tool uses nothing else of the module (.float(), .eval(), .state_dict(), .yaml)."""
+
+    def __init__(self, yaml, sd):
+        super().__init__()
+        self.yaml = yaml
+        for k, v in sd.items():
+            *path, leaf = k.split(".")
+            mod = self
+            for p in path:
+                if p not in mod._modules:
+                    mod.add_module(p, torch.nn.Module())
+                mod = mod._modules[p]
+            mod.register_buffer(leaf, v)
+
+
+def test_reference_checkpoint_bridge(tmp_path, golden_dir):
     """§8f-3: a checkpoint as the REFERENCE trainer writes it (pickled module, engine/trainer.py:513-546) -> tools/export_reference_weights.py
-    (runs where the reference is importable) -> tensor-only file -> YOLO(path): same YAML, nc, every tensor equal."""
-    import subprocess
+    -> tensor-only file -> YOLO(path): same YAML, nc, every tensor equal.  The pickled module holds what the reference's
+    DetectionModel('yolo11n-test.yaml', nc=10) holds, as the reference recorded it (tests/golden/ref_checkpoint_n_nc10.json: parsed `yaml`
+    dict, state_dict keys, shapes, dtypes)."""
     import sys
+    g = json.load(open(os.path.join(golden_dir, "ref_checkpoint_n_nc10.json")))
+    sd = synth.synth_state_dict({k: tuple(s) for k, s in g["state_shapes"].items()})
+    m = _RefCheckpointModel(g["yaml"], {k: v.to(getattr(torch, g["state_dtypes"][k])) for k, v in sd.items()})
     ref_pt, out_pt = str(tmp_path / "ref_best.pt"), str(tmp_path / "bridge.pt")
-    code = f"""
-import sys
-sys.path.insert(0, {os.path.join(ROOT, 'tests', 'golden')!r}); sys.path.insert(0, {ROOT!r})
-import _ref_import; _ref_import.setup()
-import torch, synthdata as synth
-from ultralytics.nn.tasks import DetectionModel
-m = DetectionModel('yolo11n-test.yaml', ch=3, nc=10, verbose=False)
-m.load_state_dict(synth.synth_state_dict({{k: tuple(v.shape) for k, v in m.state_dict().items()}}))
-torch.save({{'epoch': 3, 'model': None, 'ema': m.half(), 'train_args': {{}}}}, {ref_pt!r})   # the trainer's checkpoint layout
-sys.path.insert(0, {os.path.join(ROOT, 'tools')!r})
-import export_reference_weights as ex
-print(ex.export({ref_pt!r}, {out_pt!r}))
-"""
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    torch.save({"epoch": 3, "model": None, "ema": m.half(), "train_args": {}}, ref_pt)  # the trainer's checkpoint layout
+    tools = os.path.join(ROOT, "tools")
+    sys.path.insert(0, tools)
+    try:
+        import export_reference_weights as ex
+    finally:
+        sys.path.remove(tools)
+    assert ex.export(ref_pt, out_pt) == (len(sd), False)
     ck = torch.load(out_pt, weights_only=True)  # tensor-only: the safe loader reads it
     assert ck["nc"] == 10 and ck["fused"] is False and isinstance(ck["yaml"], dict)
     y = edge_yolo_amd.YOLO(out_pt)
