@@ -1770,7 +1770,7 @@ __global__ __launch_bounds__(256) void conv_pwr_kernel(ConvP p) {
           for (int j = 0; j < 8; ++j) o.set(j, v[8 * q + j]);
           o.store(yp + 8 * q);
         }
-      } else {  // 4-element accesses (the host only dispatches here when the views allow them and Cout % (4*NT...) holds)
+      } else {  // 4-element accesses (the host only dispatches here when the views allow them and Cout == 16 * NT)
 #pragma unroll
         for (int q = 0; q < NT; ++q) {
           if (rp) {
@@ -1942,6 +1942,12 @@ extern "C" int ey_conv_pack_weight(int dtype, int Cout, int Cin, int k, const fl
 
 #endif
 
+// kind*1000 + NT*10 + x of the kernel the last ey_conv2d launched (profiling labels, tests; see ey_conv_last_variant); defined in the f16 translation unit
+#if EY_CONV_PART == 16
+thread_local int g_last_variant = 0;
+#else
+extern thread_local int g_last_variant;
+#endif
 template <typename T, int NT, int MT>
 static bool conv_lds_ok() {  // one-time opt-in to > 64 KiB of dynamic LDS for the big-tile / f32 variants
   static const bool ok = [] {
@@ -1962,10 +1968,12 @@ static bool launch_conv(const ConvP& p, int ngroup, hipStream_t st) {
     if (!conv_lds_ok<T, NT, 2>()) return false;
     dim3 grid((unsigned)((M + 127) / 128), ntiles, ngroup);
     hipLaunchKernelGGL((conv_igemm_kernel<T, NT, 2>), grid, dim3(256), lds, st, p);
+    g_last_variant = 13000 + NT * 10 + 2;
   } else {
     if (!conv_lds_ok<T, NT, 1>()) return false;
     dim3 grid((unsigned)((M + 63) / 64), ntiles, ngroup);
     hipLaunchKernelGGL((conv_igemm_kernel<T, NT, 1>), grid, dim3(256), lds, st, p);
+    g_last_variant = 13000 + NT * 10 + 1;
   }
   return true;
 }
@@ -1973,12 +1981,6 @@ static bool launch_conv(const ConvP& p, int ngroup, hipStream_t st) {
 // ---- tunables (defaults measured on MI355X; EY_* environment variables override them for sweeps)
 #include <stdlib.h>
 #include "tune.h"
-// kind*1000 + NT*10 + x of the kernel the last ey_conv2d launched (profiling labels); defined in the f16 translation unit
-#if EY_CONV_PART == 16
-thread_local int g_last_variant = 0;
-#else
-extern thread_local int g_last_variant;
-#endif
 // ---- weight-stationary dispatch
 static int ws_ls(int Kpad) { return Kpad; }  // conv_kpad() already makes the row pitch conflict-free for the LDS fragment reads
 static const int WS_NT[5] = {8, 5, 4, 2, 1};
@@ -2028,6 +2030,7 @@ static bool ws_launch(ConvP p, int ngroup, hipStream_t st) {
   }
   dim3 grid((unsigned)gx, ntiles_n, ngroup);
   hipLaunchKernelGGL((conv_ws_kernel<T, NT, MT, KS>), grid, dim3(512), lds, st, p);
+  g_last_variant = 12000 + NT * 100 + MT * 10 + KS;
   return true;
 }
 
@@ -2079,6 +2082,7 @@ static int halo_launch(ConvP p, int ngroup, hipStream_t st) {
   hipLaunchKernelGGL((conv3_halo_kernel<T, NT, S>), dim3((unsigned)gx, ntn, ngroup), dim3(512), lds, st, p);
   hipError_t e_ = hipGetLastError();
   if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(halo): %s", hipGetErrorString(e_));
+  g_last_variant = 11000 + NT * 10 + S;
   return 1;
 }
 
@@ -2370,6 +2374,7 @@ static int small_launch(ConvP p, int ngroup, hipStream_t st) {
   hipLaunchKernelGGL((conv_small_kernel<T, NT, BATCH>), dim3((unsigned)((waves + 3) / 4), 1, ngroup), dim3(256), 0, st, p);
   hipError_t e_ = hipGetLastError();
   if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(small): %s", hipGetErrorString(e_));
+  g_last_variant = 10000 + NT * 10 + BATCH;
   return 1;
 }
 
@@ -2494,6 +2499,7 @@ static int dispatch_pwr(ConvP p, int ngroup, hipStream_t st) {
   if (p.k != 1 || p.stride != 1 || ngroup != 1 || M < tune().pwr_m || !p.vec_store || M >= (1L << 27)) return 0;
   const int ntp = conv_nt(p.Cout);
   if (conv_cout_pad(p.Cout) != 16 * ntp) return 0;  // one channel tile covers Cout (Cout <= 128)
+  if (p.Cout != 16 * ntp) return 0;  // ... exactly: the epilogue stores whole 4*NT-channel groups with no channel-tail predicate
   const int ks = (p.srcC[0] + 31) / 32 + (p.nsrc == 2 ? (p.srcC[1] + 31) / 32 : 0);
   if (ks * ntp > tune().pwr_frags || ks > 4) return 0;
   for (int s2 = 0; s2 < p.nsrc; ++s2) {
@@ -2848,7 +2854,9 @@ extern "C" int ey_conv_variant(int dtype, int Cout, int Cin, int k, int stride, 
   return nt * 10 + ((M + 127) / 128 * ntiles * (ngroup > 0 ? ngroup : 1) >= 512 ? 2 : 1);
 }
 extern "C" int ey_conv_pack_nt(int Cout) { return conv_nt(Cout); }
-// kind*1000 + NT*10 + x of the kernel the last ey_conv2d on this thread launched; 0 when ey_conv_variant() describes it
-// (kind 4 = conv_pw_kernel<T,NT,..>, x = number of sources).
+// kind*1000 + NT*10 + x of the kernel the last ey_conv2d on this thread launched (profiling labels and tests): kind 3 = conv_pwn<KS,NTW>
+// (KS*10 + NTW), 4 = conv_pw<T,NT,..> (x = number of sources), 5 = conv_pwr<T,NT,KS>, 6 = conv3_tile<T,NT,S>, 7 = conv3r<NT,S>,
+// 8 = conv3s<NT,MT,..> (NT*100 + MT*10 + 5 if the 9-deep ring + S), 9 = conv3p<NT,FAST>, 10 = conv_small<T,NT,BATCH>, 11 = conv3_halo<T,NT,S>,
+// 12 = conv_ws<T,NT,MT,KS> (NT*100 + MT*10 + KS), 13 = conv_igemm<T,NT,MT>.
 extern "C" int ey_conv_last_variant(void) { return g_last_variant; }
 #endif  // EY_CONV_PART

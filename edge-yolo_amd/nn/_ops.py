@@ -173,18 +173,22 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
     if TRACE is not None:
         M = B * Ho * Wo
         es = x0.element_size()
-        var = L.lib().ey_conv_variant(d.dtype, cout, cin, k, s, int(len(srcs) == 1 and not up[0]), M, ngroup)
         tn = "f16" if es == 2 else "f32"
-        name = (f"conv_small_kernel<{tn},{var % 1000 // 10},{var % 10}>" if var >= 3000 else
-                f"conv3_halo_kernel<{tn},{var % 1000 // 10},{s}>" if var >= 2000 else
-                f"conv_ws_kernel<{tn},{var % 1000 // 10},{var % 10},{k}>" if var >= 1000 else f"conv_igemm_kernel<{tn},{var // 10},{var % 10}>")
         nbytes = ngroup * (_nb(*srcs) + M * cout * es * (2 if res is not None else 1) + _nb(addz)) + cout * cin * k * k * es
-        rec = _tr(name, nbytes, 2.0 * ngroup * M * cout * cin * k * k,
+        rec = _tr("conv", nbytes, 2.0 * ngroup * M * cout * cin * k * k,
                   note=f"{cin}->{cout} k{k}s{s} {H}x{W} g{ngroup}{' +res' if res is not None else ''}{' +addz' if addz is not None else ''}{' 2src' if len(srcs) > 1 else ''}")
         with rec:
             L.check(L.lib().ey_conv2d(ctypes.byref(d), L.stream()), "ey_conv2d")
             lv = L.lib().ey_conv_last_variant()
-            if lv >= 9000:
+            if lv >= 13000:
+                rec.kernel = f"conv_igemm_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
+            elif lv >= 12000:
+                rec.kernel = f"conv_ws_kernel<{tn},{lv % 1000 // 100},{lv % 100 // 10},{lv % 10}>"
+            elif lv >= 11000:
+                rec.kernel = f"conv3_halo_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
+            elif lv >= 10000:
+                rec.kernel = f"conv_small_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
+            elif lv >= 9000:
                 rec.kernel = f"conv3p_kernel<{lv % 1000 // 10}>"
             elif lv >= 8000:
                 rec.kernel = f"conv3s_kernel<{lv % 1000 // 100},{lv % 100 // 10},{lv % 10}>"
@@ -198,6 +202,8 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
                 rec.kernel = f"conv_pw_kernel<{tn},{lv % 1000 // 10}>"
             elif lv >= 3000:
                 rec.kernel = f"conv_pwn_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
+            else:  # every launch path of ey_conv2d reports its instantiation (ey_conv_last_variant)
+                raise AssertionError(f"ey_conv2d launched without reporting its kernel (variant {lv})")
         return out
     L.check(L.lib().ey_conv2d(ctypes.byref(d), L.stream()), "ey_conv2d")
     return out

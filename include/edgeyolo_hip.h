@@ -94,14 +94,15 @@ int ey_conv2d(const ey_conv_desc* d, ey_stream_t stream);
 /* Kernel instantiation ey_conv2d launches for a shape (profiling only): kind*1000 + NT*10 + MT, kind 3 =
  * conv_small_kernel<T,NT,BATCH> (small-M latency kernel), 2 = conv3_halo_kernel<T,NT,stride> (3x3, LDS halo tile),
  * 1 = conv_ws_kernel<T,NT,MT,k> (weight-stationary persistent), 0 = conv_igemm_kernel<T,NT,MT> (K-chunked fallback).
- * plain_single_source = one source, no upsample.  Shapes taken by the pointwise / tile / register-stationary kernels are
- * reported by ey_conv_last_variant() after the launch. */
+ * plain_single_source = one source, no upsample.  A prediction for tools: it ignores the tunables and the kernels tried
+ * before these; ey_conv_last_variant() reports what a launch actually ran. */
 int ey_conv_variant(int dtype, int Cout, int Cin, int k, int stride, int plain_single_source, long M, int ngroup);
-/* Code of the kernel the last ey_conv2d on this thread launched when ey_conv_variant() does not describe it (else 0):
- * 4000 + NT*10 + nsrc = conv_pw_kernel<T,NT,...> (lean pointwise kernel for small maps); 5000 + NT*10 + KS =
- * conv_pwr_kernel<T,NT,KS,...> (register-stationary pointwise kernel for large maps); 6000 + NT*10 + stride =
- * conv3_tile_kernel<T,NT,S,...> (3x3 LDS tile kernel); 7000 + NT*10 + stride = conv3r_kernel<NT,S> (register-stationary
- * 3x3 kernel for Cin = 16).  Profiling labels only. */
+/* Code of the kernel the last ey_conv2d on this thread launched (every launch path reports it; 0 before any launch):
+ * 3000 + KS*10 + NTW = conv_pwn_kernel<KS,NTW>; 4000 + NT*10 + nsrc = conv_pw_kernel<T,NT,...>; 5000 + NT*10 + KS =
+ * conv_pwr_kernel<T,NT,KS,...>; 6000 + NT*10 + stride = conv3_tile_kernel<T,NT,S,...>; 7000 + NT*10 + stride = conv3r_kernel<NT,S>;
+ * 8000 + NT*100 + MT*10 + stride = conv3s_kernel<NT,MT,...>; 9000 + NT*10 + fast = conv3p_kernel<NT,FAST>;
+ * 10000 + NT*10 + BATCH = conv_small_kernel<T,NT,BATCH>; 11000 + NT*10 + stride = conv3_halo_kernel<T,NT,S>;
+ * 12000 + NT*100 + MT*10 + k = conv_ws_kernel<T,NT,MT,k>; 13000 + NT*10 + MT = conv_igemm_kernel<T,NT,MT>.  Profiling labels / tests. */
 int ey_conv_last_variant(void);
 /* ---- two chained pointwise convs in one kernel, registers only: y = act2(W2 . act1(W1 . x + b1) + b2) -- the last two 1x1 convs
  * of the Detect class tower (Conv(c3,c3,1)+SiLU, nn.Conv2d(c3,nc,1); head.py:68-70).  w1_packed = ey_conv_pack_weight(Cmid, Cin, 1);

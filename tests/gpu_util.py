@@ -1,5 +1,7 @@
 """Helpers shared by the -m gpu parity tests: same name-keyed synthetic weights go into the HIP modules (through
 their reference-compatible state_dict keys) and into the CPU oracle."""
+import contextlib
+
 import torch
 
 import synthdata as synth
@@ -27,3 +29,25 @@ def check(got, want, dtype, scale=1.0, what=""):
     got = got.detach().float().cpu()
     t = TOL[dtype]
     torch.testing.assert_close(got, want, rtol=t["rtol"], atol=t["atol"] * scale, msg=lambda m: f"{what}: {m}")
+
+
+@contextlib.contextmanager
+def tuned(**kv):
+    from edge_yolo_amd import _lib as L
+    old = {k: L.lib().ey_tune_get(k.encode()) for k in kv}
+    try:
+        for k, v in kv.items():
+            L.check(L.lib().ey_tune_set(k.encode(), int(v)), "tune")
+        yield
+    finally:
+        for k, v in old.items():
+            L.check(L.lib().ey_tune_set(k.encode(), int(v)), "tune")
+
+
+def _traced(fn):
+    """(result, kernel labels of the launches fn() made)."""
+    from edge_yolo_amd import profiling
+    with profiling.trace() as t:
+        y = fn()
+    torch.cuda.synchronize()
+    return y, [r[0] for r in t.records]

@@ -34,7 +34,9 @@ def _worker(rank, world, port, n_images, max_det, q):
             boxes += step
             out = g(boxes, count)
         rows = g.results()
-        q.put((rank, [r.clone() for r in rows]))
+        # numpy arrays are pickled by value: a torch tensor would travel as a shared-memory fd that the parent can only
+        # receive while this process is still alive (it may already have exited: ConnectionResetError in recvfds)
+        q.put((rank, [r.numpy().copy() for r in rows]))
     finally:
         dist.destroy_process_group()
 
@@ -53,7 +55,7 @@ def test_gather_boxes_gloo_world2():
         assert p.exitcode == 0
     full_b, full_c = _fake_results(0, n_images, max_det)
     for rank in range(world):
-        rows = got[rank]
+        rows = [torch.from_numpy(r) for r in got[rank]]
         assert len(rows) == n_images  # every rank ends up with every image's rows, in image order
         for i, r in enumerate(rows):
             n = int(full_c[i])

@@ -1,7 +1,5 @@
 """-m gpu: the DSBottleneck pair kernel (ey_dsb_pair; reference block.py:1467-1503) at the benchmarked shapes and at ragged ones:
 bit-identical to its two-launch form (2 x ey_dsconv, register-strip kernels) and within the f16 tolerance of the CPU oracle."""
-import contextlib
-
 import pytest
 import torch
 
@@ -9,29 +7,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import model as om
 import synthdata as synth  # noqa: E402
-from gpu_util import check, load_synth, to_dev  # noqa: E402
-
-
-@contextlib.contextmanager
-def tuned(**kv):
-    from edge_yolo_amd import _lib as L
-    old = {k: L.lib().ey_tune_get(k.encode()) for k in kv}
-    try:
-        for k, v in kv.items():
-            L.check(L.lib().ey_tune_set(k.encode(), int(v)), "tune")
-        yield
-    finally:
-        for k, v in old.items():
-            L.check(L.lib().ey_tune_set(k.encode(), int(v)), "tune")
-
-
-def _traced(fn):
-    """(result, kernel labels of the launches fn() made)."""
-    from edge_yolo_amd import profiling
-    with profiling.trace() as t:
-        y = fn()
-    torch.cuda.synchronize()
-    return y, [r[0] for r in t.records]
+from gpu_util import _traced, check, load_synth, to_dev, tuned  # noqa: E402
+import fp64_ref as R  # noqa: E402
 
 
 def _module(c, k2, add=True, seed=0):
@@ -57,6 +34,18 @@ def test_pair_is_bit_identical_to_two_launches_and_matches_oracle(c, k2, b, h, w
     assert ker2 == ["dsconv_strip_kernel<3>", f"dsconv_strip_kernel<{k2}>"], ker2
     assert torch.equal(got, two), f"max |diff| {float((got.float() - two.float()).abs().max())}"
     check(got, om.dsbottleneck(sd, "dsb0", x.half().float(), 3, k2), torch.float16, what=f"DSBottleneck C{c} k3->k{k2} {h}x{w}")
+    R.check_chain(f"dsb_pair C{c} k3->k{k2} {b}x{h}x{w}", ker[0], got, [xd], _dsb_stages(m, xd, k2))
+
+
+def _dsb_stages(m, x, k2, add=True):
+    """the four convs of the pair as the kernel (and its two-launch form) rounds them: depthwise -> f16 -> pointwise + SiLU -> f16 ->
+    depthwise -> f16 -> pointwise + SiLU [+ x]"""
+    st = []
+    for i, (cv, k) in enumerate(((m.cv1, 3), (m.cv2, k2))):
+        (wd, bd), (wp, bp) = cv._dw_folded(), cv._pw_folded()
+        st.append(R.stage(wd.half(), bd, k, 1, k // 2, dw=True))
+        st.append(R.stage(wp.half(), bp, act=R.ACT_SILU, res=x if (i == 1 and add) else None))
+    return st
 
 
 @pytest.mark.parametrize("rb", [1, 2, 3, 7, 64])

@@ -7,7 +7,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import model as om
 import synthdata as synth  # noqa: E402
-from gpu_util import check, load_synth, to_dev  # noqa: E402
+from gpu_util import _traced, check, load_synth, to_dev  # noqa: E402
+import fp64_ref as R  # noqa: E402
 
 DT = [torch.float32, torch.float16]
 
@@ -288,8 +289,12 @@ def test_stem_mfma_agrees_with_f32_kernel(M, h, w, c2):
         m.conv.weight.copy_(m.conv.weight.half().float())
     x = torch.rand(2, 3, h, w).half()
     want = to_dev(m, torch.float32)(x.float().cuda()).float().cpu()
-    got = to_dev(m, torch.float16)(x.cuda()).float().cpu()
+    got, ker = _traced(lambda: to_dev(m, torch.float16)(x.cuda()))
+    got = got.float().cpu()
     torch.testing.assert_close(got, want, rtol=2e-3, atol=2e-3 * float(want.abs().max()))
+    assert ker == ["stem_kernel"], ker
+    wh, bh = m.folded()
+    R.check_chain(f"stem {h}x{w} ->{c2}", ker[0], got, [x.cuda()], [R.stage(wh.half(), bh, 3, 2, 1, R.ACT_SILU)])
 
 
 @pytest.mark.parametrize("n_hw", [(20, 20), (13, 9), (16, 16), (7, 5), (20, 19)])
@@ -332,9 +337,11 @@ def test_pointwise_chain_kernel_agrees_with_two_f32_convs(M, cin, cout, h, w):
     want = _Plain(c2f).run(mid.half().float(), L.empty_nhwc(2, cout, h, w, torch.float32, "cuda")).float().cpu()  # mid rounded to f16 like the fused kernel
     c1h, c2h = to_dev(c1, torch.float16), c2.cuda().half()
     out = L.empty_nhwc(2, cout, h, w, torch.float16, "cuda")
-    got = _ops.conv_pw_chain(_Plain(c2h), x.cuda(), c1h.folded, L.ACT_SILU, lambda: fold_bn(c2h.weight, c2h.bias, None), L.ACT_NONE, out)
-    assert got is not None
+    got, ker = _traced(lambda: _ops.conv_pw_chain(_Plain(c2h), x.cuda(), c1h.folded, L.ACT_SILU, lambda: fold_bn(c2h.weight, c2h.bias, None), L.ACT_NONE, out))
+    assert got is not None and ker == ["conv_pw2_kernel"], ker
     torch.testing.assert_close(got.float().cpu(), want, rtol=3e-3, atol=3e-3 * float(want.abs().max()))
+    (w1, b1), (w2, b2) = c1h.folded(), fold_bn(c2h.weight, c2h.bias, None)
+    R.check_chain(f"pw2 {cin}->80->{cout} {h}x{w}", ker[0], got, [x.cuda()], [R.stage(w1.half(), b1, act=L.ACT_SILU), R.stage(w2.half(), b2)])
 
 
 @pytest.mark.parametrize("c1,c2,s,hw,B", [(64, 64, 2, 160, 4), (128, 128, 2, 80, 4), (128, 256, 2, 40, 8), (64, 64, 2, 80, 5), (128, 128, 2, 40, 7),

@@ -9,7 +9,8 @@ pytestmark = pytest.mark.gpu
 from oracle import model as om
 import synthdata as synth  # noqa: E402
 from gpu_util import check, load_synth, to_dev  # noqa: E402
-from test_gpu_dsb import _traced, tuned  # noqa: E402
+from gpu_util import _traced, tuned  # noqa: E402
+import fp64_ref as R  # noqa: E402
 
 
 def _mods(cin):
@@ -41,6 +42,10 @@ def test_pw3_bitwise_and_oracle(b, h, w, c0, c1, form):
     if b * h * w <= 100_000:
         xr = x.half().float()
         check(got, om.conv(sd, "p3", om.conv(sd, "p1", xr, 1, 1), 3, 2), torch.float16, what=f"pw3 {h}x{w}")
+    # fp64 at every shape: the 64-channel map between the two convs is kept as f16 in LDS
+    (w1, b1), (w3, b3) = cv2.folded(), c3.folded()
+    R.check_chain(f"pw3 form {form} {b}x{h}x{w} {c0}+{c1}", ker[0], got, srcs,
+                  [R.stage(w1.half(), b1, 1, 1, 0, R.ACT_SILU), R.stage(w3.half(), b3, 3, 2, 1, R.ACT_SILU)])
 
 
 def test_model_takes_the_fused_layers_2_3():

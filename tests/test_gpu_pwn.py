@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 from oracle import model as om
 import synthdata as synth  # noqa: E402
 from gpu_util import check, load_synth, to_dev  # noqa: E402
-from test_gpu_dsb import _traced, tuned  # noqa: E402
+from gpu_util import _traced, tuned  # noqa: E402
 
 
 # (batch, H, W, source channels, Cout, act): layers 4/6/8 cv1, the neck's 2-source cv2s, SPPF cv2, C2PSA qkv (no activation), ragged maps

@@ -8,7 +8,8 @@ pytestmark = pytest.mark.gpu
 from oracle import model as om
 import synthdata as synth  # noqa: E402
 from gpu_util import check, load_synth, to_dev  # noqa: E402
-from test_gpu_dsb import _traced, tuned  # noqa: E402
+from gpu_util import _traced, tuned  # noqa: E402
+import fp64_ref as R  # noqa: E402
 
 
 def _pair():
@@ -36,6 +37,10 @@ def test_stem_pair_bitwise_and_oracle(b, h, w, tile):
     if b * h * w <= 1_000_000:
         xr = x.half().float()
         check(got, om.conv(sd, "s1", om.conv(sd, "s0", xr, 3, 2), 3, 2), torch.float16, what=f"stem pair {h}x{w}")
+    # fp64 at every shape: the stem's output is kept as f16 in LDS, as the two-launch form stores it
+    (w0, b0), (w1, b1) = m0.folded(), m1.folded()
+    R.check_chain(f"stem_pair {b}x{h}x{w} tile {tile}", ker[0], got, [xd],
+                  [R.stage(w0.half(), b0, 3, 2, 1, R.ACT_SILU), R.stage(w1.half(), b1, 3, 2, 1, R.ACT_SILU)])
 
 
 def test_model_takes_the_fused_stem_and_matches_two_launch_form():
