@@ -86,7 +86,9 @@ SIGNATURES = {
     "ey_stem_pair": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_dsb_pair": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_dwt_haar": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_dwt": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_wavelet_z": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, C.c_long, _vp, _vp, _vp, _i, _vp]),
+    "ey_wavelet_z2": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, C.c_long, _vp, _vp, _vp, _i, _vp]),
     "ey_sppf_pool": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_copy_nhwc": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ey_nchw_to_nhwc": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

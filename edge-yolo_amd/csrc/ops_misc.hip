@@ -451,6 +451,95 @@ extern "C" int ey_dwt_haar(int dtype, int B, int H, int W, int C, const void* x,
   return EY_OK;
 }
 
+// ============================================================================ general DWT (one level, any even-length filter bank)
+// _PywtDWT2D.forward (block.py:3619-3642) for a k-tap bank: F.pad(reflect, pad = k/2 - 1) then a depthwise k x k conv, stride 2, no
+// padding.  The padded map is never built: row / column indices reflect into the map (pad < H, W is checked on the host, so one
+// reflection always lands inside it).  taps: [4][k][k] floats (LL, LH, HL, HH), already the values the reference convolves with.
+// fp32 accumulation in (row, column) tap order; one output pixel x V channels per thread.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void dwt_general_kernel(int B, int H, int W, int C, int k, const float* __restrict__ taps, const T* __restrict__ x,
+                                                          int xCs, T* __restrict__ y, int yCs) {
+  const int Ho = H >> 1, Wo = W >> 1, cv = C / V, pad = k / 2 - 1, kk = k * k;
+  const long total = (long)B * Ho * Wo * cv;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c0 = (int)(idx % cv) * V;
+  long m = idx / cv;
+  const int ox = (int)(m % Wo);
+  const long t = m / Wo;
+  const int oy = (int)(t % Ho);
+  const int b = (int)(t / Ho);
+  float acc[4][V];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[q][j] = 0.f;
+  for (int i = 0; i < k; ++i) {
+    int iy = 2 * oy + i - pad;
+    iy = iy < 0 ? -iy : iy >= H ? 2 * H - 2 - iy : iy;
+    const T* row = x + ((long)b * H + iy) * W * xCs + c0;
+    for (int jx = 0; jx < k; ++jx) {
+      int ix = 2 * ox + jx - pad;
+      ix = ix < 0 ? -ix : ix >= W ? 2 * W - 2 - ix : ix;
+      const float t0 = taps[i * k + jx], t1 = taps[kk + i * k + jx], t2 = taps[2 * kk + i * k + jx], t3 = taps[3 * kk + i * k + jx];
+      float v[V];
+      if constexpr (V == 8) {
+        Vec8<T> a;
+        a.load(row + (long)ix * xCs);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = a.get(j);
+      } else {
+        v[0] = to_f(row[(long)ix * xCs]);
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        acc[0][j] = __builtin_fmaf(t0, v[j], acc[0][j]);
+        acc[1][j] = __builtin_fmaf(t1, v[j], acc[1][j]);
+        acc[2][j] = __builtin_fmaf(t2, v[j], acc[2][j]);
+        acc[3][j] = __builtin_fmaf(t3, v[j], acc[3][j]);
+      }
+    }
+  }
+  T* yp = y + m * yCs + c0;
+  if constexpr (V == 8) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      Vec8<T> o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o.set(j, acc[q][j]);
+      o.store(yp + q * C);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) yp[q * C] = from_f<T>(acc[q][0]);
+  }
+}
+
+extern "C" int ey_dwt(int dtype, int B, int H, int W, int C, int k, const float* taps, const void* x, int x_cstride, void* y, int y_cstride,
+                      ey_stream_t stream) {
+  EY_CHECK(x && y && taps, "dwt: null pointer");
+  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "dwt: bad dtype");
+  EY_CHECK(k >= 2 && k <= 64 && k % 2 == 0, "dwt: filter length %d (even, 2..64)", k);
+  EY_CHECK(B > 0 && H >= 2 && W >= 2 && C > 0, "dwt: bad extent");
+  EY_CHECK(k / 2 - 1 < H && k / 2 - 1 < W, "dwt: reflect padding %d needs a map larger than %dx%d", k / 2 - 1, H, W);
+  EY_CHECK(x_cstride >= C && y_cstride >= 4 * C, "dwt: cstride");
+  const int es = dtype == EY_F16 ? 2 : 4;
+  const bool vec = C % 8 == 0 && (x_cstride * es) % 16 == 0 && (y_cstride * es) % 16 == 0 && ey_aligned(x, 16) && ey_aligned(y, 16);
+  const long total = (long)B * (H / 2) * (W / 2) * (vec ? C / 8 : C);
+  EY_CHECK((total + 255) / 256 < (1L << 31), "dwt: too many pixels");
+  dim3 grid((unsigned)((total + 255) / 256));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == EY_F16) {
+    if (vec) hipLaunchKernelGGL((dwt_general_kernel<f16, 8>), grid, dim3(256), 0, st, B, H, W, C, k, taps, (const f16*)x, x_cstride, (f16*)y, y_cstride);
+    else hipLaunchKernelGGL((dwt_general_kernel<f16, 1>), grid, dim3(256), 0, st, B, H, W, C, k, taps, (const f16*)x, x_cstride, (f16*)y, y_cstride);
+  } else {
+    if (vec) hipLaunchKernelGGL((dwt_general_kernel<float, 8>), grid, dim3(256), 0, st, B, H, W, C, k, taps, (const float*)x, x_cstride, (float*)y, y_cstride);
+    else hipLaunchKernelGGL((dwt_general_kernel<float, 1>), grid, dim3(256), 0, st, B, H, W, C, k, taps, (const float*)x, x_cstride, (float*)y, y_cstride);
+  }
+  EY_LAUNCH_CHECK("ey_dwt");
+  return EY_OK;
+}
+
 // ============================================================================ SPPF: three chained 5x5 max pools
 // block = one image x CV consecutive 8-channel vectors; the whole (H x W x 8*CV ch) plane lives in LDS; separable max (row pass,
 // column pass) applied three times, exactly the reference's chain (padding acts as -inf).  CV = 8 for f16 at 20x20 (64 channels =

@@ -22,6 +22,12 @@ struct WzP {
   int tiles_x, tiles_y;
   int xcd;  // XCD-contiguous tile order (ey_xcd_block)
 };
+struct WzPX : WzP {   // the arguments of every instantiation but the Haar / dense-f_h one (whose kernel arguments stay exactly WzP)
+  const float* taps;  // KF > 2: [4][KF][KF] DWT taps (LL, LH, HL, HH), the values ey_dwt convolves with
+  const f16* w_dw;    // DS: f_h's depthwise 3x3 weights [3][3][C]
+};
+template <int KF, bool DS> struct WzArgs { using T = WzPX; };
+template <> struct WzArgs<2, false> { using T = WzP; };
 
 __host__ __device__ constexpr int wz_nt(int cout) { return cout <= 16 ? 1 : cout <= 32 ? 2 : cout <= 64 ? 4 : cout <= 80 ? 5 : 8; }
 __host__ __device__ constexpr int wz_kpad(int K) {  // == ey_conv_kpad(K, 2): 2 (mod 4) 16-byte units
@@ -32,8 +38,11 @@ __host__ __device__ constexpr int wz_kpad(int K) {  // == ey_conv_kpad(K, 2): 2 
 
 // NS: the output-channel blocks of both contractions are split over NS wave groups (4 x NS waves per workgroup): wide channel counts sit
 // on small maps (c = 128 at 20x20: 3 tiles per image), where four waves walking 500 dependent MFMA steps each would be pure latency.
-template <int C, int TH, int NS, bool GS>
-__global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
+// KF: DWT filter length (2 = Haar; 4, 6, 8 = any bank of that length through p.taps, reflect border as ey_dwt).  DS: f_h is a DSConv --
+// its depthwise 3x3 runs on the high sub-bands in LDS (VALU, zero padding, rounded to f16 as the unfused ey_dsconv's intermediate) and
+// its pointwise 1x1 (BN folded, packed as a centre-tap 3x3 like f_ll) then takes the centre tap's k-steps only.
+template <int C, int TH, int NS, bool GS, int KF = 2, bool DS = false>
+__global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(typename WzArgs<KF, DS>::T p) {
   constexpr int TW = 16, RH = TH + 2, RW = TW + 2, NPOS = RH * RW, SS = C + 8, PS = 2 * C + 8, H2 = C / 2, CV = C / 8, NTHR = 256 * NS;
   constexpr int NTs_all = wz_nt(H2), NTz_all = wz_nt(C), MT = TH / 4;
   constexpr int NTs = NTs_all / NS, NTz = NTz_all / NS;
@@ -50,7 +59,7 @@ __global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
   const int ty0 = ty * TH, tx0 = tx * TW;
   // ---- 1. Haar sub-bands of the halo'd tile -> LDS (zero outside the half-resolution map: the 3x3 conv's padding).  All of a thread's
   // 2x2 input patches are requested before the first butterfly (one memory round trip instead of one per position).
-  {
+  if constexpr (KF == 2) {
     const float sq = 0.70710678118654752440f, tp = sq * sq;
     constexpr int NIT = (NPOS * CV + NTHR - 1) / NTHR;
     const long xbytes = ((long)p.B * p.H * p.W - 1) * p.xCs * 2 + C * 2;
@@ -87,6 +96,93 @@ __global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
         ll.store(sp); lh.store(sp + NPOS * SS); hl.store(sp + 2 * NPOS * SS); hh.store(sp + 3 * NPOS * SS);
       }
     }
+  } else {  // KF-tap bank: the arithmetic of dwt_general_kernel (fp32 FMA over (row, column) taps from 0, one f16 rounding)
+    constexpr int NIT = (NPOS * CV + NTHR - 1) / NTHR, PAD = KF / 2 - 1, KK = KF * KF;
+#pragma unroll 1
+    for (int n = 0; n < NIT; ++n) {
+      const int it = tid + n * NTHR;
+      if (it < NPOS * CV) {
+        const int pos = it / CV, c8 = (it - pos * CV) * 8;
+        const int ry = pos / RW, rx_ = pos - ry * RW;
+        const int hy = ty0 - 1 + ry, hx = tx0 - 1 + rx_;
+        float acc[4][8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[q][j] = 0.f;
+        if (hy >= 0 && hy < p.Ho && hx >= 0 && hx < p.Wo) {  // (pad < H, W is checked on the host: one reflection lands inside the map)
+#pragma unroll 1
+          for (int i = 0; i < KF; ++i) {
+            int iy = 2 * hy + i - PAD;
+            iy = iy < 0 ? -iy : iy >= p.H ? 2 * p.H - 2 - iy : iy;
+            const f16* row = p.x + ((long)b * p.H + iy) * p.W * p.xCs + c8;
+#pragma unroll
+            for (int jx = 0; jx < KF; ++jx) {
+              int ix = 2 * hx + jx - PAD;
+              ix = ix < 0 ? -ix : ix >= p.W ? 2 * p.W - 2 - ix : ix;
+              Vec8<f16> a;
+              a.load(row + (long)ix * p.xCs);
+              const float t0 = p.taps[i * KF + jx], t1 = p.taps[KK + i * KF + jx], t2 = p.taps[2 * KK + i * KF + jx], t3 = p.taps[3 * KK + i * KF + jx];
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const float v = a.get(j);
+                acc[0][j] = __builtin_fmaf(t0, v, acc[0][j]);
+                acc[1][j] = __builtin_fmaf(t1, v, acc[1][j]);
+                acc[2][j] = __builtin_fmaf(t2, v, acc[2][j]);
+                acc[3][j] = __builtin_fmaf(t3, v, acc[3][j]);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          Vec8<f16> o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o.set(j, acc[q][j]);
+          o.store(S + q * NPOS * SS + pos * SS + c8);
+        }
+      }
+    }
+  }
+  // ---- 1b. (DS) f_h's depthwise 3x3 over LH, HL, HH at the tile's own pixels, zero padding (S is zero outside the map), fp32 FMA over
+  // (dy, dx) from 0, rounded to f16; written over the centre positions of the sub-band once every wave has read its neighbourhood.
+  if constexpr (DS) {
+    constexpr int NPX = TH * 16 * CV, NDW = (NPX + NTHR - 1) / NTHR;
+#pragma unroll 1
+    for (int band = 1; band < 4; ++band) {  // (band by band: few registers; a band's writes never meet the next band's reads)
+      __syncthreads();
+      Vec8<f16> dv[NDW];
+#pragma unroll
+      for (int n = 0; n < NDW; ++n) {
+        const int it = tid + n * NTHR;
+        if (it < NPX) {
+          const int px = it / CV, c8 = (it - px * CV) * 8, py = px >> 4, pxx = px & 15;
+          float acc[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+          for (int t = 0; t < 9; ++t) {
+            const int dy = t / 3, dx = t - dy * 3;
+            Vec8<f16> w, v;
+            w.load(p.w_dw + t * C + c8);
+            v.load(S + band * NPOS * SS + ((py + dy) * RW + pxx + dx) * SS + c8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(w.get(j), v.get(j), acc[j]);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) dv[n].set(j, acc[j]);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int n = 0; n < NDW; ++n) {
+        const int it = tid + n * NTHR;
+        if (it < NPX) {
+          const int px = it / CV, c8 = (it - px * CV) * 8, py = px >> 4, pxx = px & 15;
+          dv[n].store(S + band * NPOS * SS + ((py + 1) * RW + pxx + 1) * SS + c8);
+        }
+      }
+    }
   }
   // ---- 2. the four sub-band convs -> P (f16, [pixel][LL | LH | HL | HH processed, c/2 each]).
   // GS = false: a wave owns MT pixel rows and the NTs channel blocks of its wave group, and walks the four sub-bands in turn;
@@ -99,16 +195,17 @@ __global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
   {
     constexpr int MT2 = GS ? TH : MT, NT2 = NTs;
     constexpr int KS_ALL = (9 * C + 31) / 32, J0 = (4 * C) / 32, J1 = (5 * C + 31) / 32, N0 = J1 - J0;
+    constexpr int KSH = DS ? N0 : KS_ALL, JH0 = DS ? J0 : 0;  // k-steps of a high sub-band and the first one (DS: the centre tap only)
     constexpr int UB = (NT2 * 9 <= 12) ? 9 : 12 / NT2;  // steps per batch: two batches of fragments (4 VGPRs each) are live
     const int wave16 = tid >> 6;
     const int mygrp = GS ? (wave16 & 3) : 0, nt0 = ns * NTs, row0 = GS ? 0 : wave * MT;
-    const int T = GS ? (mygrp == 0 ? N0 : KS_ALL) : N0 + 3 * KS_ALL;
+    const int T = GS ? (mygrp == 0 ? N0 : KSH) : N0 + 3 * KSH;
     const __amdgpu_buffer_rsrc_t rws = ey_rsrc(p.w_sub, (unsigned)((p.w_set + (long)16 * NTs_all * KPs) * 2));
     const unsigned wvoff = (unsigned)((r * KPs + 8 * g) * 2);
     auto decode = [&](int s_, int& grp, int& j) {  // (wave-uniform)
-      if constexpr (GS) { grp = mygrp; j = (mygrp == 0 ? J0 : 0) + s_; }
+      if constexpr (GS) { grp = mygrp; j = (mygrp == 0 ? J0 : JH0) + s_; }
       else if (s_ < N0) { grp = 0; j = J0 + s_; }
-      else { const int t = s_ - N0; grp = 1 + t / KS_ALL; j = t - (grp - 1) * KS_ALL; }
+      else { const int t = s_ - N0; grp = 1 + t / KSH; j = JH0 + t - (grp - 1) * KSH; }
     };
     auto issue = [&](int s0, Vec8<f16> (&af)[UB][NT2]) {
 #pragma unroll
@@ -146,7 +243,7 @@ __global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
           for (int mt = 0; mt < MT2; ++mt)
 #pragma unroll
             for (int nt = 0; nt < NT2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[u][nt].v, bf[mt].v, acc[mt][nt], 0, 0, 0);
-          if (j == (grp == 0 ? J1 : KS_ALL) - 1) {  // last k-step of this sub-band: bias + SiLU -> P, start the next sub-band from zero
+          if (j == ((grp == 0 || DS) ? J1 : KS_ALL) - 1) {  // last k-step of this sub-band: bias + SiLU -> P, start the next sub-band from zero
             const float* bias = p.b_sub + (grp == 0 ? 0 : H2);
 #pragma unroll
             for (int mt = 0; mt < MT2; ++mt) {
@@ -232,13 +329,16 @@ __global__ __launch_bounds__(256 * NS) void wavelet_z_kernel(WzP p) {
   }
 }
 
-template <int C, int TH, int NS, bool GS>
-static int wz_launch(WzP p, hipStream_t st) {
+template <int C, int TH, int NS, bool GS, int KF, bool DS>
+static int wz_launch(WzPX px, hipStream_t st) {
+  typename WzArgs<KF, DS>::T p;
+  static_cast<WzP&>(p) = px;
+  if constexpr (KF != 2 || DS) { p.taps = px.taps; p.w_dw = px.w_dw; }
   constexpr int NPOS = (TH + 2) * 18;
   const size_t lds = (size_t)(4 * NPOS * (C + 8) + TH * 16 * (2 * C + 8)) * 2;
   static bool attr_done = false;
   if (lds > 64 * 1024 && !attr_done) {
-    if (hipFuncSetAttribute((const void*)wavelet_z_kernel<C, TH, NS, GS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)wavelet_z_kernel<C, TH, NS, GS, KF, DS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return ey_set_error(EY_ELAUNCH, "wavelet_z: cannot reserve %zu B of LDS", lds);
     attr_done = true;
   }
@@ -247,29 +347,51 @@ static int wz_launch(WzP p, hipStream_t st) {
   const long nblk = (long)p.B * p.tiles_x * p.tiles_y;
   if (nblk >= (1L << 31)) return ey_set_error(EY_EINVAL, "wavelet_z: too many tiles");
   p.xcd = (int)((tune().xcd_map >> 2) & 1);
-  hipLaunchKernelGGL((wavelet_z_kernel<C, TH, NS, GS>), dim3((unsigned)nblk), dim3(256 * NS), lds, st, p);
+  hipLaunchKernelGGL((wavelet_z_kernel<C, TH, NS, GS, KF, DS>), dim3((unsigned)nblk), dim3(256 * NS), lds, st, p);
   EY_LAUNCH_CHECK("ey_wavelet_z");
   return EY_OK;
 }
 
-extern "C" int ey_wavelet_z(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const void* w_sub_packed, long w_set_stride, const float* b_sub,
-                            const void* w_z_packed, void* z, int z_cstride, ey_stream_t stream) {
+template <int C, int TH, int NS, bool GS>
+static int wz_dispatch(int k, bool ds, WzPX p, hipStream_t st) {
+  switch (k) {
+    case 2: return ds ? wz_launch<C, TH, NS, GS, 2, true>(p, st) : wz_launch<C, TH, NS, GS, 2, false>(p, st);
+    case 4: return ds ? wz_launch<C, TH, NS, GS, 4, true>(p, st) : wz_launch<C, TH, NS, GS, 4, false>(p, st);
+    case 6: return ds ? wz_launch<C, TH, NS, GS, 6, true>(p, st) : wz_launch<C, TH, NS, GS, 6, false>(p, st);
+    default: return ds ? wz_launch<C, TH, NS, GS, 8, true>(p, st) : wz_launch<C, TH, NS, GS, 8, false>(p, st);
+  }
+}
+
+extern "C" int ey_wavelet_z2(int dtype, int B, int H, int W, int C, int k, const float* taps, int use_ds, const void* w_dw_kkc, const void* x,
+                             int x_cstride, const void* w_sub_packed, long w_set_stride, const float* b_sub, const void* w_z_packed, void* z,
+                             int z_cstride, ey_stream_t stream) {
   if (dtype != EY_F16) return ey_set_error(EY_EUNSUPPORTED, "wavelet_z: f16 only (the fp32 parity mode keeps the per-layer kernels)");
   if (!(C == 16 || C == 32 || C == 64 || C == 128)) return ey_set_error(EY_EUNSUPPORTED, "wavelet_z: built for c in {16, 32, 64, 128}, got %d", C);
+  if (!(k == 2 || k == 4 || k == 6 || k == 8)) return ey_set_error(EY_EUNSUPPORTED, "wavelet_z: built for filter lengths 2, 4, 6, 8, got %d", k);
   EY_CHECK(x && w_sub_packed && b_sub && w_z_packed && z && B > 0 && H >= 2 && W >= 2, "wavelet_z: bad arguments");
+  EY_CHECK(k == 2 || taps, "wavelet_z: a %d-tap bank needs its taps", k);
+  EY_CHECK(k / 2 - 1 < H && k / 2 - 1 < W, "wavelet_z: reflect padding %d needs a map larger than %dx%d", k / 2 - 1, H, W);
+  EY_CHECK(!use_ds || (w_dw_kkc && ey_aligned(w_dw_kkc, 16)), "wavelet_z: use_ds needs 16-byte aligned depthwise weights");
   EY_CHECK(x_cstride >= C && (x_cstride * 2) % 16 == 0 && ey_aligned(x, 16) && z_cstride >= C && (z_cstride * 2) % 8 == 0 && ey_aligned(z, 8),
            "wavelet_z: view alignment");
   EY_CHECK(ey_aligned(w_sub_packed, 16) && ey_aligned(w_z_packed, 16) && (w_set_stride * 2) % 16 == 0 && w_set_stride >= 0, "wavelet_z: weight alignment");
   EY_CHECK(((long)B * H * W - 1) * x_cstride * 2 + C * 2 < (1L << 31), "wavelet_z: input view of 2 GiB or more");
-  WzP p;
+  WzPX p;
   p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
   p.x = (const f16*)x; p.xCs = x_cstride; p.w_sub = (const f16*)w_sub_packed; p.w_set = w_set_stride; p.b_sub = b_sub; p.w_z = (const f16*)w_z_packed;
   p.z = (f16*)z; p.zCs = z_cstride;
+  p.taps = taps; p.w_dw = (const f16*)w_dw_kkc;
   hipStream_t st = (hipStream_t)stream;
+  const bool ds = use_ds != 0;
   switch (C) {
-    case 16: return wz_launch<16, 8, 1, false>(p, st);
-    case 32: return wz_launch<32, 8, 1, false>(p, st);
-    case 64: return wz_launch<64, 8, 2, false>(p, st);
-    default: return wz_launch<128, 4, 2, true>(p, st);
+    case 16: return wz_dispatch<16, 8, 1, false>(k, ds, p, st);
+    case 32: return wz_dispatch<32, 8, 1, false>(k, ds, p, st);
+    case 64: return wz_dispatch<64, 8, 2, false>(k, ds, p, st);
+    default: return wz_dispatch<128, 4, 2, true>(k, ds, p, st);
   }
+}
+
+extern "C" int ey_wavelet_z(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const void* w_sub_packed, long w_set_stride, const float* b_sub,
+                            const void* w_z_packed, void* z, int z_cstride, ey_stream_t stream) {
+  return ey_wavelet_z2(dtype, B, H, W, C, 2, nullptr, 0, nullptr, x, x_cstride, w_sub_packed, w_set_stride, b_sub, w_z_packed, z, z_cstride, stream);
 }

@@ -558,30 +558,60 @@ def dwt_haar(x, out=None):
     return out
 
 
-def wavelet_z(mod, b, sets_fn, z_fn):
-    """Half-resolution branch of _WaveletEnhancer in ONE kernel (ey_wavelet_z): b (B,c,H,W) -> Z (B,c,H/2,W/2).  sets_fn() ->
-    ((w_ll3x3, b_ll), (w_h, b_h)) BN-folded fp32; z_fn() -> (w_z (c,2c,1,1), None).  Returns None when the shape is outside the fused
-    kernel (fp32 mode, c not in {16,32,64,128}, while a block program is recorded): the caller runs dwt + the two convs."""
+def dwt(x, taps, k, out=None):
+    """(B,C,H,W) -> (B,4C,H/2,W/2) with channel blocks LL|LH|HL|HH for a k-tap filter bank (ey_dwt, reflect border).  taps: device
+    fp32 (4,k,k), already rounded to x's dtype.  Not a block-program stage: a recorded chain stops here and runs per layer."""
+    L.require_device(x, "dwt")
+    x = L.as_nhwc(x)
+    B, c, H, W = x.shape
+    if k // 2 - 1 >= H or k // 2 - 1 >= W:
+        raise ValueError(f"dwt: a {k}-tap filter bank reflect-pads by {k // 2 - 1}, which needs a map larger than {H}x{W}")
+    _no_block("dwt with a general filter bank")
+    if out is None:
+        out = L.empty_nhwc(B, 4 * c, H // 2, W // 2, x.dtype, x.device)
+    with _tr(f"dwt_general_kernel<k{k}>", _nb(x, out), 8.0 * k * k * c * B * (H // 2) * (W // 2)):
+        L.check(L.lib().ey_dwt(L.dtype_code(x.dtype), B, H, W, c, k, taps.data_ptr(), x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out),
+                               L.stream()), "ey_dwt")
+    return out
+
+
+def wavelet_z(mod, b, sets_fn, z_fn, dwt=None, dw_fn=None):
+    """Half-resolution branch of _WaveletEnhancer in ONE kernel (ey_wavelet_z / ey_wavelet_z2): b (B,c,H,W) -> Z (B,c,H/2,W/2).  sets_fn()
+    -> ((w_ll3x3, b_ll), (w_h, b_h)) BN-folded fp32 (use_ds: w_h = the pointwise 1x1 as a centre-tap 3x3); z_fn() -> (w_z (c,2c,1,1), None);
+    dwt: the _PywtDWT2D (None = Haar); dw_fn (use_ds) -> f_h's depthwise 3x3 weights (c,1,3,3).  Returns None when the shape is outside the
+    fused kernel (fp32 mode, c not in {16,32,64,128}, a filter length other than 2/4/6/8, while a block program is recorded): the caller
+    runs dwt + the sub-band convs + Z."""
     L.require_device(b, "wavelet_z")
     b = L.as_nhwc(b)
     B, c, H, W = b.shape
-    if RECORD is not None or b.dtype != torch.float16 or c not in (16, 32, 64, 128) or H < 2 or W < 2 or (L.cstride(b) * 2) % 16 or b.data_ptr() % 16:
+    k = 2 if dwt is None or dwt.haar else dwt.k
+    if (RECORD is not None or b.dtype != torch.float16 or c not in (16, 32, 64, 128) or k not in (2, 4, 6, 8) or H < 2 or W < 2 or k // 2 - 1 >= min(H, W)
+            or (L.cstride(b) * 2) % 16 or b.data_ptr() % 16):
         return None
 
     def build():
         (wl, bl), (wh, bh) = sets_fn()
         wz, _ = z_fn()
         packs = [pack_conv_weight(w, b.dtype, b.device) for w in (wl, wh)]
+        wdw = dw_fn().float().view(c, 3, 3).permute(1, 2, 0).contiguous().to(b.device, b.dtype) if dw_fn is not None else None  # [3][3][c]
         return (torch.cat(packs), packs[0].numel() // 2, torch.cat([bl.to(b.device).float(), bh.to(b.device).float()]).contiguous(),
-                pack_conv_weight(wz, b.dtype, b.device))
+                pack_conv_weight(wz, b.dtype, b.device), wdw)
 
-    wsub, wset, bias, wz = mod._packed(_dev_key(b, "wavelet_z"), build)
+    wsub, wset, bias, wz, wdw = mod._packed(_dev_key(b, "wavelet_z"), build)
     z = L.empty_nhwc(B, c, H // 2, W // 2, b.dtype, b.device)
     M = B * (H // 2) * (W // 2)
     flops = 2.0 * M * ((c // 2) * c + 3 * (c // 2) * 9 * c + c * 2 * c) + 4.0 * b.numel()
-    with _tr("wavelet_z_kernel", _nb(b, z) + ((c // 2) * 10 * c + 2 * c * c) * 2, flops, note=f"C{c} {H}x{W}"):
-        L.check(L.lib().ey_wavelet_z(L.dtype_code(b.dtype), B, H, W, c, b.data_ptr(), L.cstride(b), wsub.data_ptr(), wset, bias.data_ptr(), wz.data_ptr(),
-                                     z.data_ptr(), L.cstride(z), L.stream()), "ey_wavelet_z")
+    if k == 2 and wdw is None:
+        with _tr("wavelet_z_kernel", _nb(b, z) + ((c // 2) * 10 * c + 2 * c * c) * 2, flops, note=f"C{c} {H}x{W}"):
+            L.check(L.lib().ey_wavelet_z(L.dtype_code(b.dtype), B, H, W, c, b.data_ptr(), L.cstride(b), wsub.data_ptr(), wset, bias.data_ptr(), wz.data_ptr(),
+                                         z.data_ptr(), L.cstride(z), L.stream()), "ey_wavelet_z")
+        return z
+    taps = dwt.taps(b) if k > 2 else None
+    label = f"wavelet_z_kernel<k{k}{',ds' if wdw is not None else ''}>"
+    with _tr(label, _nb(b, z) + ((c // 2) * 10 * c + 2 * c * c) * 2, flops, note=f"C{c} {H}x{W}"):
+        L.check(L.lib().ey_wavelet_z2(L.dtype_code(b.dtype), B, H, W, c, k, taps.data_ptr() if taps is not None else None, int(wdw is not None),
+                                      wdw.data_ptr() if wdw is not None else None, b.data_ptr(), L.cstride(b), wsub.data_ptr(), wset, bias.data_ptr(),
+                                      wz.data_ptr(), z.data_ptr(), L.cstride(z), L.stream()), "ey_wavelet_z2")
     return z
 
 

@@ -360,18 +360,65 @@ class DSC3k(C3):
         self.m = nn.Sequential(*(DSBottleneck(c_, c_, shortcut=shortcut, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n)))
 
 
-class _PywtDWT2D(nn.Module):
-    """Single-level 2-D Haar analysis (reference block.py:3582-3642).  The pywt filter bank is the constant
-    1/sqrt(2) pair; the kernel applies the squared taps exactly as the reference's depthwise conv does."""
+_FILTERS = None
+_HAAR = (0.7071067811865476, 0.7071067811865476), (-0.7071067811865476, 0.7071067811865476)  # pywt.Wavelet("haar").dec_lo / dec_hi
+
+
+def wavelet_filters():
+    """{name: (dec_lo, dec_hi)} of every discrete PyWavelets wavelet with at most 64 taps, and {name: length} of the longer ones
+    (nn/wavelet_filters.json, recorded from pywt.Wavelet(name); the package does not need pywt)."""
+    global _FILTERS
+    if _FILTERS is None:
+        import json
+        import os
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wavelet_filters.json")) as f:
+            d = json.load(f)
+        _FILTERS = ({k: (tuple(v["dec_lo"]), tuple(v["dec_hi"])) for k, v in d["filters"].items()}, dict(d["too_long"]))
+    return _FILTERS
+
+
+class _PywtDWT2D(_Packed):
+    """Single-level 2-D analysis with a pywt filter bank (reference block.py:3582-3642): reflect padding by k/2 - 1, then a depthwise
+    k x k conv with stride 2 over the outer products of h0 = dec_lo[::-1] and h1 = dec_hi[::-1] (fp32, cast to the activation dtype).
+    A bank equal to Haar's (haar, db1, ...) runs the dedicated 2x2 kernel; every other bank runs ey_dwt.  `mode` is stored and ignored,
+    as in the reference (always reflect)."""
 
     def __init__(self, wave="haar", mode="symmetric"):
         super().__init__()
-        if wave not in ("haar", "db1"):
-            raise NotImplementedError(f"wavelet '{wave}': only the Haar bank is on the detection path")
+        table, too_long = wavelet_filters()
+        if wave in too_long:
+            raise NotImplementedError(f"wavelet '{wave}': {too_long[wave]} taps; filter banks longer than 64 taps are not built")
+        if wave not in table:
+            raise NotImplementedError(f"wavelet '{wave}': not a discrete PyWavelets wavelet (pywt.wavelist(kind='discrete') names them)")
         self.wave_name, self.mode = wave, mode
+        lo, hi = table[wave]
+        self.k = len(lo)
+        self.pad = self.k // 2 - 1  # (every discrete pywt bank has even length)
+        self.haar = (lo, hi) == _HAAR
+        h0 = torch.tensor(lo[::-1], dtype=torch.float32)
+        h1 = torch.tensor(hi[::-1], dtype=torch.float32)
+        e = lambda a, b: torch.einsum("i,j->ij", a, b)  # noqa: E731  (fp32 products, rounded once: block.py:3604-3607)
+        self.taps32 = torch.stack([e(h0, h0), e(h0, h1), e(h1, h0), e(h1, h1)])  # (4,k,k) CPU constant, not module state
+
+    def taps(self, x):
+        """Device fp32 taps with the values the reference convolves with in x's dtype (self.weight.to(dtype=x.dtype))."""
+        return self._packed(("taps", x.dtype, x.device), lambda: self.taps32.to(x.dtype).float().to(x.device).contiguous())
+
+    def check_size(self, H, W):
+        if H < 2 or W < 2:
+            raise ValueError(f"_PywtDWT2D: feature map {H}x{W} is too small for a 2x2 Haar step" if self.haar else
+                             f"_PywtDWT2D: feature map {H}x{W} is too small")
+        if self.pad >= H or self.pad >= W:  # F.pad(mode="reflect") refuses these in the reference
+            raise ValueError(f"_PywtDWT2D('{self.wave_name}'): reflect padding {self.pad} needs a feature map larger than {H}x{W}")
+
+    def subbands(self, x):
+        """(B,C,H,W) -> (B,4C,H/2,W/2) with channel blocks LL|LH|HL|HH."""
+        self.check_size(x.shape[2], x.shape[3])
+        x = L.as_nhwc(x)
+        return ops.dwt_haar(x) if self.haar else ops.dwt(x, self.taps(x), self.k)
 
     def forward(self, x):
-        y = ops.dwt_haar(x)
+        y = self.subbands(x)
         c = x.shape[1]
         return y[:, :c], y[:, c:2 * c], y[:, 2 * c:3 * c], y[:, 3 * c:]
 
@@ -403,7 +450,12 @@ class _WaveletEnhancer(_Packed):
 
     def _subband_sets(self):
         wl, bl = self.f_ll.folded()
-        wh, bh = self.f_h.folded()
+        if isinstance(self.f_h, DSConv):  # use_ds: the pointwise 1x1 of f_h (BN folded), also written as a centre-tap 3x3
+            wp, bh = self.f_h._pw_folded()
+            wh = torch.zeros(wp.shape[0], wp.shape[1], 3, 3, dtype=wp.dtype, device=wp.device)
+            wh[:, :, 1:2, 1:2] = wp
+        else:
+            wh, bh = self.f_h.folded()
         w3 = torch.zeros_like(wh)
         w3[:, :, 1:2, 1:2] = wl  # 1x1 == 3x3 with only the centre tap (pad 1)
         return (w3, bl), (wh, bh)
@@ -426,24 +478,30 @@ class _WaveletEnhancer(_Packed):
         one launch (ops.conv_pw_pair) and (y, y_then) is returned; y_then is None when the caller has to run that conv itself."""
         b = L.as_nhwc(b)
         B, c, H, W = b.shape
-        if H < 2 or W < 2:
-            raise ValueError(f"_WaveletEnhancer: feature map {H}x{W} is too small for a 2x2 Haar step")
-        if isinstance(self.f_h, DSConv):
-            raise NotImplementedError("use_ds=True sub-band path is not built (no YAML enables it)")
+        self.dwt.check_size(H, W)
+        use_ds = isinstance(self.f_h, DSConv)
         h = c // 2
         g = self._packed("tanh_gamma", lambda: float(torch.tanh(self.gamma.detach().float())))  # host scalar, cached (graph capture)
         if self.fused_z:  # f16: DWT + the four sub-band convs + Z in ONE kernel, only Z touches HBM
-            Z = ops.wavelet_z(self, b, self._subband_sets, self._fuse_z)
+            Z = ops.wavelet_z(self, b, self._subband_sets, self._fuse_z, dwt=self.dwt, dw_fn=(lambda: self.f_h._dw_folded()[0]) if use_ds else None)
             if Z is not None:
                 if then is not None:
                     return ops.conv_pw_pair(dict(mod=self, srcs=[b], folded_fn=self._fuse_b, act=L.ACT_SILU, out=out, res=b, addz=Z, out_scale=g, tag="b"), then)
                 return ops.conv2d(self, [b], self._fuse_b, 1, 1, 0, L.ACT_SILU, out=out, res=b, addz=Z, out_scale=g, tag="b")
-        sub = ops.dwt_haar(b)  # (B,4c,H/2,W/2): LL|LH|HL|HH
+        sub = self.dwt.subbands(b)  # (B,4c,H/2,W/2): LL|LH|HL|HH
         P = L.empty_nhwc(B, 2 * c, H // 2, W // 2, b.dtype, b.device)
+        if use_ds:  # f_ll (1x1) on LL, then the shared DSConv f_h on each high band: channel-offset views of `sub` into slices of `P`
+            self.f_ll(sub[:, :c], out=P[:, :h])
+            for i in (1, 2, 3):
+                self.f_h(sub[:, i * c:(i + 1) * c], out=P[:, i * h:(i + 1) * h])
+            return self._tail(b, P, g, out, then)
         # ONE launch for the four sub-band convs: group 0 = f_ll (a 1x1 conv written as a centre-tap 3x3) on LL, groups 1-3 =
         # the shared f_h on LH, HL, HH (weight set min(g, 1)); the groups are channel-offset slices of `sub` and `P`
         ops.conv2d(self, [sub[:, :c]], self._subband_sets, 3, 1, 1, L.ACT_SILU, out=P[:, :h], ngroup=4, src_gstride=c, y_gstride=h, w_sets=2,
                    tag="sub")
+        return self._tail(b, P, g, out, then)
+
+    def _tail(self, b, P, g, out, then):
         Z = ops.conv2d(self, [P], self._fuse_z, 1, 1, 0, L.ACT_NONE, tag="z")
         y = ops.conv2d(self, [b], self._fuse_b, 1, 1, 0, L.ACT_SILU, out=out, res=b, addz=Z, out_scale=g, tag="b")
         return (y, None) if then is not None else y

@@ -89,6 +89,9 @@ def parse_model(d, ch, verbose=False):
             if m not in globals():
                 raise NotImplementedError(f"module '{m}' is not in the edge-yolo_amd registry (SURVEY.md §8a lists what is)")
             m = globals()[m]
+        kw = args.pop() if m is DSC3K2_Wavelet and args and isinstance(args[-1], dict) else {}  # build-only extension: trailing {wave:, use_ds:, mode:}
+        if set(kw) - {"wave", "use_ds", "mode"}:
+            raise ValueError(f"layer {i}: DSC3K2_Wavelet keyword arguments are wave, use_ds and mode, got {sorted(kw)}")
         for j, a in enumerate(args):
             if isinstance(a, str):
                 with contextlib.suppress(ValueError):
@@ -113,7 +116,7 @@ def parse_model(d, ch, verbose=False):
             m.legacy = legacy
         else:
             c2 = ch[f]
-        m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        m_ = nn.Sequential(*(m(*args, **kw) for _ in range(n))) if n > 1 else m(*args, **kw)
         t = f"{m.__module__}.{m.__name__}".replace("edge_yolo_amd", "ultralytics") if m is not Upsample else "torch.nn.modules.upsampling.Upsample"
         m_.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t

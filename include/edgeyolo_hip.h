@@ -200,6 +200,15 @@ int ey_dsconv_last_variant(void);
 int ey_dwt_haar(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y, int y_cstride,
                 ey_stream_t stream);
 
+/* ---- K4 (any filter bank): single-level 2-D analysis with a k-tap pywt bank (_PywtDWT2D, block.py:3582-3642):
+ * F.pad(mode="reflect", pad = k/2 - 1), then a depthwise k x k conv with stride 2 and no padding.  The padded map is never built
+ * (reflect indexing).  x [B,H,W,C] -> y [B,H/2,W/2,4C] with channel blocks LL|LH|HL|HH, as ey_dwt_haar.  taps: DEVICE fp32
+ * [4][k][k] = (LL, LH, HL, HH) outer products of h0 = dec_lo[::-1] and h1 = dec_hi[::-1] (LH: rows h0, columns h1), each rounded
+ * once in fp32 and then to the activation dtype, as the reference convolves with.  k even, 2..64.  EY_EINVAL (nothing launched)
+ * when pad >= H or pad >= W: torch refuses that reflect padding too. */
+int ey_dwt(int dtype, int B, int H, int W, int C, int k, const float* taps, const void* x, int x_cstride, void* y, int y_cstride,
+           ey_stream_t stream);
+
 /* ---- K4+K5 fused: the half-resolution branch of _WaveletEnhancer (block.py:3688-3706) in one kernel (f16 only):
  *   Z = W_z . cat[ SiLU(f_ll(LL)+b), SiLU(f_h(LH)+b), SiLU(f_h(HL)+b), SiLU(f_h(HH)+b) ]   with (LL,LH,HL,HH) = Haar DWT of x
  * x [B,H,W,C] -> z [B,H/2,W/2,C].  w_sub_packed: two ey_conv_pack_weight(EY_F16, C/2, C, 3) sets w_set_stride ELEMENTS apart (set 0 =
@@ -209,6 +218,14 @@ int ey_dwt_haar(int dtype, int B, int H, int W, int C, const void* x, int x_cstr
  * tensor and the 2C-channel P. */
 int ey_wavelet_z(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const void* w_sub_packed, long w_set_stride, const float* b_sub,
                  const void* w_z_packed, void* z, int z_cstride, ey_stream_t stream);
+/* The same branch for a k-tap pywt bank and / or a DSConv f_h (_PywtDWT2D block.py:3582-3642 with reflect padding k/2 - 1;
+ * _WaveletEnhancer(use_ds=True) block.py:3686).  ey_wavelet_z is this call with k = 2, taps = NULL, use_ds = 0.
+ * k in {2, 4, 6, 8}; taps: DEVICE fp32 [4][k][k] as for ey_dwt (unused for k = 2, which is the Haar kernel).  use_ds: set 1 of
+ * w_sub_packed is f_h's pointwise 1x1 (BN folded) written as a centre-tap 3x3, like f_ll, and w_dw_kkc the depthwise 3x3 weights,
+ * DEVICE f16 [3][3][C], 16-byte aligned; the depthwise output is rounded to f16 like ey_dsconv's.  EY_EUNSUPPORTED (nothing launched)
+ * for fp32, other C or other k; EY_EINVAL when k/2 - 1 >= H or >= W. */
+int ey_wavelet_z2(int dtype, int B, int H, int W, int C, int k, const float* taps, int use_ds, const void* w_dw_kkc, const void* x, int x_cstride,
+                  const void* w_sub_packed, long w_set_stride, const float* b_sub, const void* w_z_packed, void* z, int z_cstride, ey_stream_t stream);
 
 /* ---- K6: the three chained 5x5/s1/p2 max-pools of SPPF (block.py:219-223): y1=mp(x), y2=mp(y1), y3=mp(y2). */
 int ey_sppf_pool(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y1, void* y2, void* y3,

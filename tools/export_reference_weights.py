@@ -14,6 +14,32 @@ import sys
 import torch
 
 
+def _record_wavelet_kwargs(model, cfg):
+    """The DWT filter of a reference _PywtDWT2D is a non-persistent buffer, and wave= / use_ds= are constructor kwargs its YAML
+    cannot express: a state_dict alone would load as a Haar / dense-f_h model.  Each DSC3K2_Wavelet layer whose enhancer is not
+    the default gets a trailing {wave:, use_ds:, mode:} mapping in its yaml args (edge-yolo_amd's parse_model reads it)."""
+    rows = None
+    for layer in model.modules():
+        if type(layer).__name__ != "DSC3K2_Wavelet":
+            continue
+        enh = layer.wave
+        wave, mode = getattr(enh.dwt, "wave_name", "haar"), getattr(enh.dwt, "mode", "symmetric")
+        use_ds = type(enh.f_h).__name__ == "DSConv"
+        if wave == "haar" and not use_ds and mode == "symmetric":
+            continue
+        if rows is None:
+            cfg["backbone"] = [list(r) for r in cfg["backbone"]]
+            cfg["head"] = [list(r) for r in cfg["head"]]
+            rows = cfg["backbone"] + cfg["head"]
+        row = rows[layer.i]  # (parse_model sets .i, the layer's index in backbone + head)
+        args = list(row[3])
+        extra = dict(args.pop()) if args and isinstance(args[-1], dict) else {}
+        extra.update(wave=wave, use_ds=use_ds)
+        if mode != "symmetric":
+            extra["mode"] = mode
+        row[3] = args + [extra]
+
+
 def export(src, dst):
     ck = torch.load(src, map_location="cpu", weights_only=False)  # a reference checkpoint: pickled nn.Module (trusted input of the reference's user)
     model = ck.get("ema") or ck["model"] if isinstance(ck, dict) else ck
@@ -23,6 +49,7 @@ def export(src, dst):
     cfg = {k: (list(v) if isinstance(v, tuple) else v) for k, v in cfg.items()}
     first_conv = next(k for k in sd if k.endswith("conv.weight"))
     fused = first_conv.replace("conv.weight", "bn.weight") not in sd  # BaseModel.fuse() deleted the BatchNorms (tasks.py:214-242)
+    _record_wavelet_kwargs(model, cfg)
     torch.save({"yaml": cfg, "nc": int(cfg["nc"]), "fused": bool(fused), "state_dict": sd}, dst)
     return len(sd), fused
 
