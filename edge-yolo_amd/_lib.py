@@ -98,6 +98,8 @@ SIGNATURES = {
     "ey_letterbox_batch": (_i, [_i, _vp, _i, _i, _i, _i, C.c_long, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ey_linear_attention": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ey_softmax_attention": (_i, [_i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp]),
+    "ey_attention_last_variant": (_i, []),
+    "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "ey_head_decode_levels_xyxy": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

@@ -25,6 +25,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 // (one broadcast ds_read_b128 feeds 4 FMAs) instead of 64 ds_bpermute per pixel.
 #define LA_WAVES 8
 #define LA_U 4
+// kernel the last ey_linear_attention / ey_softmax_attention on this thread launched (see ey_attention_last_variant); 0 = none
+static thread_local int g_attn_variant = 0;
+extern "C" int ey_attention_last_variant(void) { return g_attn_variant; }
 template <typename T>
 __global__ __launch_bounds__(64 * LA_WAVES) void linattn_kernel(int N, int C, int heads, int d, const T* __restrict__ qkv, int qCs, T* __restrict__ y, int yCs) {
   __shared__ float ctx[64][64];
@@ -130,7 +133,9 @@ __global__ __launch_bounds__(64 * LA_WAVES) void linattn_kernel(int N, int C, in
     for (int u = 0; u < LA_U; ++u) {
       const int n = n0 + u * LA_WAVES;
       if (n >= N) break;  // wave-uniform
-      rb[lane] = __expf(qq[u] - qm) * qinv;
+      // lanes >= d hold no channel: their column max is -inf and exp(-inf - -inf) is NaN, which would reach every output
+      // through the 0 rows of ctx (NaN * 0)
+      rb[lane] = act ? __expf(qq[u] - qm) * qinv : 0.f;
       __builtin_amdgcn_wave_barrier();
       float o = 0.f;
 #pragma unroll
@@ -166,6 +171,7 @@ __global__ __launch_bounds__(512) void linattn_mfma_kernel(int N, int C, int hea
 }
 
 extern "C" int ey_linear_attention(int dtype, int B, int N, int C, int heads, const void* qkv, int qkv_cstride, void* y, int y_cstride, ey_stream_t stream) {
+  g_attn_variant = 0;
   EY_CHECK(qkv && y, "linear_attention: null pointer");
   EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "linear_attention: bad dtype");
   EY_CHECK(B > 0 && N > 0 && heads > 0 && C % heads == 0, "linear_attention: B=%d N=%d C=%d heads=%d", B, N, C, heads);
@@ -175,10 +181,12 @@ extern "C" int ey_linear_attention(int dtype, int B, int N, int C, int heads, co
   dim3 grid(B * heads);
   const bool mfma_off = !tune().linattn_mfma;
   if (dtype == EY_F16 && d == 64 && !mfma_off && (qkv_cstride * 2) % 16 == 0 && ey_aligned(qkv, 16) && C % 8 == 0 && (y_cstride * 2) % 8 == 0 && ey_aligned(y, 8)) {
+    g_attn_variant = EY_ATTN_LIN_MFMA;
     hipLaunchKernelGGL(linattn_mfma_kernel, grid, dim3(512), 0, (hipStream_t)stream, N, C, heads, (const f16*)qkv, qkv_cstride, (f16*)y, y_cstride);
     EY_LAUNCH_CHECK("ey_linear_attention(mfma)");
     return EY_OK;
   }
+  g_attn_variant = dtype == EY_F16 ? EY_ATTN_LIN_F16 : EY_ATTN_LIN_F32;
   if (dtype == EY_F16) hipLaunchKernelGGL(linattn_kernel<f16>, grid, dim3(64 * LA_WAVES), 0, (hipStream_t)stream, N, C, heads, d, (const f16*)qkv, qkv_cstride, (f16*)y, y_cstride);
   else hipLaunchKernelGGL(linattn_kernel<float>, grid, dim3(64 * LA_WAVES), 0, (hipStream_t)stream, N, C, heads, d, (const float*)qkv, qkv_cstride, (float*)y, y_cstride);
   EY_LAUNCH_CHECK("ey_linear_attention");
@@ -346,6 +354,7 @@ static int softattn_mfma_launch(int B, int N, int heads, float scale, const void
     if (hipFuncSetAttribute((const void*)softattn_mfma_kernel<NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
     attr = true;
   }
+  g_attn_variant = EY_ATTN_SOFT_MFMA + NKS;
   hipLaunchKernelGGL((softattn_mfma_kernel<NKS>), dim3(B * heads), dim3(512), lds, st, N, heads, scale, (const f16*)qkv, qCs, (f16*)y, yCs);
   hipError_t e_ = hipGetLastError();
   if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_softmax_attention(mfma): %s", hipGetErrorString(e_));
@@ -354,6 +363,7 @@ static int softattn_mfma_launch(int B, int N, int heads, float scale, const void
 
 extern "C" int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, int hd, float scale, const void* qkv, int qkv_cstride, void* y, int y_cstride,
                                     ey_stream_t stream) {
+  g_attn_variant = 0;
   EY_CHECK(qkv && y, "softmax_attention: null pointer");
   EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "softmax_attention: bad dtype");
   EY_CHECK(B > 0 && N > 0 && heads > 0 && kd > 0 && hd > 0, "softmax_attention: bad extent");
@@ -384,6 +394,7 @@ extern "C" int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, 
   do {                                                                                                                                   \
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)softattn_kernel<T, KL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
       return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);                                                               \
+    g_attn_variant = EY_ATTN_SOFT_VALU + (dtype == EY_F16 ? 4 : 0) + (KL ? 2 : 0) + (nsplit == 1 ? 1 : 0);                             \
     hipLaunchKernelGGL((softattn_kernel<T, KL>), grid, dim3(256), lds, st, N, heads, kd, hd, scale, (const T*)qkv, qkv_cstride, (T*)y, y_cstride, n_per_block); \
   } while (0)
   if (dtype == EY_F16) { if (k_lds) SOFTATT(f16, true); else SOFTATT(f16, false); }

@@ -199,6 +199,10 @@ __global__ __launch_bounds__(HD_ANCH) void head_decode_kernel(int B, HdLevels lv
   }
 }
 
+// form of head_decode_kernel the last ey_head_decode* on this thread launched (see ey_head_decode_last_variant); 0 = none
+static thread_local int g_hd_variant = 0;
+extern "C" int ey_head_decode_last_variant(void) { return g_hd_variant; }
+
 static int hd_pad(int elems, int es) {  // row stride (elements): 16-byte aligned, odd number of 16-byte units
   int units = (elems * es + 15) / 16;
   if (!(units & 1)) ++units;
@@ -208,6 +212,7 @@ static int hd_pad(int elems, int es) {  // row stride (elements): 16-byte aligne
 static int head_decode_impl(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box, const int* box_cstride,
                             const void* const* cls, const int* cls_cstride, int nc, const float* const* q_w1, const float* const* q_b1,
                             const float* const* q_w2, const float* const* q_b2, int q_hidden, float* pred, int A_total, const int* a_off, HdNms nm, ey_stream_t stream) {
+  g_hd_variant = 0;
   EY_CHECK((pred || nm.keys) && H && W && stride && box && cls && box_cstride && cls_cstride && a_off, "head_decode: null pointer");
   EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "head_decode: bad dtype");
   EY_CHECK(nlevels >= 1 && nlevels <= HD_MAXL, "head_decode: %d levels (1..%d)", nlevels, HD_MAXL);
@@ -238,13 +243,16 @@ static int head_decode_impl(int dtype, int B, int nlevels, const int* H, const i
   EY_CHECK(lds <= 160 * 1024, "head_decode: nc=%d needs %zu B of LDS", nc, lds);
   dim3 grid((unsigned)nblk);
   hipStream_t st = (hipStream_t)stream;
+  const int variant = (vec ? EY_HD_VEC : EY_HD_SCALAR) + (quality ? EY_HD_QUALITY : 0) + (nm.keys ? EY_HD_NMS : 0);
   if (dtype == EY_F16) {
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)head_decode_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return ey_set_error(EY_ELAUNCH, "head_decode: cannot reserve %zu B of LDS", lds);
+    g_hd_variant = variant;
     hipLaunchKernelGGL(head_decode_kernel<f16>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, nm);
   } else {
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)head_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return ey_set_error(EY_ELAUNCH, "head_decode: cannot reserve %zu B of LDS", lds);
+    g_hd_variant = variant;
     hipLaunchKernelGGL(head_decode_kernel<float>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, nm);
   }
   EY_LAUNCH_CHECK("ey_head_decode");

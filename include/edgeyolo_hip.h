@@ -269,6 +269,13 @@ int ey_linear_attention(int dtype, int B, int N, int C, int heads, const void* q
 int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, int hd, float scale, const void* qkv,
                          int qkv_cstride, void* y, int y_cstride, ey_stream_t stream);
 
+/* Kernel the last ey_linear_attention / ey_softmax_attention on this thread launched (tests); 0 = nothing launched.
+ * Linear: EY_ATTN_LIN_F32 / _F16 (linattn_kernel<T>, fp32 VALU), EY_ATTN_LIN_MFMA (linattn_mfma_kernel).
+ * Softmax VALU: EY_ATTN_SOFT_VALU + 4 (f16) + 2 (K staged in LDS: K_LDS) + 1 (nsplit == 1: one query block per (image, head)).
+ * Softmax MFMA: EY_ATTN_SOFT_MFMA + NKS (softattn_mfma_kernel<NKS>, NKS = 4, 8, 10, 13). */
+enum { EY_ATTN_LIN_F32 = 101, EY_ATTN_LIN_F16 = 102, EY_ATTN_LIN_MFMA = 103, EY_ATTN_SOFT_VALU = 200, EY_ATTN_SOFT_MFMA = 300 };
+int ey_attention_last_variant(void);
+
 /* ---- K9+K10: DGQP quality + DFL expectation + anchor decode + score modulation for ONE pyramid level.
  * Detect._inference (head.py:117-148), DFL (block.py:87-90), make_anchors/dist2bbox (utils/tal.py:333-357),
  * GF2Detect._compute_quality_from_logits / _inference_with_quality (head.py:227-243,301-345).
@@ -319,6 +326,12 @@ int ey_head_decode_levels_xyxy(int dtype, int B, int nlevels, const int* H, cons
 size_t ey_e2e_topk_workspace_bytes(int B, int nc, int A);
 int ey_e2e_topk(int B, int nc, int A, const float* pred_xyxy, int k, float* out_rows, int32_t* out_index, void* workspace,
                 size_t workspace_bytes, ey_stream_t stream);
+
+/* Form of head_decode_kernel the last ey_head_decode* on this thread launched (tests); 0 = nothing launched.
+ * EY_HD_VEC (16-byte staging: nc % 8 == 0, aligned views) or EY_HD_SCALAR, + EY_HD_QUALITY (DGQP quality head) + EY_HD_NMS (fused
+ * NMS candidates). */
+enum { EY_HD_VEC = 1, EY_HD_SCALAR = 2, EY_HD_QUALITY = 10, EY_HD_NMS = 100 };
+int ey_head_decode_last_variant(void);
 
 /* ---- Block programs: a chain of layers on SMALL feature maps (<= 4096 pixels per image; built for the 20x20 part of the network at
  * 640x640: stride-2 Conv -> DSC3K2_Wavelet -> SPPF -> C2PSA_LinearAttention, nn/modules/block.py:204-223,3412-3497,3749-3788; the

@@ -9,6 +9,7 @@ from oracle import model as om
 import synthdata as synth  # noqa: E402
 from gpu_util import _traced, check, load_synth, to_dev  # noqa: E402
 import fp64_ref as R  # noqa: E402
+import fp64_attn_ref as AR  # noqa: E402
 
 DT = [torch.float32, torch.float16]
 
@@ -260,6 +261,15 @@ def test_dsconv_f16_kernel_agrees_with_exact_f32_kernel(M, c, k, h, w):
     torch.testing.assert_close(got, want, rtol=4e-3, atol=4e-3 * scale)
 
 
+def _fp64_check(case, got, y, E, Y, dt):
+    """attention output `got` (logical NCHW) against the fp64 reference rows y (B, N, C) with the bound E + one output rounding."""
+    g = got.permute(0, 2, 3, 1).reshape(y.shape)
+    if dt == torch.float16:
+        R.report(case, "f16", g, y, AR.out_bound(y, E, dt))
+    else:
+        AR.report32(case, "f32", g, y, AR.out_bound(y, E, dt), Y, 4.0)
+
+
 @pytest.mark.parametrize("n_hw", [(20, 20), (13, 9), (40, 40), (7, 5)])
 def test_linear_attention_mfma_agrees_with_f32_kernel(n_hw):
     """f16 mode runs the MFMA linear-attention kernel (head_dim 64), f32 mode the fp32 VALU kernel: same f16-representable qkv ->
@@ -275,6 +285,10 @@ def test_linear_attention_mfma_agrees_with_f32_kernel(n_hw):
     q32.copy_(qkv.float())
     want = _ops.linear_attention(q32, 2).float().cpu()
     torch.testing.assert_close(got, want, rtol=1e-2, atol=2e-3 * float(want.abs().max()))
+    # each kernel against fp64 (tests/fp64_attn_ref.py): the MFMA kernel with its f16 rounding points, the VALU kernel in fp32
+    for t, dt, f16p in ((got, torch.float16, True), (want, torch.float32, False)):
+        y, E, Y = AR.linear_attention_ref(qkv, 2, f16_points=f16p)
+        _fp64_check(f"linear attention {h}x{w}", t, y, E, Y, dt)
 
 
 @pytest.mark.parametrize("h,w,c2", [(64, 64, 16), (96, 128, 16), (70, 200, 32), (33, 40, 48), (640, 640, 16)])
@@ -312,6 +326,9 @@ def test_softmax_attention_mfma_agrees_with_f32_kernel(n_hw):
     q32.copy_(qkv.float())
     want = _ops.softmax_attention(q32, 2, 32, 64, 32 ** -0.5).float().cpu()
     torch.testing.assert_close(got, want, rtol=1e-2, atol=3e-3 * float(want.abs().max()))
+    for t, dt, f16p in ((got, torch.float16, True), (want, torch.float32, False)):
+        y, E, Y = AR.softmax_attention_ref(qkv, 2, 32, 64, 32 ** -0.5, f16_points=f16p)
+        _fp64_check(f"softmax attention {h}x{w}", t, y, E, Y, dt)
 
 
 @pytest.mark.parametrize("cin,cout,h,w", [(80, 80, 40, 40), (96, 80, 23, 17), (72, 68, 20, 20), (80, 80, 80, 80)])
