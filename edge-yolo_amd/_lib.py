@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libedgeyolo_hip.so")
 
 F16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
+ATTN_AREA_F32, ATTN_AREA_F16, ATTN_AREA_MFMA = 401, 402, 403  # ey_attention_last_variant of ey_area_attention
 
 
 class HipLibraryError(RuntimeError):
@@ -91,6 +92,7 @@ SIGNATURES = {
     "ey_wavelet_z2": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, C.c_long, _vp, _vp, _vp, _i, _vp]),
     "ey_sppf_pool": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_copy_nhwc": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_scale_add_channels": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_nchw_to_nhwc": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ey_nhwc_to_nchw": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ey_letterbox": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -99,6 +101,7 @@ SIGNATURES = {
     "ey_linear_attention": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ey_softmax_attention": (_i, [_i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp]),
     "ey_attention_last_variant": (_i, []),
+    "ey_area_attention": (_i, [_i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

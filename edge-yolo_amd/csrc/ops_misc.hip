@@ -875,3 +875,31 @@ extern "C" int ey_letterbox(int out_dtype, const uint8_t* src_hwc, int src_h, in
   return ey_letterbox_batch(out_dtype, src_hwc, 1, src_h, src_w, src_row_bytes, (long)src_h * src_row_bytes, dst_chw, H, W, new_h, new_w, top, left, pad_value, swap_rb,
                             stream);
 }
+
+// y = x + gamma[c] * t per channel (A2C2f layer scale): the product is rounded (to T) before the add, and never contracted into an FMA
+template <typename T>
+__global__ __launch_bounds__(256) void scale_add_kernel(long total, int C, const T* __restrict__ x, int xCs, const float* __restrict__ gamma,
+                                                        const T* __restrict__ t, int tCs, T* __restrict__ y, int yCs) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % C);
+  const long m = idx / C;
+  const float p = to_f(from_f<T>(__fmul_rn(gamma[c], to_f(t[m * tCs + c]))));
+  y[m * yCs + c] = from_f<T>(__fadd_rn(to_f(x[m * xCs + c]), p));
+}
+
+extern "C" int ey_scale_add_channels(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const float* gamma, const void* t, int t_cstride,
+                                     void* y, int y_cstride, ey_stream_t stream) {
+  EY_CHECK(x && gamma && t && y, "scale_add_channels: null pointer");
+  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "scale_add_channels: bad dtype");
+  EY_CHECK(B > 0 && H > 0 && W > 0 && C > 0 && x_cstride >= C && t_cstride >= C && y_cstride >= C, "scale_add_channels: bad extent");
+  const long total = (long)B * H * W * C;
+  dim3 grid((unsigned)((total + 255) / 256));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == EY_F16)
+    hipLaunchKernelGGL(scale_add_kernel<f16>, grid, dim3(256), 0, st, total, C, (const f16*)x, x_cstride, gamma, (const f16*)t, t_cstride, (f16*)y, y_cstride);
+  else
+    hipLaunchKernelGGL(scale_add_kernel<float>, grid, dim3(256), 0, st, total, C, (const float*)x, x_cstride, gamma, (const float*)t, t_cstride, (float*)y, y_cstride);
+  EY_LAUNCH_CHECK("ey_scale_add_channels");
+  return EY_OK;
+}

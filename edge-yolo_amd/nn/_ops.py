@@ -699,6 +699,46 @@ def softmax_attention(qkv, heads, kd, hd, scale, out=None):
     return out
 
 
+def area_attention(q, k, v, heads, area, scale, out=None):
+    """Area attention core (ey_area_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim -> (B,C,H,W).  The H*W tokens of an
+    image, row-major, are cut into `area` equal runs attended separately; N % area != 0 is refused like the reference's reshape."""
+    L.require_device(q, "area_attention")
+    _no_block("area attention")
+    q, k, v = L.as_nhwc(q), L.as_nhwc(k), L.as_nhwc(v)
+    B, c, H, W = q.shape
+    N = H * W
+    if N % area:
+        raise ValueError(f"area_attention: {H}x{W} = {N} tokens do not split into {area} equal areas")
+    if c % heads or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"area_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
+    if out is None:
+        out = L.empty_nhwc(B, c, H, W, q.dtype, q.device)
+    hd = c // heads
+    rec = _tr("area_attn_kernel", _nb(q, k, v, out), 4.0 * B * heads * N * (N // area) * hd, note=f"{H}x{W} area{area} h{heads}")
+    with rec:
+        L.check(L.lib().ey_area_attention(L.dtype_code(q.dtype), B, N, area, heads, hd, float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(),
+                                          L.cstride(k), v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream()), "ey_area_attention")
+        if TRACE is not None and L.lib().ey_attention_last_variant() == L.ATTN_AREA_MFMA:
+            rec.kernel = "area_attn_mfma_kernel"
+    return out
+
+
+def scale_add_channels(x, gamma, t, out=None):
+    """out = x + gamma[c] * t (per-channel layer scale + residual, one HIP launch); gamma: device fp32 (C,)."""
+    L.require_device(t, "scale_add_channels")
+    _no_block("layer scale")
+    x, t = L.as_nhwc(x), L.as_nhwc(t)
+    B, c, H, W = t.shape
+    if tuple(x.shape) != (B, c, H, W) or gamma.numel() != c or gamma.dtype != torch.float32:
+        raise ValueError(f"scale_add_channels: x {tuple(x.shape)}, t {tuple(t.shape)}, gamma {tuple(gamma.shape)} {gamma.dtype}")
+    if out is None:
+        out = L.empty_nhwc(B, c, H, W, t.dtype, t.device)
+    with _tr("scale_add_kernel", _nb(x, t, out)):
+        L.check(L.lib().ey_scale_add_channels(L.dtype_code(t.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), gamma.data_ptr(), t.data_ptr(),
+                                              L.cstride(t), out.data_ptr(), L.cstride(out), L.stream()), "ey_scale_add_channels")
+    return out
+
+
 def head_decode(box, cls, stride, q, pred, a_off):
     """One pyramid level of the fused DGQP + DFL + decode; q = (w1[hid,20], b1, w2[hid], b2) fp32 device tensors or None."""
     L.require_device(box, "head_decode")

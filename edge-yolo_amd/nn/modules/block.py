@@ -14,7 +14,7 @@ from .. import _ops as ops
 from ... import _lib as L
 
 __all__ = ("DFL", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
-           "PSABlock_LinearAttention", "C2PSA_LinearAttention", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet")
+           "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet")
 
 
 def _slot(buf, i, c):
@@ -331,6 +331,109 @@ class C2PSA_LinearAttention(_Chains):
         if res is None:  # (not block-executable: the same tail, one launch per conv)
             return tail(y, t)[0]
         return res[0]
+
+
+# ----------------------------------------------------------------------------------------------- area attention (YOLOv12)
+class AAttn(_Packed):
+    """Area attention (reference block.py:1272-1356): y = proj(attn(q, k, v) + pe(v)).  qk holds [q: heads*32 | k: heads*32]; the H*W
+    tokens are cut into `area` contiguous row-major runs attended separately (ey_area_attention).  qk and v run as one stacked 1x1 conv,
+    and proj reads the virtual concat [attn | pe(v)] with its weight repeated (one launch, no add kernel)."""
+
+    def __init__(self, dim, num_heads, area=1):
+        super().__init__()
+        self.area = area
+        self.num_heads = num_heads
+        self.head_dim = head_dim = dim // num_heads
+        all_head_dim = head_dim * self.num_heads
+        self.qk = Conv(dim, all_head_dim * 2, 1, act=False)
+        self.v = Conv(dim, all_head_dim, 1, act=False)
+        self.proj = Conv(all_head_dim, dim, 1, act=False)
+        self.pe = Conv(all_head_dim, dim, 5, 1, 2, g=dim, act=False)
+
+    def _qkv(self):
+        (w1, b1), (w2, b2) = self.qk.folded(), self.v.folded()
+        return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
+
+    def _proj2(self):
+        w, b = self.proj.folded()
+        return torch.cat((w, w), 1), b
+
+    def forward(self, x, out=None, res=None):
+        B, _, H, W = x.shape
+        if (H * W) % self.area:  # the reference's reshape to (B*area, N/area, C) fails here too
+            raise ValueError(f"AAttn: {H}x{W} = {H * W} tokens do not split into {self.area} equal areas")
+        x = L.as_nhwc(ops.as_tensor(x))
+        c = self.num_heads * self.head_dim
+        qkv = ops.conv2d(self, [x], self._qkv, 1, 1, 0, L.ACT_NONE, tag="qkv")  # [q | k | v]
+        v = qkv[:, 2 * c:]
+        p = self.pe(v)
+        a = ops.area_attention(qkv[:, :c], qkv[:, c:2 * c], v, self.num_heads, self.area, self.head_dim ** -0.5)
+        return ops.conv2d(self, [a, p], self._proj2, 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj2")
+
+
+class ABlock(nn.Module):
+    """x + AAttn(x); x + mlp(x) (reference block.py:1359-1406)."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=1.2, area=1):
+        super().__init__()
+        self.attn = AAttn(dim, num_heads=num_heads, area=area)
+        mlp_hidden_dim = int(dim * mlp_ratio)
+        self.mlp = nn.Sequential(Conv(dim, mlp_hidden_dim, 1), Conv(mlp_hidden_dim, dim, 1, act=False))
+        self.apply(self._init_weights)
+
+    def _init_weights(self, m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.trunc_normal_(m.weight, std=0.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x, out=None):
+        x = self.attn(x, res=x)
+        h = self.mlp[0](x)
+        if h.shape[1] % 8 == 0:
+            return self.mlp[1](h, out=out, res=x)
+        # a hidden width off the MFMA conv's 8-channel granularity (the default mlp_ratio 1.2 at 64 channels; the YAMLs use 2.0 / 1.5)
+        # takes the direct conv, which has no residual epilogue: the add is the layer-scale kernel with gamma = 1 (exact)
+        d = self.__dict__.setdefault("_ones", {})
+        key = (h.device, x.shape[1])
+        if key not in d:
+            d[key] = torch.ones(x.shape[1], device=h.device)
+        return ops.scale_add_channels(x, d[key], self.mlp[1](h), out=out)
+
+
+class A2C2f(_Packed):
+    """R-ELAN (reference block.py:1409-1465): cv1 -> n x (2 ABlocks | C3k) chained -> cv2 over the concat of all of them, written
+    straight into slices of one buffer; with a2 and residual, x + gamma * cv2(...) as one per-channel HIP launch."""
+
+    def __init__(self, c1, c2, n=1, a2=True, area=1, residual=False, mlp_ratio=2.0, e=0.5, g=1, shortcut=True):
+        super().__init__()
+        c_ = int(c2 * e)
+        assert c_ % 32 == 0, "Dimension of ABlock be a multiple of 32."
+        num_heads = c_ // 32
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv((1 + n) * c_, c2, 1)
+        init_values = 0.01
+        self.gamma = nn.Parameter(init_values * torch.ones((c2)), requires_grad=True) if a2 and residual else None
+        self.m = nn.ModuleList(
+            nn.Sequential(*(ABlock(c_, num_heads, mlp_ratio, area) for _ in range(2))) if a2 else C3k(c_, c_, 2, shortcut, g) for _ in range(n))
+
+    def forward(self, x, out=None):
+        B, _, H, W = x.shape  # x may be a VirtualCat (upsample+concat folded into cv1)
+        c, n = self.cv1.conv.out_channels, len(self.m)
+        buf = L.empty_nhwc(B, (1 + n) * c, H, W, x.dtype, x.device)
+        self.cv1(x, out=buf[:, :c])
+        for i, m in enumerate(self.m):
+            src, dst = _slot(buf, i, c), _slot(buf, 1 + i, c)
+            if isinstance(m, nn.Sequential):
+                for j, blk in enumerate(m):
+                    src = blk(src, out=dst if j == len(m) - 1 else None)
+            else:
+                m(src, out=dst)
+        if self.gamma is None:
+            return self.cv2(buf, out=out)
+        x = ops.as_tensor(x)
+        gamma = self._packed(("gamma", x.dtype, x.device), lambda: self.gamma.detach().to(x.dtype).float().to(x.device).contiguous())
+        return ops.scale_add_channels(x, gamma, self.cv2(buf), out=out)
 
 
 # ----------------------------------------------------------------------------------------------- DS / wavelet

@@ -109,7 +109,25 @@ class Conv(_Packed):
             return ops.conv2d(self, [x], self.folded, k, s, p, act, out=out, res=res)
         if g == c.in_channels == c.out_channels and s == 1 and k in (3, 5, 7) and p == k // 2 and res is None:
             return ops.dwconv(self, x, self.folded, k, act, out=out)
+        cg, og = c.in_channels // g, c.out_channels // g
+        if res is None and cg % 8 == 0 and og % 8 == 0:
+            # grouped conv on the MFMA implicit GEMM: one launch, group i reads input channels [i*cg, (i+1)*cg) with weight set i and
+            # writes output channels [i*og, (i+1)*og)
+            x = L.as_nhwc(ops.as_tensor(x))
+            if ops.igemm_ok([x[:, :cg]], k, s, p):
+                B, _, H, W = x.shape
+                Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+                if out is None:
+                    out = L.empty_nhwc(B, c.out_channels, Ho, Wo, x.dtype, x.device)
+                ops.conv2d(self, [x[:, :cg]], self._group_sets, k, s, p, act, out=out[:, :og], ngroup=g, src_gstride=cg, y_gstride=og, w_sets=g,
+                           tag="grp")
+                return out
         return ops.conv2d_direct(self, x, self.folded, k, s, p, g, act, out=out, res=res)
+
+    def _group_sets(self):
+        w, b = self.folded()
+        og = w.shape[0] // self.conv.groups
+        return [(w[i * og:(i + 1) * og], b[i * og:(i + 1) * og]) for i in range(self.conv.groups)]
 
     forward_fuse = forward
 

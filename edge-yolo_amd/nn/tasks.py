@@ -13,7 +13,7 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2_Wavelet, DSConv, DWConv, Detect, E2EDetect, GF2Detect,
+from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2_Wavelet, DSConv, DWConv, Detect, E2EDetect, GF2Detect,
                       GFLHeadv2_uniH, SPPF, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
@@ -21,8 +21,8 @@ from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv}
-_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention}
+_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f}
+_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f}
 _HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH}
 
 
@@ -109,6 +109,11 @@ def parse_model(d, ch, verbose=False):
                 legacy = False
                 if scale in "lx":
                     args[3] = True
+            if m is A2C2f:
+                legacy = False
+                if scale in "lx":  # residual=True, mlp_ratio=1.5 (reference tasks.py:1073-1077)
+                    args.append(True)
+                    args.append(1.5)
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m in _HEADS:
@@ -351,7 +356,7 @@ class DetectionModel(BaseModel):
                 consumers.setdefault((m.i + j) if j < 0 else j, []).append(m)
 
         def takes_virtual(m):
-            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention)):
+            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f)):
                 return True
             return isinstance(m, Conv) and m.conv.kernel_size == (1, 1) and m.conv.groups == 1
 

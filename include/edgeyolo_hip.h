@@ -231,6 +231,11 @@ int ey_wavelet_z2(int dtype, int B, int H, int W, int C, int k, const float* tap
 int ey_sppf_pool(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y1, void* y2, void* y3,
                  int y_cstride, ey_stream_t stream);
 
+/* Per-channel layer scale with residual (A2C2f, reference block.py:1459-1463):  y[p][c] = x[p][c] + gamma[c] * t[p][c], the product
+ * rounded to the activation dtype before the add as the reference does.  gamma: DEVICE fp32 [C].  y may alias t or x. */
+int ey_scale_add_channels(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const float* gamma, const void* t, int t_cstride,
+                          void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
@@ -269,11 +274,23 @@ int ey_linear_attention(int dtype, int B, int N, int C, int heads, const void* q
 int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, int hd, float scale, const void* qkv,
                          int qkv_cstride, void* y, int y_cstride, ey_stream_t stream);
 
-/* Kernel the last ey_linear_attention / ey_softmax_attention on this thread launched (tests); 0 = nothing launched.
+/* ---- K8c: area attention core (AAttn.forward of YOLOv12's A2C2f, reference block.py:1313-1356).  q, k, v, y are [B,N,*] views
+ * with their own channel strides; head h owns channels h*hd..h*hd+hd-1 of each (the qk conv's order [q: heads*hd | k: heads*hd],
+ * block.py:1318-1319, 1332).  The N = H*W tokens of an image, in row-major order, are cut into `area` contiguous runs of N/area tokens
+ * (block.py:1324-1327) and each (run, head) is attended separately:  y = softmax(q k^T * scale) v.  EY_EINVAL (nothing launched)
+ * when N % area != 0, as the reference's reshape fails there.  f16 with hd = 32 (the only head_dim the YAMLs produce), 16-byte
+ * aligned q/k/v and 8-byte aligned y: MFMA flash kernel with online softmax, any N/area >= 1.  Otherwise (fp32, other hd <= 64):
+ * VALU kernel in fp32 (exact fp32 arithmetic for fp32 I/O), N/area <= 10176 (LDS).  Writes y only. */
+int ey_area_attention(int dtype, int B, int N, int area, int heads, int hd, float scale, const void* q, int q_cstride, const void* k,
+                      int k_cstride, const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream);
+
+/* Kernel the last ey_linear_attention / ey_softmax_attention / ey_area_attention on this thread launched (tests); 0 = nothing launched.
  * Linear: EY_ATTN_LIN_F32 / _F16 (linattn_kernel<T>, fp32 VALU), EY_ATTN_LIN_MFMA (linattn_mfma_kernel).
  * Softmax VALU: EY_ATTN_SOFT_VALU + 4 (f16) + 2 (K staged in LDS: K_LDS) + 1 (nsplit == 1: one query block per (image, head)).
- * Softmax MFMA: EY_ATTN_SOFT_MFMA + NKS (softattn_mfma_kernel<NKS>, NKS = 4, 8, 10, 13). */
-enum { EY_ATTN_LIN_F32 = 101, EY_ATTN_LIN_F16 = 102, EY_ATTN_LIN_MFMA = 103, EY_ATTN_SOFT_VALU = 200, EY_ATTN_SOFT_MFMA = 300 };
+ * Softmax MFMA: EY_ATTN_SOFT_MFMA + NKS (softattn_mfma_kernel<NKS>, NKS = 4, 8, 10, 13).
+ * Area: EY_ATTN_AREA_F32 / _F16 (area_attn_kernel<T>, fp32 VALU), EY_ATTN_AREA_MFMA (area_attn_mfma_kernel). */
+enum { EY_ATTN_LIN_F32 = 101, EY_ATTN_LIN_F16 = 102, EY_ATTN_LIN_MFMA = 103, EY_ATTN_SOFT_VALU = 200, EY_ATTN_SOFT_MFMA = 300,
+       EY_ATTN_AREA_F32 = 401, EY_ATTN_AREA_F16 = 402, EY_ATTN_AREA_MFMA = 403 };
 int ey_attention_last_variant(void);
 
 /* ---- K9+K10: DGQP quality + DFL expectation + anchor decode + score modulation for ONE pyramid level.
