@@ -93,6 +93,10 @@ SIGNATURES = {
     "ey_sppf_pool": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_copy_nhwc": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ey_scale_add_channels": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "ey_avgpool2": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_dwconv_s2": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ey_hypergraph_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ey_hypergraph_conv": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ey_nchw_to_nhwc": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ey_nhwc_to_nchw": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ey_letterbox": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

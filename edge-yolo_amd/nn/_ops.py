@@ -739,6 +739,91 @@ def scale_add_channels(x, gamma, t, out=None):
     return out
 
 
+def avgpool2(x, out=None):
+    """AvgPool2d(2) with floor semantics (ey_avgpool2): (B,C,H,W) -> (B,C,H//2,W//2); out= may be a channel slot of a concat buffer."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "avgpool2")
+    _no_block("average pool")
+    B, c, H, W = x.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"avgpool2: a {H}x{W} map has no 2x2 window")
+    if out is None:
+        out = L.empty_nhwc(B, c, H // 2, W // 2, x.dtype, x.device)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H // 2, W // 2) or out.dtype != x.dtype:
+        raise ValueError(f"avgpool2: out= must be an NHWC view of shape {(B, c, H // 2, W // 2)} {x.dtype}")
+    with _tr("avgpool2_kernel", _nb(x, out), 4.0 * out.numel(), note=f"C{c} {H}x{W}"):
+        L.check(L.lib().ey_avgpool2(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()),
+                "ey_avgpool2")
+    return out
+
+
+def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
+    """Depthwise kxk, stride 2, pad k//2 (ey_dwconv_s2): the depthwise half of DSConv(c, c, k, 2)."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "dwconv_s2")
+    _no_block("stride-2 depthwise conv")
+    B, c, H, W = x.shape
+
+    def build():
+        w, b = folded_fn()  # (C,1,k,k)
+        wk = w.view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)  # [k][k][C]
+        return wk, (b.to(x.device).float().contiguous() if b is not None else None)
+
+    wk, bias = mod._packed(_dev_key(x, tag), build)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device)
+    with _tr(f"dwconv_s2_kernel<{k}>", _nb(x, out), 2.0 * B * Ho * Wo * c * k * k, note=f"C{c} {H}x{W}"):
+        L.check(L.lib().ey_dwconv_s2(L.dtype_code(x.dtype), B, H, W, c, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(),
+                                     bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out), L.stream()), "ey_dwconv_s2")
+    return out
+
+
+HG_CONTEXT = {"both": 0, "mean": 1, "max": 2}
+HG_LAUNCHES = 5  # kernels behind one ey_hypergraph_conv call
+
+
+def hypergraph_conv(mod, x, out=None):
+    """AdaHGConv on the H*W tokens of each image of x (B,D,H,W) (ey_hypergraph_conv) -> (B,D,H,W).  mod: the AdaHGConv (weights are
+    packed once per dtype / device; the workspace is cached per shape, so a captured graph replays with no host work)."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "hypergraph_conv")
+    _no_block("hypergraph convolution")
+    B, D, H, W = x.shape
+    N = H * W
+    g = mod.edge_generator
+    E = g.num_hyperedges
+    if D != g.prototype_base.shape[1]:
+        raise ValueError(f"hypergraph_conv: input has {D} channels, the module {g.prototype_base.shape[1]}")
+    half = x.dtype == torch.float16
+
+    def build():
+        f = lambda t: t.detach().float().to(x.device).contiguous()  # noqa: E731
+        nw = mod.node_proj[0].weight.detach().float()
+        if half:
+            kp = (D + 31) // 32 * 32
+            wn = torch.zeros((D, kp), dtype=torch.float16)
+            wn[:, :D] = nw.cpu().half()
+            wn = wn.to(x.device)
+        else:
+            wn = f(nw.t())
+        return (f(g.prototype_base), f(g.context_net.weight.t()), f(g.context_net.bias), f(g.pre_head_proj.weight), f(g.pre_head_proj.bias),
+                f(mod.edge_proj[0].weight.t()), f(mod.edge_proj[0].bias), wn, f(mod.node_proj[0].bias))
+
+    w = mod._packed(_dev_key(x, "hypergraph"), build)
+    nbytes = L.lib().ey_hypergraph_workspace_bytes(B, N, D, E)
+    ws = mod._packed(("hg_ws", B, N, D, x.device), lambda: torch.empty(nbytes, dtype=torch.uint8, device=x.device))
+    if out is None:
+        out = L.empty_nhwc(B, D, H, W, x.dtype, x.device)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, D, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"hypergraph_conv: out= must be an NHWC view of shape {(B, D, H, W)} {x.dtype}")
+    flops = 2.0 * B * N * D * (E * 3 + D) + 2.0 * B * E * D * (D * 2 + (2 if g.context == "both" else 1) * D)
+    with _tr("hypergraph_kernels", _nb(x, x, x, out) + 8.0 * B * N * E, flops, note=f"{H}x{W} D{D} E{E}", kernels=HG_LAUNCHES):
+        L.check(L.lib().ey_hypergraph_conv(L.dtype_code(x.dtype), B, N, D, E, g.num_heads, HG_CONTEXT[g.context], x.data_ptr(), L.cstride(x), out.data_ptr(),
+                                           L.cstride(out), *[t.data_ptr() for t in w], ws.data_ptr(), ws.numel(), L.stream()), "ey_hypergraph_conv")
+    return out
+
+
 def head_decode(box, cls, stride, q, pred, a_off):
     """One pyramid level of the fused DGQP + DFL + decode; q = (w1[hid,20], b1, w2[hid], b2) fp32 device tensors or None."""
     L.require_device(box, "head_decode")

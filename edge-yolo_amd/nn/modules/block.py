@@ -14,7 +14,8 @@ from .. import _ops as ops
 from ... import _lib as L
 
 __all__ = ("DFL", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
-           "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet")
+           "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
+           "DSC3K2", "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
 
 
 def _slot(buf, i, c):
@@ -649,3 +650,201 @@ class DSC3K2_Wavelet(nn.Module):
             y = ops.pw_conv3s2(self.cv2, tail, [t[:, :c], buf])
             return y if y is not None else tail(ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, L.ACT_SILU))
         return ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, L.ACT_SILU, out=out)
+
+
+# ----------------------------------------------------------------------------------------------- YOLOv13: HyperACE / FullPAD
+class DSC3K2(C2f):
+    """reference block.py:1564-1638: C2f whose blocks are DSC3k(c, c, n=2, e=1.0) (dsc3k) or DSBottleneck(c, c, e=1.0, k1, k2, d2)."""
+
+    def __init__(self, c1, c2, n=1, dsc3k=False, e=0.5, g=1, shortcut=True, k1=3, k2=7, d2=1):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        if dsc3k:
+            self.m = nn.ModuleList(DSC3k(self.c, self.c, n=2, shortcut=shortcut, g=g, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n))
+        else:
+            self.m = nn.ModuleList(DSBottleneck(self.c, self.c, shortcut=shortcut, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n))
+
+
+class AdaHyperedgeGen(nn.Module):
+    """reference block.py:1640-1716: parameter holder.  The participation matrix A is computed inside ey_hypergraph_conv (AdaHGConv)."""
+
+    def __init__(self, node_dim, num_hyperedges, num_heads=4, dropout=0.1, context="both"):
+        super().__init__()
+        self.num_heads = num_heads
+        self.num_hyperedges = num_hyperedges
+        self.head_dim = node_dim // num_heads
+        self.context = context
+        self.prototype_base = nn.Parameter(torch.Tensor(num_hyperedges, node_dim))
+        nn.init.xavier_uniform_(self.prototype_base)
+        if context in ("mean", "max"):
+            self.context_net = nn.Linear(node_dim, num_hyperedges * node_dim)
+        elif context == "both":
+            self.context_net = nn.Linear(2 * node_dim, num_hyperedges * node_dim)
+        else:
+            raise ValueError(f"Unsupported context '{context}'. Expected one of: 'mean', 'max', 'both'.")
+        self.pre_head_proj = nn.Linear(node_dim, node_dim)
+        self.dropout = nn.Dropout(dropout)  # identity in eval
+        self.scaling = math.sqrt(self.head_dim)
+
+    def forward(self, X):
+        raise NotImplementedError("AdaHyperedgeGen runs inside AdaHGConv (ey_hypergraph_conv); A is never materialised")
+
+
+class AdaHGConv(_Packed):
+    """reference block.py:1719-1774: Y = GELU(node_proj(A . GELU(edge_proj(A^T X)))) + X, A = softmax over all tokens of the hyperedge
+    logits -- one ey_hypergraph_conv call (five launches).  X: (B,D,H,W) NHWC (a token per pixel) or the reference's (B,N,D)."""
+
+    def __init__(self, embed_dim, num_hyperedges=16, num_heads=4, dropout=0.1, context="both"):
+        super().__init__()
+        self.edge_generator = AdaHyperedgeGen(embed_dim, num_hyperedges, num_heads, dropout, context)
+        self.edge_proj = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.GELU())
+        self.node_proj = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.GELU())
+
+    def forward(self, X, out=None):
+        if torch.is_tensor(X) and X.dim() == 3:  # (B,N,D) contiguous == an NHWC (B,D,1,N) map
+            y = ops.hypergraph_conv(self, X.permute(0, 2, 1).unsqueeze(2))
+            return y.squeeze(2).permute(0, 2, 1)
+        return ops.hypergraph_conv(self, X, out=out)
+
+
+class AdaHGComputation(nn.Module):
+    """reference block.py:1777-1815: the (B,C,H,W) <-> tokens reshapes are free in NHWC."""
+
+    def __init__(self, embed_dim, num_hyperedges=16, num_heads=8, dropout=0.1, context="both"):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.hgnn = AdaHGConv(embed_dim=embed_dim, num_hyperedges=num_hyperedges, num_heads=num_heads, dropout=dropout, context=context)
+
+    def forward(self, x, out=None):
+        return self.hgnn(x, out=out)
+
+
+class C3AH(_Packed):
+    """reference block.py:1818-1851: cv3(cat(m(cv1(x)), cv2(x))).  cv1 | cv2 run as one stacked 1x1 conv and cv3 reads the two halves as
+    a virtual concat."""
+
+    def __init__(self, c1, c2, e=1.0, num_hyperedges=8, context="both"):
+        super().__init__()
+        c_ = int(c2 * e)
+        assert c_ % 16 == 0, "Dimension of AdaHGComputation should be a multiple of 16."
+        num_heads = c_ // 16
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.m = AdaHGComputation(embed_dim=c_, num_hyperedges=num_hyperedges, num_heads=num_heads, dropout=0.1, context=context)
+        self.cv3 = Conv(2 * c_, c2, 1)
+
+    def _cv12(self):
+        (w1, b1), (w2, b2) = self.cv1.folded(), self.cv2.folded()
+        return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
+
+    def forward(self, x, out=None, cv12=None):
+        """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (HyperACE stacks both branches)."""
+        from .conv import _act_code
+        c_ = self.cv1.conv.out_channels
+        if cv12 is None:
+            cv12 = ops.conv2d(self, [L.as_nhwc(ops.as_tensor(x))], self._cv12, 1, 1, 0, _act_code(self.cv1.act), tag="cv12")
+        h = self.m(cv12[:, :c_])
+        return ops.conv2d(self.cv3, [h, cv12[:, c_:]], self.cv3.folded, 1, 1, 0, _act_code(self.cv3.act), out=out)
+
+
+class FuseModule(nn.Module):
+    """reference block.py:1854-1892: conv_out(cat(avgpool2(x0), x1, up2x(x2))).  The pooled x0 and a copy of x1 share one buffer, which
+    conv_out reads together with x2 through its nearest x2 upsample (a two-source 1x1 conv): the concat is never written."""
+
+    def __init__(self, c_in, channel_adjust):
+        super(FuseModule, self).__init__()
+        self.downsample = nn.AvgPool2d(kernel_size=2)
+        self.upsample = nn.Upsample(scale_factor=2, mode="nearest")
+        if channel_adjust:
+            self.conv_out = Conv(4 * c_in, c_in, 1)
+        else:
+            self.conv_out = Conv(3 * c_in, c_in, 1)
+
+    def forward(self, x, out=None):
+        from .conv import _act_code
+        x0, x1, x2 = (L.as_nhwc(ops.as_tensor(t)) for t in x)
+        B, c1, H, W = x1.shape
+        c0 = x0.shape[1]
+        if (x0.shape[2] // 2, x0.shape[3] // 2) != (H, W) or (2 * x2.shape[2], 2 * x2.shape[3]) != (H, W):
+            raise ValueError(f"FuseModule: inputs {tuple(x0.shape)}, {tuple(x1.shape)}, {tuple(x2.shape)} do not align at {H}x{W}")
+        buf = L.empty_nhwc(B, c0 + c1, H, W, x1.dtype, x1.device)
+        ops.avgpool2(x0, out=buf[:, :c0])
+        ops.copy_slice(x1, buf[:, c0:])
+        c = self.conv_out
+        return ops.conv2d(c, [buf, x2], c.folded, 1, 1, 0, _act_code(c.act), out=out, up=[0, 1])
+
+
+class HyperACE(_Packed):
+    """reference block.py:1895-1949: fuse -> cv1 -> [y0, C3AH_1(y1), y2, m chained from y2, C3AH_2(y1)] -> cv2.  Every part is written
+    into its slot of one buffer; the four 1x1 convs of the two C3AH branches (all reading y1) run as one stacked launch."""
+
+    def __init__(self, c1, c2, n=1, num_hyperedges=8, dsc3k=True, shortcut=False, e1=0.5, e2=1, context="both", channel_adjust=True):
+        super().__init__()
+        self.c = int(c2 * e1)
+        self.cv1 = Conv(c1, 3 * self.c, 1, 1)
+        self.cv2 = Conv((4 + n) * self.c, c2, 1)
+        self.m = nn.ModuleList(
+            DSC3k(self.c, self.c, 2, shortcut, k1=3, k2=7) if dsc3k else DSBottleneck(self.c, self.c, shortcut=shortcut) for _ in range(n))
+        self.fuse = FuseModule(c1, channel_adjust)
+        self.branch1 = C3AH(self.c, self.c, e2, num_hyperedges, context)
+        self.branch2 = C3AH(self.c, self.c, e2, num_hyperedges, context)
+
+    def _cv1234(self):
+        ws, bs = zip(*(m.folded() for b in (self.branch1, self.branch2) for m in (b.cv1, b.cv2)))
+        return torch.cat(ws, 0), torch.cat(bs, 0)
+
+    def forward(self, X, out=None):
+        from .conv import _act_code
+        x = self.fuse(X)
+        B, _, H, W = x.shape
+        c, n = self.c, len(self.m)
+        buf = L.empty_nhwc(B, (4 + n) * c, H, W, x.dtype, x.device)  # [y0 | out1 | y2 | m_1 .. m_n | out2]
+        self.cv1(x, out=buf[:, :3 * c])
+        b1, b2 = self.branch1, self.branch2
+        acts = {_act_code(m.act) for b in (b1, b2) for m in (b.cv1, b.cv2)}
+        if len(acts) == 1:
+            t = ops.conv2d(self, [_slot(buf, 1, c)], self._cv1234, 1, 1, 0, acts.pop(), tag="cv1234")  # [b1.cv1 | b1.cv2 | b2.cv1 | b2.cv2]
+            h = b1.cv1.conv.out_channels
+            t1, t2 = t[:, :2 * h], t[:, 2 * h:]
+        else:
+            t1 = t2 = None
+        y1 = _slot(buf, 1, c)
+        if t1 is None:
+            t1 = ops.conv2d(b1, [y1], b1._cv12, 1, 1, 0, _act_code(b1.cv1.act), tag="cv12")
+            t2 = ops.conv2d(b2, [y1], b2._cv12, 1, 1, 0, _act_code(b2.cv1.act), tag="cv12")
+        b1(y1, out=_slot(buf, 1, c), cv12=t1)  # y1 is dead once both branches' 1x1 convs have read it
+        b2(y1, out=_slot(buf, 3 + n, c), cv12=t2)
+        for i, m in enumerate(self.m):
+            m(_slot(buf, 2 + i, c), out=_slot(buf, 3 + i, c))
+        return self.cv2(buf, out=out)
+
+
+class DownsampleConv(nn.Module):
+    """reference block.py:1952-1985: channel_adjust(AvgPool2d(2)(x)), a 1x1 Conv c -> 2c or Identity."""
+
+    def __init__(self, in_channels, channel_adjust=True):
+        super().__init__()
+        self.downsample = nn.AvgPool2d(kernel_size=2)
+        if channel_adjust:
+            self.channel_adjust = Conv(in_channels, in_channels * 2, 1)
+        else:
+            self.channel_adjust = nn.Identity()
+
+    def forward(self, x, out=None):
+        if isinstance(self.channel_adjust, Conv):
+            return self.channel_adjust(ops.avgpool2(x), out=out)
+        return ops.avgpool2(x, out=out)
+
+
+class FullPAD_Tunnel(_Packed):
+    """reference block.py:1988-2008: x[0] + gate * x[1] (ey_scale_add_channels with the 0-d gate broadcast, rounded to the activation
+    dtype as the reference's product is)."""
+
+    def __init__(self):
+        super().__init__()
+        self.gate = nn.Parameter(torch.tensor(0.0))
+
+    def forward(self, x, out=None):
+        a, t = (L.as_nhwc(ops.as_tensor(v)) for v in x)
+        C = t.shape[1]
+        gamma = self._packed(("gate", t.dtype, t.device, C), lambda: self.gate.detach().to(t.dtype).float().expand(C).to(t.device).contiguous())
+        return ops.scale_add_channels(a, gamma, t, out=out)

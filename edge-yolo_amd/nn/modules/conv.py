@@ -160,8 +160,13 @@ class DSConv(_Packed):
 
     def forward(self, x, out=None, res=None):
         k, s, d = self.dw.kernel_size[0], self.dw.stride[0], self.dw.dilation[0]
+        if s == 2 and d == 1 and self.dw.padding[0] == k // 2 and k in (3, 5, 7) and self.dw.stride[1] == 2:
+            # DSConv(c, c, k, 2) (yolov13 layers 5 and 7): stride-2 depthwise (rounded to the storage type like the reference's
+            # intermediate tensor), then the pointwise 1x1 + BN + SiLU on the MFMA conv
+            t = ops.dwconv_s2(self, x, self._dw_folded, k, L.ACT_NONE)
+            return ops.conv2d(self, [t], self._pw_folded, 1, 1, 0, L.ACT_SILU, out=out, res=res, tag="pw")
         if s != 1 or d != 1 or self.dw.padding[0] != k // 2:
-            raise NotImplementedError("DSConv with stride/dilation != 1 is outside the EdgeLine-YOLO detection path")
+            raise NotImplementedError("DSConv with dilation != 1 or a stride other than 1 and 2 is outside the detection path")
         y = ops.dsconv(self, x, self._dw_folded, self._pw_folded, k, L.ACT_SILU, out=out, res=res)  # one fused kernel
         if y is not None:
             return y

@@ -13,16 +13,16 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2_Wavelet, DSConv, DWConv, Detect, E2EDetect, GF2Detect,
-                      GFLHeadv2_uniH, SPPF, Upsample)
+from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
+                      E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, SPPF, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f}
-_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f}
+_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2}
+_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2}
 _HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH}
 
 
@@ -74,6 +74,8 @@ def parse_model(d, ch, verbose=False):
     if scales:
         if not scale:
             scale = tuple(scales.keys())[0]
+        if scale not in scales:
+            raise KeyError(f"model scale '{scale}' is not defined in {d.get('yaml_file', 'this YAML')} (scales: {', '.join(scales)})")
         depth, width, max_channels = scales[scale]
     if act:
         Conv.default_act = eval(act)  # noqa: S307  (same YAML contract as the reference, tasks.py:974-975)
@@ -105,7 +107,7 @@ def parse_model(d, ch, verbose=False):
             if m in _REPEAT_MODULES:
                 args.insert(2, n)
                 n = 1
-            if m in {C3k2, DSC3K2_Wavelet}:
+            if m in {C3k2, DSC3K2_Wavelet, DSC3K2}:
                 legacy = False
                 if scale in "lx":
                     args[3] = True
@@ -114,6 +116,28 @@ def parse_model(d, ch, verbose=False):
                 if scale in "lx":  # residual=True, mlp_ratio=1.5 (reference tasks.py:1073-1077)
                     args.append(True)
                     args.append(1.5)
+        elif m is HyperACE:  # reference tasks.py:1106-1118
+            legacy = False
+            c1 = ch[f[1]]
+            c2 = make_divisible(min(args[0], max_channels) * width, 8)
+            he = args[1]
+            if scale in "n":
+                he = int(args[1] * 0.5)
+            elif scale in "x":
+                he = int(args[1] * 1.5)
+            args = [c1, c2, n, he, *args[2:]]
+            n = 1
+            if scale in "lx":  # channel_adjust=False
+                args.append(False)
+        elif m is DownsampleConv:  # reference tasks.py:1119-1125
+            c1 = ch[f]
+            c2 = c1 * 2
+            args = [c1]
+            if scale in "lx":
+                args.append(False)
+                c2 = c1
+        elif m is FullPAD_Tunnel:
+            c2 = ch[f[0]]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m in _HEADS:
@@ -131,6 +155,21 @@ def parse_model(d, ch, verbose=False):
             ch = []
         ch.append(c2)
     return nn.Sequential(*layers), sorted(save)
+
+
+def _layer_down(m, down):
+    """Downsampling factor of layer m's output, given those of the layers before it (`down`)."""
+    f = m.f if isinstance(m.f, int) else m.f[1 if isinstance(m, HyperACE) else 0]  # HyperACE works at its middle input's resolution
+    src = 1.0 if m.i == 0 else (down[f] if f != -1 else down[-1])
+    if isinstance(m, Conv):
+        src *= m.conv.stride[0]
+    elif isinstance(m, DSConv):
+        src *= m.dw.stride[0]
+    elif isinstance(m, DownsampleConv):
+        src *= 2
+    elif isinstance(m, Upsample):
+        src /= 2
+    return src
 
 
 class BaseModel(nn.Module):
@@ -373,12 +412,7 @@ class DetectionModel(BaseModel):
         block programs.  `_down[i]` = downsampling factor of layer i's output; `_block_of[i]` = (lo, hi, down) of the run i lies in."""
         down = []
         for m in self.model:
-            f = m.f if isinstance(m.f, int) else m.f[0]
-            src = 1.0 if m.i == 0 else (down[f] if f != -1 else down[-1])
-            if isinstance(m, Conv):
-                src *= m.conv.stride[0]
-            elif isinstance(m, Upsample):
-                src /= 2
+            src = _layer_down(m, down)
             down.append(src)
         self._down = down
         top = max(down[:-1]) if len(down) > 1 else 0
@@ -399,12 +433,7 @@ class DetectionModel(BaseModel):
     def _graph_strides(self, ch):
         down = []
         for m in self.model:
-            f = m.f if isinstance(m.f, int) else m.f[0]
-            src = 1.0 if (m.i == 0) else (down[f] if f != -1 else down[-1])
-            if isinstance(m, Conv):
-                src *= m.conv.stride[0]
-            elif isinstance(m, Upsample):
-                src /= 2
+            src = _layer_down(m, down)
             if isinstance(m, Detect):
                 return [float(down[j]) for j in m.f]
             down.append(src)

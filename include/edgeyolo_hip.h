@@ -236,6 +236,37 @@ int ey_sppf_pool(int dtype, int B, int H, int W, int C, const void* x, int x_cst
 int ey_scale_add_channels(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const float* gamma, const void* t, int t_cstride,
                           void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- YOLOv13 (HyperACE / FullPAD, reference block.py:1564-2008, conv.py:87-104) --------------------------------------------------------
+ * AvgPool2d(2) (FuseModule.downsample / DownsampleConv.downsample, block.py:1858,1985): y[b,i,j,c] = mean of the 2x2 window at (2i, 2j),
+ * floor semantics (Ho = H/2, Wo = W/2; an odd last row / column is dropped), summed in fp32 in row-major order and rounded once.  x and y
+ * are channel windows of NHWC buffers (y may be a slot of a concat buffer).  H, W >= 2. */
+int ey_avgpool2(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y, int y_cstride, ey_stream_t stream);
+
+/* Depthwise kxk, STRIDE 2, pad k/2 (DSConv(c1, c2, k, s=2).dw, conv.py:94-97; yolov13 layers 5 and 7): Ho = (H-1)/2 + 1.  w: [k][k][C]
+ * in `dtype`; k in {3,5,7}; bias fp32 [C] or NULL; any C.  The 1x1 behind it runs on ey_conv2d.  Stride-1 depthwise is ey_dwconv. */
+int ey_dwconv_s2(int dtype, int B, int H, int W, int C, int k, int act, const void* x, int x_cstride, const void* w_kkc, const float* bias,
+                 void* y, int y_cstride, ey_stream_t stream);
+
+/* Adaptive hypergraph convolution (AdaHGConv.forward, block.py:1765-1774, with AdaHyperedgeGen.forward, block.py:1686-1716) on the
+ * N = H*W tokens of each of B images, x / y [B,N,D] channel windows (no transpose: a token is a pixel).  E hyperedges, `heads` heads
+ * (head_dim = D/heads), context 0 "both" / 1 "mean" / 2 "max".  Y = GELU(node_proj(A . GELU(edge_proj(A^T X)))) + X with A = the softmax
+ * over all N tokens of each hyperedge's logits.  Device weights, all fp32 except node_w:
+ *   proto_base [E][D]; ctx_wT = context_net.weight^T [K][E*D] (K = 2D for "both", else D); ctx_b [E*D];
+ *   pre_w = pre_head_proj.weight [D][D] (as stored: [out][in]); pre_b [D];  edge_wT = edge_proj[0].weight^T [D in][D out]; edge_b [D];
+ *   node_w: f16 -> node_proj[0].weight in f16, [D out][Kp] with Kp = D rounded up to 32 and a zero tail (16-byte aligned); fp32 ->
+ *   node_proj[0].weight^T [D in][D out];  node_b [D].
+ * pre_head_proj is folded per image (logits = (X . P Wp^T' + P . bp) / (sqrt(head_dim) * heads)), so it costs N*D*E, not N*D*D.
+ * Five launches; every reduction has a fixed order: bit-identical run to run.  f16: node_proj on MFMA with fp32
+ * accumulation, softmax statistics and all intermediates in fp32, A.He' rounded to f16 as its operand.  fp32: exact fp32 VALU.
+ * workspace: ey_hypergraph_workspace_bytes(B, N, D, E) bytes, 16-byte aligned; nothing is allocated and the host never waits, so the
+ * call can be captured into a graph.  EY_EINVAL (nothing launched): D not a multiple of 16 in [16, 384], E not in [1, 16], heads not
+ * dividing D, overlapping x / y windows, a short or misaligned workspace. */
+size_t ey_hypergraph_workspace_bytes(int B, int N, int D, int E);
+int ey_hypergraph_conv(int dtype, int B, int N, int D, int E, int heads, int context, const void* x, int x_cstride, void* y, int y_cstride,
+                       const float* proto_base, const float* ctx_wT, const float* ctx_b, const float* pre_w, const float* pre_b,
+                       const float* edge_wT, const float* edge_b, const void* node_w, const float* node_b, void* workspace,
+                       size_t workspace_bytes, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
