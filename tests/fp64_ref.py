@@ -186,10 +186,11 @@ def safe_density(K, cap=400.0):
     return min(1.0, cap / (2.0 * K)) if K > 0 else 1.0
 
 
-def stage(w, b=None, k=1, s=1, p=0, act=ACT_NONE, dw=False, addz=None, out_scale=1.0, res=None):
+def stage(w, b=None, k=1, s=1, p=0, act=ACT_NONE, dw=False, addz=None, out_scale=1.0, res=None, K=None):
     """One conv of a fused chain for check_chain: w as the kernel holds it (f16-rounded in f16 mode), b fp32; dw = depthwise
-    (w is (C, 1, k, k)); addz / out_scale / res as in conv_ref."""
-    return dict(w=w, b=b, k=k, s=s, p=p, act=act, dw=dw, addz=addz, out_scale=out_scale, res=res)
+    (w is (C, 1, k, k)); addz / out_scale / res as in conv_ref.  K: accumulated terms of one output where the default (the taps,
+    the bias, the addz taps) overstates them (a stage without a bias)."""
+    return dict(w=w, b=b, k=k, s=s, p=p, act=act, dw=dw, addz=addz, out_scale=out_scale, res=res, K=K)
 
 
 def _dense(w):
@@ -199,24 +200,37 @@ def _dense(w):
     return d
 
 
-def check_chain(case, label, got, srcs, stages, up=None, got_mid=None):
-    """A fused kernel that runs `stages` back to back and keeps every intermediate as f16: the fp64 reference rounds each
-    intermediate to f16 where the kernel rounds it; the bound of a stage is its own bound (`bound`) plus the error its input
-    inherits (`propagate` of `mid_error` of the stage before).  got_mid: optional {stage index: kernel output of that stage}
-    (fused kernels that also write an intermediate).  Returns (max err/bound, mean ulp) of the final output."""
+def chain_ref(srcs, stages, up=None, f16_points=True, on_stage=None):
+    """(y, bound) of the last of `stages` run back to back on `srcs`, every intermediate rounded to f16 where a fused kernel rounds
+    it: the bound of a stage is its own bound (`bound`) plus the error its input inherits (`propagate` of `mid_error` of the stage
+    before).  on_stage(i, y, bound) is called for every stage.  f16_points=False: nothing is rounded (the plain fp64 composition; the
+    bound returned then only describes a kernel that keeps fp32 intermediates)."""
     x, err = list(srcs), None
     for i, st in enumerate(stages):
         w = _dense(st["w"]) if st["dw"] else st["w"]
         y, A, Y = conv_ref(x, w, st["b"], st["k"], st["s"], st["p"], st["act"], up=up if i == 0 else None, addz=st["addz"],
                            out_scale=st["out_scale"], res=st["res"])
-        K = (1 if st["dw"] else w.shape[1]) * st["k"] ** 2 + 1 + (4 if st["addz"] is not None else 0)
+        K = st.get("K") or (1 if st["dw"] else w.shape[1]) * st["k"] ** 2 + 1 + (4 if st["addz"] is not None else 0)
         bnd = bound(y, A, Y, K, st["out_scale"])
         if err is not None:
             bnd = bnd + propagate(err, w, st["k"], st["s"], st["p"]) * abs(st["out_scale"])
+        if on_stage is not None:
+            on_stage(i, y, bnd)
         if i == len(stages) - 1:
-            return report(case, label, got, y, bnd)
-        if got_mid is not None and i in got_mid:
-            report(f"{case} stage {i}", label, got_mid[i], y, bnd)
-        mid = y.to(torch.float16).double()
-        err = mid_error(bnd, mid)
+            return y, bnd
+        mid = y.to(torch.float16).double() if f16_points else y
+        err = mid_error(bnd, mid) if f16_points else bnd
         x = [mid]
+
+
+def check_chain(case, label, got, srcs, stages, up=None, got_mid=None):
+    """A fused kernel that runs `stages` back to back and keeps every intermediate as f16: the fp64 reference rounds each
+    intermediate to f16 where the kernel rounds it; the bound of a stage is its own bound (`bound`) plus the error its input
+    inherits (`propagate` of `mid_error` of the stage before).  got_mid: optional {stage index: kernel output of that stage}
+    (fused kernels that also write an intermediate).  Returns (max err/bound, mean ulp) of the final output."""
+    def mids(i, y, bnd):
+        if got_mid is not None and i in got_mid and i < len(stages) - 1:
+            report(f"{case} stage {i}", label, got_mid[i], y, bnd)
+
+    y, bnd = chain_ref(srcs, stages, up=up, on_stage=mids)
+    return report(case, label, got, y, bnd)
