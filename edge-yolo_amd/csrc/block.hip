@@ -43,9 +43,10 @@ struct BlkEpi {
   const f16* res;
   const f16* z;
   int y_cs, res_cs, addz_cs, Hz, Wz, act;
+  int nq;  // TAIL: quads of the lane's 4*NTI channels that lie below Cout (a Cout that is not a multiple of 4*NTI ends inside a lane's run)
   float zsy, zsx, out_scale;
 };
-template <int NTI>
+template <int NTI, bool TAIL = false>
 __device__ __forceinline__ void blk_epilogue(const BlkEpi& e, const f32x4 (&acc)[NTI], int m, int oy, int ox, int yrow = -1, int rrow = -1) {
   // (yrow / rrow: row index inside an LDS-resident tile instead of the pixel index m, block_tile_kernel)
   long z00 = 0, z01 = 0, z10 = 0, z11 = 0;
@@ -62,6 +63,7 @@ __device__ __forceinline__ void blk_epilogue(const BlkEpi& e, const f32x4 (&acc)
   const f16* rp = e.res ? e.res + (long)(rrow >= 0 ? rrow : m) * e.res_cs : nullptr;
 #pragma unroll
   for (int q = 0; q < NTI; ++q) {
+    if (TAIL && q >= e.nq) break;  // channels >= Cout: neither read (bias, res, addz) nor written
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = acc[q][j];
@@ -209,9 +211,14 @@ __device__ void blk_conv(const BlkStage& sg, const BlkExt& ext, int b) {
     e.res = resptr ? resptr + (long)grp * y_g + ch0 : nullptr;
     e.z = zptr ? zptr + (long)grp * y_g + ch0 : nullptr;
     e.y_cs = y_cs; e.res_cs = res_cs; e.addz_cs = addz_cs; e.Hz = Hz; e.Wz = Wz; e.act = act; e.zsy = zsy; e.zsx = zsx; e.out_scale = out_scale;
+    e.nq = min(NTI, (Cout - ch0) >> 2);
+    const bool tail = Cout % (4 * NTI) != 0;  // (uniform over the stage)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
-      if (pv[mt]) blk_epilogue<NTI>(e, acc[mt], (mt_i * MT + mt) * 16 + r, oy[mt], ox[mt]);
+      if (pv[mt]) {
+        if (tail) blk_epilogue<NTI, true>(e, acc[mt], (mt_i * MT + mt) * 16 + r, oy[mt], ox[mt]);
+        else blk_epilogue<NTI>(e, acc[mt], (mt_i * MT + mt) * 16 + r, oy[mt], ox[mt]);
+      }
   }
 }
 
@@ -460,6 +467,7 @@ __device__ __forceinline__ void tile_conv(const TStage& t, f16* lds, int b, int 
     e.z = t.z ? t.z + ch0 : nullptr;
     e.addz_cs = t.addz_cs; e.Hz = t.Hz; e.Wz = t.Wz; e.act = t.act; e.zsy = t.zsy; e.zsx = t.zsx; e.out_scale = t.out_scale;
     e.y_cs = t.y_cs; e.res_cs = t.res_cs;
+    e.nq = min(NTI, (t.Cout - ch0) >> 2);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
       if (!pv[mt]) continue;
@@ -468,7 +476,9 @@ __device__ __forceinline__ void tile_conv(const TStage& t, f16* lds, int b, int 
       e.y = (t.y_lds >= 0 ? lds + t.y_lds : t.y) + ch0;
       e.res = t.res ? (t.res_lds >= 0 ? lds + t.res_lds : t.res) + ch0 : nullptr;
       const int oy = mm[mt] / Wo;
-      blk_epilogue<NTI>(e, acc[mt], mm[mt], oy, mm[mt] - oy * Wo, t.y_lds >= 0 ? row : -1, (t.res && t.res_lds >= 0) ? row : -1);
+      const int yrow = t.y_lds >= 0 ? row : -1, rrow = (t.res && t.res_lds >= 0) ? row : -1;
+      if (t.Cout % (4 * NTI) != 0) blk_epilogue<NTI, true>(e, acc[mt], mm[mt], oy, mm[mt] - oy * Wo, yrow, rrow);  // (uniform over the stage)
+      else blk_epilogue<NTI>(e, acc[mt], mm[mt], oy, mm[mt] - oy * Wo, yrow, rrow);
     }
   }
 }

@@ -234,3 +234,128 @@ def check_chain(case, label, got, srcs, stages, up=None, got_mid=None):
 
     y, bnd = chain_ref(srcs, stages, up=up, on_stage=mids)
     return report(case, label, got, y, bnd)
+
+
+# ---- graph form: stages name their sources / res / addz by key (block programs: nn/_block.py, csrc/block.hip)
+def gnode(out, srcs, w=None, b=None, k=1, s=1, p=None, act=ACT_NONE, dw=False, addz=None, out_scale=1.0, res=None, K=None, op="conv",
+          into=None, ngroup=1, taps=None):
+    """One stage of graph_ref.  out: key of the result.  srcs: 1-2 source specs, each a key or (key, lo, hi) = a channel slice.
+    op "conv": w / b / k / s / p / act / dw / addz / out_scale / res / K as in `stage`, res and addz being source specs; with
+    ngroup > 1 the single source holds ngroup channel groups side by side, w and b are lists of weight sets (group g takes set
+    min(g, len - 1)), and res / addz / the result hold ngroup * Cout channels.  op "dwt": taps (4, 2, 2) as the kernel holds them,
+    stride 2, result [LL | LH | HL | HH].  op "pool": result [y1 | y2 | y3], y_i = max_pool2d(5, 1, 2) applied i times.
+    into = (key, lo): the (f16-rounded) result also replaces channels [lo, lo + C) of tensor `key` (a stage that writes in place)."""
+    return dict(out=out, srcs=list(srcs), w=w, b=b, k=k, s=s, p=k // 2 if p is None else p, act=act, dw=dw, addz=addz, out_scale=out_scale,
+                res=res, K=K, op=op, into=into, ngroup=ngroup, taps=taps)
+
+
+def _gget(env, spec):
+    if spec is None:
+        return None, None
+    key, lo, hi = (spec, None, None) if isinstance(spec, str) else spec
+    v, e = env[key]
+    if lo is None:
+        return v, e
+    return v[:, lo:hi], (e[:, lo:hi] if e is not None else None)
+
+
+def _gcat_err(vals, errs):
+    if all(e is None for e in errs):
+        return None
+    return torch.cat([e if e is not None else torch.zeros_like(v) for v, e in zip(vals, errs)], 1)
+
+
+def _gconv(nd, xs, es, w, b, z, ze, r, re):
+    w = _dense(w) if nd["dw"] else w
+    k, s, p = nd["k"], nd["s"], nd["p"]
+    y, A, Y = conv_ref(xs, w, b, k, s, p, nd["act"], addz=z, out_scale=nd["out_scale"], res=r)
+    K = nd["K"] or (1 if nd["dw"] else w.shape[1]) * k ** 2 + 1 + (4 if z is not None else 0)
+    bnd = bound(y, A, Y, K, nd["out_scale"])
+    err = _gcat_err(xs, es)
+    if err is not None:
+        bnd = bnd + propagate(err, w, k, s, p) * abs(nd["out_scale"])
+    if ze is not None:  # an erroneous addz map passes the bilinear taps (convex weights) and the activation
+        bnd = bnd + 1.1 * resize_addz(ze, y.shape[2], y.shape[3])[0] * abs(nd["out_scale"])
+    if re is not None:
+        bnd = bnd + re
+    return y, bnd
+
+
+def graph_ref(inputs, nodes, f16_points=True, on_node=None, device=None):
+    """fp64 reference of a DAG of stages (`gnode`).  inputs {key: tensor} carry no error; a stage's result is kept, for the stages
+    that read it, rounded to f16 where the kernels round it, with error mid_error(bound of that stage).  A stage's bound is
+    bound(...) plus `propagate` over each erroneous source plus the error of an erroneous res (and addz); two sources concatenate
+    along channels before conv_ref, as the kernels do.  Returns {out key: (y, bound)} with y unrounded; on_node(nd, y, bound) is
+    called per stage.  f16_points=False: nothing is rounded (plain fp64 composition)."""
+    dev = device or next(iter(inputs.values())).device
+    env = {k: (v.to(device=dev, dtype=torch.float64), None) for k, v in inputs.items()}
+    res = {}
+    for nd in nodes:
+        got = [_gget(env, sp) for sp in nd["srcs"]]
+        xs, es = [g[0] for g in got], [g[1] for g in got]
+        if nd["op"] == "conv":
+            z, ze = _gget(env, nd["addz"])
+            r, re = _gget(env, nd["res"])
+            ng = nd["ngroup"]
+            if ng == 1:
+                y, bnd = _gconv(nd, xs, es, nd["w"], nd["b"], z, ze, r, re)
+            else:
+                assert len(xs) == 1 and xs[0].shape[1] % ng == 0
+                ci, ys, bs = xs[0].shape[1] // ng, [], []
+                co = nd["w"][0].shape[0]
+
+                def grp(t, g, c):
+                    return t[:, g * c:(g + 1) * c] if t is not None else None
+                for g in range(ng):
+                    q = min(g, len(nd["w"]) - 1)
+                    yg, bg = _gconv(nd, [grp(xs[0], g, ci)], [grp(es[0], g, ci)], nd["w"][q], nd["b"][q] if nd["b"] is not None else None,
+                                    grp(z, g, co), grp(ze, g, co), grp(r, g, co), grp(re, g, co))
+                    ys.append(yg)
+                    bs.append(bg)
+                y, bnd = torch.cat(ys, 1), torch.cat(bs, 1)
+        elif nd["op"] == "dwt":
+            c = xs[0].shape[1]
+            taps = nd["taps"].to(device=dev, dtype=torch.float64)
+            ys, bs = [], []
+            for band in range(4):
+                wd = _dense(taps[band].expand(c, 1, 2, 2))
+                yb, A, Y = conv_ref(xs, wd, None, 2, 2, 0)
+                bb = bound(yb, A, Y, 4)
+                if es[0] is not None:
+                    bb = bb + propagate(es[0], wd, 2, 2, 0, slope=1.0)
+                ys.append(yb)
+                bs.append(bb)
+            y, bnd = torch.cat(ys, 1), torch.cat(bs, 1)
+        elif nd["op"] == "pool":  # max of f16 values: exact; an input error passes through the max unchanged
+            ys, bs, v, e = [], [], xs[0], es[0]
+            for _ in range(3):
+                v = F.max_pool2d(v, 5, 1, 2)
+                e = F.max_pool2d(e, 5, 1, 2) if e is not None else None
+                ys.append(v)
+                bs.append(e if e is not None else torch.zeros_like(v))
+            y, bnd = torch.cat(ys, 1), torch.cat(bs, 1)
+        else:
+            raise ValueError(nd["op"])
+        if on_node is not None:
+            on_node(nd, y, bnd)
+        res[nd["out"]] = (y, bnd)
+        if nd["op"] == "pool":
+            mid, err = y, (bnd if es[0] is not None else None)
+        else:
+            mid = y.to(torch.float16).double() if f16_points else y
+            err = mid_error(bnd, mid) if f16_points else bnd
+        env[nd["out"]] = (mid, err)
+        if nd["into"] is not None:
+            key, lo = nd["into"]
+            v, e = env[key]
+            v, e = v.clone(), (e.clone() if e is not None else torch.zeros_like(v))
+            v[:, lo:lo + mid.shape[1]] = mid
+            e[:, lo:lo + mid.shape[1]] = err if err is not None else 0
+            env[key] = (v, e)
+    return res
+
+
+def check_graph(case, label, got, inputs, nodes, mean_ulp_max=0.5):
+    """got {out key: kernel output}: each against graph_ref's y and bound (`report`).  Returns {key: (max err/bound, mean ulp)}."""
+    ref = graph_ref(inputs, nodes)
+    return {k: report(f"{case} {k}", label, g, ref[k][0], ref[k][1], mean_ulp_max) for k, g in got.items()}

@@ -8,7 +8,8 @@ against an fp64 reference (tests/fp64_ref.py), in both dtypes.
 * Schedules: the persistent / XCD-ordered kernels repeat ragged cases with grid_div = 7 and xcd_map = 0 (same bits).
 * Bounded (f16, SiLU, general data): the per-element fp64 bound and the mean-ulp gate of fp64_ref.report, the fast epilogues included.
 * The benchmarked step: every conv-family label of a batch-32 and a batch-1 forward at 640x640 is covered here (COVERED), and every
-  distinct conv2d call of both forwards is replayed at its exact shape / views with exact data."""
+  distinct conv2d call of both forwards is replayed at its exact shape / views with exact data.  Block programs are not excused:
+  every block_ label of the step is in test_gpu_block_exact.BLOCK_COVERED and every recorded chain is replayed AS A CHAIN."""
 import zlib
 
 import pytest
@@ -450,6 +451,7 @@ def test_dw_dsconv_f16_silu_within_fp64_bound(case):
 # ------------------------------------------------------------------------------------------------------------------------ §4 the step
 _FAMILY = ("conv", "stem", "pw3", "dsb_pair", "dsconv", "dwconv")
 _STEP = {}
+_STEP_CHAINS = {}  # batch -> the chains BlockCache.run recorded during the forward (tag, input views, their conv2d calls, output pointers)
 
 
 def _step_forward(batch):
@@ -459,15 +461,31 @@ def _step_forward(batch):
     launch with HIP events, which a graph replay never passes through -- there are no per-launch labels to collect there.  The
     kernels are the same: every dispatch rule reads only the call's shape, views and tunables, which the runner's stages share with
     this forward (same model, same batch, same 640x640 input).  Layers the forward runs as a block program (nn/_block.py) go through
-    block_tile_kernel in both; their conv2d calls are recorded and replayed here through ey_conv2d at the same shape."""
+    block_tile_kernel in both; their conv2d calls are recorded twice over: one by one (replayed through ey_conv2d at the same shape)
+    and grouped by the BlockCache.run that recorded them (_STEP_CHAINS: replayed as a chain through block_tile_kernel)."""
     if batch in _STEP:
         return _STEP[batch]
     import bench
-    from edge_yolo_amd.nn import _ops
+    from edge_yolo_amd.nn import _block, _ops
     from edge_yolo_amd import _lib as L
     m, _ = bench.build_model("yolo11n-test.yaml", torch.float16, "cuda")
-    calls = []
+    calls, chains = [], []
     orig = _ops.conv2d
+    orig_run = _block.BlockCache.run
+
+    def ptr(t):
+        t = L.as_nhwc(t)
+        return (t.data_ptr(), t.untyped_storage().data_ptr())
+
+    def run_rec(cache, fn, ins, outs=None):
+        n0 = len(calls)
+        got = orig_run(cache, fn, ins, outs)
+        if got is not None and len(calls) > n0:  # recorded in this call: the chain's conv2d calls, in order
+            def vw(t):
+                t = L.as_nhwc(t)
+                return ((tuple(t.shape), L.cstride(t), (t.data_ptr() - t.untyped_storage().data_ptr()) // t.element_size() % L.cstride(t)), t.untyped_storage().data_ptr())
+            chains.append(dict(tag=cache.tag, tiled=cache.tiled, ins=[vw(t) for t in ins], calls=calls[n0:], outs={L.as_nhwc(t).data_ptr() for t in got}))
+        return got
 
     def rec(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=None, addz=None, out_scale=1.0, ngroup=1, src_gstride=0, y_gstride=0,
             group_C=None, w_sets=1, _build_only=False):
@@ -495,19 +513,24 @@ def _step_forward(batch):
             cout = (w[0][0] if w_sets > 1 else w[0]).shape[0]
             calls.append(dict(srcs=sv, up=list(up2 or [0] * len(ss)), k=k, s=s, p=p, act=act, out=view(r if out is None else out),
                               res=view(res), addz=view(addz), out_scale=float(out_scale), ngroup=ngroup, src_gstride=src_gstride, y_gstride=y_gstride,
-                              group_C=group_C, w_sets=w_sets, cout=cout, label=lab))
+                              group_C=group_C, w_sets=w_sets, cout=cout, label=lab,
+                              ptrs=dict(srcs=[ptr(t) if t is not None else None for t in ss], out=ptr(r if out is None else out),
+                                        res=ptr(res) if res is not None else None)))
         return r
 
     x = torch.rand((batch, 3, 640, 640), generator=torch.Generator().manual_seed(batch)).half().cuda()
     _ops.conv2d = rec
+    _block.BlockCache.run = run_rec
     try:
         with torch.no_grad():
             _, labels = _traced(lambda: m(x))
     finally:
         _ops.conv2d = orig
+        _block.BlockCache.run = orig_run
     del m, x
     torch.cuda.empty_cache()
     _STEP[batch] = (labels, calls)
+    _STEP_CHAINS[batch] = chains
     return _STEP[batch]
 
 
@@ -522,7 +545,7 @@ def test_step_conv_kernels_are_covered(batch):
 
 
 def _replay_key(c):
-    return repr({k: v for k, v in c.items() if k != "label"})
+    return repr({k: v for k, v in c.items() if k not in ("label", "ptrs")})
 
 
 def _replay_one(c, gen):
@@ -601,7 +624,8 @@ def _replay_one(c, gen):
 def test_step_conv_calls_replay_exact(batch):
     """every distinct conv2d call of the step, at its exact shape, views, groups and epilogue operands, with exact data: bit-identical
     to fp64, through the same kernel instantiation the step launched.  (Calls recorded into a block program run inside
-    block_tile_kernel in the step and have no label of their own; their replay goes through ey_conv2d at the same shape.)"""
+    block_tile_kernel in the step and have no label of their own; here they go through ey_conv2d at the same shape, and
+    test_step_block_chains_replay_exact runs them again as the chain they were recorded into.)"""
     _, calls = _step_forward(batch)
     seen = {}
     for c in calls:
@@ -618,3 +642,23 @@ def test_step_conv_calls_replay_exact(batch):
         for j, (got, y) in enumerate(outs):
             R.assert_exact(f"replay b{batch} #{i} g{j} {c['srcs'][0][0]}->{c['cout']} k{c['k']}s{c['s']}", labels[0], got, y)
         torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("batch", [32, 1])
+def test_step_block_chains_replay_exact(batch):
+    """every block_ label of the step is held to fp64 by test_gpu_block_exact.py (BLOCK_COVERED), and every chain the forward recorded
+    is replayed AS A CHAIN through block_tile_kernel: the step's shapes, channel strides and offsets, the same dataflow (LDS-resident
+    intermediates, the in-place write over the input slice, the read-back), exact data (ReLU / none in place of SiLU): bit for bit."""
+    import test_gpu_block_exact as BE
+    labels, _ = _step_forward(batch)
+    blk = sorted({lab for lab in labels if lab.startswith("block_")})
+    chains = _STEP_CHAINS[batch]
+    print(f"[step] batch {batch}: block programs {blk}; recorded chains {[(c['tag'], len(c['calls'])) for c in chains]}")
+    assert blk, "no block program traced: the default pointwise chain of C2PSA_LinearAttention did not run"
+    missing = sorted(set(blk) - set(BE.BLOCK_COVERED))
+    assert not missing, f"batch {batch}: block programs of the step that test_gpu_block_exact.py does not cover: {missing}"
+    assert {f"block_tile_kernel<{c['tag']}>" if c["tiled"] else f"block_kernel<{c['tag']}>" for c in chains} == set(blk), "a traced block program was not recorded"
+    for i, ch in enumerate(chains):
+        assert ch["tiled"], ch["tag"]
+        ntis = BE.replay_step_chain(ch, i)
+        print(f"[step] batch {batch}: chain {ch['tag']} replayed exact, tile_nti {ntis}")
