@@ -1896,967 +1896,3 @@ __global__ __launch_bounds__(256) void conv_pw2_kernel(ConvP p, ChainP q) {
     for (int t = 0; t < KS1; ++t) cur[t] = nxt[t];
   }
 }
-
-// ------------------------------------------------------------------------------------------------ host side
-static int conv_nt(int Cout) {  // channels per block tile / 16
-  if (Cout <= 16) return 1;
-  if (Cout <= 32) return 2;
-  if (Cout <= 64) return 4;
-  if (Cout <= 80) return 5;
-  if (Cout <= 128) return 8;
-  if (Cout % 128 == 0) return 8;
-  if (Cout % 80 == 0) return 5;
-  if (Cout % 64 == 0) return 4;
-  return 8;
-}
-static int conv_cout_pad(int Cout) { int bn = 16 * conv_nt(Cout); return (Cout + bn - 1) / bn * bn; }
-static int conv_kpad(int Cin, int k, int es) { return ey_conv_kpad(k * k * Cin, es); }
-
-#if EY_CONV_PART == 16
-extern "C" size_t ey_conv_packed_bytes(int dtype, int Cout, int Cin, int k) {
-  return (size_t)conv_cout_pad(Cout) * conv_kpad(Cin, k, dtype == EY_F16 ? 2 : 4) * (dtype == EY_F16 ? 2 : 4);
-}
-
-extern "C" int ey_conv_pack_weight(int dtype, int Cout, int Cin, int k, const float* w, void* out, size_t out_bytes) {
-  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "pack: bad dtype %d", dtype);
-  EY_CHECK(Cout > 0 && Cin > 0 && (k == 1 || k == 3), "pack: Cout=%d Cin=%d k=%d", Cout, Cin, k);
-  EY_CHECK(out_bytes >= ey_conv_packed_bytes(dtype, Cout, Cin, k), "pack: output buffer too small");
-  const int NT = conv_nt(Cout), BN = 16 * NT, Kp = conv_kpad(Cin, k, dtype == EY_F16 ? 2 : 4), rows = conv_cout_pad(Cout);
-  for (int row = 0; row < rows; ++row) {
-    // MFMA row rho = 4g+j of n-block nt inside block tile nb  <->  channel nb*BN + g*4NT + 4nt + j
-    const int nb = row / BN, within = row % BN, nt = within / 16, rho = within % 16, g = rho / 4, j = rho % 4;
-    const int ch = nb * BN + g * 4 * NT + 4 * nt + j;
-    for (int kk = 0; kk < Kp; ++kk) {
-      float val = 0.f;
-      if (ch < Cout && kk < k * k * Cin) {
-        const int tap = kk / Cin, c = kk % Cin, ky = tap / k, kx = tap % k;
-        val = w[(((long)ch * Cin + c) * k + ky) * k + kx];
-      }
-      const long o = (long)row * Kp + kk;
-      if (dtype == EY_F16) ((f16*)out)[o] = (f16)val;
-      else ((float*)out)[o] = val;
-    }
-  }
-  return EY_OK;
-}
-
-#endif
-
-// kind*1000 + NT*10 + x of the kernel the last ey_conv2d launched (profiling labels, tests; see ey_conv_last_variant); defined in the f16 translation unit
-#if EY_CONV_PART == 16
-thread_local int g_last_variant = 0;
-#else
-extern thread_local int g_last_variant;
-#endif
-template <typename T, int NT, int MT>
-static bool conv_lds_ok() {  // one-time opt-in to > 64 KiB of dynamic LDS for the big-tile / f32 variants
-  static const bool ok = [] {
-    const size_t lds = 2 * (size_t)(16 * NT) * CONV_LS * sizeof(T);
-    return lds <= 64 * 1024 ||
-           hipFuncSetAttribute((const void*)conv_igemm_kernel<T, NT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  }();
-  return ok;
-}
-
-template <typename T, int NT>
-static bool launch_conv(const ConvP& p, int ngroup, hipStream_t st) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int ntiles = (p.Cout + 16 * NT - 1) / (16 * NT);
-  const long blocks2 = (M + 127) / 128 * ntiles * ngroup;
-  const size_t lds = 2 * (size_t)(16 * NT) * CONV_LS * sizeof(T);
-  if (blocks2 >= 512) {
-    if (!conv_lds_ok<T, NT, 2>()) return false;
-    dim3 grid((unsigned)((M + 127) / 128), ntiles, ngroup);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, NT, 2>), grid, dim3(256), lds, st, p);
-    g_last_variant = 13000 + NT * 10 + 2;
-  } else {
-    if (!conv_lds_ok<T, NT, 1>()) return false;
-    dim3 grid((unsigned)((M + 63) / 64), ntiles, ngroup);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, NT, 1>), grid, dim3(256), lds, st, p);
-    g_last_variant = 13000 + NT * 10 + 1;
-  }
-  return true;
-}
-
-// ---- tunables (defaults measured on MI355X; EY_* environment variables override them for sweeps)
-#include <stdlib.h>
-#include "tune.h"
-// ---- weight-stationary dispatch
-static int ws_ls(int Kpad) { return Kpad; }  // conv_kpad() already makes the row pitch conflict-free for the LDS fragment reads
-static const int WS_NT[5] = {8, 5, 4, 2, 1};
-// largest NT (<= the packing NT, dividing it into whole 16-row blocks) whose weight tile fits `budget` bytes of LDS
-static int ws_pick_nt(int Cout, int Kpad, int es, size_t budget) {
-  const int ntp = conv_nt(Cout);
-  for (int i = 0; i < 5; ++i) {
-    const int nt = WS_NT[i];
-    if (nt > ntp || ntp % nt) continue;
-    if ((size_t)16 * nt * ws_ls(Kpad) * es <= budget) return nt;
-  }
-  return 0;
-}
-
-template <typename T, int NT, int MT, int KS>
-static bool ws_launch(ConvP p, int ngroup, hipStream_t st) {
-  const size_t lds = (size_t)16 * NT * p.LSw * sizeof(T);
-  static size_t reserved = 0;
-  if (lds > 64 * 1024 && lds > reserved) {
-    if (hipFuncSetAttribute((const void*)conv_ws_kernel<T, NT, MT, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    reserved = lds;
-  }
-  const long M = (long)p.B * p.Ho * p.Wo;
-  p.ntile = (M + 16 * MT - 1) / (16 * MT);
-  const int ntiles_n = (conv_cout_pad(p.Cout)) / (16 * NT);
-  // resident workgroups per CU: LDS AND registers decide (a 512-thread workgroup of a 172-VGPR instantiation fits once per
-  // CU whatever its LDS footprint); a persistent grid larger than that runs in two rounds and stages every weight tile twice
-  static size_t occ_lds = ~(size_t)0;
-  static int occ = 1;
-  if (occ_lds != lds) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv_ws_kernel<T, NT, MT, KS>, 512, lds) != hipSuccess || n < 1) n = 1;
-    occ = n;
-    occ_lds = lds;
-  }
-  const int wg_per_cu = occ < (int)tune().ws_wg_cu ? occ : (int)tune().ws_wg_cu;
-  // persistent grid: one workgroup per resident slot; tiles are dealt round-robin over workgroups first, then waves,
-  // so a small layer still spreads over all CUs
-  long cap = (long)256 * wg_per_cu / ((long)ntiles_n * ngroup);
-  if (cap < 1) cap = 1;
-  cap = cap / tune().grid_div > 0 ? cap / tune().grid_div : 1;
-  long gx = p.ntile < cap ? p.ntile : cap;
-  if (tune().tiles_per_wave > 0) {
-    long want = (p.ntile + 8 * tune().tiles_per_wave - 1) / (8 * tune().tiles_per_wave);
-    if (want < 1) want = 1;
-    if (want < gx) gx = want;
-  }
-  dim3 grid((unsigned)gx, ntiles_n, ngroup);
-  hipLaunchKernelGGL((conv_ws_kernel<T, NT, MT, KS>), grid, dim3(512), lds, st, p);
-  g_last_variant = 12000 + NT * 100 + MT * 10 + KS;
-  return true;
-}
-
-template <typename T, int NT, int KS>
-static bool ws_launch_mt(const ConvP& p, int ngroup, hipStream_t st) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  // enough wave tiles to give every SIMD work: 2 pixel blocks per wave when M is large, else 1
-  if (M >= tune().mt2_min_m) return ws_launch<T, NT, 2, KS>(p, ngroup, st);  // measured: below this, more (smaller) wave tiles hide latency better
-  return ws_launch<T, NT, 1, KS>(p, ngroup, st);
-}
-
-template <typename T, int KS>
-static bool ws_launch_nt(const ConvP& p, int nt, int ngroup, hipStream_t st) {
-  switch (nt) {
-    case 1: return ws_launch_mt<T, 1, KS>(p, ngroup, st);
-    case 2: return ws_launch_mt<T, 2, KS>(p, ngroup, st);
-    case 4: return ws_launch_mt<T, 4, KS>(p, ngroup, st);
-    case 5: return ws_launch_mt<T, 5, KS>(p, ngroup, st);
-    default: return ws_launch_mt<T, 8, KS>(p, ngroup, st);
-  }
-}
-
-// ---- 3x3 halo-tile dispatch
-template <typename T, int NT, int S>
-static int halo_launch(ConvP p, int ngroup, hipStream_t st) {
-  constexpr int MT = (S == 1) ? 2 : 1, TR = 8, TC = 16 * MT, HR = (TR - 1) * S + 3, HC = (TC - 1) * S + 3;
-  const int C = p.srcC[0];
-  const size_t lds = ((size_t)16 * NT * p.LSw + (size_t)HR * HC * (C + 8)) * sizeof(T);
-  static size_t reserved = 0;
-  if (lds > 64 * 1024 && lds > reserved) {
-    if (hipFuncSetAttribute((const void*)conv3_halo_kernel<T, NT, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "conv: cannot reserve %zu B of LDS for the halo tile", lds);
-    reserved = lds;
-  }
-  const long ntile = (long)p.B * ((p.Wo + TC - 1) / TC) * ((p.Ho + TR - 1) / TR);
-  const int ntn = conv_cout_pad(p.Cout) / (16 * NT);
-  static size_t occ_lds = ~(size_t)0;
-  static int occ = 1;
-  if (occ_lds != lds) {  // resident workgroups per CU from LDS and registers (see ws_launch)
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv3_halo_kernel<T, NT, S>, 512, lds) != hipSuccess || n < 1) n = 1;
-    occ = n;
-    occ_lds = lds;
-  }
-  const int per_cu = occ < 2 ? occ : 2;
-  long gx = (long)256 * per_cu / ((long)ntn * ngroup);
-  if (gx < 1) gx = 1;
-  if (gx > ntile) gx = ntile;
-  hipLaunchKernelGGL((conv3_halo_kernel<T, NT, S>), dim3((unsigned)gx, ntn, ngroup), dim3(512), lds, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(halo): %s", hipGetErrorString(e_));
-  g_last_variant = 11000 + NT * 10 + S;
-  return 1;
-}
-
-// largest NT dividing the packing NT such that weights + halo fit LDS; 0 = does not fit
-template <typename T>
-static int halo_pick_nt(const ConvP& p, int S) {
-  const int MT = (S == 1) ? 2 : 1, TC = 16 * MT, HR = 7 * S + 3, HC = (TC - 1) * S + 3, C = p.srcC[0];
-  const size_t halo = (size_t)HR * HC * (C + 8) * sizeof(T);
-  const int ntp = conv_nt(p.Cout);
-  for (int i = 0; i < 5; ++i) {
-    const int nt = WS_NT[i];
-    if (nt > ntp || ntp % nt) continue;
-    if (halo + (size_t)16 * nt * ws_ls(p.Kpad) * sizeof(T) <= 158 * 1024) return nt;
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_halo(ConvP p, int ngroup, hipStream_t st) {
-  if (p.k != 3 || p.nsrc != 1 || p.srcUp[0] || p.srcC[0] > 64 || p.srcC[0] < tune().halo_min_c) return 0;  // measured: wins for Cin=64 on large maps
-  const int S = p.stride;
-  {  // the per-thread register halo holds HV=10 vectors
-    const int MT = (S == 1) ? 2 : 1, HR = 7 * S + 3, HC = (16 * MT - 1) * S + 3;
-    if ((long)HR * HC * (p.srcC[0] >> 3) > 512L * 10) return 0;
-  }
-  const long npix = (long)p.B * p.H * p.W;
-  const long bytes = ((npix - 1) * p.srcCs[0] + p.srcC[0]) * (long)sizeof(T);
-  if (bytes >= (1L << 31) || p.srcG * (long)sizeof(T) * (ngroup - 1) >= (1L << 31)) return 0;
-  p.srcBytes[0] = (unsigned)bytes;
-  p.NTpack = conv_nt(p.Cout);
-  p.LSw = ws_ls(p.Kpad);
-  const int nt = halo_pick_nt<T>(p, S);
-  if (!nt) return 0;
-#define HALO(NTV)                                                     \
-  case NTV: return S == 1 ? halo_launch<T, NTV, 1>(p, ngroup, st) : halo_launch<T, NTV, 2>(p, ngroup, st);
-  switch (nt) {
-    HALO(1) HALO(2) HALO(4) HALO(5) HALO(8)
-  }
-#undef HALO
-  return 0;
-}
-
-// ---- 3x3 tile dispatch
-template <typename T, int NT, int S>
-static int tile_launch(ConvP p, int ngroup, hipStream_t st) {
-  constexpr int TR = 8, TC = (S == 1) ? 32 : 16, HR = (TR - 1) * S + 3, HC = (TC - 1) * S + 3, LROW = (S == 1) ? HC : 2 * ((HC + 1) / 2);
-  const bool wlds = tune().tile_wlds == 1 || (tune().tile_wlds == 2 && S == 1);
-  const size_t lds = ((size_t)HR * LROW + (wlds ? 9 * 16 * NT : 0)) * 40 * sizeof(T);
-  int tr = TR, tc = TC;
-  if (S == 1 && tune().tile_flat) {  // flattened tile: the (rows x cols) with <= 256 pixels and <= 340 halo pixels that wastes the fewest slots
-    double best = 0.0;
-    const int cands[8] = {16, 20, 24, 28, 32, 36, 40, p.Wo};
-    for (int i = 0; i < 8; ++i) {
-      const int c = cands[i];
-      if (c < 8 || c > 80) continue;
-      int rr = 256 / c;
-      while (rr > 1 && (rr + 2) * (c + 2) > 340) --rr;
-      if (rr < 1 || (rr + 2) * (c + 2) > 340) continue;
-      const long cov = (long)((p.Wo + c - 1) / c) * ((p.Ho + rr - 1) / rr) * 256;
-      const double eff = (double)p.Wo * p.Ho / (double)cov;
-      if (eff > best + 1e-9) { best = eff; tr = rr; tc = c; }
-    }
-  }
-  p.tTR = tr; p.tTC = tc;
-  const long tiles = (long)p.B * ((p.Wo + tc - 1) / tc) * ((p.Ho + tr - 1) / tr);
-  const dim3 grid((unsigned)tiles, (unsigned)(conv_cout_pad(p.Cout) / (16 * NT)), (unsigned)ngroup);
-  p.xcd = (int)((tune().xcd_map >> 4) & 1) && grid.y == 1 && grid.z == 1;  // (x alone decides the XCD only for a 1-D grid)
-  static bool attr = false;
-  if (!attr) {  // up to 46 + 46 KB of dynamic LDS
-    (void)hipFuncSetAttribute((const void*)conv3_tile_kernel<T, NT, S, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    attr = true;
-  }
-  if (wlds) hipLaunchKernelGGL((conv3_tile_kernel<T, NT, S, true>), grid, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((conv3_tile_kernel<T, NT, S, false>), grid, dim3(256), lds, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(tile): %s", hipGetErrorString(e_));
-  g_last_variant = 6000 + NT * 10 + S;
-  return 1;
-}
-
-template <typename T>
-static int dispatch_tile(ConvP p, int ngroup, hipStream_t st) {
-  if (sizeof(T) != 2) return 0;  // f16 throughput mode (the f32 parity mode keeps the exact-f32 kernels below)
-  if (p.k != 3 || p.nsrc != 1 || p.srcUp[0] || 9L * p.srcC[0] < tune().tile_mink) return 0;
-  if (p.stride == 2 && (p.srcC[0] < tune().tile_s2_minc || (long)p.B * p.Ho * p.Wo < tune().tile_s2_minm)) return 0;
-  const int ntp = conv_nt(p.Cout);
-  int nt = ntp % 4 == 0 ? 4 : ntp == 2 ? 2 : ntp == 1 ? 1 : 0;
-  if (!nt) return 0;
-  // small maps: too few tiles to fill 256 CUs -> narrower channel tiles (more workgroups) beat the bigger register tile
-  if (p.stride == 1 && tune().tile_minwg > 0) {
-    const long tiles = (long)p.B * (((long)p.Ho * p.Wo + 239) / 240);
-    while (nt > 1 && tiles * (conv_cout_pad(p.Cout) / (16 * nt)) * ngroup < tune().tile_minwg) nt >>= 1;
-  }
-  const long npix = (long)p.B * p.H * p.W;
-  const long bytes = ((npix - 1) * p.srcCs[0] + p.srcC[0]) * (long)sizeof(T);
-  if (bytes >= (1L << 31) || p.srcG * (long)sizeof(T) * (ngroup - 1) >= (1L << 31)) return 0;
-  if ((long)conv_cout_pad(p.Cout) * p.Kpad * (long)sizeof(T) >= (1L << 31)) return 0;
-  p.srcBytes[0] = (unsigned)bytes;
-  p.NTpack = ntp;
-  if constexpr (sizeof(T) == 2) {
-    if (p.stride == 1) return nt == 4 ? tile_launch<T, 4, 1>(p, ngroup, st) : nt == 2 ? tile_launch<T, 2, 1>(p, ngroup, st) : tile_launch<T, 1, 1>(p, ngroup, st);
-    return nt == 4 ? tile_launch<T, 4, 2>(p, ngroup, st) : nt == 2 ? tile_launch<T, 2, 2>(p, ngroup, st) : tile_launch<T, 1, 2>(p, ngroup, st);
-  }
-  return 0;
-}
-
-// ---- register-stationary 3x3 dispatch (Cin == 16)
-template <int NT, int S>
-static int c3r_launch(const ConvP& p, int ngroup, hipStream_t st) {
-  static int occ = 0;
-  if (!occ) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv3r_kernel<NT, S>, 256, 0) != hipSuccess || n < 1) n = 1;
-    occ = n > 4 ? 4 : n;
-  }
-  const long ntile = (long)p.B * p.Ho * ((p.Wo + 15) / 16);
-  if (ntile >= (1L << 31)) return 0;
-  long gx = (long)256 * occ / ngroup / tune().grid_div;
-  if (gx > (ntile + 3) / 4) gx = (ntile + 3) / 4;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((conv3r_kernel<NT, S>), dim3((unsigned)gx, 1, (unsigned)ngroup), dim3(256), 0, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(c3r): %s", hipGetErrorString(e_));
-  g_last_variant = 7000 + NT * 10 + S;
-  return 1;
-}
-
-template <typename T>
-static int dispatch_c3r(ConvP p, int ngroup, hipStream_t st) {
-  if (sizeof(T) != 2 || !tune().c3r) return 0;
-  if (p.k != 3 || p.nsrc != 1 || p.srcUp[0] || p.srcC[0] != 16 || (p.srcCs[0] * 2) % 8) return 0;
-  if (p.stride != 2 && tune().c3r < 2) return 0;  // measured: wins for the stride-2 layer (68 -> 58 us), loses 10 % to the tile kernel at stride 1
-  const int ntp = conv_nt(p.Cout);
-  if (ntp > 2 || conv_cout_pad(p.Cout) != 16 * ntp) return 0;
-  const long npix = (long)p.B * p.H * p.W;
-  const long bytes = ((npix - 1) * p.srcCs[0] + p.srcC[0]) * 2L;
-  if (bytes >= (1L << 31) || p.srcG * 2L * (ngroup - 1) >= (1L << 31)) return 0;
-  p.srcBytes[0] = (unsigned)bytes;
-  p.NTpack = ntp;
-  if constexpr (sizeof(T) == 2) {
-    if (p.stride == 1) return ntp == 1 ? c3r_launch<1, 1>(p, ngroup, st) : c3r_launch<2, 1>(p, ngroup, st);
-    return ntp == 1 ? c3r_launch<1, 2>(p, ngroup, st) : c3r_launch<2, 2>(p, ngroup, st);
-  }
-  return 0;
-}
-
-// ---- persistent 3x3 tile kernel dispatch (f16, Cin = 64, stride 1, Cout a multiple of 64 or exactly 32 / 16)
-template <int NT>
-static int c3p_launch(ConvP p, hipStream_t st) {
-  // flattened tile: the (rows x cols) with <= 256 pixels and <= 340 halo pixels that wastes the fewest slots (as tile_launch)
-  int tr = 8, tc = 32;
-  {
-    double best = 0.0;
-    const int cands[8] = {16, 20, 24, 28, 32, 36, 40, p.Wo};
-    for (int i = 0; i < 8; ++i) {
-      const int c = cands[i];
-      if (c < 8 || c > 80) continue;
-      int rr = 256 / c;
-      while (rr > 1 && (rr + 2) * (c + 2) > 340) --rr;
-      if (rr < 1 || (rr + 2) * (c + 2) > 340) continue;
-      const long cov = (long)((p.Wo + c - 1) / c) * ((p.Ho + rr - 1) / rr) * 256;
-      const double eff = (double)p.Wo * p.Ho / (double)cov;
-      if (eff > best + 1e-9) { best = eff; tr = rr; tc = c; }
-    }
-  }
-  p.tTR = tr; p.tTC = tc;
-  const long tiles = (long)p.B * ((p.Wo + tc - 1) / tc) * ((p.Ho + tr - 1) / tr);
-  if (tiles >= (1L << 30)) return 0;
-  const int ny = conv_cout_pad(p.Cout) / (16 * NT);
-  const size_t lds = ((size_t)9 * 16 * NT + 340) * 80 * 2;
-  static bool reserved = false;
-  if (!reserved) {
-    if (hipFuncSetAttribute((const void*)conv3p_kernel<NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv3p_kernel<NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return 0;
-    reserved = true;
-  }
-  long gx = 256 / ny;
-  if (gx < 1) gx = 1;
-  if (gx > tiles) gx = tiles;
-  // the interleaved epilogue: bias + SiLU only, whole 16-byte-aligned channel tiles, output view addressable with 32-bit offsets
-  const long ybytes = (((long)p.B * p.Ho * p.Wo - 1) * p.yCs + p.Cout) * 2L;
-  const bool fast = tune().c3p_fast && p.bias && p.act == EY_ACT_SILU && p.out_scale == 1.f && !p.res && !p.addz && p.vec_store == 2 && p.Cout % (16 * NT) == 0 &&
-                    ybytes < (1L << 31);
-  p.srcBytes[1] = fast ? (unsigned)ybytes : 0u;
-  const dim3 gg((unsigned)gx, (unsigned)ny, 1);
-  if (fast) hipLaunchKernelGGL((conv3p_kernel<NT, true>), gg, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((conv3p_kernel<NT, false>), gg, dim3(256), lds, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(c3p): %s", hipGetErrorString(e_));
-  g_last_variant = 9000 + NT * 10 + (fast ? 1 : 0);
-  return 1;
-}
-template <typename T>
-static int dispatch_c3p(ConvP p, int ngroup, hipStream_t st) {
-  if constexpr (sizeof(T) != 2) return 0;
-  else {
-    if (!tune().c3p || p.k != 3 || p.stride != 1 || p.nsrc != 1 || p.srcUp[0] || ngroup != 1 || p.srcC[0] != 64) return 0;
-    const int ntp = conv_nt(p.Cout);
-    if (ntp % 4 != 0 || conv_cout_pad(p.Cout) % 64) return 0;
-    const long M = (long)p.B * p.Ho * p.Wo;
-    if (tune().c3p < 2 && M < tune().c3p_min_m) return 0;
-    const long npix = (long)p.B * p.H * p.W;
-    const long bytes = ((npix - 1) * p.srcCs[0] + p.srcC[0]) * 2L;
-    if (bytes >= (1L << 31) || (long)conv_cout_pad(p.Cout) * p.Kpad * 2L >= (1L << 31)) return 0;
-    p.srcBytes[0] = (unsigned)bytes;
-    p.NTpack = ntp;
-    return c3p_launch<4>(p, st);
-  }
-}
-
-// ---- 3x3 stream kernel dispatch (f16, Cin in {64, 128, 256}, one source, no groups)
-template <int NT, int MT, int UPT, int S, int NB>
-static int c3s_launch2(ConvP p, hipStream_t st) {
-  const size_t lds = (size_t)16 * NT * p.LSw * 2;
-  static size_t reserved = 0;
-  if (lds > 64 * 1024 && lds > reserved) {
-    if (hipFuncSetAttribute((const void*)conv3s_kernel<NT, MT, UPT, S, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
-    reserved = lds;
-  }
-  const long M = (long)p.B * p.Ho * p.Wo;
-  p.ntile = (M + 16 * MT - 1) / (16 * MT);
-  const int ny = conv_cout_pad(p.Cout) / (16 * NT);
-  long gx = 256 / ny;  // one workgroup per CU over all channel tiles
-  if (gx < 1) gx = 1;
-  if (gx * 8 > p.ntile) gx = (p.ntile + 7) / 8;
-  p.xcd = (int)((tune().xcd_map >> 3) & 1) && (ny == 1 || gx % 8 == 0);
-  hipLaunchKernelGGL((conv3s_kernel<NT, MT, UPT, S, NB>), dim3((unsigned)gx, (unsigned)ny, 1), dim3(512), lds, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(c3s): %s", hipGetErrorString(e_));
-  g_last_variant = 8000 + NT * 100 + MT * 10 + (NB == 9 ? 5 : 0) + S;
-  return 1;
-}
-template <int NT, int MT, int UPT, int NB>
-static int c3s_launch1(const ConvP& p, hipStream_t st) { return p.stride == 1 ? c3s_launch2<NT, MT, UPT, 1, NB>(p, st) : c3s_launch2<NT, MT, UPT, 2, NB>(p, st); }
-template <int NT, int MT, int NB>
-static int c3s_launch0(const ConvP& p, hipStream_t st) {
-  switch (p.srcC[0]) {
-    case 64: return c3s_launch1<NT, MT, 1, NB>(p, st);
-    case 128: return c3s_launch1<NT, MT, 2, NB>(p, st);
-    default: return c3s_launch1<NT, MT, 4, NB>(p, st);
-  }
-}
-template <typename T>
-static int dispatch_c3s(ConvP p, int ngroup, hipStream_t st) {
-  if constexpr (sizeof(T) != 2) return 0;
-  else {
-    if (!tune().c3s || p.k != 3 || p.nsrc != 1 || p.srcUp[0] || ngroup != 1) return 0;
-    const int Cin = p.srcC[0];
-    if (Cin != 64 && Cin != 128 && Cin != 256) return 0;
-    const int ntp = conv_nt(p.Cout);
-    if (conv_cout_pad(p.Cout) != p.Cout && conv_cout_pad(p.Cout) / 16 != ntp) return 0;
-    // widest channel tile (a whole number of 16-row blocks of the packing tile) whose [16*NT][Kpad] weights fit one CU's LDS
-    int nt = 0;
-    const int opts[3] = {4, 2, 1};
-    for (int i = 0; i < 3 && !nt; ++i)
-      if (opts[i] <= ntp && ntp % opts[i] == 0 && (size_t)16 * opts[i] * p.Kpad * 2 <= 156 * 1024) nt = opts[i];
-    if (!nt) return 0;
-    const long npix = (long)p.B * p.H * p.W;
-    const long bytes = ((npix - 1) * p.srcCs[0] + p.srcC[0]) * 2L;
-    if (bytes >= (1L << 31) || (long)conv_cout_pad(p.Cout) * p.Kpad * 2L >= (1L << 31)) return 0;
-    p.srcBytes[0] = (unsigned)bytes;
-    p.NTpack = ntp;
-    p.LSw = ws_ls(p.Kpad);
-    const long M = (long)p.B * p.Ho * p.Wo;
-    // Measured at batch 32 (tools/c3s_bench.sh, profiles/r03_c3s_vs_tile.txt): the stream kernel wins where the layer is big enough to
-    // keep every CU streaming -- the stride-2 down-sampling convs (layer 3: 68 -> 47 us, 5: 56 -> 38, 7: 34 -> 27, 17: 19.5 -> 16) -- and
-    // loses to the LDS-halo tile kernel at stride 1 (every input line goes through the vector-memory path 9 times: L2 hits, but at
-    // ~30 B/clk per CU that is 13 us for the 80x80 box-tower convs) and on the smallest maps.  c3s = 2 forces it everywhere (tests).
-    const long work = M * (conv_cout_pad(p.Cout) / (16 * nt));
-    if (tune().c3s < 2 && (p.stride != 2 || work < tune().c3s_min_work)) return 0;
-    // wave tile: 4 pixel blocks per wave on the big layers, 2 (more, smaller wave tiles) otherwise
-    long cfg = tune().c3s_cfg;  // (developer knob: MT * 10 + ring depth)
-    if (!cfg) cfg = (nt == 4 && M >= tune().c3s_mt4_m) ? 43 : 23;
-    if (nt == 4) return cfg == 43 ? c3s_launch0<4, 4, 3>(p, st) : c3s_launch0<4, 2, 3>(p, st);
-    if (nt == 2) return c3s_launch0<2, 2, 3>(p, st);
-    return c3s_launch0<1, 2, 3>(p, st);
-  }
-}
-
-// ---- small-M dispatch
-template <typename T, int NT>
-static int small_launch(ConvP p, int ngroup, hipStream_t st) {
-  constexpr int BATCH = sizeof(T) == 2 ? 8 : 4;
-  const long M = (long)p.B * p.Ho * p.Wo;
-  p.ntile = (M + 15) / 16;
-  p.ntn = conv_cout_pad(p.Cout) / (16 * NT);
-  const long waves = p.ntile * p.ntn;
-  hipLaunchKernelGGL((conv_small_kernel<T, NT, BATCH>), dim3((unsigned)((waves + 3) / 4), 1, ngroup), dim3(256), 0, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(small): %s", hipGetErrorString(e_));
-  g_last_variant = 10000 + NT * 10 + BATCH;
-  return 1;
-}
-
-static int small_pick_nt(int Cout, int es) {
-  const int ntp = conv_nt(Cout);
-  const int cap = es == 2 ? 5 : 2;
-  const int opts[4] = {5, 4, 2, 1};
-  for (int i = 0; i < 4; ++i)
-    if (opts[i] <= cap && opts[i] <= ntp && ntp % opts[i] == 0) return opts[i];
-  return 1;
-}
-
-// The latency-oriented kernel wins (measured) for 1x1 convs on small maps as long as the weights every wave re-reads
-// from L2 stay a small total: (#16-pixel tiles) x (weight bytes) <= 48 MB.  Larger weights: weight-stationary kernel.
-#define EY_SMALL_M 100000
-static bool small_ok(int Cout, int Kpad, int k, long M, int es) {
-  if (k != 1 || M >= tune().small_m) return false;
-  return ((M + 15) / 16) * (long)conv_cout_pad(Cout) * Kpad * es <= (tune().small_wmb << 20);
-}
-
-template <typename T>
-static int dispatch_small(ConvP p, int ngroup, hipStream_t st) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  if (!small_ok(p.Cout, p.Kpad, p.k, M, sizeof(T))) return 0;
-  p.Ctot = 0; p.nsteps = 0;
-  for (int s2 = 0; s2 < p.nsrc; ++s2) {
-    p.Ctot += p.srcC[s2];
-    p.nsteps += (p.srcC[s2] + 31) / 32;
-    const int up = p.srcUp[s2];
-    const long npix = (long)p.B * (p.H >> up) * (p.W >> up);
-    const long bytes = ((npix - 1) * p.srcCs[s2] + p.srcC[s2]) * (long)sizeof(T);
-    if (bytes >= (1L << 31) || p.srcG * (long)sizeof(T) * (ngroup - 1) >= (1L << 31)) return 0;
-    p.srcBytes[s2] = (unsigned)bytes;
-  }
-  p.nsteps *= p.k * p.k;
-  if (p.nsrc == 1) { p.srcC[1] = p.srcC[0]; p.srcCs[1] = p.srcCs[0]; p.srcUp[1] = p.srcUp[0]; p.src[1] = p.src[0]; }
-  p.NTpack = conv_nt(p.Cout);
-  switch (small_pick_nt(p.Cout, sizeof(T))) {
-    case 5: if constexpr (sizeof(T) == 2) return small_launch<T, 5>(p, ngroup, st); else return small_launch<T, 1>(p, ngroup, st);
-    case 4: if constexpr (sizeof(T) == 2) return small_launch<T, 4>(p, ngroup, st); else return small_launch<T, 2>(p, ngroup, st);
-    case 2: return small_launch<T, 2>(p, ngroup, st);
-    default: return small_launch<T, 1>(p, ngroup, st);
-  }
-}
-
-// ---- lean pointwise dispatch
-
-static int pw_pick_nt(int Cout, long mtiles, int es) {
-  const int ntp = conv_nt(Cout), rows = conv_cout_pad(Cout) / 16;
-  const int opts[5] = {8, 5, 4, 2, 1};
-  int pick = 0;
-  for (int i = 0; i < 5; ++i) {
-    const int nt = opts[i];
-    if (nt > ntp || ntp % nt || (es == 4 && nt > 4)) continue;
-    pick = nt;  // candidates come widest first; keep narrowing until there are enough waves (but stay >= 2 for 16-byte stores)
-    if (mtiles * (rows / nt) >= tune().pw_waves || nt <= 2) break;
-  }
-  return pick;
-}
-
-template <typename T, int NT>
-static int pw_launch(const ConvP& p, bool two, bool geo, hipStream_t st) {
-  // k-steps in flight per wave: as many as keep the wave at <= ~128 VGPRs (4 waves per SIMD)
-  constexpr int BATCH = (sizeof(T) == 2 ? (NT <= 2 ? 8 : NT <= 5 ? 4 : 2) : (NT <= 2 ? 4 : 2));
-  const dim3 grid((unsigned)((p.ntile + 3) / 4), (unsigned)(conv_cout_pad(p.Cout) / (16 * NT)), 1);
-  if (two) {
-    if (geo) hipLaunchKernelGGL((conv_pw_kernel<T, NT, BATCH, true, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_pw_kernel<T, NT, BATCH, true, false>), grid, dim3(256), 0, st, p);
-  } else {
-    if (geo) hipLaunchKernelGGL((conv_pw_kernel<T, NT, BATCH, false, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_pw_kernel<T, NT, BATCH, false, false>), grid, dim3(256), 0, st, p);
-  }
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(pw): %s", hipGetErrorString(e_));
-  g_last_variant = 4000 + NT * 10 + (two ? 2 : 1);
-  return 1;
-}
-
-// ---- register-stationary pointwise dispatch (large maps, few channels)
-template <typename T, int NT, int KS, bool TWO, bool GEO>
-static int pwr_launch2(const ConvP& p, hipStream_t st) {
-  // persistent grid = exactly the waves that are resident at once (register-limited), tiles dealt round-robin
-  static int occ = 0;
-  if (!occ) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv_pwr_kernel<T, NT, KS, TWO, GEO>, 256, 0) != hipSuccess || n < 1) n = 1;
-    occ = n > 4 ? 4 : n;
-  }
-  const unsigned ny = (unsigned)(conv_cout_pad(p.Cout) / (16 * NT));
-  long gx = (long)256 * occ / ny / tune().grid_div;
-  const long need = (p.ntile + 3) / 4;
-  if (gx > need) gx = need;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((conv_pwr_kernel<T, NT, KS, TWO, GEO>), dim3((unsigned)gx, ny, 1), dim3(256), 0, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(pwr): %s", hipGetErrorString(e_));
-  g_last_variant = 5000 + NT * 10 + KS;
-  return 1;
-}
-
-template <typename T, int NT, int KS>
-static int pwr_launch(const ConvP& p, bool two, bool geo, hipStream_t st) {
-  if (two) return geo ? pwr_launch2<T, NT, KS, true, true>(p, st) : pwr_launch2<T, NT, KS, true, false>(p, st);
-  return geo ? pwr_launch2<T, NT, KS, false, true>(p, st) : pwr_launch2<T, NT, KS, false, false>(p, st);
-}
-
-template <typename T, int NT>
-static int pwr_launch_ks(const ConvP& p, int ks, bool two, bool geo, hipStream_t st) {
-  switch (ks) {
-    case 1: return pwr_launch<T, NT, 1>(p, two, geo, st);
-    case 2: return pwr_launch<T, NT, 2>(p, two, geo, st);
-    case 3: return pwr_launch<T, NT, 3>(p, two, geo, st);
-    case 4: if constexpr (NT <= 4) return pwr_launch<T, NT, 4>(p, two, geo, st); else return 0;
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_pwr(ConvP p, int ngroup, hipStream_t st) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  if (sizeof(T) != 2) return 0;  // f16 throughput mode only (an f32 fragment is twice the registers)
-  if (p.k != 1 || p.stride != 1 || ngroup != 1 || M < tune().pwr_m || !p.vec_store || M >= (1L << 27)) return 0;
-  const int ntp = conv_nt(p.Cout);
-  if (conv_cout_pad(p.Cout) != 16 * ntp) return 0;  // one channel tile covers Cout (Cout <= 128)
-  if (p.Cout != 16 * ntp) return 0;  // ... exactly: the epilogue stores whole 4*NT-channel groups with no channel-tail predicate
-  const int ks = (p.srcC[0] + 31) / 32 + (p.nsrc == 2 ? (p.srcC[1] + 31) / 32 : 0);
-  if (ks * ntp > tune().pwr_frags || ks > 4) return 0;
-  for (int s2 = 0; s2 < p.nsrc; ++s2) {
-    const int up = p.srcUp[s2];
-    const long npix = (long)p.B * (p.H >> up) * (p.W >> up);
-    const long bytes = ((npix - 1) * p.srcCs[s2] + p.srcC[s2]) * (long)sizeof(T);
-    if (bytes >= (1L << 31)) return 0;
-    p.srcBytes[s2] = (unsigned)bytes;
-  }
-  p.ntile = (M + 15) / 16;
-  p.NTpack = ntp;
-  const bool two = p.nsrc == 2, geo = p.addz != nullptr || p.srcUp[0] || (two && p.srcUp[1]);
-  if constexpr (sizeof(T) == 2) {
-    switch (ntp) {
-      case 1: return pwr_launch_ks<T, 1>(p, ks, two, geo, st);
-      case 2: return pwr_launch_ks<T, 2>(p, ks, two, geo, st);
-      case 4: return pwr_launch_ks<T, 4>(p, ks, two, geo, st);
-      case 5: return pwr_launch_ks<T, 5>(p, ks, two, geo, st);
-      case 8: return pwr_launch_ks<T, 8>(p, ks, two, geo, st);
-    }
-  }
-  return 0;
-}
-
-template <typename T>
-static int dispatch_pw(ConvP p, int ngroup, hipStream_t st) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  if (p.k != 1 || p.stride != 1 || ngroup != 1 || M >= tune().pw_m) return 0;
-  if (((M + 15) / 16) * (long)conv_cout_pad(p.Cout) * p.Kpad * (long)sizeof(T) > (tune().pw_wmb << 20)) return 0;  // every wave re-reads its weight rows
-  if ((long)conv_cout_pad(p.Cout) * p.Kpad * (long)sizeof(T) >= (1L << 31)) return 0;
-  for (int s2 = 0; s2 < p.nsrc; ++s2) {
-    const int up = p.srcUp[s2];
-    const long npix = (long)p.B * (p.H >> up) * (p.W >> up);
-    const long bytes = ((npix - 1) * p.srcCs[s2] + p.srcC[s2]) * (long)sizeof(T);
-    if (bytes >= (1L << 31)) return 0;
-    p.srcBytes[s2] = (unsigned)bytes;
-  }
-  p.ntile = (M + 15) / 16;
-  p.NTpack = conv_nt(p.Cout);
-  const bool two = p.nsrc == 2, geo = p.addz != nullptr || p.srcUp[0] || (two && p.srcUp[1]);
-  switch (pw_pick_nt(p.Cout, p.ntile, sizeof(T))) {
-    case 8: if constexpr (sizeof(T) == 2) return pw_launch<T, 8>(p, two, geo, st); else return 0;
-    case 5: if constexpr (sizeof(T) == 2) return pw_launch<T, 5>(p, two, geo, st); else return 0;
-    case 4: return pw_launch<T, 4>(p, two, geo, st);
-    case 2: return pw_launch<T, 2>(p, two, geo, st);
-    case 1: return pw_launch<T, 1>(p, two, geo, st);
-  }
-  return 0;
-}
-
-// ---- N-split pointwise kernel (conv_pwn_kernel): small maps, K = 128 ... 512, Cout % 128 == 0
-template <int KS, int NTW>
-static int pwn_launch(ConvP p, hipStream_t st) {
-  int units = KS * 4;
-  while ((units & 3) != 2) ++units;  // LDS pixel pitch: 2 (mod 4) 16-byte units (conflict-free fragment reads)
-  p.LSw = units * 8;
-  const size_t lds = (size_t)64 * p.LSw * 2;
-  static bool reserved = false;
-  if (lds > 64 * 1024 && !reserved) {
-    if (hipFuncSetAttribute((const void*)conv_pwn_kernel<KS, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "conv(pwn): cannot reserve %zu B of LDS", lds);
-    reserved = true;
-  }
-  const long M = (long)p.B * p.Ho * p.Wo;
-  g_last_variant = 3000 + KS * 10 + NTW;
-  hipLaunchKernelGGL((conv_pwn_kernel<KS, NTW>), dim3((unsigned)((M + 63) / 64), (unsigned)(p.Cout / (128 * NTW))), dim3(512), lds, st, p);
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(pwn): %s", hipGetErrorString(e_));
-  return 1;
-}
-template <typename T>
-static int dispatch_pwn(ConvP p, int ngroup, hipStream_t st) {
-  if constexpr (sizeof(T) != 2) return 0;
-  else {
-    const long M = (long)p.B * p.Ho * p.Wo;
-    if (!tune().pwn || p.k != 1 || p.stride != 1 || ngroup != 1 || M > tune().pwn_max_m || M < 1024 || p.Cout % 128 || p.res || p.addz || p.out_scale != 1.f ||
-        p.vec_store != 2 || (p.bias && !ey_aligned(p.bias, 16)))
-      return 0;
-    int K = 0;
-    for (int s2 = 0; s2 < p.nsrc; ++s2) {
-      if (p.srcC[s2] % 32) return 0;
-      K += p.srcC[s2];
-      const int up = p.srcUp[s2];
-      const long bytes = (((long)p.B * (p.H >> up) * (p.W >> up) - 1) * p.srcCs[s2] + p.srcC[s2]) * 2;
-      if (bytes >= (1L << 31)) return 0;
-      p.srcBytes[s2] = (unsigned)bytes;
-    }
-    if (K < 128 || K > 512 || M * p.yCs * 2 >= (1L << 31)) return 0;
-    p.NTpack = 8;
-    p.Ctot = K;
-    long ntw = tune().pwn_ntw;
-    if (ntw != 1 && ntw != 2) ntw = (p.Cout % 256 == 0 && (M + 63) / 64 >= 192) ? 2 : 1;  // 256-channel slabs once the pixel tiles alone fill the chip
-    if (p.Cout % 256) ntw = 1;
-#define PWN(KSV) if (K == 32 * KSV) return ntw == 2 ? pwn_launch<KSV, 2>(p, st) : pwn_launch<KSV, 1>(p, st);
-    PWN(4) PWN(6) PWN(8) PWN(12) PWN(16)
-#undef PWN
-    return 0;
-  }
-}
-
-// returns 1 if launched, 0 if this shape does not fit the weight-stationary kernel, <0 on error
-template <typename T>
-static int dispatch_ws(ConvP p, int ngroup, hipStream_t st) {
-  int nt = ws_pick_nt(p.Cout, p.Kpad, sizeof(T), (size_t)(tune().ws_lds_kb << 10));
-  if (!nt) nt = ws_pick_nt(p.Cout, p.Kpad, sizeof(T), 156 * 1024);
-  if (!nt) return 0;
-  if (p.k == 3 && nt < tune().ws_k3_minnt && nt < conv_nt(p.Cout)) return 0;
-  p.NTpack = conv_nt(p.Cout);
-  p.LSw = ws_ls(p.Kpad);
-  p.Ctot = 0; p.nsteps = 0;
-  for (int s2 = 0; s2 < p.nsrc; ++s2) { p.Ctot += p.srcC[s2]; p.nsteps += (p.srcC[s2] + 31) / 32; }
-  p.nsteps *= p.k * p.k;
-  if (p.nsrc == 1) { p.srcC[1] = p.srcC[0]; p.srcCs[1] = p.srcCs[0]; p.srcUp[1] = p.srcUp[0]; }
-  for (int s2 = 0; s2 < p.nsrc; ++s2) {
-    const int up = p.srcUp[s2];
-    const long npix = (long)p.B * (p.H >> up) * (p.W >> up);
-    const long bytes = ((npix - 1) * p.srcCs[s2] + p.srcC[s2] + (ngroup - 1) * p.srcG * 0) * (long)sizeof(T);
-    if (bytes >= (1L << 31) || p.srcG * (long)sizeof(T) * (ngroup - 1) >= (1L << 31)) return 0;  // beyond 32-bit buffer offsets: chunked kernel
-    p.srcBytes[s2] = (unsigned)bytes;
-  }
-  const bool ok = p.k == 1 ? ws_launch_nt<T, 1>(p, nt, ngroup, st) : ws_launch_nt<T, 3>(p, nt, ngroup, st);
-  if (!ok) return ey_set_error(EY_ELAUNCH, "conv: cannot reserve LDS for the weight tile");
-  hipError_t e_ = hipGetLastError();
-  if (e_ != hipSuccess) return ey_set_error(EY_ELAUNCH, "ey_conv2d(ws): %s", hipGetErrorString(e_));
-  return 1;
-}
-
-template <typename T>
-static int dispatch_conv(const ConvP& p, int ngroup, hipStream_t st) {
-  bool ok;
-  switch (conv_nt(p.Cout)) {
-    case 1: ok = launch_conv<T, 1>(p, ngroup, st); break;
-    case 2: ok = launch_conv<T, 2>(p, ngroup, st); break;
-    case 4: ok = launch_conv<T, 4>(p, ngroup, st); break;
-    case 5: ok = launch_conv<T, 5>(p, ngroup, st); break;
-    default: ok = launch_conv<T, 8>(p, ngroup, st); break;
-  }
-  if (!ok) return ey_set_error(EY_ELAUNCH, "conv: cannot reserve LDS for the weight tile");
-  EY_LAUNCH_CHECK("ey_conv2d");
-  return EY_OK;
-}
-
-// dispatch order: lean pointwise -> small-M -> 3x3 halo tile -> weight-stationary -> K-chunked fallback
-template <typename T>
-static int conv2d_typed(const ConvP& p, int ngroup, hipStream_t st) {
-  const int pw = dispatch_pw<T>(p, ngroup, st);
-  if (pw != 0) return pw < 0 ? pw : EY_OK;
-  const int pn = dispatch_pwn<T>(p, ngroup, st);
-  if (pn != 0) return pn < 0 ? pn : EY_OK;
-  const int pwr = dispatch_pwr<T>(p, ngroup, st);
-  if (pwr != 0) return pwr < 0 ? pwr : EY_OK;
-  const int sm = dispatch_small<T>(p, ngroup, st);
-  if (sm != 0) return sm < 0 ? sm : EY_OK;
-  const int cr = dispatch_c3r<T>(p, ngroup, st);
-  if (cr != 0) return cr < 0 ? cr : EY_OK;
-  const int cs = dispatch_c3s<T>(p, ngroup, st);
-  if (cs != 0) return cs < 0 ? cs : EY_OK;
-  const int cp = dispatch_c3p<T>(p, ngroup, st);
-  if (cp != 0) return cp < 0 ? cp : EY_OK;
-  const int tl = dispatch_tile<T>(p, ngroup, st);
-  if (tl != 0) return tl < 0 ? tl : EY_OK;
-  const int halo = dispatch_halo<T>(p, ngroup, st);
-  if (halo != 0) return halo < 0 ? halo : EY_OK;
-  const int ws = dispatch_ws<T>(p, ngroup, st);
-  if (ws != 0) return ws < 0 ? ws : EY_OK;
-  return dispatch_conv<T>(p, ngroup, st);
-}
-
-// the f16 and f32 instantiations live in two translation units (conv_f16.hip / conv_f32.hip) so that they compile in parallel
-int ey_conv2d_run_f16(const ConvP& p, int ngroup, hipStream_t st);
-int ey_conv2d_run_f32(const ConvP& p, int ngroup, hipStream_t st);
-#if EY_CONV_PART == 32
-int ey_conv2d_run_f32(const ConvP& p, int ngroup, hipStream_t st) { return conv2d_typed<float>(p, ngroup, st); }
-#else
-int ey_conv2d_run_f16(const ConvP& p, int ngroup, hipStream_t st) { return conv2d_typed<f16>(p, ngroup, st); }
-
-static int conv_desc_to_p(const ey_conv_desc* d, ConvP& p, int& ngroup) {
-  EY_CHECK(d, "conv: null desc");
-  EY_CHECK(d->dtype == EY_F16 || d->dtype == EY_F32, "conv: bad dtype %d", d->dtype);
-  const int es = d->dtype == EY_F16 ? 2 : 4;
-  EY_CHECK(d->B > 0 && d->H > 0 && d->W > 0 && d->Cout > 0, "conv: bad extent B=%d H=%d W=%d Cout=%d", d->B, d->H, d->W, d->Cout);
-  EY_CHECK((d->k == 1 || d->k == 3) && (d->stride == 1 || d->stride == 2) && d->pad == d->k / 2,
-           "conv: k=%d stride=%d pad=%d unsupported by the MFMA kernel (use ey_conv2d_direct)", d->k, d->stride, d->pad);
-  EY_CHECK(d->Ho == (d->H + 2 * d->pad - d->k) / d->stride + 1 && d->Wo == (d->W + 2 * d->pad - d->k) / d->stride + 1,
-           "conv: Ho/Wo (%d,%d) inconsistent with H/W (%d,%d)", d->Ho, d->Wo, d->H, d->W);
-  EY_CHECK(d->nsrc == 1 || d->nsrc == 2, "conv: nsrc=%d", d->nsrc);
-  EY_CHECK(d->w && d->y, "conv: null weight/output");
-  int Cin = 0;
-  for (int s = 0; s < d->nsrc; ++s) {
-    EY_CHECK(d->src[s], "conv: null src%d", s);
-    EY_CHECK(d->src_C[s] > 0 && d->src_C[s] % 8 == 0, "conv: src%d channels %d not a multiple of 8 (use ey_conv2d_direct)", s, d->src_C[s]);
-    EY_CHECK(d->src_cstride[s] >= d->src_C[s] && (d->src_cstride[s] * es) % 16 == 0 && ey_aligned(d->src[s], 16),
-             "conv: src%d view (cstride %d) not 16-byte aligned", s, d->src_cstride[s]);
-    EY_CHECK(d->src_up[s] == 0 || d->src_up[s] == 1, "conv: src_up must be 0/1");
-    EY_CHECK(!d->src_up[s] || (d->H % 2 == 0 && d->W % 2 == 0), "conv: upsampled source needs even H,W");
-    Cin += d->src_C[s];
-  }
-  EY_CHECK(d->y_cstride >= d->Cout, "conv: y_cstride %d < Cout %d", d->y_cstride, d->Cout);
-  EY_CHECK(!d->res || d->res_cstride >= d->Cout, "conv: res_cstride");
-  EY_CHECK(!d->addz || (d->addz_H > 0 && d->addz_W > 0 && d->addz_cstride >= d->Cout), "conv: addz extent/cstride");
-  ngroup = d->ngroup > 0 ? d->ngroup : 1;
-  EY_CHECK(ngroup == 1 || d->nsrc == 1, "conv: ngroup>1 needs a single source");
-  p.B = d->B; p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout; p.k = d->k; p.stride = d->stride;
-  p.pad = d->pad; p.act = d->act; p.nsrc = d->nsrc;
-  for (int s = 0; s < 2; ++s) {
-    p.src[s] = s < d->nsrc ? d->src[s] : nullptr;
-    p.srcC[s] = s < d->nsrc ? d->src_C[s] : 0;
-    p.srcCs[s] = s < d->nsrc ? d->src_cstride[s] : 0;
-    p.srcUp[s] = s < d->nsrc ? d->src_up[s] : 0;
-  }
-  p.w = d->w; p.bias = d->bias; p.y = d->y; p.yCs = d->y_cstride; p.res = d->res; p.resCs = d->res_cstride;
-  p.out_scale = d->out_scale; p.addz = d->addz; p.addzCs = d->addz_cstride; p.Hz = d->addz_H; p.Wz = d->addz_W;
-  p.zsy = d->addz ? (float)d->addz_H / (float)d->Ho : 0.f; p.zsx = d->addz ? (float)d->addz_W / (float)d->Wo : 0.f; p.srcG = d->src_gstride; p.yG = d->y_gstride;
-  p.wG = d->w_gstride; p.wGmax = d->w_gmax > 0 ? d->w_gmax : 0;
-  p.Kpad = conv_kpad(Cin, d->k, es);
-  p.xcd = 0;
-  p.nchunks = 0;
-  for (int s2 = 0; s2 < d->nsrc; ++s2) p.nchunks += (d->src_C[s2] + CONV_CH - 1) / CONV_CH;
-  p.nchunks *= d->k * d->k;
-  const int va = 4 * es;  // 4-element vector access alignment
-  p.vec_store = d->Cout % 4 == 0 && (d->y_cstride * es) % va == 0 && ey_aligned(d->y, va) && (d->y_gstride * es) % va == 0 &&
-                (!d->res || ((d->res_cstride * es) % va == 0 && ey_aligned(d->res, va))) &&
-                (!d->addz || ((d->addz_cstride * es) % va == 0 && ey_aligned(d->addz, va))) && (!d->bias || ey_aligned(d->bias, 16));
-  if (p.vec_store && (d->y_cstride * es) % 16 == 0 && ey_aligned(d->y, 16) && (d->y_gstride * es) % 16 == 0 &&
-      (!d->res || ((d->res_cstride * es) % 16 == 0 && ey_aligned(d->res, 16))))
-    p.vec_store = 2;  // 16-byte epilogue accesses allowed
-  return EY_OK;
-}
-
-extern "C" int ey_conv2d(const ey_conv_desc* d, ey_stream_t stream) {
-  ConvP p;
-  int ngroup = 1;
-  const int rc = conv_desc_to_p(d, p, ngroup);
-  if (rc != EY_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  g_last_variant = 0;
-  return d->dtype == EY_F16 ? ey_conv2d_run_f16(p, ngroup, st) : ey_conv2d_run_f32(p, ngroup, st);
-}
-
-// ---- two chained pointwise convs (conv_pwc_kernel): the second reads exactly what the first writes
-extern "C" int ey_conv_pw_pair(const ey_conv_desc* first, const ey_conv_desc* second, ey_stream_t stream) {
-  ConvP p, q;
-  int g1 = 1, g2 = 1;
-  int rc = conv_desc_to_p(first, p, g1);
-  if (rc != EY_OK) return rc;
-  rc = conv_desc_to_p(second, q, g2);
-  if (rc != EY_OK) return rc;
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int nt = conv_nt(p.Cout);
-  const bool fits = tune().pwc && first->dtype == EY_F16 && second->dtype == EY_F16 && g1 == 1 && g2 == 1 && p.k == 1 && q.k == 1 && p.stride == 1 && q.stride == 1 &&
-                    p.nsrc == 1 && q.nsrc == 1 && !p.srcUp[0] && !q.srcUp[0] && (p.Cout == 64 || p.Cout == 128) && q.Cout == p.Cout && q.srcC[0] == p.Cout &&
-                    p.srcC[0] % 32 == 0 && p.srcC[0] <= 128 && q.src[0] == p.y && q.srcCs[0] == p.yCs && q.B == p.B && q.H == p.Ho && q.W == p.Wo && !q.res && !q.addz &&
-                    q.y != p.y && p.vec_store == 2 && q.vec_store == 2 && M <= tune().pw_m && nt * 16 == p.Cout;
-  if (!fits) return ey_set_error(EY_EUNSUPPORTED, "conv_pw_pair: shapes outside the chained kernel (f16, 1x1 -> 1x1, 64 or 128 channels, small maps)");
-  for (ConvP* c : {&p, &q}) {
-    const long bytes = (((long)c->B * c->H * c->W - 1) * c->srcCs[0] + c->srcC[0]) * 2;
-    if (bytes >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "conv_pw_pair: view larger than 2 GiB");
-    c->srcBytes[0] = (unsigned)bytes;
-    c->NTpack = nt;
-    c->ntile = (M + 15) / 16;
-  }
-  const dim3 grid((unsigned)((p.ntile + 3) / 4));
-  const bool ag = tune().pwc == 2;
-  if (nt == 4) {
-    if (ag) hipLaunchKernelGGL((conv_pwc_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, p, q);
-    else hipLaunchKernelGGL((conv_pwc_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, p, q);
-  } else {
-    if (ag) hipLaunchKernelGGL((conv_pwc_kernel<8, true>), grid, dim3(256), 0, (hipStream_t)stream, p, q);
-    else hipLaunchKernelGGL((conv_pwc_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, p, q);
-  }
-  EY_LAUNCH_CHECK("ey_conv_pw_pair");
-  return EY_OK;
-}
-
-
-// ---- chained pointwise pair (see conv_pw2_kernel)
-extern "C" int ey_conv_chain_kperm(int Cmid, int* perm, int perm_len) {
-  const int nt1 = conv_nt(Cmid);
-  EY_CHECK(Cmid == 16 * nt1 && perm, "chain_kperm: Cmid=%d must be a whole channel tile (16, 32, 64, 80, 128)", Cmid);
-  const int ks2 = (4 * nt1 + 7) / 8;
-  EY_CHECK(perm_len == 32 * ks2, "chain_kperm: perm_len must be %d", 32 * ks2);
-  for (int s2 = 0; s2 < ks2; ++s2)
-    for (int g = 0; g < 4; ++g)
-      for (int j = 0; j < 8; ++j) {
-        const int idx = 8 * s2 + j;
-        perm[32 * s2 + 8 * g + j] = idx < 4 * nt1 ? g * 4 * nt1 + idx : -1;  // -1: zero column
-      }
-  return EY_OK;
-}
-extern "C" int ey_conv_chain_klen(int Cmid) { const int nt1 = conv_nt(Cmid); return Cmid == 16 * nt1 ? 32 * ((4 * nt1 + 7) / 8) : 0; }
-
-template <int NT1, int KS1, int NT2>
-static int pw2_launch(const ConvP& p, const ChainP& q, hipStream_t st) {
-  static int occ = 0;
-  if (!occ) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv_pw2_kernel<NT1, KS1, NT2>, 256, 0) != hipSuccess || n < 1) n = 1;
-    occ = n > 4 ? 4 : n;
-  }
-  long gx = 256L * occ / tune().grid_div;
-  if (gx > (p.ntile + 3) / 4) gx = (p.ntile + 3) / 4;
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((conv_pw2_kernel<NT1, KS1, NT2>), dim3((unsigned)gx), dim3(256), 0, st, p, q);
-  EY_LAUNCH_CHECK("ey_conv_pw_chain");
-  return EY_OK;
-}
-
-extern "C" int ey_conv_pw_chain(int dtype, int B, int H, int W, int Cin, int Cmid, int Cout, const void* x, int x_cstride, const void* w1_packed, const float* b1,
-                                int act1, const void* w2_packed, const float* b2, int act2, void* y, int y_cstride, ey_stream_t stream) {
-  EY_CHECK(dtype == EY_F16, "conv_pw_chain: f16 only");
-  EY_CHECK(x && w1_packed && w2_packed && y && B > 0 && H > 0 && W > 0, "conv_pw_chain: bad arguments");
-  const int nt1 = conv_nt(Cmid), nt2 = conv_nt(Cout), ks1 = (Cin + 31) / 32;
-  // two shapes of the Detect class tower (head.py:59,68-70; c3 = max(ch[0], min(nc, 100))): nc = 80 -> 80 -> 80 -> 80, and small class
-  // counts (GC10-DET, nc = 10: c3 = 64) -> 64 -> 64 -> nc <= 16
-  const bool wide = nt1 == 5 && Cmid == 80 && nt2 == 5 && Cout <= 80 && Cout % 4 == 0 && ks1 == 3 && Cin % 8 == 0;
-  const bool narrow = nt1 == 4 && Cmid == 64 && nt2 == 1 && Cout >= 1 && Cout <= 16 && ks1 == 2 && Cin % 8 == 0;
-  if (!wide && !narrow)
-    return ey_set_error(EY_EUNSUPPORTED, "conv_pw_chain: built for Cin 72..96 -> 80 -> <= 80 and Cin 40..64 -> 64 -> <= 16 (got %d -> %d -> %d)", Cin, Cmid, Cout);
-  EY_CHECK(x_cstride >= Cin && (x_cstride * 2) % 16 == 0 && ey_aligned(x, 16) && y_cstride >= Cout && (y_cstride * 2) % 8 == 0 && ey_aligned(y, 8), "conv_pw_chain: view alignment");
-  (void)0;
-  const long M = (long)B * H * W, bytes = ((M - 1) * x_cstride + Cin) * 2L;
-  EY_CHECK(bytes < (1L << 31) && M < (1L << 27), "conv_pw_chain: tensor too large");
-  ConvP p;
-  p.B = B; p.H = H; p.W = W; p.Ho = H; p.Wo = W; p.Cout = Cmid; p.act = act1; p.nsrc = 1;
-  p.src[0] = x; p.srcC[0] = Cin; p.srcCs[0] = x_cstride; p.srcBytes[0] = (unsigned)bytes;
-  p.w = w1_packed; p.bias = b1; p.Kpad = conv_kpad(Cin, 1, 2); p.ntile = (M + 15) / 16;
-  ChainP q;
-  q.w2 = w2_packed; q.b2 = b2; q.act2 = act2; q.Cout2 = Cout; q.Kpad2 = conv_kpad(ey_conv_chain_klen(Cmid), 1, 2); q.y2 = y; q.y2Cs = y_cstride;
-  return wide ? pw2_launch<5, 3, 5>(p, q, (hipStream_t)stream) : pw2_launch<4, 2, 1>(p, q, (hipStream_t)stream);
-}
-
-// Which kernel instantiation ey_conv2d launches for a shape (profiling / documentation only): kind*1000 + NT*10 + MT,
-// kind 3 = conv_small_kernel<T,NT,BATCH> (last digit = BATCH), 2 = conv3_halo_kernel<T,NT,stride>,
-// 1 = conv_ws_kernel<T,NT,MT,k>, 0 = conv_igemm_kernel<T,NT,MT>.
-extern "C" int ey_conv_variant(int dtype, int Cout, int Cin, int k, int stride, int plain_single_source, long M, int ngroup) {
-  const int es = dtype == EY_F16 ? 2 : 4, Kpad = conv_kpad(Cin, k, es);
-  if (small_ok(Cout, Kpad, k, M, es)) return 3000 + small_pick_nt(Cout, es) * 10 + (es == 2 ? 8 : 4);
-  if (k == 3 && plain_single_source && Cin <= 64 && Cin >= 48) {
-    ConvP p;
-    p.Cout = Cout; p.srcC[0] = Cin; p.Kpad = Kpad;
-    const int MT = stride == 1 ? 2 : 1, HR = 7 * stride + 3, HC = (16 * MT - 1) * stride + 3;
-    if ((long)HR * HC * (Cin >> 3) <= 512L * 10) {
-      const int nt = es == 2 ? halo_pick_nt<f16>(p, stride) : halo_pick_nt<float>(p, stride);
-      if (nt) return 2000 + nt * 10 + MT;
-    }
-  }
-  int nt = ws_pick_nt(Cout, Kpad, es, 76 * 1024);
-  if (!nt) nt = ws_pick_nt(Cout, Kpad, es, 156 * 1024);
-  if (nt) return 1000 + nt * 10 + (M >= 300000 ? 2 : 1);
-  nt = conv_nt(Cout);
-  const int ntiles = (Cout + 16 * nt - 1) / (16 * nt);
-  return nt * 10 + ((M + 127) / 128 * ntiles * (ngroup > 0 ? ngroup : 1) >= 512 ? 2 : 1);
-}
-extern "C" int ey_conv_pack_nt(int Cout) { return conv_nt(Cout); }
-// kind*1000 + NT*10 + x of the kernel the last ey_conv2d on this thread launched (profiling labels and tests): kind 3 = conv_pwn<KS,NTW>
-// (KS*10 + NTW), 4 = conv_pw<T,NT,..> (x = number of sources), 5 = conv_pwr<T,NT,KS>, 6 = conv3_tile<T,NT,S>, 7 = conv3r<NT,S>,
-// 8 = conv3s<NT,MT,..> (NT*100 + MT*10 + 5 if the 9-deep ring + S), 9 = conv3p<NT,FAST>, 10 = conv_small<T,NT,BATCH>, 11 = conv3_halo<T,NT,S>,
-// 12 = conv_ws<T,NT,MT,KS> (NT*100 + MT*10 + KS), 13 = conv_igemm<T,NT,MT>.
-extern "C" int ey_conv_last_variant(void) { return g_last_variant; }
-#endif  // EY_CONV_PART

@@ -18,7 +18,7 @@ NONE, SILU, RELU = R.ACT_NONE, R.ACT_SILU, R.ACT_RELU
 
 # ---------------------------------------------------------------------------------------------- host-side mirrors of ey_block_compile
 def conv_nt(cout):
-    """conv_nt of csrc/conv_igemm.inc.h: 16-channel row blocks per packed block tile."""
+    """conv_nt of csrc/conv_dispatch.inc.h: 16-channel row blocks per packed block tile."""
     for lim, nt in ((16, 1), (32, 2), (64, 4), (80, 5), (128, 8)):
         if cout <= lim:
             return nt
