@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libedgeyolo_hip.so")
 F16, F32 = 0, 1
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
 ATTN_AREA_F32, ATTN_AREA_F16, ATTN_AREA_MFMA = 401, 402, 403  # ey_attention_last_variant of ey_area_attention
+ATTN_FLASH_MFMA, ATTN_FLASH_F32, ATTN_FLASH_F16 = 500, 501, 502  # ... of ey_flash_attention (MFMA: + head_dim)
+DWG_PLAIN, DWG_GATE, DWG_RESIDUAL = 0, 1, 2  # ey_dwconv_gate epilogues
 
 
 class HipLibraryError(RuntimeError):
@@ -106,6 +108,13 @@ SIGNATURES = {
     "ey_softmax_attention": (_i, [_i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp]),
     "ey_attention_last_variant": (_i, []),
     "ey_area_attention": (_i, [_i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_flash_attention": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_dwconv_gate": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ey_sigmoid_gate": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_gelu": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_cmlp": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_layernorm_channels": (_i, [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ey_unpool2_layernorm": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

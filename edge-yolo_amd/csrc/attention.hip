@@ -599,3 +599,179 @@ extern "C" int ey_area_attention(int dtype, int B, int N, int area, int heads, i
   EY_LAUNCH_CHECK("ey_area_attention");
   return EY_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Flash attention core over ALL tokens of an image (GlobalSparseAttn.forward of the LGL block, reference block.py:3147-3152):
+//   y[n][h*HD + c] = sum_m softmax_m(scale * q[n][h*HD:].k[m][h*HD:]) v[m][h*HD + c],   HD in {16, 32, 64}.
+// The loop of area_attn_mfma_kernel with the head dim as a template parameter (that kernel itself is left as it is: its hd = 32
+// code object is pinned by tests): a 256-thread workgroup takes 64 queries of one (image, head), 16 per wave, Q fragments in
+// registers; keys stream through LDS in tiles of 64 (zero-filled past N and masked to -inf, so a padded key never scores);
+// online softmax with fp32 running max / sum per query.  LDS is 2 x 64 x (HD + 8) f16 whatever N is.
+//   S^T = K Q^T     HD 32 / 64: one / two 16x16x32 MFMAs per 16-key block.  HD 16: ONE v_mfma_f32_16x16x16_f16 -- the 16-deep form has
+//                   the same result layout at the same cycles as a half-empty 32-deep one, and needs no zero half in the K rows of LDS
+//                   nor in the Q registers (8-byte instead of 16-byte fragment reads)
+//   Y^T += V^T P^T  HD/16 output blocks x 2 steps of 32 keys, contraction in the order the scores already sit in the registers
+template <int HD>
+__global__ __launch_bounds__(256) void flash_attn_kernel(int N, int heads, int qtiles, float scale, const f16* __restrict__ q, int qCs,
+                                                          const f16* __restrict__ k, int kCs, const f16* __restrict__ v, int vCs, f16* __restrict__ y, int yCs) {
+  constexpr int LS = HD + 8;     // LDS row stride (f16): the four 4-row steps of a wave's 2-byte V gathers land 0/16/32/48 dwords apart (mod 64) for HD 16, 32 and 64 -> 32 distinct banks
+  constexpr int NCB = HD / 16;   // 16-channel output blocks
+  constexpr int NQS = HD / 32;   // 32-deep contraction steps of q.k (0: the 16-deep MFMA)
+  constexpr int OCT = HD / 8;    // 16-byte vectors per row
+  __shared__ __attribute__((aligned(16))) f16 Ks[AA_KT * LS];
+  __shared__ __attribute__((aligned(16))) f16 Vs[AA_KT * LS];
+  const int qt = blockIdx.x % qtiles, bh = blockIdx.x / qtiles;
+  const int b = bh / heads, h = bh - b * heads;
+  const long p0 = (long)b * N;  // first token of the image
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+  const int n = (qt * 4 + wave) * 16 + r;  // this lane's query
+  Vec8<f16> qf[NQS ? NQS : 1];
+  f16x4 q4 = (f16x4)(f16)0;
+  if constexpr (NQS == 0) {
+    qf[0].zero();
+    if (n < N) q4 = *reinterpret_cast<const f16x4*>(q + (p0 + n) * qCs + h * HD + 4 * g);
+  } else {
+#pragma unroll
+    for (int s = 0; s < NQS; ++s) {
+      if (n < N) qf[s].load(q + (p0 + n) * qCs + h * HD + 32 * s + 8 * g);
+      else qf[s].zero();
+    }
+  }
+  const f16* kp = k + p0 * kCs + h * HD;
+  const f16* vp = v + p0 * vCs + h * HD;
+  float m = -INFINITY, l = 0.f;
+  f32x4 acc[NCB];
+#pragma unroll
+  for (int cb = 0; cb < NCB; ++cb) acc[cb] = (f32x4)0.f;
+  for (int t0 = 0; t0 < N; t0 += AA_KT) {
+#pragma unroll
+    for (int i = tid; i < AA_KT * OCT; i += 256) {  // staging: 64 keys x OCT vectors of K and of V
+      const int skey = i / OCT, soct = i % OCT;
+      Vec8<f16> a, c;
+      if (t0 + skey < N) {
+        a.load(kp + (long)(t0 + skey) * kCs + 8 * soct);
+        c.load(vp + (long)(t0 + skey) * vCs + 8 * soct);
+      } else {
+        a.zero();
+        c.zero();
+      }
+      a.store(Ks + skey * LS + 8 * soct);
+      c.store(Vs + skey * LS + 8 * soct);
+    }
+    __syncthreads();
+    f32x4 S[4];
+    float mt = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      S[kb] = (f32x4)0.f;
+      if constexpr (NQS == 0) {
+        const f16x4 kf = *reinterpret_cast<const f16x4*>(Ks + (kb * 16 + r) * LS + 4 * g);
+        S[kb] = __builtin_amdgcn_mfma_f32_16x16x16f16(kf, q4, S[kb], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int s = 0; s < NQS; ++s) {
+          Vec8<f16> kf;
+          kf.load(Ks + (kb * 16 + r) * LS + 32 * s + 8 * g);
+          S[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf.v, qf[s].v, S[kb], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (t0 + kb * 16 + 4 * g + t >= N) S[kb][t] = -INFINITY;  // padded keys
+        mt = fmaxf(mt, S[kb][t]);
+      }
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 16));
+    mt = fmaxf(mt, __shfl_xor(mt, 32));
+    const float mn = fmaxf(m, mt);
+    const float mu = mn == -INFINITY ? 0.f : mn;  // (every tile holds a real key: mn is finite; the guard is for exp(-inf - -inf))
+    const float alpha = __expf((m - mu) * scale);  // 0 on the first tile (m = -inf)
+    float ps = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { S[kb][t] = __expf((S[kb][t] - mu) * scale); ps += S[kb][t]; }
+    ps += __shfl_xor(ps, 16);
+    ps += __shfl_xor(ps, 32);
+    l = l * alpha + ps;
+    m = mn;
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) acc[cb] *= alpha;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      Vec8<f16> pf;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { pf.v[t] = (f16)S[2 * s][t]; pf.v[4 + t] = (f16)S[2 * s + 1][t]; }
+      const f16* vs = Vs + (32 * s + 4 * g) * LS + r;
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        Vec8<f16> vf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vf.v[j] = vs[(16 * (j >> 2) + (j & 3)) * LS + cb * 16];
+        acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf.v, pf.v, acc[cb], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  if (n < N) {
+    const float inv = __builtin_amdgcn_rcpf(l);
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      const f16x4 o = {(f16)(acc[cb][0] * inv), (f16)(acc[cb][1] * inv), (f16)(acc[cb][2] * inv), (f16)(acc[cb][3] * inv)};
+      *reinterpret_cast<f16x4*>(y + (p0 + n) * yCs + h * HD + cb * 16 + 4 * g) = o;
+    }
+  }
+}
+
+#define FA_VALU_MAX_TOKENS ((160 * 1024 / 4 - 4 * 64) / 4)  // area_attn_kernel keeps 4 fp32 score rows of N in LDS: 10176
+extern "C" int ey_flash_attention(int dtype, int B, int N, int heads, int hd, float scale, const void* q, int q_cstride, const void* k, int k_cstride,
+                                  const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream) {
+  g_attn_variant = 0;
+  EY_CHECK(q && k && v && y, "flash_attention: null pointer");
+  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "flash_attention: bad dtype");
+  EY_CHECK(B > 0 && N > 0 && heads > 0 && hd > 0, "flash_attention: B=%d N=%d heads=%d hd=%d", B, N, heads, hd);
+  if (hd > 64) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: head_dim %d > 64", hd);
+  EY_CHECK(q_cstride >= heads * hd && k_cstride >= heads * hd && v_cstride >= heads * hd && y_cstride >= heads * hd, "flash_attention: cstride");
+  const long groups = (long)B * heads;
+  hipStream_t st = (hipStream_t)stream;
+  const bool mfma = dtype == EY_F16 && (hd == 16 || hd == 32 || hd == 64) && ey_aligned(q, 16) && ey_aligned(k, 16) && ey_aligned(v, 16) && ey_aligned(y, 8) &&
+                    q_cstride % 8 == 0 && k_cstride % 8 == 0 && v_cstride % 8 == 0 && y_cstride % 4 == 0;
+  if (mfma) {
+    const int qtiles = (N + 63) / 64;
+    if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: grid too large");
+    const dim3 grid((unsigned)(groups * qtiles));
+    g_attn_variant = EY_ATTN_FLASH_MFMA + hd;
+#define FLASH(HD)                                                                                                                                  \
+  hipLaunchKernelGGL(flash_attn_kernel<HD>, grid, dim3(256), 0, st, N, heads, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride, \
+                     (const f16*)v, v_cstride, (f16*)y, y_cstride)
+    if (hd == 16) FLASH(16);
+    else if (hd == 32) FLASH(32);
+    else FLASH(64);
+#undef FLASH
+    EY_LAUNCH_CHECK("ey_flash_attention(mfma)");
+    return EY_OK;
+  }
+  // fp32, unaligned views, other head dims: the VALU area kernel with one area per image
+  if (N > FA_VALU_MAX_TOKENS)
+    return ey_set_error(EY_EUNSUPPORTED, "flash_attention: %d tokens exceed the %d-token limit of the VALU kernel (fp32, unaligned views, head_dim not 16/32/64)", N,
+                        FA_VALU_MAX_TOKENS);
+  const size_t lds = (4 * 64 + 4 * (size_t)N) * sizeof(float);
+  const int qtiles = (N + AA_VQ - 1) / AA_VQ;
+  if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: grid too large");
+  const dim3 grid((unsigned)(groups * qtiles));
+  if (dtype == EY_F16) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
+    g_attn_variant = EY_ATTN_FLASH_F16;
+    hipLaunchKernelGGL(area_attn_kernel<f16>, grid, dim3(256), lds, st, N, heads, hd, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride,
+                       (const f16*)v, v_cstride, (f16*)y, y_cstride);
+  } else {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
+    g_attn_variant = EY_ATTN_FLASH_F32;
+    hipLaunchKernelGGL(area_attn_kernel<float>, grid, dim3(256), lds, st, N, heads, hd, qtiles, scale, (const float*)q, q_cstride, (const float*)k,
+                       k_cstride, (const float*)v, v_cstride, (float*)y, y_cstride);
+  }
+  EY_LAUNCH_CHECK("ey_flash_attention");
+  return EY_OK;
+}

@@ -824,6 +824,163 @@ def hypergraph_conv(mod, x, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------------------------- LGL block (YOLOv13 DSC3K2_LGL)
+def _out_like(x, out, what, hw=None):
+    B, c, H, W = x.shape
+    H, W = hw or (H, W)
+    if out is None:
+        return L.empty_nhwc(B, c, H, W, x.dtype, x.device)
+    if not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H, W) or out.dtype != x.dtype:
+        raise ValueError(f"{what}: out= must be an NHWC view of shape {(B, c, H, W)} {x.dtype}, got {tuple(out.shape)} {out.dtype}")
+    return out
+
+
+def flash_attention(q, k, v, heads, scale, out=None):
+    """Softmax attention over all H*W tokens of each image (ey_flash_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim."""
+    L.require_device(q, "flash_attention")
+    _no_block("flash attention")
+    q, k, v = L.as_nhwc(q), L.as_nhwc(k), L.as_nhwc(v)
+    B, c, H, W = q.shape
+    N = H * W
+    if c % heads or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"flash_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
+    out = _out_like(q, out, "flash_attention")
+    hd = c // heads
+    rec = _tr("area_attn_kernel", _nb(q, k, v, out), 4.0 * B * heads * N * N * hd, note=f"{H}x{W} h{heads} hd{hd}")
+    with rec:
+        L.check(L.lib().ey_flash_attention(L.dtype_code(q.dtype), B, N, heads, hd, float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(), L.cstride(k),
+                                           v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream()), "ey_flash_attention")
+        if TRACE is not None and L.lib().ey_attention_last_variant() == L.ATTN_FLASH_MFMA + hd:
+            rec.kernel = f"flash_attn_kernel<{hd}>"
+    return out
+
+
+def dwconv_gate(mod, x, conv, mode, out=None, tag=""):
+    """Depthwise kxk + bias of the nn.Conv2d `conv` (k 3 or 9) with the epilogue `mode` (L.DWG_PLAIN / _GATE / _RESIDUAL), ey_dwconv_gate."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "dwconv_gate")
+    _no_block("gated depthwise conv")
+    B, c, H, W = x.shape
+    k = conv.kernel_size[0]
+
+    def build():
+        wk = conv.weight.detach().float().view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)  # [k][k][C]
+        return wk, (conv.bias.detach().float().to(x.device).contiguous() if conv.bias is not None else None)
+
+    wk, bias = mod._packed(_dev_key(x, "dwg" + tag), build)
+    out = _out_like(x, out, "dwconv_gate")
+    with _tr(f"lgl_dw_kernel<{k}>", _nb(x, out), 2.0 * x.numel() * k * k, note=f"C{c} {H}x{W} mode{mode}"):
+        L.check(L.lib().ey_dwconv_gate(L.dtype_code(x.dtype), B, H, W, c, k, mode, x.data_ptr(), L.cstride(x), wk.data_ptr(),
+                                       bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out), L.stream()), "ey_dwconv_gate")
+    return out
+
+
+def sigmoid_gate(x, g, out=None):
+    """out = x + x * (sigmoid(g) - 1/2) (ey_sigmoid_gate)."""
+    x, g = L.as_nhwc(as_tensor(x)), L.as_nhwc(g)
+    L.require_device(x, "sigmoid_gate")
+    _no_block("sigmoid gate")
+    B, c, H, W = x.shape
+    if g.shape != x.shape or g.dtype != x.dtype:
+        raise ValueError(f"sigmoid_gate: x {tuple(x.shape)} {x.dtype}, g {tuple(g.shape)} {g.dtype}")
+    out = _out_like(x, out, "sigmoid_gate")
+    with _tr("lgl_gate_kernel", _nb(x, g, out), 4.0 * x.numel()):
+        L.check(L.lib().ey_sigmoid_gate(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), g.data_ptr(), L.cstride(g), out.data_ptr(),
+                                        L.cstride(out), L.stream()), "ey_sigmoid_gate")
+    return out
+
+
+def gelu(x, out=None):
+    """Exact (erf) GELU (ey_gelu); out= may be x itself."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "gelu")
+    _no_block("GELU")
+    B, c, H, W = x.shape
+    out = _out_like(x, out, "gelu")
+    with _tr("lgl_gelu_kernel", _nb(x, out), 8.0 * x.numel()):
+        L.check(L.lib().ey_gelu(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()), "ey_gelu")
+    return out
+
+
+def cmlp(mod, x, fc1, fc2, bn=None, gate=False, out=None):
+    """fc2(GELU(fc1(bn(x)))) of a CMlp whose convs are grouped per channel (ey_cmlp), optionally gated: x + x * (sigmoid(.) - 1/2).
+    mod: the module caching the packed weights; fc1 / fc2: nn.Conv2d(C, rC, 3, 1, 1, groups=C) / (rC, C, 3, 1, 1, groups=C)."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "cmlp")
+    _no_block("CMlp")
+    B, c, H, W = x.shape
+    hid = fc1.out_channels
+    if (fc1.groups != c or fc2.groups != c or fc1.in_channels != c or fc2.out_channels != c or hid % c or fc2.in_channels != hid
+            or fc1.kernel_size != (3, 3) or fc2.kernel_size != (3, 3) or fc1.padding != (1, 1) or fc2.padding != (1, 1)):
+        raise NotImplementedError("cmlp: the kernel takes Conv2d(C, rC, 3, pad 1, groups=C) -> GELU -> Conv2d(rC, C, 3, pad 1, groups=C)")
+    r = hid // c
+
+    def build():
+        f = lambda t: t.detach().float().to(x.device).contiguous()  # noqa: E731
+        w1 = fc1.weight.detach().float().view(c, r, 9).permute(1, 2, 0)  # [r][9][C]
+        w2 = fc2.weight.detach().float().view(c, r, 9).permute(1, 2, 0)
+        b1 = fc1.bias.detach().float().view(c, r).t() if fc1.bias is not None else torch.zeros(r, c)
+        b2 = fc2.bias.detach().float() if fc2.bias is not None else torch.zeros(c)
+        if bn is None:
+            return None, None, f(w1), f(b1), f(w2), f(b2)
+        s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        return f(s), f(bn.bias.detach().float() - bn.running_mean.detach().float() * s), f(w1), f(b1), f(w2), f(b2)
+
+    sc, sh, w1, b1, w2, b2 = mod._packed(_dev_key(x, "cmlp"), build)
+    out = _out_like(x, out, "cmlp")
+    with _tr("lgl_cmlp_kernel", _nb(x, out), 2.0 * x.numel() * r * 9 * 10, note=f"C{c} r{r} {H}x{W}"):
+        L.check(L.lib().ey_cmlp(L.dtype_code(x.dtype), B, H, W, c, r, int(bool(gate)), x.data_ptr(), L.cstride(x), sc.data_ptr() if sc is not None else None,
+                                sh.data_ptr() if sh is not None else None, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(),
+                                L.cstride(out), L.stream()), "ey_cmlp")
+    return out
+
+
+def _ln_params(mod, x, ln, tag):
+    c = x.shape[1]
+    if tuple(ln.normalized_shape) != (c,):
+        raise ValueError(f"layernorm: nn.LayerNorm{tuple(ln.normalized_shape)} on {c} channels")
+
+    def build():
+        w = ln.weight.detach().float() if ln.weight is not None else torch.ones(c)
+        b = ln.bias.detach().float() if ln.bias is not None else torch.zeros(c)
+        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
+
+    return mod._packed(_dev_key(x, "ln" + tag), build)
+
+
+def layernorm_channels(mod, x, ln, pool=False, out=None, tag=""):
+    """nn.LayerNorm `ln` over the channels of each pixel of x (B,C,H,W) (ey_layernorm_channels); pool: followed by the ceil-mode 2x2
+    average pool in the same kernel -> (B,C,ceil(H/2),ceil(W/2))."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "layernorm_channels")
+    _no_block("LayerNorm")
+    B, c, H, W = x.shape
+    g, b = _ln_params(mod, x, ln, tag)
+    out = _out_like(x, out, "layernorm_channels", ((H + 1) // 2, (W + 1) // 2) if pool else None)
+    with _tr("lgl_layernorm_kernel", _nb(x, out), 8.0 * x.numel(), note=f"C{c} {H}x{W}{' +pool' if pool else ''}"):
+        L.check(L.lib().ey_layernorm_channels(L.dtype_code(x.dtype), B, H, W, c, float(ln.eps), int(bool(pool)), x.data_ptr(), L.cstride(x), g.data_ptr(),
+                                              b.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_layernorm_channels")
+    return out
+
+
+def unpool2_layernorm(mod, t, deconv, ln, H, W, out=None, tag="up"):
+    """LayerNorm(resize(ConvTranspose2d_{k2,s2,depthwise}(t))) (ey_unpool2_layernorm): t (B,C,ceil(H/2),ceil(W/2)) -> (B,C,H,W)."""
+    t = L.as_nhwc(as_tensor(t))
+    L.require_device(t, "unpool2_layernorm")
+    _no_block("un-pool + LayerNorm")
+    B, c, Hs, Ws = t.shape
+    if (deconv.kernel_size != (2, 2) or deconv.stride != (2, 2) or deconv.groups != c or deconv.in_channels != c or deconv.out_channels != c
+            or deconv.bias is not None or deconv.padding != (0, 0) or deconv.output_padding != (0, 0)):
+        raise NotImplementedError("unpool2_layernorm: the kernel takes a depthwise ConvTranspose2d(C, C, 2, 2, groups=C, bias=False)")
+    g, b = _ln_params(mod, t, ln, tag)
+    w = mod._packed(_dev_key(t, "unpool" + tag), lambda: deconv.weight.detach().float().view(c, 2, 2).permute(1, 2, 0).contiguous().to(t.device))  # [a][b][C]
+    out = _out_like(t, out, "unpool2_layernorm", (H, W))
+    with _tr("lgl_unpool_ln_kernel", _nb(t, out), 10.0 * out.numel(), note=f"C{c} {Hs}x{Ws}->{H}x{W}"):
+        L.check(L.lib().ey_unpool2_layernorm(L.dtype_code(t.dtype), B, Hs, Ws, H, W, c, float(ln.eps), t.data_ptr(), L.cstride(t), w.data_ptr(), g.data_ptr(),
+                                             b.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_unpool2_layernorm")
+    return out
+
+
 def head_decode(box, cls, stride, q, pred, a_off):
     """One pyramid level of the fused DGQP + DFL + decode; q = (w1[hid,20], b1, w2[hid], b2) fp32 device tensors or None."""
     L.require_device(box, "head_decode")

@@ -15,7 +15,8 @@ from ... import _lib as L
 
 __all__ = ("DFL", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
-           "DSC3K2", "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
+           "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
+           "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
 
 
 def _slot(buf, i, c):
@@ -662,6 +663,237 @@ class DSC3K2(C2f):
             self.m = nn.ModuleList(DSC3k(self.c, self.c, n=2, shortcut=shortcut, g=g, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n))
         else:
             self.m = nn.ModuleList(DSBottleneck(self.c, self.c, shortcut=shortcut, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n))
+
+
+
+# ----------------------------------------------------------------------------------------------- YOLOv13-LGL: Local-Global-Local block
+def _linear_folded(lin):
+    """nn.Linear on the channels of each pixel = a 1x1 conv: (w (out, in, 1, 1), b) in fp32."""
+    w = lin.weight.detach().float()
+    return w.view(*w.shape, 1, 1), (lin.bias.detach().float() if lin.bias is not None else torch.zeros(w.shape[0], device=w.device))
+
+
+class Mlp(_Packed):
+    """Token MLP fc2(GELU(fc1(x))) (reference block.py:3042-3058) on the channels of each pixel of an NHWC map: two 1x1 convs on the MFMA
+    conv with the exact-erf GELU kernel between them; `res` rides in fc2's epilogue.  drop is an inference no-op."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        if act_layer is not nn.GELU:
+            raise NotImplementedError("Mlp: only the exact GELU has a kernel")
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x, out=None, res=None):
+        h = ops.conv2d(self, [x], lambda: _linear_folded(self.fc1), 1, 1, 0, L.ACT_NONE, tag="fc1")
+        ops.gelu(h, out=h)
+        return ops.conv2d(self, [h], lambda: _linear_folded(self.fc2), 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="fc2")
+
+
+class CMlp(_Packed):
+    """Conv2d(c, rc, 3, groups=c) -> GELU -> Conv2d(rc, c, 3, groups=c) (reference block.py:3060-3076): no channel mixing, so one
+    per-channel stencil kernel (ey_cmlp) with the r hidden maps in registers.  `bn`: a BatchNorm2d applied to the input inside the kernel
+    (zero padding after it, as the reference pads); `gate`: return x + x * (sigmoid(.) - 1/2)."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        if act_layer is not nn.GELU:
+            raise NotImplementedError("CMlp: only the exact GELU has a kernel")
+        self.fc1 = nn.Conv2d(in_features, hidden_features, 3, padding=1, groups=in_features)
+        self.act = act_layer()
+        self.fc2 = nn.Conv2d(hidden_features, out_features, 3, padding=1, groups=in_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x, out=None, bn=None, gate=False):
+        return ops.cmlp(self, x, self.fc1, self.fc2, bn=bn, gate=gate, out=out)
+
+
+class LocalAgg(_Packed):
+    """reference block.py:3078-3096, three gated steps x <- x + x * (sigmoid(f(x)) - 1/2): f = dw9 (gate in the depthwise kernel's
+    epilogue); f = conv2(dw9(conv1(BN1(x)))) (BN1 folded into conv1, exact in front of a 1x1; the gate as its own launch); f = CMlp(BN2(x))
+    (one kernel, BN2 applied inside because the zero padding comes after it).  drop / drop_path are inference no-ops."""
+
+    def __init__(self, dim, mlp_ratio=4.0, drop=0.0, drop_path=0.0, act_layer=nn.GELU):
+        super().__init__()
+        self.pos_embed = nn.Conv2d(dim, dim, 9, padding=4, groups=dim)
+        self.norm1 = nn.BatchNorm2d(dim)
+        self.conv1 = nn.Conv2d(dim, dim, 1)
+        self.conv2 = nn.Conv2d(dim, dim, 1)
+        self.attn = nn.Conv2d(dim, dim, 9, padding=4, groups=dim)
+        self.drop_path = nn.Identity()
+        self.norm2 = nn.BatchNorm2d(dim)
+        mlp_hidden_dim = int(dim * mlp_ratio)
+        self.mlp = CMlp(in_features=dim, hidden_features=mlp_hidden_dim, act_layer=act_layer, drop=drop)
+        self.sg = nn.Sigmoid()
+
+    def _conv1(self):
+        bn = self.norm1
+        w, b = self.conv1.weight.detach().float(), self.conv1.bias.detach().float()
+        s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        sh = bn.bias.detach().float() - bn.running_mean.detach().float() * s
+        return w * s.view(1, -1, 1, 1), b + w.flatten(1) @ sh
+
+    def forward(self, x, out=None):
+        x = ops.dwconv_gate(self, x, self.pos_embed, L.DWG_GATE, tag="pos")
+        t = ops.conv2d(self, [x], self._conv1, 1, 1, 0, L.ACT_NONE, tag="conv1")
+        t = ops.dwconv_gate(self, t, self.attn, L.DWG_PLAIN, tag="attn")
+        g = ops.conv2d(self, [t], lambda: fold_bn(self.conv2.weight, self.conv2.bias, None), 1, 1, 0, L.ACT_NONE, tag="conv2")
+        x = ops.sigmoid_gate(x, g, out=g)
+        return self.mlp(x, out=out, bn=self.norm2, gate=True)
+
+
+class GlobalSparseAttn(_Packed):
+    """reference block.py:3098-3170: softmax attention over the tokens of the sr-pooled map, un-pooled by a depthwise transposed conv.
+    Here: [LayerNorm + ceil-mode 2x2 average pool] (one kernel, `norm` = the caller's LayerNorm) -> qkv 1x1 conv -> ey_flash_attention over
+    all Hs*Ws tokens -> [un-pool + (odd maps) bilinear resize + LayerNorm] (one kernel) -> proj 1x1 conv (+ `res`).  sr_ratio 1 or 2.
+    x: an NHWC (B,C,H,W) map, or the reference's tokens (B,H*W,C) with H and W."""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0.0, proj_drop=0.0, sr_ratio=1):
+        super().__init__()
+        self.num_heads = int(num_heads)
+        head_dim = dim // self.num_heads
+        self.scale = qk_scale or head_dim ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
+        self.sr = int(sr_ratio)
+        if self.sr > 2:
+            raise NotImplementedError("GlobalSparseAttn: sr_ratio 1 and 2 have kernels (the YAMLs use 2)")
+        if self.sr > 1:
+            self.sampler = nn.AvgPool2d(kernel_size=self.sr, stride=self.sr, ceil_mode=True)
+            self.LocalProp = nn.ConvTranspose2d(dim, dim, kernel_size=self.sr, stride=self.sr, groups=dim, bias=False)
+            self.norm = nn.LayerNorm(dim)
+        else:
+            self.sampler = nn.Identity()
+            self.LocalProp = nn.Identity()
+            self.norm = nn.Identity()
+
+    def forward(self, x, H=None, W=None, norm=None, out=None, res=None):
+        if x.dim() == 3:  # (B, N, C) contiguous tokens == an NHWC (B,C,H,W) map
+            B, N, C = x.shape
+            if N != H * W:
+                raise ValueError(f"input tokens {N} != H*W {H * W}")
+            y = self.forward(x.contiguous().view(B, H, W, C).permute(0, 3, 1, 2), norm=norm)
+            return y.permute(0, 2, 3, 1).reshape(B, N, C)
+        x = L.as_nhwc(ops.as_tensor(x))
+        B, C, H, W = x.shape
+        if C % self.num_heads:
+            raise ValueError(f"GlobalSparseAttn: {C} channels do not split into {self.num_heads} heads")
+        if self.sr > 1:
+            if norm is None:  # the ceil-mode pool only exists fused behind a LayerNorm (SelfAttn.norm1)
+                raise NotImplementedError("GlobalSparseAttn with sr_ratio 2 pools inside the LayerNorm kernel: pass norm=")
+            t = ops.layernorm_channels(self, x, norm, pool=True, tag="pre")
+        else:
+            t = ops.layernorm_channels(self, x, norm, tag="pre") if norm is not None else x
+        qkv = ops.conv2d(self, [t], lambda: _linear_folded(self.qkv), 1, 1, 0, L.ACT_NONE, tag="qkv")  # [q | k | v]
+        a = ops.flash_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], self.num_heads, self.scale)
+        if self.sr > 1:
+            a = ops.unpool2_layernorm(self, a, self.LocalProp, self.norm, H, W)
+        return ops.conv2d(self, [a], lambda: _linear_folded(self.proj), 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj")
+
+
+class SelfAttn(_Packed):
+    """reference block.py:3172-3196: x + dw3(x); x + attn(norm1(x)); x + mlp(norm2(x)) -- the token reshapes are free in NHWC, both
+    residual adds ride in the 1x1 convs' epilogues, norm1 runs inside the attention's pooling kernel."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop=0.0, attn_drop=0.0, drop_path=0.0, act_layer=nn.GELU,
+                 norm_layer=nn.LayerNorm, sr_ratio=1):
+        super().__init__()
+        if norm_layer is not nn.LayerNorm:
+            raise NotImplementedError("SelfAttn: only nn.LayerNorm has a kernel")
+        self.pos_embed = nn.Conv2d(dim, dim, 3, padding=1, groups=dim)
+        self.norm1 = norm_layer(dim)
+        self.attn = GlobalSparseAttn(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=drop, sr_ratio=sr_ratio)
+        self.drop_path = nn.Identity()
+        self.norm2 = norm_layer(dim)
+        mlp_hidden_dim = int(dim * mlp_ratio)
+        self.mlp = Mlp(in_features=dim, hidden_features=mlp_hidden_dim, act_layer=act_layer, drop=drop)
+
+    def forward(self, x, out=None):
+        x = ops.dwconv_gate(self, x, self.pos_embed, L.DWG_RESIDUAL, tag="pos")
+        x = self.attn(x, norm=self.norm1, res=x)
+        return self.mlp(ops.layernorm_channels(self, x, self.norm2, tag="n2"), out=out, res=x)
+
+
+class LGLBlock(nn.Module):
+    """reference block.py:3198-3210: LocalAgg (only with sr_ratio > 1) then SelfAttn."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop=0.0, attn_drop=0.0, drop_path=0.0, act_layer=nn.GELU,
+                 norm_layer=nn.LayerNorm, sr_ratio=1):
+        super().__init__()
+        self.LocalAgg = LocalAgg(dim, mlp_ratio, drop, drop_path, act_layer) if sr_ratio > 1 else nn.Identity()
+        self.SelfAttn = SelfAttn(dim, num_heads, mlp_ratio, qkv_bias, qk_scale, drop, attn_drop, drop_path, act_layer, norm_layer, sr_ratio)
+
+    def forward(self, x, out=None):
+        return self.SelfAttn(self.LocalAgg(x), out=out)
+
+
+class _DSUnit(nn.Module):
+    """reference block.py:3213-3228: [x +] DSConv_k2(DSConv_k1(x)), the arithmetic of DSBottleneck(c, c, e=1) under the keys ds1 / ds2."""
+
+    def __init__(self, c, k1=3, k2=7, d2=1, shortcut=True):
+        super().__init__()
+        self.ds1 = DSConv(c, c, k=k1, s=1, d=1, bias=False)
+        self.ds2 = DSConv(c, c, k=k2, s=1, d=d2, bias=False)
+        self.add = bool(shortcut)
+
+    def forward(self, x, out=None):
+        y = ops.dsb_pair(self.ds1, self.ds2, x, self.add, out=out)
+        if y is not None:
+            return y
+        return self.ds2(self.ds1(x), out=out, res=x if self.add else None)
+
+
+class _LGLAdapter(_Packed):
+    """reference block.py:3230-3273: x + gamma * LGLBlock(x), gamma a (1,) parameter (0 at initialisation) broadcast over the channels by
+    ey_scale_add_channels.  heads = max(1, c // 64), moved to the nearest divisor of c."""
+
+    def __init__(self, c, num_heads=None, sr_ratio=2, mlp_ratio=4.0, drop=0.0, attn_drop=0.0):
+        super().__init__()
+        if num_heads is None:
+            num_heads = max(1, c // 64)
+        if c % num_heads != 0:
+            num_heads = min((d for d in range(1, c + 1) if c % d == 0), key=lambda d: abs(d - num_heads))
+        self.lgl = LGLBlock(dim=c, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=True, qk_scale=None, drop=drop, attn_drop=attn_drop,
+                            drop_path=0.0, sr_ratio=sr_ratio)
+        self.gamma = nn.Parameter(torch.zeros(1))
+
+    def forward(self, x, out=None):
+        x = L.as_nhwc(ops.as_tensor(x))
+        C = x.shape[1]
+        gamma = self._packed(("gamma", x.dtype, x.device, C), lambda: self.gamma.detach().to(x.dtype).float().expand(C).to(x.device).contiguous())
+        return ops.scale_add_channels(x, gamma, self.lgl(x), out=out)
+
+
+class _DSUnitWithLGL(nn.Module):
+    """reference block.py:3276-3290: y = DSUnit(x); y + gamma * LGL(y)."""
+
+    def __init__(self, c, k1, k2, d2, shortcut, lgl_heads, lgl_sr, lgl_mlp, lgl_drop, lgl_attn_drop):
+        super().__init__()
+        self.core = _DSUnit(c, k1=k1, k2=k2, d2=d2, shortcut=shortcut)
+        self.lgl = _LGLAdapter(c, num_heads=lgl_heads, sr_ratio=lgl_sr, mlp_ratio=lgl_mlp, drop=lgl_drop, attn_drop=lgl_attn_drop)
+
+    def forward(self, x, out=None):
+        return self.lgl(self.core(x), out=out)
+
+
+class DSC3K2_LGL(C2f):
+    """reference block.py:3293-3345: C2f whose n blocks are _DSUnitWithLGL(c); dsc3k and g are accepted and ignored as there."""
+
+    def __init__(self, c1, c2, n=1, dsc3k=False, e=0.5, g=1, shortcut=True, k1=3, k2=7, d2=1, lgl_heads=None, lgl_sr_ratio=2, lgl_mlp_ratio=4.0,
+                 lgl_drop=0.0, lgl_attn_drop=0.0, **kwargs):
+        assert e > 0, "e must be > 0"
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.c1, self.c2 = c1, c2
+        self.m = nn.ModuleList(_DSUnitWithLGL(c=self.c, k1=k1, k2=k2, d2=d2, shortcut=shortcut, lgl_heads=lgl_heads, lgl_sr=lgl_sr_ratio,
+                                              lgl_mlp=lgl_mlp_ratio, lgl_drop=lgl_drop, lgl_attn_drop=lgl_attn_drop) for _ in range(n))
 
 
 class AdaHyperedgeGen(nn.Module):

@@ -13,7 +13,7 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
+from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
                       E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, SPPF, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
@@ -21,8 +21,8 @@ from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2}
-_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2}
+_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
+_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
 _HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH}
 
 
@@ -107,7 +107,7 @@ def parse_model(d, ch, verbose=False):
             if m in _REPEAT_MODULES:
                 args.insert(2, n)
                 n = 1
-            if m in {C3k2, DSC3K2_Wavelet, DSC3K2}:
+            if m in {C3k2, DSC3K2_Wavelet, DSC3K2, DSC3K2_LGL}:  # (DSC3K2_LGL ignores the flag: reference tasks.py:1069-1072)
                 legacy = False
                 if scale in "lx":
                     args[3] = True

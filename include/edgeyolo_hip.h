@@ -267,6 +267,41 @@ int ey_hypergraph_conv(int dtype, int B, int N, int D, int E, int heads, int con
                        const float* edge_wT, const float* edge_b, const void* node_w, const float* node_b, void* workspace,
                        size_t workspace_bytes, ey_stream_t stream);
 
+/* ---- LGL block (LGLBlock = LocalAgg + SelfAttn, reference block.py:3042-3210; YOLOv13 DSC3K2_LGL, block.py:3213-3345) ------------------
+ * All sums, gates and statistics below are fp32 in both storage types; x / y are channel windows of NHWC buffers.
+ *
+ * Depthwise kxk, stride 1, pad k/2, + bias with an epilogue (k in {3, 9}; C % 8 == 0; w: [k][k][C] in `dtype`, 32-byte aligned; bias fp32
+ * [C] or NULL):  mode 0: y = dw(x) + b (LocalAgg.attn, block.py:3085,3094);  1: y = x + x * (sigmoid(dw(x) + b) - 1/2) (LocalAgg.pos_embed
+ * and its gate, block.py:3081,3093);  2: y = x + dw(x) + b (SelfAttn.pos_embed, block.py:3180,3190).  ey_dwconv (k 3/5/7, no epilogue) is
+ * unchanged. */
+enum { EY_DWG_PLAIN = 0, EY_DWG_GATE = 1, EY_DWG_RESIDUAL = 2 };
+int ey_dwconv_gate(int dtype, int B, int H, int W, int C, int k, int mode, const void* x, int x_cstride, const void* w_kkc, const float* bias,
+                   void* y, int y_cstride, ey_stream_t stream);
+/* y = x + x * (sigmoid(g) - 1/2): the gate of LocalAgg's second step, whose g is a 1x1 conv output (block.py:3094).  Any C; y may alias g. */
+int ey_sigmoid_gate(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const void* g, int g_cstride, void* y, int y_cstride,
+                    ey_stream_t stream);
+/* Exact GELU, 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU() behind Mlp.fc1, block.py:3047-3054).  Any C; y may alias x. */
+int ey_gelu(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y, int y_cstride, ey_stream_t stream);
+/* CMlp behind BatchNorm, per channel (LocalAgg step 3, block.py:3060-3076,3095): a = scale[c] * x + shift[c] inside the map and ZERO outside
+ * (the reference zero-pads the BatchNorm output, so the affine cannot be folded into the weights); hidden_j = GELU(b1[j][c] + 3x3(a; w1[j]))
+ * for the r hidden maps of channel c (fc1 = Conv2d(C, rC, 3, pad 1, groups=C): output channel c*r + j), zero outside the map (fc2's padding);
+ * o = b2[c] + sum_j 3x3(hidden_j; w2[j]) (fc2 = Conv2d(rC, C, 3, pad 1, groups=C)).  The hidden maps stay in registers.  gate != 0:
+ * y = x + x * (sigmoid(o) - 1/2), else y = o.  Device fp32: scale / shift [C] or NULL (identity), w1 / w2 [r][9][C], b1 [r][C], b2 [C];
+ * r in 1..8; any C. */
+int ey_cmlp(int dtype, int B, int H, int W, int C, int r, int gate, const void* x, int x_cstride, const float* scale, const float* shift,
+            const float* w1, const float* b1, const float* w2, const float* b2, void* y, int y_cstride, ey_stream_t stream);
+/* nn.LayerNorm(C) over the channels of each pixel (SelfAttn.norm1 / norm2, block.py:3181,3185,3193-3194): two-pass fp32 mean and variance
+ * on registers, y = (x - mean) / sqrt(var + eps) * gamma + beta; C a multiple of 8 up to 384; gamma, beta fp32 [C].  pool != 0: followed by
+ * AvgPool2d(2, 2, ceil_mode=True) of the normalised values (GlobalSparseAttn.sampler, block.py:3120,3140) in the same kernel: y is
+ * [B, ceil(H/2), ceil(W/2), C], a partial window divides by its in-bounds count.  ey_avgpool2 (floor mode) is unchanged. */
+int ey_layernorm_channels(int dtype, int B, int H, int W, int C, float eps, int pool, const void* x, int x_cstride, const float* gamma,
+                          const float* beta, void* y, int y_cstride, ey_stream_t stream);
+/* GlobalSparseAttn.LocalProp + norm (block.py:3122-3123,3155-3162): depthwise ConvTranspose2d(k 2, s 2, no bias) of t [B,Hs,Ws,C]
+ * (U[2i+a][2j+b][c] = t[i][j][c] * w[a][b][c]; w_abc fp32 [2][2][C]), a bilinear resize (align_corners=False) of U to H x W only when
+ * (2Hs, 2Ws) != (H, W), then LayerNorm over channels: y [B,H,W,C].  Hs = ceil(H/2), Ws = ceil(W/2); C as ey_layernorm_channels. */
+int ey_unpool2_layernorm(int dtype, int B, int Hs, int Ws, int H, int W, int C, float eps, const void* t, int t_cstride, const float* w_abc,
+                         const float* gamma, const float* beta, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
@@ -315,13 +350,25 @@ int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, int hd, flo
 int ey_area_attention(int dtype, int B, int N, int area, int heads, int hd, float scale, const void* q, int q_cstride, const void* k,
                       int k_cstride, const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream);
 
-/* Kernel the last ey_linear_attention / ey_softmax_attention / ey_area_attention on this thread launched (tests); 0 = nothing launched.
+/* ---- K8d: softmax attention over ALL tokens of an image, the core of GlobalSparseAttn.forward of the LGL block (reference
+ * block.py:3147-3152: attn = softmax(q k^T * scale); y = attn v).  Views as ey_area_attention with one area: q, k, v, y [B,N,*] with their
+ * own channel strides, head h owns channels h*hd..h*hd+hd-1 (the qkv Linear's order [q: heads*hd | k | v], block.py:3148).
+ * f16 with hd in {16, 32, 64}, 16-byte aligned q/k/v (cstrides multiples of 8) and 8-byte aligned y: MFMA flash kernel, online softmax
+ * with fp32 statistics, any N >= 1 at a fixed 2 x 64 x (hd + 8) f16 of LDS; keys past N are masked to -inf, queries past N are not
+ * stored.  Otherwise (fp32, unaligned views, other hd <= 64): the fp32 VALU kernel of ey_area_attention, N <= 10176 (its score rows
+ * live in LDS); more tokens -> EY_EUNSUPPORTED, nothing launched.  Writes y only. */
+int ey_flash_attention(int dtype, int B, int N, int heads, int hd, float scale, const void* q, int q_cstride, const void* k, int k_cstride,
+                       const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream);
+
+/* Kernel the last ey_linear_attention / ey_softmax_attention / ey_area_attention / ey_flash_attention on this thread launched (tests); 0 = nothing launched.
+ * Flash: EY_ATTN_FLASH_MFMA + hd (flash_attn_kernel<hd>, hd = 16, 32, 64), EY_ATTN_FLASH_F32 / _F16 (area_attn_kernel<T>, fp32 VALU).
  * Linear: EY_ATTN_LIN_F32 / _F16 (linattn_kernel<T>, fp32 VALU), EY_ATTN_LIN_MFMA (linattn_mfma_kernel).
  * Softmax VALU: EY_ATTN_SOFT_VALU + 4 (f16) + 2 (K staged in LDS: K_LDS) + 1 (nsplit == 1: one query block per (image, head)).
  * Softmax MFMA: EY_ATTN_SOFT_MFMA + NKS (softattn_mfma_kernel<NKS>, NKS = 4, 8, 10, 13).
  * Area: EY_ATTN_AREA_F32 / _F16 (area_attn_kernel<T>, fp32 VALU), EY_ATTN_AREA_MFMA (area_attn_mfma_kernel). */
 enum { EY_ATTN_LIN_F32 = 101, EY_ATTN_LIN_F16 = 102, EY_ATTN_LIN_MFMA = 103, EY_ATTN_SOFT_VALU = 200, EY_ATTN_SOFT_MFMA = 300,
-       EY_ATTN_AREA_F32 = 401, EY_ATTN_AREA_F16 = 402, EY_ATTN_AREA_MFMA = 403 };
+       EY_ATTN_AREA_F32 = 401, EY_ATTN_AREA_F16 = 402, EY_ATTN_AREA_MFMA = 403,
+       EY_ATTN_FLASH_MFMA = 500, EY_ATTN_FLASH_F32 = 501, EY_ATTN_FLASH_F16 = 502 };
 int ey_attention_last_variant(void);
 
 /* ---- K9+K10: DGQP quality + DFL expectation + anchor decode + score modulation for ONE pyramid level.
