@@ -129,6 +129,8 @@ SIGNATURES = {
     "ey_block_run_tiles": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_void_p), _i, _vp]),
     "ey_block_run_timed": (_i, [_vp, _i, _i, C.POINTER(C.c_void_p), _i, _vp, _vp]),
     "ey_nms_candidates_bytes": (_sz, [_i, _i]),
+    "ey_head_tail_decode_levels_nms": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                             _vp, _i, _vp, _f, _vp, _vp, _sz, _vp]),
     "ey_head_decode_levels_nms": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _f, _vp, _vp, _sz, _vp]),
     "ey_nms_candidates": (_i, [_i, _i, _i, _vp, _sz, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "ey_nms_workspace_bytes": (_sz, [_i, _i]),

@@ -36,8 +36,199 @@ struct HdNms {
   int P;
   int xyxy;  // end2end heads: rows 0-3 of pred = x1,y1,x2,y2 (decode_bboxes with xywh=False, head.py:163-165) instead of cx,cy,w,h
 };
+// Best class of one anchor without scoring every class (candidates only, no pred; f16 rows of nc % 8 == 0 logits in LDS).
+// score_c = ey_sigmoid(l_c) * q with q > 0, and ey_sigmoid is non-decreasing over the ordered f16 values (measured on the hardware for
+// all 63 488 finite ones, tests/test_gpu_head_fused.py), so is the fp32 product: the best score is the score of m = max_c l_c, and
+// every class with l_c < m scores at most what pred16(m), the next lower f16, scores.  Where that is strictly below the score of m,
+// the first index the full loop would keep is the first c with l_c == m (by value: +0 and -0 score the same).  Two packed passes over
+// the row (v_pk_max_f16, then one compare + select per class) and 2 sigmoids instead of nc.  false: the row has a NaN or an infinity, or
+// m sits on a plateau of the fp32 score (saturated sigmoid, products that round together); the caller then runs the full loop.
+// v_pk_max_f16 on two packed pairs.  Written out because the compiler quiets a possible signalling NaN of every loaded operand first
+// (a v_pk_max_f16 x, x, x in front of each maximum: twice the instructions); what comes out for a NaN operand does not matter here.
+__device__ __forceinline__ unsigned hd_pk_max_f16(unsigned a, unsigned b) {
+  unsigned r;
+  asm("v_pk_max_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ unsigned hd_pk_max_u16(unsigned a, unsigned b) {  // (the compiler unpacks the masked halves before it packs them again)
+  unsigned r;
+  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ bool hd_best_lean(const f16* cp, int nc, float q, float& best, int& bi) {
+  typedef f16 f16x2 __attribute__((ext_vector_type(2)));
+  u32x4 mx = *reinterpret_cast<const u32x4*>(cp);
+  u32x4 ax = mx & 0x7FFF7FFFu;  // running maximum of |l| as 16-bit integers: >= 0x7C00 = an infinity or a NaN seen
+  for (int c8 = 8; c8 < nc; c8 += 8) {
+    const u32x4 t = *reinterpret_cast<const u32x4*>(cp + c8);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      mx[j] = hd_pk_max_f16(mx[j], t[j]);
+      ax[j] = hd_pk_max_u16(ax[j], t[j] & 0x7FFF7FFFu);
+    }
+  }
+  const f16x2 m2 = __builtin_bit_cast(f16x2, hd_pk_max_f16(hd_pk_max_f16(mx[0], mx[1]), hd_pk_max_f16(mx[2], mx[3])));
+  const f16 m = __builtin_fmaxf16(m2[0], m2[1]);
+  const unsigned a2 = hd_pk_max_u16(hd_pk_max_u16(ax[0], ax[1]), hd_pk_max_u16(ax[2], ax[3]));
+  const unsigned am = max(a2 & 0xFFFFu, a2 >> 16);
+  if (am >= 0x7C00) return false;  // an infinity or a NaN somewhere in the row
+  const unsigned short mb = __builtin_bit_cast(unsigned short, m);
+  const unsigned short pb = (mb & 0x7FFF) == 0 ? (unsigned short)0x8001 : (mb & 0x8000) ? (unsigned short)(mb + 1) : (unsigned short)(mb - 1);
+  const float sm = ey_sigmoid((float)m) * q, sp = ey_sigmoid((float)__builtin_bit_cast(f16, pb)) * q;
+  if (!(sp < sm)) return false;
+  int first = 0;
+  for (int c8 = nc - 8; c8 >= 0; c8 -= 8) {
+    const f16x8 t = *reinterpret_cast<const f16x8*>(cp + c8);
+    int r = 8;  // first position of m in these 8 (constant operands: one compare + one select per class)
+#pragma unroll
+    for (int i = 7; i >= 0; --i)
+      if (t[i] == m) r = i;
+    if (r < 8) first = c8 + r;
+  }
+  best = sm;
+  bi = first;
+  return true;
+}
+
+// ---- the per-anchor decode, shared by head_decode_kernel and head_tail_decode_kernel
+// bp: the anchor's 64 box logits -> dist[4] (DFL expectation per side) and q (DGQP quality, 1 without the head)
 template <typename T>
-__global__ __launch_bounds__(HD_ANCH) void head_decode_kernel(int B, HdLevels lv, int nc, int hid, float* __restrict__ pred, int A, int boxLs, int clsLs, int vec, HdNms nm) {
+__device__ __forceinline__ void hd_box_stats(const T* bp, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+                                             const float* __restrict__ b2, int hid, float (&dist)[4], float& q) {
+  float stat[20];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float l[16];
+    {
+      Vec8<T> v0, v1;
+      v0.load(bp + s * 16);
+      v1.load(bp + s * 16 + 8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { l[i] = v0.get(i); l[8 + i] = v1.get(i); }
+    }
+    float mx = l[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, l[i]);
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { l[i] = __expf(l[i] - mx); sum += l[i]; }
+    const float inv = 1.f / sum;
+    float e = 0.f, t0 = -1.f, t1 = -1.f, t2 = -1.f, t3 = -1.f, psum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float pr = l[i] * inv;
+      e += pr * (float)i;
+      psum += pr;
+      // insert into the sorted top-4 (descending)
+      float v = pr, u;
+      u = fmaxf(t0, v); v = fminf(t0, v); t0 = u;
+      u = fmaxf(t1, v); v = fminf(t1, v); t1 = u;
+      u = fmaxf(t2, v); v = fminf(t2, v); t2 = u;
+      t3 = fmaxf(t3, v);
+    }
+    dist[s] = e;
+    stat[s * 5 + 0] = t0; stat[s * 5 + 1] = t1; stat[s * 5 + 2] = t2; stat[s * 5 + 3] = t3;
+    stat[s * 5 + 4] = psum * (1.f / 16.f);
+  }
+  q = 1.f;
+  if (w1) {
+    float o = b2[0];
+    // 20 -> hid -> 1 on the VALU: packed fp32 FMAs (v_pk_fma_f32: two lanes of the dot product per instruction, even / odd inputs in the
+    // two halves) -- this file is compiled without FMA contraction for the NMS arithmetic, which had turned every multiply-add of
+    // this loop into a separate v_mul + v_add
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 st2[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) st2[i] = f32x2{stat[2 * i], stat[2 * i + 1]};
+    // The weights are wave-uniform: read straight from global memory with uniform addresses they arrive by SCALAR loads (s_load_dwordx4 /
+    // x8 into SGPRs, the FMAs take them as scalar operands) -- no LDS broadcast read per 4 multiply-adds (320 ds_read_b128 per wave
+    // before, the kernel's bound).  Same operands in the same order: bit-identical.
+    const float* __restrict__ gw1 = w1;
+    const float* __restrict__ gb1 = b1;
+    const float* __restrict__ gw2 = w2;
+#pragma unroll 4
+    for (int j = 0; j < hid; ++j) {
+      const f32x4* wr = reinterpret_cast<const f32x4*>(gw1 + j * 20);
+      f32x2 h2 = {gb1[j], 0.f};
+#pragma unroll
+      for (int i4 = 0; i4 < 5; ++i4) {
+        const f32x4 w4 = wr[i4];
+        h2 = __builtin_elementwise_fma(f32x2{w4[0], w4[1]}, st2[2 * i4], h2);
+        h2 = __builtin_elementwise_fma(f32x2{w4[2], w4[3]}, st2[2 * i4 + 1], h2);
+      }
+      o = __builtin_fmaf(gw2[j], fmaxf(h2[0] + h2[1], 0.f), o);
+    }
+    q = fminf(fmaxf(ey_sigmoid(o), 1e-6f), 1.f - 1e-6f);
+  }
+}
+
+// cp: the anchor's nc class logits (LDS row) -> box rows, scores, candidate key
+template <typename T>
+__device__ __forceinline__ void hd_emit(const float (&dist)[4], float q, const T* cp, int nc, int vec, int lean, int b, int a, int ax, int ay, float stride,
+                                        int a_off, float* __restrict__ pred, int A, const HdNms& nm) {
+  const float cx0 = ax + 0.5f, cy0 = ay + 0.5f;
+  const float x1 = cx0 - dist[0], y1 = cy0 - dist[1], x2 = cx0 + dist[2], y2 = cy0 + dist[3];
+  const float bcx = (x1 + x2) * 0.5f * stride, bcy = (y1 + y2) * 0.5f * stride, bw = (x2 - x1) * stride, bh = (y2 - y1) * stride;
+  float best = 0.f;
+  int bi = 0;
+  if (pred) {
+    float* pp = pred + (long)b * (4 + nc) * A + a_off + a;
+    if (nm.xyxy) { pp[0] = x1 * stride; pp[(long)A] = y1 * stride; pp[2L * A] = x2 * stride; pp[3L * A] = y2 * stride; }  // dist2bbox(xywh=False) * strides
+    else { pp[0] = bcx; pp[(long)A] = bcy; pp[2L * A] = bw; pp[3L * A] = bh; }
+    if (vec) {
+      for (int c8 = 0; c8 < nc; c8 += 8) {
+        Vec8<T> t;
+        t.load(cp + c8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float sc = ey_sigmoid(t.get(i)) * q;
+          pp[(long)(4 + c8 + i) * A] = sc;
+          if (c8 + i == 0 || sc > best) { best = sc; bi = c8 + i; }
+        }
+      }
+    } else {
+      for (int c = 0; c < nc; ++c) {
+        const float sc = ey_sigmoid(to_f(cp[c])) * q;
+        pp[(long)(4 + c) * A] = sc;
+        if (c == 0 || sc > best) { best = sc; bi = c; }
+      }
+    }
+  } else if (vec) {
+    bool found = false;
+    if constexpr (sizeof(T) == 2) {
+      if (lean) found = hd_best_lean(cp, nc, q, best, bi);
+    }
+    if (!found) {  // (per lane: a row the lean search declines is scored class by class, as every row is with lean == 0)
+      for (int c8 = 0; c8 < nc; c8 += 8) {
+        Vec8<T> t;
+        t.load(cp + c8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float sc = ey_sigmoid(t.get(i)) * q;
+          if (c8 + i == 0 || sc > best) { best = sc; bi = c8 + i; }
+        }
+      }
+    }
+  } else {
+    for (int c = 0; c < nc; ++c) {
+      const float sc = ey_sigmoid(to_f(cp[c])) * q;
+      if (c == 0 || sc > best) { best = sc; bi = c; }
+    }
+  }
+  if (nm.keys) {
+    const int ga = a_off + a;
+    float* bx = nm.box4 + (long)b * 4 * A + ga;
+    bx[0] = bcx; bx[(long)A] = bcy; bx[2L * A] = bw; bx[3L * A] = bh;
+    unsigned long long key = 0ull;
+    if (best > nm.conf && (!nm.mask || nm.mask[bi]))
+      key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)ga);
+    nm.keys[(long)b * nm.P + ga] = key;
+    nm.cls_id[(long)b * nm.P + ga] = bi;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(HD_ANCH) void head_decode_kernel(int B, HdLevels lv, int nc, int hid, float* __restrict__ pred, int A, int boxLs, int clsLs, int vec, int lean, HdNms nm) {
   int l = 0;
 #pragma unroll
   for (int i = 1; i < HD_MAXL; ++i)
@@ -78,125 +269,9 @@ __global__ __launch_bounds__(HD_ANCH) void head_decode_kernel(int B, HdLevels lv
   const int b = (int)(idx / HW), a = (int)(idx - (long)b * HW);
   const int ay = a / W, ax = a - ay * W;
   const T* bp = vec ? box + idx * boxCs : s_box + tid * boxLs;
-  float stat[20], dist[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    float l[16];
-    {
-      Vec8<T> v0, v1;
-      v0.load(bp + s * 16);
-      v1.load(bp + s * 16 + 8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { l[i] = v0.get(i); l[8 + i] = v1.get(i); }
-    }
-    float mx = l[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, l[i]);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { l[i] = __expf(l[i] - mx); sum += l[i]; }
-    const float inv = 1.f / sum;
-    float e = 0.f, t0 = -1.f, t1 = -1.f, t2 = -1.f, t3 = -1.f, psum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float pr = l[i] * inv;
-      e += pr * (float)i;
-      psum += pr;
-      // insert into the sorted top-4 (descending)
-      float v = pr, u;
-      u = fmaxf(t0, v); v = fminf(t0, v); t0 = u;
-      u = fmaxf(t1, v); v = fminf(t1, v); t1 = u;
-      u = fmaxf(t2, v); v = fminf(t2, v); t2 = u;
-      t3 = fmaxf(t3, v);
-    }
-    dist[s] = e;
-    stat[s * 5 + 0] = t0; stat[s * 5 + 1] = t1; stat[s * 5 + 2] = t2; stat[s * 5 + 3] = t3;
-    stat[s * 5 + 4] = psum * (1.f / 16.f);
-  }
-  float q = 1.f;
-  if (w1) {
-    float o = b2[0];
-    // 20 -> hid -> 1 on the VALU: packed fp32 FMAs (v_pk_fma_f32: two lanes of the dot product per instruction, even / odd inputs in the
-    // two halves) -- this file is compiled without FMA contraction for the NMS arithmetic, which had turned every multiply-add of
-    // this loop into a separate v_mul + v_add
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 st2[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) st2[i] = f32x2{stat[2 * i], stat[2 * i + 1]};
-    // The weights are wave-uniform: read straight from global memory with uniform addresses they arrive by SCALAR loads (s_load_dwordx4 /
-    // x8 into SGPRs, the FMAs take them as scalar operands) -- no LDS broadcast read per 4 multiply-adds (320 ds_read_b128 per wave
-    // before, the kernel's bound).  Same operands in the same order: bit-identical.
-    const float* __restrict__ gw1 = w1;
-    const float* __restrict__ gb1 = b1;
-    const float* __restrict__ gw2 = w2;
-#pragma unroll 4
-    for (int j = 0; j < hid; ++j) {
-      const f32x4* wr = reinterpret_cast<const f32x4*>(gw1 + j * 20);
-      f32x2 h2 = {gb1[j], 0.f};
-#pragma unroll
-      for (int i4 = 0; i4 < 5; ++i4) {
-        const f32x4 w4 = wr[i4];
-        h2 = __builtin_elementwise_fma(f32x2{w4[0], w4[1]}, st2[2 * i4], h2);
-        h2 = __builtin_elementwise_fma(f32x2{w4[2], w4[3]}, st2[2 * i4 + 1], h2);
-      }
-      o = __builtin_fmaf(gw2[j], fmaxf(h2[0] + h2[1], 0.f), o);
-    }
-    q = fminf(fmaxf(ey_sigmoid(o), 1e-6f), 1.f - 1e-6f);
-  }
-  const float cx0 = ax + 0.5f, cy0 = ay + 0.5f;
-  const float x1 = cx0 - dist[0], y1 = cy0 - dist[1], x2 = cx0 + dist[2], y2 = cy0 + dist[3];
-  const float bcx = (x1 + x2) * 0.5f * stride, bcy = (y1 + y2) * 0.5f * stride, bw = (x2 - x1) * stride, bh = (y2 - y1) * stride;
-  const T* cp = s_cls + tid * clsLs;
-  float best = 0.f;
-  int bi = 0;
-  if (pred) {
-    float* pp = pred + (long)b * (4 + nc) * A + a_off + a;
-    if (nm.xyxy) { pp[0] = x1 * stride; pp[(long)A] = y1 * stride; pp[2L * A] = x2 * stride; pp[3L * A] = y2 * stride; }  // dist2bbox(xywh=False) * strides
-    else { pp[0] = bcx; pp[(long)A] = bcy; pp[2L * A] = bw; pp[3L * A] = bh; }
-    if (vec) {
-      for (int c8 = 0; c8 < nc; c8 += 8) {
-        Vec8<T> t;
-        t.load(cp + c8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float sc = ey_sigmoid(t.get(i)) * q;
-          pp[(long)(4 + c8 + i) * A] = sc;
-          if (c8 + i == 0 || sc > best) { best = sc; bi = c8 + i; }
-        }
-      }
-    } else {
-      for (int c = 0; c < nc; ++c) {
-        const float sc = ey_sigmoid(to_f(cp[c])) * q;
-        pp[(long)(4 + c) * A] = sc;
-        if (c == 0 || sc > best) { best = sc; bi = c; }
-      }
-    }
-  } else if (vec) {
-    for (int c8 = 0; c8 < nc; c8 += 8) {
-      Vec8<T> t;
-      t.load(cp + c8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float sc = ey_sigmoid(t.get(i)) * q;
-        if (c8 + i == 0 || sc > best) { best = sc; bi = c8 + i; }
-      }
-    }
-  } else {
-    for (int c = 0; c < nc; ++c) {
-      const float sc = ey_sigmoid(to_f(cp[c])) * q;
-      if (c == 0 || sc > best) { best = sc; bi = c; }
-    }
-  }
-  if (nm.keys) {
-    const int ga = a_off + a;
-    float* bx = nm.box4 + (long)b * 4 * A + ga;
-    bx[0] = bcx; bx[(long)A] = bcy; bx[2L * A] = bw; bx[3L * A] = bh;
-    unsigned long long key = 0ull;
-    if (best > nm.conf && (!nm.mask || nm.mask[bi]))
-      key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)ga);
-    nm.keys[(long)b * nm.P + ga] = key;
-    nm.cls_id[(long)b * nm.P + ga] = bi;
-  }
+  float dist[4], q;
+  hd_box_stats<T>(bp, w1, b1, w2, b2, hid, dist, q);
+  hd_emit<T>(dist, q, s_cls + tid * clsLs, nc, vec, lean, b, a, ax, ay, stride, a_off, pred, A, nm);
 }
 
 // form of head_decode_kernel the last ey_head_decode* on this thread launched (see ey_head_decode_last_variant); 0 = none
@@ -243,17 +318,18 @@ static int head_decode_impl(int dtype, int B, int nlevels, const int* H, const i
   EY_CHECK(lds <= 160 * 1024, "head_decode: nc=%d needs %zu B of LDS", nc, lds);
   dim3 grid((unsigned)nblk);
   hipStream_t st = (hipStream_t)stream;
+  const int lean = tune().head_lean != 0;
   const int variant = (vec ? EY_HD_VEC : EY_HD_SCALAR) + (quality ? EY_HD_QUALITY : 0) + (nm.keys ? EY_HD_NMS : 0);
   if (dtype == EY_F16) {
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)head_decode_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return ey_set_error(EY_ELAUNCH, "head_decode: cannot reserve %zu B of LDS", lds);
     g_hd_variant = variant;
-    hipLaunchKernelGGL(head_decode_kernel<f16>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, nm);
+    hipLaunchKernelGGL(head_decode_kernel<f16>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, lean, nm);
   } else {
     if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)head_decode_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return ey_set_error(EY_ELAUNCH, "head_decode: cannot reserve %zu B of LDS", lds);
     g_hd_variant = variant;
-    hipLaunchKernelGGL(head_decode_kernel<float>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, nm);
+    hipLaunchKernelGGL(head_decode_kernel<float>, grid, dim3(HD_ANCH), lds, st, B, lv, nc, quality ? q_hidden : 0, pred, A_total, boxLs, clsLs, vec, lean, nm);
   }
   EY_LAUNCH_CHECK("ey_head_decode");
   return EY_OK;
@@ -273,6 +349,207 @@ extern "C" int ey_head_decode_levels_xyxy(int dtype, int B, int nlevels, const i
   EY_CHECK(pred, "head_decode: null pred");
   HdNms nm = {nullptr, nullptr, nullptr, nullptr, 0.f, 0, 1};
   return head_decode_impl(dtype, B, nlevels, H, W, stride, box, box_cstride, cls, cls_cstride, nc, q_w1, q_b1, q_w2, q_b2, q_hidden, pred, A_total, a_off, nm, stream);
+}
+
+// ============================================================================ head decode with the towers' closing 1x1 convs inside
+// Predict mode: each head tower closes with a 1x1 conv that only the decode reads (box: nn.Conv2d(64, 64, 1), Detect.cv2[i][2];
+// class: Conv(80, 80, 1) + SiLU -> nn.Conv2d(80, nc, 1), Detect.cv3[i][1][1] and [2]).  This kernel takes the tower FEATURES in front
+// of them and builds the logits of its anchors by MFMA straight into the LDS rows the per-anchor decode reads -- the logits never
+// exist in global memory (34 + 43 MB written and re-read per step at batch 32, 640x640) and six launches go.
+//
+// Workgroup = 8 waves = 512 anchors of one level.  The level's weights are staged ONCE per workgroup into LDS as MFMA A fragments
+// (fragment f, lane: 16 bytes at (f * 64 + lane) * 16 -- consecutive lanes, conflict free): 8 box + 15 + 15 class fragments = 38 KB per
+// 512 anchors (74 B per anchor against 288 B of features).  A wave owns 64 anchors and a private [64][rowLs] f16 region of LDS, used
+// twice: box logits -> DFL / quality statistics, then class logits -> scores.  Nothing but the weights crosses waves, so one workgroup
+// barrier (after the staging) is all; inside a wave LDS operations complete in order.  LDS: 38 KB + 8 x 11 KB = 126 KB, one workgroup
+// = 8 waves per CU (two 4-wave workgroups would need 2 x 83 KB).
+//
+// Arithmetic = the unfused kernels', operation by operation (tests/test_gpu_head_fused.py compares bytes):
+//   box   acc = sum over the two 32-channel k-steps of mfma(w[t][nt], x[t]) ; + bias ; one rounding to f16   (ey_conv2d, ACT_NONE)
+//   class conv_pw2_kernel<5,3,5>: first GEMM over 3 k-steps (feature channels past Cin read as zero), + b1, SiLU as an fp32 product of
+//         its own (ey_silu_rn: the conv kernel rounds twice), f16 into the lane's OWN B fragments, second GEMM over W2 in the
+//         ey_conv_chain_kperm column order, + b2, f16.
+// lane (r, g) of a 16-pixel tile ends with channels g * 4 NT + 4 nt + j of pixel r (row permutation of ey_conv_pack_weight).
+#define HT_WAVES 8
+#define HT_ANCH (64 * HT_WAVES)
+#define HT_FRAG_BOX 8          // 2 k-steps x 4 channel blocks
+#define HT_FRAG_CLS 30         // 3 x 5 (W1) + 3 x 5 (W2)
+struct HtTails {
+  const f16* wb[HD_MAXL]; const float* bb[HD_MAXL];  // box tail 64 -> 64: ey_conv_pack_weight layout, bias
+  const f16* w1[HD_MAXL]; const float* b1[HD_MAXL];  // class chain Cin -> 80 (SiLU)
+  const f16* w2[HD_MAXL]; const float* b2[HD_MAXL];  // ... 80 -> nc, input columns permuted (ey_conv_chain_kperm)
+  int clsC[HD_MAXL], kp1[HD_MAXL];                   // class feature channels (72..96) and packed row length of W1
+  unsigned boxBytes[HD_MAXL], clsBytes[HD_MAXL];     // byte extent of the feature views (buffer-load range check)
+  int kpb, kp2;                                      // packed row lengths of the box weights and of W2
+};
+__device__ __forceinline__ f32x4 ht_mma(const Vec8<f16>& a, const Vec8<f16>& b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.v, b.v, c, 0, 0, 0); }
+// orders this wave's LDS traffic for the compiler (rows written by one lane are read by another); the hardware keeps a wave's LDS
+// operations in order, so no wait is needed and the feature loads in flight stay in flight
+__device__ __forceinline__ void ht_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool CLS>  // CLS: lv.cls = class-tower features, chain in here; else lv.cls = class logits (staged as head_decode_kernel does)
+__global__ __launch_bounds__(HT_ANCH) void head_tail_decode_kernel(int B, HdLevels lv, HtTails tw, int nc, int hid, float* __restrict__ pred, int A, int rowLs, int lean, HdNms nm) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < HD_MAXL; ++i)
+    if (i < lv.nl && (int)blockIdx.x >= lv.blk0[i]) l = i;
+  const int H = lv.H[l], W = lv.W[l], boxCs = lv.boxCs[l], clsCs = lv.clsCs[l], a_off = lv.a_off[l];
+  const float stride = lv.stride[l];
+  const int blk = (int)blockIdx.x - lv.blk0[l];
+  constexpr int NFRAG = HT_FRAG_BOX + (CLS ? HT_FRAG_CLS : 0);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  f16x8* s_w = reinterpret_cast<f16x8*>(smem);  // [NFRAG][64]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+  f16* s_rows = reinterpret_cast<f16*>(smem + NFRAG * 1024) + wave * 64 * rowLs;  // this wave's [64][rowLs]
+  const int HW = H * W;
+  const long total = (long)B * HW;
+  const long wave0 = (long)blk * HT_ANCH + wave * 64;  // first anchor of this wave (flat index over B x H x W)
+  const int nrow = (int)max(0L, min(64L, total - wave0));
+  // ---- this wave's feature fragments: all loads issued up front (pixel 16 mt + r, channels 32 t + 8 g ...; rows past the end and
+  // channels past Cin come back as zeros from the range check)
+  Vec8<f16> xb[4][2], xc[4][CLS ? 3 : 1];
+  {
+    const __amdgpu_buffer_rsrc_t rs = ey_rsrc(lv.box[l], tw.boxBytes[l]);
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const unsigned v = 16 * mt + r < nrow ? (unsigned)(((int)(wave0 + 16 * mt + r) * boxCs + 8 * g) * 2) : EY_OOB;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) BufLoad8<f16>::load(xb[mt][t], rs, v, t * 64);
+    }
+  }
+  if constexpr (CLS) {
+    const __amdgpu_buffer_rsrc_t rs = ey_rsrc(lv.cls[l], tw.clsBytes[l]);
+    const int C0 = tw.clsC[l];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const unsigned v = 16 * mt + r < nrow ? (unsigned)(((int)(wave0 + 16 * mt + r) * clsCs + 8 * g) * 2) : EY_OOB;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) BufLoad8<f16>::load(xc[mt][t], rs, (32 * t + 8 * g) < C0 ? v : EY_OOB, t * 64);
+    }
+  }
+  // ---- the level's weights -> LDS, as fragments (lane (r, g) of fragment (t, nt): packed row 16 nt + r, k = 32 t + 8 g ...)
+  {
+    const f16* __restrict__ wb = tw.wb[l];
+    const f16* __restrict__ w1 = tw.w1[l];
+    const f16* __restrict__ w2 = tw.w2[l];
+    const int kpb = tw.kpb, kp1 = tw.kp1[l], kp2 = tw.kp2;
+    for (int f = tid; f < NFRAG * 64; f += HT_ANCH) {
+      const int frag = f >> 6, ln = f & 63, rr = ln & 15, gg = ln >> 4;
+      const f16* src;
+      if (frag < HT_FRAG_BOX) src = wb + ((frag & 3) * 16 + rr) * kpb + (frag >> 2) * 32 + 8 * gg;
+      else if (frag < HT_FRAG_BOX + 15) { const int f1 = frag - HT_FRAG_BOX, t = f1 / 5, nt = f1 - 5 * t; src = w1 + (nt * 16 + rr) * kp1 + t * 32 + 8 * gg; }
+      else { const int f2 = frag - HT_FRAG_BOX - 15, t = f2 / 5, nt = f2 - 5 * t; src = w2 + (nt * 16 + rr) * kp2 + t * 32 + 8 * gg; }
+      s_w[f] = *reinterpret_cast<const f16x8*>(src);
+    }
+  }
+  __syncthreads();
+  if (nrow <= 0) return;  // (whole wave, behind the only workgroup barrier)
+  // ---- box logits -> rows
+  {
+    Vec8<f16> af[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) af[t][nt].v = s_w[(t * 4 + nt) * 64 + lane];
+    float bias[16];
+    const float* __restrict__ bb = tw.bb[l] + g * 16;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bias[i] = bb[i];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      f32x4 acc[4];
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4)0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[nt] = ht_mma(af[t][nt], xb[mt][t], acc[nt]);
+      f16* yp = s_rows + (16 * mt + r) * rowLs + g * 16;
+#pragma unroll
+      for (int q8 = 0; q8 < 2; ++q8) {
+        Vec8<f16> o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o.set(j, acc[2 * q8 + (j >> 2)][j & 3] + bias[8 * q8 + j]);
+        o.store(yp + 8 * q8);
+      }
+    }
+  }
+  ht_wave_sync();
+  const bool valid = lane < nrow;
+  const long idx = valid ? wave0 + lane : 0;
+  const int b = (int)(idx / HW), a = (int)(idx - (long)b * HW);
+  const int ay = a / W, ax = a - ay * W;
+  float dist[4] = {0.f, 0.f, 0.f, 0.f}, q = 1.f;
+  if (valid) hd_box_stats<f16>(s_rows + lane * rowLs, lv.w1[l], lv.b1[l], lv.w2[l], lv.b2[l], hid, dist, q);
+  ht_wave_sync();
+  // ---- class logits -> the same rows
+  if constexpr (CLS) {
+    Vec8<f16> mid[4][3];
+    {
+      Vec8<f16> a1[3][5];
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int nt = 0; nt < 5; ++nt) a1[t][nt].v = s_w[(HT_FRAG_BOX + t * 5 + nt) * 64 + lane];
+      float b1v[20];
+      const float* __restrict__ b1 = tw.b1[l] + g * 20;
+#pragma unroll
+      for (int i = 0; i < 20; ++i) b1v[i] = b1[i];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        f32x4 acc[5];
+#pragma unroll
+        for (int nt = 0; nt < 5; ++nt) acc[nt] = (f32x4)0.f;
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+#pragma unroll
+          for (int nt = 0; nt < 5; ++nt) acc[nt] = ht_mma(a1[t][nt], xc[mt][t], acc[nt]);
+#pragma unroll
+        for (int i = 0; i < 24; ++i) mid[mt][i >> 3].set(i & 7, i < 20 ? ey_silu_rn(acc[i < 20 ? i >> 2 : 0][i & 3] + b1v[i < 20 ? i : 0]) : 0.f);
+      }
+    }
+    Vec8<f16> a2[3][5];
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 5; ++nt) a2[t][nt].v = s_w[(HT_FRAG_BOX + 15 + t * 5 + nt) * 64 + lane];
+    float b2v[20];
+    const float* __restrict__ b2 = tw.b2[l];
+#pragma unroll
+    for (int i = 0; i < 20; ++i) b2v[i] = g * 20 + i < nc ? b2[g * 20 + i] : 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      f32x4 acc[5];
+#pragma unroll
+      for (int nt = 0; nt < 5; ++nt) acc[nt] = (f32x4)0.f;
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int nt = 0; nt < 5; ++nt) acc[nt] = ht_mma(a2[t][nt], mid[mt][t], acc[nt]);
+      f16* yp = s_rows + (16 * mt + r) * rowLs + g * 20;
+#pragma unroll
+      for (int nt = 0; nt < 5; ++nt)
+        if (g * 20 + 4 * nt + 4 <= nc) {  // (nc % 8 == 0: whole groups of 4)
+          const f16x4 o = {(f16)(acc[nt][0] + b2v[4 * nt]), (f16)(acc[nt][1] + b2v[4 * nt + 1]), (f16)(acc[nt][2] + b2v[4 * nt + 2]), (f16)(acc[nt][3] + b2v[4 * nt + 3])};
+          *reinterpret_cast<f16x4*>(yp + 4 * nt) = o;
+        }
+    }
+  } else {
+    const f16* __restrict__ cls = (const f16*)lv.cls[l];
+    const int cv = nc >> 3;
+    for (int v = lane; v < nrow * cv; v += 64) {
+      const int row = v / cv, c8 = (v - row * cv) << 3;
+      Vec8<f16> t;
+      t.load(cls + (wave0 + row) * clsCs + c8);
+      t.store(s_rows + row * rowLs + c8);
+    }
+  }
+  ht_wave_sync();
+  if (valid) hd_emit<f16>(dist, q, s_rows + lane * rowLs, nc, 1, lean, b, a, ax, ay, stride, a_off, pred, A, nm);
 }
 
 static int nms_pow2(int A);
@@ -301,6 +578,80 @@ extern "C" int ey_head_decode_levels_nms(int dtype, int B, int nlevels, const in
   nm.P = P;
   nm.xyxy = 0;
   return head_decode_impl(dtype, B, nlevels, H, W, stride, box, box_cstride, cls, cls_cstride, nc, q_w1, q_b1, q_w2, q_b2, q_hidden, pred_or_null, A_total, a_off, nm, stream);
+}
+
+extern "C" int ey_head_tail_decode_levels_nms(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box_feat,
+                                              const int* box_cstride, int box_cin, int box_cout, const void* const* box_w, const float* const* box_b,
+                                              const void* const* cls, const int* cls_cstride, int fuse_cls, const int* cls_cin, int cls_cmid,
+                                              const void* const* cls_w1, const float* const* cls_b1, const void* const* cls_w2, const float* const* cls_b2, int nc,
+                                              const float* const* q_w1, const float* const* q_b1, const float* const* q_w2, const float* const* q_b2, int q_hidden,
+                                              float* pred_or_null, int A_total, const int* a_off, float conf_thres, const uint8_t* class_mask, void* candidates,
+                                              size_t candidates_bytes, ey_stream_t stream) {
+  g_hd_variant = 0;
+  EY_CHECK(H && W && stride && box_feat && box_cstride && box_w && box_b && cls && cls_cstride && a_off, "head_tail_decode: null pointer");
+  EY_CHECK(!fuse_cls || (cls_cin && cls_w1 && cls_b1 && cls_w2 && cls_b2), "head_tail_decode: null pointer (class chain)");
+  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "head_tail_decode: bad dtype");
+  EY_CHECK(nlevels >= 1 && B > 0 && nc > 0 && A_total > 0, "head_tail_decode: bad extent");
+  EY_CHECK(candidates && ey_aligned(candidates, 16) && candidates_bytes >= ey_nms_candidates_bytes(B, A_total), "head_tail_decode: candidate buffer missing / too small");
+  EY_CHECK(conf_thres >= 0.f && conf_thres <= 1.f, "head_tail_decode: Invalid Confidence threshold %f, valid values are between 0.0 and 1.0", conf_thres);
+  // ---- shape gate: refuse before anything is launched (the caller runs the convs and ey_head_decode_levels_nms)
+  if (dtype != EY_F16 || nlevels > HD_MAXL || box_cin != 64 || box_cout != 64 || nc % 8 != 0 || nc <= 64 || nc > 80 || (fuse_cls && cls_cmid != 80))
+    return ey_set_error(EY_EUNSUPPORTED, "head_tail_decode: built for f16, <= %d levels, box tail 64 -> 64, class chain Cin 72..96 -> 80 -> nc, nc %% 8 == 0, 64 < nc <= 80", HD_MAXL);
+  const bool quality = q_w1 && q_w1[0];
+  HdLevels lv;
+  HtTails tw;
+  lv.nl = nlevels;
+  tw.kpb = ey_conv_kpad(64, 2);
+  tw.kp2 = ey_conv_kpad(96, 2);  // ey_conv_chain_klen(80) = 96 columns
+  long nblk = 0, covered = 0;
+  for (int l = 0; l < HD_MAXL; ++l) {
+    const int s = l < nlevels ? l : 0;
+    EY_CHECK(box_feat[s] && cls[s] && box_w[s] && box_b[s] && H[s] > 0 && W[s] > 0, "head_tail_decode: level %d: bad extent / null pointer", s);
+    EY_CHECK(!fuse_cls || (cls_w1[s] && cls_b1[s] && cls_w2[s] && cls_b2[s]), "head_tail_decode: level %d: null class-chain weights", s);
+    EY_CHECK(a_off[s] >= 0 && a_off[s] + H[s] * W[s] <= A_total, "head_tail_decode: level [%d,%d) outside A=%d", a_off[s], a_off[s] + H[s] * W[s], A_total);
+    EY_CHECK(!quality || (q_w1[s] && q_b1 && q_b1[s] && q_w2 && q_w2[s] && q_b2 && q_b2[s] && q_hidden > 0), "head_tail_decode: incomplete quality head");
+    const int ccin = fuse_cls ? cls_cin[s] : nc;
+    EY_CHECK(box_cstride[s] >= 64 && cls_cstride[s] >= ccin, "head_tail_decode: cstride");
+    if (fuse_cls && (ccin < 72 || ccin > 96 || ccin % 8))
+      return ey_set_error(EY_EUNSUPPORTED, "head_tail_decode: class feature of %d channels (72..96, multiple of 8)", ccin);
+    if ((box_cstride[s] * 2) % 16 || (cls_cstride[s] * 2) % 16 || !ey_aligned(box_feat[s], 16) || !ey_aligned(cls[s], 16) || !ey_aligned(box_w[s], 16) ||
+        (fuse_cls && (!ey_aligned(cls_w1[s], 16) || !ey_aligned(cls_w2[s], 16))))
+      return ey_set_error(EY_EUNSUPPORTED, "head_tail_decode: level %d: view not 16-byte aligned", s);
+    const long M = (long)B * H[s] * W[s], bbytes = ((M - 1) * box_cstride[s] + 64) * 2L, cbytes = ((M - 1) * cls_cstride[s] + ccin) * 2L;
+    EY_CHECK(bbytes < (1L << 31) && cbytes < (1L << 31), "head_tail_decode: view larger than 2 GiB");
+    lv.H[l] = H[s]; lv.W[l] = W[s]; lv.stride[l] = stride[s]; lv.box[l] = box_feat[s]; lv.cls[l] = cls[s]; lv.boxCs[l] = box_cstride[s]; lv.clsCs[l] = cls_cstride[s];
+    lv.a_off[l] = a_off[s];
+    lv.w1[l] = quality ? q_w1[s] : nullptr; lv.b1[l] = quality ? q_b1[s] : nullptr; lv.w2[l] = quality ? q_w2[s] : nullptr; lv.b2[l] = quality ? q_b2[s] : nullptr;
+    tw.wb[l] = (const f16*)box_w[s]; tw.bb[l] = box_b[s];
+    tw.w1[l] = fuse_cls ? (const f16*)cls_w1[s] : nullptr; tw.b1[l] = fuse_cls ? cls_b1[s] : nullptr;
+    tw.w2[l] = fuse_cls ? (const f16*)cls_w2[s] : nullptr; tw.b2[l] = fuse_cls ? cls_b2[s] : nullptr;
+    tw.clsC[l] = ccin; tw.kp1[l] = ey_conv_kpad(ccin, 2);
+    tw.boxBytes[l] = (unsigned)bbytes; tw.clsBytes[l] = (unsigned)cbytes;
+    lv.blk0[l] = (int)nblk;
+    if (l < nlevels) { nblk += (M + HT_ANCH - 1) / HT_ANCH; covered += (long)H[s] * W[s]; }
+  }
+  lv.blk0[HD_MAXL] = (int)nblk;
+  EY_CHECK(covered == A_total, "head_tail_decode: the levels cover %ld of the %d anchors (every key slot must be written)", covered, A_total);
+  EY_CHECK(nblk < (1L << 31), "head_tail_decode: too many anchors");
+  const int P = nms_pow2(A_total);
+  HdNms nm;
+  nm.keys = (unsigned long long*)candidates;
+  nm.cls_id = (int*)(nm.keys + (size_t)B * P);
+  nm.box4 = (float*)(nm.cls_id + (size_t)B * P);
+  nm.mask = class_mask;
+  nm.conf = conf_thres;
+  nm.P = P;
+  nm.xyxy = 0;
+  const int rowLs = hd_pad(nc, 2);  // >= the 64 box logits (nc > 64)
+  const size_t lds = (size_t)(HT_FRAG_BOX + (fuse_cls ? HT_FRAG_CLS : 0)) * 1024 + (size_t)HT_ANCH * rowLs * 2;
+  const bool ok = fuse_cls ? ey_lds_reserve<head_tail_decode_kernel<true>>(lds) : ey_lds_reserve<head_tail_decode_kernel<false>>(lds);
+  if (!ok) return ey_set_error(EY_ELAUNCH, "head_tail_decode: cannot reserve %zu B of LDS", lds);
+  const int lean = tune().head_lean != 0, hid = quality ? q_hidden : 0;
+  g_hd_variant = (fuse_cls ? EY_HD_TAIL_BOX_CLS : EY_HD_TAIL_BOX) + (quality ? EY_HD_QUALITY : 0) + EY_HD_NMS;
+  if (fuse_cls) hipLaunchKernelGGL(head_tail_decode_kernel<true>, dim3((unsigned)nblk), dim3(HT_ANCH), lds, (hipStream_t)stream, B, lv, tw, nc, hid, pred_or_null, A_total, rowLs, lean, nm);
+  else hipLaunchKernelGGL(head_tail_decode_kernel<false>, dim3((unsigned)nblk), dim3(HT_ANCH), lds, (hipStream_t)stream, B, lv, tw, nc, hid, pred_or_null, A_total, rowLs, lean, nm);
+  EY_LAUNCH_CHECK("ey_head_tail_decode_levels_nms");
+  return EY_OK;
 }
 
 extern "C" int ey_head_decode(int dtype, int B, int H, int W, int nc, float stride, const void* box, int box_cstride, const void* cls,

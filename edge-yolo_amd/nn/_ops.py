@@ -209,16 +209,10 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
     return out
 
 
-def conv_pw_chain(mod, x, fold1, act1, fold2, act2, out):
-    """y = act2(W2 . act1(W1 . x + b1) + b2) in ONE kernel (two chained 1x1 convs, registers only).  Returns None when the shape is
-    outside the fused kernel (the caller then runs the two convs)."""
-    L.require_device(x, "conv_pw_chain")
-    if RECORD is not None:
-        return None  # (block programs run the two convs as two stages)
-    x = L.as_nhwc(x)
-    B, cin, H, W = x.shape
-    if x.dtype != torch.float16 or cin % 8 or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16:
-        return None
+def pw_chain_packed(mod, x, fold1, fold2):
+    """Packed weights of a chained 1x1 pair for ey_conv_pw_chain (cached on `mod`): (w1p, b1, w2p, b2, cmid, cout), or False when the
+    pair is outside the chained kernels."""
+    cin = x.shape[1]
 
     def build():
         w1, b1 = fold1()
@@ -237,7 +231,33 @@ def conv_pw_chain(mod, x, fold1, act1, fold2, act2, out):
         return (pack_conv_weight(w1, x.dtype, dev), b1.to(dev).float().contiguous() if b1 is not None else None, pack_conv_weight(w2p, x.dtype, dev),
                 b2.to(dev).float().contiguous() if b2 is not None else None, cmid, cout)
 
-    packed = mod._packed(_dev_key(x, "pwchain"), build)
+    return mod._packed(_dev_key(x, "pwchain"), build)
+
+
+def packed_conv1x1(mod, x, folded_fn):
+    """(packed weight, bias, cout, elements) of a plain 1x1 conv reading `x`, in the cache slot ops.conv2d uses for it."""
+    def build():
+        w, b = folded_fn()
+        if w.shape[1] != x.shape[1] or w.shape[2] != 1:
+            raise ValueError(f"conv 1x1: weight {tuple(w.shape)} does not match Cin={x.shape[1]}")
+        pk = pack_conv_weight(w, x.dtype, x.device)
+        return pk, (None if b is None else b.to(x.device).float().contiguous()), w.shape[0], pk.numel() // x.element_size()
+
+    return mod._packed(_dev_key(x, "igemm"), build)
+
+
+def conv_pw_chain(mod, x, fold1, act1, fold2, act2, out):
+    """y = act2(W2 . act1(W1 . x + b1) + b2) in ONE kernel (two chained 1x1 convs, registers only).  Returns None when the shape is
+    outside the fused kernel (the caller then runs the two convs)."""
+    L.require_device(x, "conv_pw_chain")
+    if RECORD is not None:
+        return None  # (block programs run the two convs as two stages)
+    x = L.as_nhwc(x)
+    B, cin, H, W = x.shape
+    if x.dtype != torch.float16 or cin % 8 or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16:
+        return None
+
+    packed = pw_chain_packed(mod, x, fold1, fold2)
     if packed is False:
         return None
     w1p, b1, w2p, b2, cmid, cout = packed
@@ -1052,6 +1072,49 @@ def head_decode_levels(levels, pred, nms=None, xyxy=False):
         fn = L.lib().ey_head_decode_levels_xyxy if xyxy else L.lib().ey_head_decode_levels
         L.check(fn(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
                    pred.data_ptr(), pred.shape[2], offs, L.stream()), "ey_head_decode_levels")
+
+
+def head_tail_decode_levels(levels, tails, pred, nms):
+    """head_decode_levels(nms=...) with the towers' closing 1x1 convs inside the decode kernel (ey_head_tail_decode_levels_nms).
+    levels: list (<= 4) of (box_feat, cls_in, stride, q-or-None, a_off); tails: per level (box_wp, box_b, chain) with chain =
+    (w1p, b1, w2p, b2) -- cls_in is then the class-tower feature in front of the chain -- or None on every level (cls_in = the
+    class logits).  nc: tails' class count = `nms[3]`.  Returns a Candidates object, or None when the shapes are outside the fused
+    kernel (nothing launched: the caller runs the convs and head_decode_levels)."""
+    n = len(levels)
+    box0 = levels[0][0]
+    L.require_device(box0, "head_tail_decode")
+    _no_block("head decode")
+    conf, mask, classes, nc = nms
+    B = box0.shape[0]
+    fuse_cls = tails[0][2] is not None
+    q0 = levels[0][3]
+    hid = q0[0].shape[0] if q0 is not None else 0
+    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
+    Hs, Ws = IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels])
+    st = FA(*[float(lv[2]) for lv in levels])
+    boxp, clsp = PA(*[lv[0].data_ptr() for lv in levels]), PA(*[lv[1].data_ptr() for lv in levels])
+    boxcs, clscs = IA(*[L.cstride(lv[0]) for lv in levels]), IA(*[L.cstride(lv[1]) for lv in levels])
+    clscin = IA(*[lv[1].shape[1] for lv in levels])
+    offs = IA(*[int(lv[4]) for lv in levels])
+    qa = [PA(*[(lv[3][j].data_ptr() if lv[3] is not None else None) for lv in levels]) for j in range(4)]
+    bw, bb = PA(*[t[0].data_ptr() for t in tails]), PA(*[(t[1].data_ptr() if t[1] is not None else None) for t in tails])
+    ch = [PA(*[(t[2][j].data_ptr() if fuse_cls and t[2][j] is not None else None) for t in tails]) for j in range(4)]
+    A = sum(lv[0].shape[2] * lv[0].shape[3] for lv in levels)
+    nb = L.lib().ey_nms_candidates_bytes(B, A)
+    buf = torch.empty(nb, dtype=torch.uint8, device=box0.device)
+    cin = box0.shape[1]
+    wbytes = sum(64 * cin * 2 + ((80 * lv[1].shape[1] + nc * 80) * 2 if fuse_cls else 0) for lv in levels)
+    flops = sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * (hid * 21 + 200 + 64 * cin + ((80 * lv[1].shape[1] + nc * 80) if fuse_cls else 0)) for lv in levels)
+    nbytes = sum(_nb(lv[0], lv[1]) for lv in levels) + wbytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0)
+    try:
+        with _tr("head_tail_decode_kernel", nbytes, flops, note=f"{n} levels, box tail{' + class chain' if fuse_cls else ''} + NMS keys"):
+            L.check(L.lib().ey_head_tail_decode_levels_nms(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, cin, 64, bw, bb, clsp, clscs, int(fuse_cls), clscin, 80,
+                                                           ch[0], ch[1], ch[2], ch[3], nc, qa[0], qa[1], qa[2], qa[3], hid, pred.data_ptr() if pred is not None else None,
+                                                           A, offs, float(conf), mask.data_ptr() if mask is not None else None, buf.data_ptr(), nb, L.stream()),
+                    "ey_head_tail_decode_levels_nms")
+    except NotImplementedError:  # EY_EUNSUPPORTED: nothing was launched (and nothing traced)
+        return None
+    return Candidates(buf, B, nc, A, conf, classes, pred)
 
 
 def scale_img(x, ratio, flip_lr=False, gs=32):

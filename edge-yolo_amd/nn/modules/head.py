@@ -106,11 +106,12 @@ class Detect(nn.Module):
         b = getattr(self, self._branch + "cv2")[i]
         self._tail(b[2]).run(b[1](b[0](x)), raw[:, :4 * self.reg_max])
 
-    def _cls_tower(self, i, x, raw):
-        """class logits -> raw[:, 64:]."""
+    def _cls_tower(self, i, x, raw, out=None):
+        """class logits -> raw[:, 64:] (or `out`)."""
         c = getattr(self, self._branch + "cv3")[i]
         t = x
-        out = raw[:, 4 * self.reg_max:]
+        if out is None:
+            out = raw[:, 4 * self.reg_max:]
         last = c[-2]
         # non-legacy tower (head.py:68-70): ... -> DWConv -> Conv(c3,c3,1)+SiLU -> nn.Conv2d(c3,nc,1): the last two 1x1 convs run as ONE
         # register-only kernel when the shape fits (ey_conv_pw_chain), the intermediate (B,c3,H,W) tensor never exists
@@ -168,7 +169,10 @@ class Detect(nn.Module):
         """nms=None: returns (pred (B,4+nc,A) fp32, raw per-level maps) like the reference.  nms=dict(conf=, classes=None, keep_pred=False)
         (predict pipelines): the decode also builds the NMS candidates for that confidence threshold / class filter in the same pass
         and returns (_ops.Candidates, raw maps) -- `utils.ops.nms_device` takes it in place of `pred`, which is then neither written nor
-        re-read (keep_pred=True still writes it, as Candidates.pred)."""
+        re-read (keep_pred=True still writes it, as Candidates.pred).  Where the head has the standard shape (f16, 64-channel box
+        tower, class chain c3 -> 80 -> nc with nc % 8 == 0, 64 < nc <= 80) the closing 1x1 convs of both towers run inside the decode
+        kernel (tunable head_fuse): their logits are then never written, and the second return value holds None per level -- pass
+        nms["keep_raw"]=True to keep the separate launches and get the raw maps."""
         if self.training:
             raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
         if self.reg_max != 16:
@@ -194,6 +198,9 @@ class Detect(nn.Module):
         smap = list(self.tower_streams) if (self.tower_streams and len(self.tower_streams) == 2 * len(xs)) else [0, 0] + [1] * (2 * len(xs) - 2)
         if fork and (getattr(self, "_side", None) is None or self._side_dev != dev or len(self._side) != max(smap)):
             self._side, self._side_dev = [torch.cuda.Stream(device=dev) for _ in range(max(smap))], dev
+        fuse = self._head_fuse(xs, nms)
+        if fuse:
+            return self._forward_fused(xs, nms, fuse, pred, fork, cur, smap)
         # every buffer a side stream WRITES is allocated before the fork: a block handed out later on the caller's stream could be one
         # that kernels still queued there are using (the caching allocator orders reuse per stream only)
         raws = [L.empty_nhwc(B, (self.no + 7) // 8 * 8, t.shape[2], t.shape[3], dt, dev)[:, :self.no] for t in xs]  # pixel stride kept 16-byte aligned for any nc
@@ -235,18 +242,114 @@ class Detect(nn.Module):
             return levels, x
         if nms is not None and len(levels) <= 4 and self.nc > 1:
             classes = nms.get("classes")
-            mask = None
-            if classes is not None:
-                key = (tuple(classes), dev)
-                if getattr(self, "_mask_key", None) != key:  # tiny host->device upload, once per filter (not inside a captured graph)
-                    m = torch.zeros(self.nc, dtype=torch.uint8)
-                    m[torch.as_tensor(list(classes), dtype=torch.long)] = 1
-                    self._mask, self._mask_key = m.to(dev), key
-                mask = self._mask
-            cand = ops.head_decode_levels(levels, pred if nms.get("keep_pred") else None, nms=(nms["conf"], mask, classes))
+            cand = ops.head_decode_levels(levels, pred if nms.get("keep_pred") else None, nms=(nms["conf"], self._class_mask(classes, dev), classes))
             return cand, x
         self._decode(levels, pred)
         return pred if self.export else (pred, x)
+
+    def _class_mask(self, classes, dev):
+        if classes is None:
+            return None
+        key = (tuple(classes), dev)
+        if getattr(self, "_mask_key", None) != key:  # tiny host->device upload, once per filter (not inside a captured graph)
+            m = torch.zeros(self.nc, dtype=torch.uint8)
+            m[torch.as_tensor(list(classes), dtype=torch.long)] = 1
+            self._mask, self._mask_key = m.to(dev), key
+        return self._mask
+
+    # ---- predict mode: the towers' closing 1x1 convs inside the decode kernel (ey_head_tail_decode_levels_nms)
+    def _head_fuse(self, xs, nms):
+        """0 = the towers write their logits and the decode reads them; 1 = the box tail (nn.Conv2d(64, 64, 1)) runs inside the decode
+        kernel; 2 = so does the class chain (Conv(c3, 80, 1) + SiLU -> nn.Conv2d(80, nc, 1)).  The tunable head_fuse (csrc/tune.h) picks the
+        level; the structure and shape gate below mirrors the kernel's."""
+        if (nms is None or nms.get("keep_raw") or getattr(self, "defer_decode", False) or self.block_fusion or not self.chain or self.legacy
+                or len(xs) > 4 or xs[0].dtype != torch.float16 or self.nc % 8 or not 64 < self.nc <= 80 or xs[0].device.type != "cuda"):
+            return 0
+        fuse = int(L.lib().ey_tune_get(b"head_fuse"))
+        if fuse not in (1, 2):
+            return 0
+        for i in range(len(xs)):
+            b, c = getattr(self, self._branch + "cv2")[i], getattr(self, self._branch + "cv3")[i]
+            if not (len(b) == 3 and isinstance(b[1], Conv) and isinstance(b[2], nn.Conv2d) and b[2].kernel_size == (1, 1) and b[2].groups == 1
+                    and b[2].in_channels == 64 and b[2].out_channels == 64 and b[2].bias is not None):
+                return 0
+            last, ct = c[-2], c[-1]
+            if not (isinstance(last, nn.Sequential) and len(last) == 2 and isinstance(last[0], DWConv) and isinstance(last[1], Conv)
+                    and last[1].conv.kernel_size == (1, 1) and last[1].conv.groups == 1 and isinstance(last[1].act, nn.SiLU)
+                    and last[1].conv.out_channels == 80 and 72 <= last[1].conv.in_channels <= 96 and last[1].conv.in_channels % 8 == 0
+                    and isinstance(ct, nn.Conv2d) and ct.kernel_size == (1, 1) and ct.groups == 1 and ct.in_channels == 80 and ct.out_channels == self.nc
+                    and ct.bias is not None):
+                return 0
+        return fuse
+
+    def _forward_fused(self, xs, nms, fuse, pred, fork, cur, smap):
+        """forward(nms=...) with head_fuse = 1 / 2: the towers stop one conv (box) / two convs (class) early, their features go to the decode
+        kernel with the packed weights of what was skipped.  Returns (Candidates, [None] * levels): the raw maps are not produced."""
+        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        n = len(xs)
+        cv2, cv3 = getattr(self, self._branch + "cv2"), getattr(self, self._branch + "cv3")
+        # (allocated before the fork, like the raw maps of the unfused path and for the same reason)
+        bfeat = [L.empty_nhwc(B, 64, t.shape[2], t.shape[3], dt, dev) for t in xs]
+        cbuf = [L.empty_nhwc(B, cv3[i][-2][1].conv.in_channels if fuse == 2 else self.nc, t.shape[2], t.shape[3], dt, dev) for i, t in enumerate(xs)]
+
+        def box_tower(i, t):
+            cv2[i][1](cv2[i][0](t), out=bfeat[i])
+
+        def cls_tower(i, t):
+            if fuse == 1:
+                return self._cls_tower(i, t, None, out=cbuf[i])
+            c = cv3[i]
+            for j in range(len(c) - 2):
+                t = c[j](t)
+            c[-2][0](t, out=cbuf[i])
+
+        if fork:
+            for side in self._side:
+                side.wait_stream(cur)
+        task = 0
+        for i, t in enumerate(xs):
+            for tower in (box_tower, cls_tower):
+                if fork and smap[task] > 0:
+                    with torch.cuda.stream(self._side[smap[task] - 1]):
+                        tower(i, t)
+                else:
+                    tower(i, t)
+                task += 1
+        if fork:
+            for side in self._side:
+                cur.wait_stream(side)
+        levels, tails, a_off = [], [], 0
+        for i, t in enumerate(xs):
+            bt, ct = cv2[i][2], cv3[i][-1]
+            wp, bias, _, _ = ops.packed_conv1x1(self._tail(bt), bfeat[i], lambda bt=bt: fold_bn(bt.weight, bt.bias, None))
+            chain = None
+            if fuse == 2:
+                chain = ops.pw_chain_packed(self._tail(ct), cbuf[i], cv3[i][-2][1].folded, lambda ct=ct: fold_bn(ct.weight, ct.bias, None))
+                chain = chain[:4] if chain else (None,) * 4  # (a pair outside the chained kernel: the separate launches below)
+            levels.append((bfeat[i], cbuf[i], self._stride_f[i], self._quality_params(i, dev), a_off))
+            tails.append((wp, bias, chain))
+            a_off += t.shape[2] * t.shape[3]
+        classes = nms.get("classes")
+        mask = self._class_mask(classes, dev)
+        keep = pred if nms.get("keep_pred") else None
+        cand = None
+        if all(tl[1] is not None and (tl[2] is None or all(w is not None for w in tl[2])) for tl in tails):  # (weights and every bias present: the kernel's gate)
+            cand = ops.head_tail_decode_levels(levels, tails, keep, (nms["conf"], mask, classes, self.nc))
+        if cand is None:  # outside the fused kernel after all (a misaligned view): the skipped convs as launches of their own, then today's decode
+            plain = []
+            for i, (bf, cb, st, q, off) in enumerate(levels):
+                raw = L.empty_nhwc(B, (self.no + 7) // 8 * 8, bf.shape[2], bf.shape[3], dt, dev)[:, :self.no]
+                self._tail(cv2[i][2]).run(bf, raw[:, :4 * self.reg_max])
+                out = raw[:, 4 * self.reg_max:]
+                if fuse == 1:
+                    out = cb
+                else:
+                    ct, mid = cv3[i][-1], cv3[i][-2][1]
+                    if ops.conv_pw_chain(self._tail(ct), cb, mid.folded, L.ACT_SILU, lambda ct=ct: fold_bn(ct.weight, ct.bias, None), L.ACT_NONE, out) is None:
+                        self._tail(ct).run(mid(cb), out)
+                plain.append((raw[:, :4 * self.reg_max], out, st, q, off))
+            cand = ops.head_decode_levels(plain, keep, nms=(nms["conf"], mask, classes))
+        return cand, [None] * n
 
     # ---- end2end (NMS-free) inference, reference head.py:93-115 (Detect) / :273-298 (GF2Detect)
     one2many_in_inference = False  # the reference also runs the one2many towers in eval mode and returns their maps next to the result,

@@ -401,6 +401,25 @@ int ey_head_decode_levels_nms(int dtype, int B, int nlevels, const int* H, const
                               const void* const* cls, const int* cls_cstride, int nc, const float* const* q_w1, const float* const* q_b1,
                               const float* const* q_w2, const float* const* q_b2, int q_hidden, float* pred_or_null, int A_total, const int* a_off,
                               float conf_thres, const uint8_t* class_mask, void* candidates, size_t candidates_bytes, ey_stream_t stream);
+/* ey_head_decode_levels_nms with the towers' closing 1x1 convs inside the decode kernel (predict mode: nothing else reads their
+ * logits) -- replaces, per level, nn.Conv2d(64, 64, 1) of the box tower and Conv(c3, c3, 1) + SiLU -> nn.Conv2d(c3, nc, 1) of the
+ * class tower (ultralytics/nn/modules/head.py:61,68-70) in front of the decode (:227-243,341-345).  Same candidates and pred, bit for
+ * bit, as ey_conv2d (ACT_NONE) + ey_conv_pw_chain (SiLU, NONE) + ey_head_decode_levels_nms on the same tensors.
+ *   box_feat[l]: (B, box_cin, H, W) output of cv2[l][1];  box_w[l] / box_b[l]: ey_conv_pack_weight(EY_F16, box_cout, box_cin, 1) / bias.
+ *   fuse_cls = 1: cls[l] = (B, cls_cin[l], H, W) output of the tower's second DWConv; cls_w1 = ey_conv_pack_weight(EY_F16, cls_cmid,
+ *     cls_cin[l], 1), cls_w2 = ey_conv_pack_weight(EY_F16, nc, ey_conv_chain_klen(cls_cmid), 1) of the column-permuted weights (as
+ *     ey_conv_pw_chain), cls_b1 / cls_b2 the fp32 biases (all required).
+ *   fuse_cls = 0: cls[l] = the (B, nc, H, W) class logits; the cls_* weight arguments are ignored (may be NULL).
+ * Shape gate -- f16, <= 4 levels, box_cin == box_cout == 64, cls_cin in 72..96 (% 8), cls_cmid == 80, nc % 8 == 0 and 64 < nc <= 80,
+ * every view 16-byte aligned: EY_EUNSUPPORTED before anything is launched otherwise; all levels of a call are fused, or none.
+ * Variant code (ey_head_decode_last_variant): EY_HD_TAIL_BOX or EY_HD_TAIL_BOX_CLS (+ EY_HD_QUALITY) + EY_HD_NMS. */
+int ey_head_tail_decode_levels_nms(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box_feat,
+                                   const int* box_cstride, int box_cin, int box_cout, const void* const* box_w, const float* const* box_b,
+                                   const void* const* cls, const int* cls_cstride, int fuse_cls, const int* cls_cin, int cls_cmid,
+                                   const void* const* cls_w1, const float* const* cls_b1, const void* const* cls_w2, const float* const* cls_b2, int nc,
+                                   const float* const* q_w1, const float* const* q_b1, const float* const* q_w2, const float* const* q_b2, int q_hidden,
+                                   float* pred_or_null, int A_total, const int* a_off, float conf_thres, const uint8_t* class_mask, void* candidates,
+                                   size_t candidates_bytes, ey_stream_t stream);
 /* Second half of ey_nms (selection + greedy suppression, utils/ops.py:277-309 + torchvision.ops.nms) on a candidate buffer
  * written by ey_head_decode_levels_nms.  Outputs as ey_nms.  The tail of the buffer (beyond keys / class ids / boxes) is the scratch of
  * the predict-mode fast path (sorted candidate records + the pairwise suppression bit matrix) and is written by this call. */
@@ -424,8 +443,9 @@ int ey_e2e_topk(int B, int nc, int A, const float* pred_xyxy, int k, float* out_
 
 /* Form of head_decode_kernel the last ey_head_decode* on this thread launched (tests); 0 = nothing launched.
  * EY_HD_VEC (16-byte staging: nc % 8 == 0, aligned views) or EY_HD_SCALAR, + EY_HD_QUALITY (DGQP quality head) + EY_HD_NMS (fused
- * NMS candidates). */
-enum { EY_HD_VEC = 1, EY_HD_SCALAR = 2, EY_HD_QUALITY = 10, EY_HD_NMS = 100 };
+ * NMS candidates).  head_tail_decode_kernel (ey_head_tail_decode_levels_nms): EY_HD_TAIL_BOX (box tail inside) or EY_HD_TAIL_BOX_CLS
+ * (box tail and class chain inside) in place of VEC / SCALAR. */
+enum { EY_HD_VEC = 1, EY_HD_SCALAR = 2, EY_HD_TAIL_BOX = 3, EY_HD_TAIL_BOX_CLS = 4, EY_HD_QUALITY = 10, EY_HD_NMS = 100 };
 int ey_head_decode_last_variant(void);
 
 /* ---- Block programs: a chain of layers on SMALL feature maps (<= 4096 pixels per image; built for the 20x20 part of the network at

@@ -78,7 +78,7 @@ def label_of(name):
         return f"dwconv_kernel<{m[1]}>"
     if "dwconv3_strip" in name:
         return "dwconv_kernel<3>"
-    for k in ("stem_kernel", "dwt_kernel", "head_decode_kernel", "linattn_kernel", "sppf_kernel", "copy_kernel", "softattn_kernel"):
+    for k in ("stem_kernel", "dwt_kernel", "head_tail_decode_kernel", "head_decode_kernel", "linattn_kernel", "sppf_kernel", "copy_kernel", "softattn_kernel"):
         if k in name:
             return k
     for k in ("nf_select_kernel", "nf_mask_kernel", "nf_resolve_kernel", "scale_img_kernel", "tta_merge_kernel"):
