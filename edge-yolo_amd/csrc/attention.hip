@@ -405,212 +405,25 @@ extern "C" int ey_softmax_attention(int dtype, int B, int N, int heads, int kd, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Area attention core (AAttn.forward, YOLOv12 R-ELAN, reference block.py:1313-1356).  The H*W pixels of an image, in row-major
-// order, are cut into `area` contiguous runs of Na = N/area tokens, and each (run, head) is attended on its own:
-//   y[n][h*hd + c] = sum_m softmax_m(scale * q[n][h*hd:].k[m][h*hd:]) v[m][h*hd + c]
-// In NHWC a run is a contiguous pixel range, so a run is simply "image" gi = b*area + a of Na pixels: no data moves.
+// Softmax attention within token groups, one kernel pair behind two entry points:
+//   y[n][h*HD + c] = sum_m softmax_m(scale * q[n][h*HD:].k[m][h*HD:]) v[m][h*HD + c]      n, m tokens of the same group
+// * ey_flash_attention (GlobalSparseAttn.forward of the LGL block, reference block.py:3147-3152): a group is an image, all N = H*W tokens.
+// * ey_area_attention (AAttn.forward, YOLOv12 R-ELAN, reference block.py:1313-1356): the H*W pixels of an image, in row-major order, are
+//   cut into `area` contiguous runs of N/area tokens, and a group is one run.  In NHWC a run is a contiguous pixel range, so a run is
+//   simply "image" gi = b*area + a of N/area pixels: no data moves.
 //
-// MFMA form (f16, hd = 32), flash style: a 256-thread workgroup takes 64 queries of one (run, head), 16 per wave, with the wave's
-// Q fragment in registers.  Keys stream through LDS in tiles of 64 (K and V, zero-padded past Na); per tile:
-//   S^T = K Q^T      4 MFMAs: A = K rows from LDS, B = Q: lane (r, g) holds query r and keys 16kb + 4g + t
-//   online softmax   running max m and sum l per query: tile max over the lane's 16 values, then across the 4 lanes of the query
-//   Y^T += V^T P^T   2 x 2 MFMAs, contraction in the order the scores already sit in the registers (as in softattn_mfma_kernel)
-// Y is scaled by 1/l once at the end.  Any Na >= 1: keys past Na are masked to -inf; queries past Na compute on zeros and are not stored.
+// MFMA form (f16, HD in {16, 32, 64}), flash style: a 256-thread workgroup takes 64 queries of one (group, head), 16 per wave, with the
+// wave's Q fragment in registers.  Keys stream through LDS in tiles of 64 (K and V, zero-filled past N and masked to -inf, so a padded
+// key never scores); queries past N compute on zeros and are not stored.  LDS is 2 x 64 x (HD + 8) f16 whatever N is.  Per tile:
+//   S^T = K Q^T      A = K rows from LDS, B = Q: lane (r, g) holds query r and keys 16kb + 4g + t.  HD 32 / 64: one / two 16x16x32 MFMAs
+//                    per 16-key block.  HD 16: ONE v_mfma_f32_16x16x16_f16 -- the 16-deep form has the same result layout at the same
+//                    cycles as a half-empty 32-deep one, and needs no zero half in the K rows of LDS nor in the Q registers (8-byte
+//                    instead of 16-byte fragment reads)
+//   online softmax   fp32 running max m and sum l per query: tile max over the lane's 16 values, then across the 4 lanes of the query
+//   Y^T += V^T P^T   HD/16 output blocks x 2 steps of 32 keys, contraction in the order the scores already sit in the registers (as in
+//                    softattn_mfma_kernel)
+// Y is scaled by 1/l once at the end.  N is the token count of a group, any N >= 1; the grid is (groups * heads) x ceil(N / 64).
 #define AA_KT 64  // keys per LDS tile
-#define AA_LS 40  // LDS row stride (f16) of the K and V tiles: the 2-byte V gathers of a wave hit 32 distinct banks
-__global__ __launch_bounds__(256) void area_attn_mfma_kernel(int Na, int heads, int qtiles, float scale, const f16* __restrict__ q, int qCs,
-                                                              const f16* __restrict__ k, int kCs, const f16* __restrict__ v, int vCs, f16* __restrict__ y, int yCs) {
-  __shared__ __attribute__((aligned(16))) f16 Ks[AA_KT * AA_LS];
-  __shared__ __attribute__((aligned(16))) f16 Vs[AA_KT * AA_LS];
-  const int qt = blockIdx.x % qtiles, gh = blockIdx.x / qtiles;
-  const int gi = gh / heads, h = gh - gi * heads;
-  const long p0 = (long)gi * Na;  // first pixel of the run
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  const int n = (qt * 4 + wave) * 16 + r;  // this lane's query
-  Vec8<f16> qf;
-  if (n < Na) qf.load(q + (p0 + n) * qCs + h * 32 + 8 * g);
-  else qf.zero();
-  const f16* kp = k + p0 * kCs + h * 32;
-  const f16* vp = v + p0 * vCs + h * 32;
-  float m = -INFINITY, l = 0.f;
-  f32x4 acc[2] = {(f32x4)0.f, (f32x4)0.f};
-  const int skey = tid >> 2, soct = tid & 3;  // staging: 64 keys x 4 octets, one K and one V vector per thread
-  for (int t0 = 0; t0 < Na; t0 += AA_KT) {
-    {
-      Vec8<f16> a, b;
-      if (t0 + skey < Na) {
-        a.load(kp + (long)(t0 + skey) * kCs + 8 * soct);
-        b.load(vp + (long)(t0 + skey) * vCs + 8 * soct);
-      } else {
-        a.zero();
-        b.zero();
-      }
-      a.store(Ks + skey * AA_LS + 8 * soct);
-      b.store(Vs + skey * AA_LS + 8 * soct);
-    }
-    __syncthreads();
-    f32x4 S[4];
-    float mt = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      Vec8<f16> kf;
-      kf.load(Ks + (kb * 16 + r) * AA_LS + 8 * g);
-      S[kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf.v, qf.v, (f32x4)0.f, 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (t0 + kb * 16 + 4 * g + t >= Na) S[kb][t] = -INFINITY;  // padded keys
-        mt = fmaxf(mt, S[kb][t]);
-      }
-    }
-    mt = fmaxf(mt, __shfl_xor(mt, 16));
-    mt = fmaxf(mt, __shfl_xor(mt, 32));
-    const float mn = fmaxf(m, mt);
-    // every tile holds a real key, so mn is finite; the guard keeps a fully masked tile from computing exp(-inf - -inf) = NaN
-    const float mu = mn == -INFINITY ? 0.f : mn;
-    const float alpha = __expf((m - mu) * scale);  // 0 on the first tile (m = -inf)
-    float ps = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { S[kb][t] = __expf((S[kb][t] - mu) * scale); ps += S[kb][t]; }
-    ps += __shfl_xor(ps, 16);
-    ps += __shfl_xor(ps, 32);
-    l = l * alpha + ps;
-    m = mn;
-    acc[0] *= alpha;
-    acc[1] *= alpha;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      Vec8<f16> pf;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { pf.v[t] = (f16)S[2 * s][t]; pf.v[4 + t] = (f16)S[2 * s + 1][t]; }
-      const f16* vs = Vs + (32 * s + 4 * g) * AA_LS + r;
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        Vec8<f16> vf;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) vf.v[j] = vs[(16 * (j >> 2) + (j & 3)) * AA_LS + cb * 16];
-        acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf.v, pf.v, acc[cb], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  if (n < Na) {
-    const float inv = __builtin_amdgcn_rcpf(l);
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const f16x4 o = {(f16)(acc[cb][0] * inv), (f16)(acc[cb][1] * inv), (f16)(acc[cb][2] * inv), (f16)(acc[cb][3] * inv)};
-      *reinterpret_cast<f16x4*>(y + (p0 + n) * yCs + h * 32 + cb * 16 + 4 * g) = o;
-    }
-  }
-}
-
-// VALU form (fp32, and f16 with hd != 32 or unaligned views): exact fp32 arithmetic in the reference's order -- scores
-// s_m = (q.k_m) * scale, e_m = exp(s_m - max), p_m = e_m / sum e, y = sum_m p_m v_m.  One wave per query at a time (4 per workgroup);
-// lanes stride over keys for the scores (kept in LDS), then over output channels.  hd <= 64.
-#define AA_VQ 16  // queries per workgroup
-template <typename T>
-__global__ __launch_bounds__(256) void area_attn_kernel(int Na, int heads, int hd, int qtiles, float scale, const T* __restrict__ q, int qCs,
-                                                         const T* __restrict__ k, int kCs, const T* __restrict__ v, int vCs, T* __restrict__ y, int yCs) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* Qs = reinterpret_cast<float*>(smem);  // [4][64]
-  float* Sc = Qs + 4 * 64;                     // [4][Na]
-  const int qt = blockIdx.x % qtiles, gh = blockIdx.x / qtiles;
-  const int gi = gh / heads, h = gh - gi * heads;
-  const long p0 = (long)gi * Na;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* qs = Qs + wave * 64;
-  float* sc = Sc + (long)wave * Na;
-  const T* kb = k + p0 * kCs + h * hd;
-  const T* vb = v + p0 * vCs + h * hd;
-  const int n1 = min(Na, (qt + 1) * AA_VQ);
-  for (int n = qt * AA_VQ + wave; n < n1; n += 4) {
-    qs[lane] = lane < hd ? to_f(q[(p0 + n) * qCs + h * hd + lane]) : 0.f;
-    __builtin_amdgcn_wave_barrier();
-    float mx = -INFINITY;
-    for (int j = lane; j < Na; j += 64) {
-      const T* kr = kb + (long)j * kCs;
-      float a = 0.f;
-      for (int c = 0; c < hd; ++c) a = fmaf(qs[c], to_f(kr[c]), a);
-      a *= scale;
-      sc[j] = a;
-      mx = fmaxf(mx, a);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < Na; j += 64) {
-      const float e = expf(sc[j] - mx);
-      sc[j] = e;
-      sum += e;
-    }
-    sum = wave_sum(sum);
-    for (int j = lane; j < Na; j += 64) sc[j] = sc[j] / sum;  // (lanes own the keys they wrote)
-    __builtin_amdgcn_wave_barrier();
-    if (lane < hd) {
-      float o = 0.f;
-      for (int j = 0; j < Na; ++j) o = fmaf(sc[j], to_f(vb[(long)j * vCs + lane]), o);
-      y[(p0 + n) * yCs + h * hd + lane] = from_f<T>(o);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-extern "C" int ey_area_attention(int dtype, int B, int N, int area, int heads, int hd, float scale, const void* q, int q_cstride, const void* k,
-                                 int k_cstride, const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream) {
-  g_attn_variant = 0;
-  EY_CHECK(q && k && v && y, "area_attention: null pointer");
-  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "area_attention: bad dtype");
-  EY_CHECK(B > 0 && N > 0 && area > 0 && heads > 0 && hd > 0, "area_attention: B=%d N=%d area=%d heads=%d hd=%d", B, N, area, heads, hd);
-  if (N % area) return ey_set_error(EY_EINVAL, "area_attention: %d tokens do not split into %d equal areas", N, area);
-  if (hd > 64) return ey_set_error(EY_EUNSUPPORTED, "area_attention: head_dim %d > 64", hd);
-  EY_CHECK(q_cstride >= heads * hd && k_cstride >= heads * hd && v_cstride >= heads * hd && y_cstride >= heads * hd, "area_attention: cstride");
-  const int Na = N / area;
-  const long groups = (long)B * area * heads;
-  hipStream_t st = (hipStream_t)stream;
-  const bool mfma = dtype == EY_F16 && hd == 32 && tune().areaattn_mfma && ey_aligned(q, 16) && ey_aligned(k, 16) && ey_aligned(v, 16) && ey_aligned(y, 8) &&
-                    q_cstride % 8 == 0 && k_cstride % 8 == 0 && v_cstride % 8 == 0 && y_cstride % 4 == 0;
-  if (mfma) {
-    const int qtiles = (Na + 63) / 64;
-    if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "area_attention: grid too large");
-    g_attn_variant = EY_ATTN_AREA_MFMA;
-    hipLaunchKernelGGL(area_attn_mfma_kernel, dim3((unsigned)(groups * qtiles)), dim3(256), 0, st, Na, heads, qtiles, scale, (const f16*)q, q_cstride,
-                       (const f16*)k, k_cstride, (const f16*)v, v_cstride, (f16*)y, y_cstride);
-    EY_LAUNCH_CHECK("ey_area_attention(mfma)");
-    return EY_OK;
-  }
-  const size_t lds = (4 * 64 + 4 * (size_t)Na) * sizeof(float);
-  if (lds > 160 * 1024) return ey_set_error(EY_EUNSUPPORTED, "area_attention: %d tokens per area need %zu B of LDS", Na, lds);
-  const int qtiles = (Na + AA_VQ - 1) / AA_VQ;
-  if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "area_attention: grid too large");
-  const dim3 grid((unsigned)(groups * qtiles));
-  if (dtype == EY_F16) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
-    g_attn_variant = EY_ATTN_AREA_F16;
-    hipLaunchKernelGGL(area_attn_kernel<f16>, grid, dim3(256), lds, st, Na, heads, hd, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride,
-                       (const f16*)v, v_cstride, (f16*)y, y_cstride);
-  } else {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
-    g_attn_variant = EY_ATTN_AREA_F32;
-    hipLaunchKernelGGL(area_attn_kernel<float>, grid, dim3(256), lds, st, Na, heads, hd, qtiles, scale, (const float*)q, q_cstride, (const float*)k,
-                       k_cstride, (const float*)v, v_cstride, (float*)y, y_cstride);
-  }
-  EY_LAUNCH_CHECK("ey_area_attention");
-  return EY_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Flash attention core over ALL tokens of an image (GlobalSparseAttn.forward of the LGL block, reference block.py:3147-3152):
-//   y[n][h*HD + c] = sum_m softmax_m(scale * q[n][h*HD:].k[m][h*HD:]) v[m][h*HD + c],   HD in {16, 32, 64}.
-// The loop of area_attn_mfma_kernel with the head dim as a template parameter (that kernel itself is left as it is: its hd = 32
-// code object is pinned by tests): a 256-thread workgroup takes 64 queries of one (image, head), 16 per wave, Q fragments in
-// registers; keys stream through LDS in tiles of 64 (zero-filled past N and masked to -inf, so a padded key never scores);
-// online softmax with fp32 running max / sum per query.  LDS is 2 x 64 x (HD + 8) f16 whatever N is.
-//   S^T = K Q^T     HD 32 / 64: one / two 16x16x32 MFMAs per 16-key block.  HD 16: ONE v_mfma_f32_16x16x16_f16 -- the 16-deep form has
-//                   the same result layout at the same cycles as a half-empty 32-deep one, and needs no zero half in the K rows of LDS
-//                   nor in the Q registers (8-byte instead of 16-byte fragment reads)
-//   Y^T += V^T P^T  HD/16 output blocks x 2 steps of 32 keys, contraction in the order the scores already sit in the registers
 template <int HD>
 __global__ __launch_bounds__(256) void flash_attn_kernel(int N, int heads, int qtiles, float scale, const f16* __restrict__ q, int qCs,
                                                           const f16* __restrict__ k, int kCs, const f16* __restrict__ v, int vCs, f16* __restrict__ y, int yCs) {
@@ -620,9 +433,9 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(int N, int heads, int q
   constexpr int OCT = HD / 8;    // 16-byte vectors per row
   __shared__ __attribute__((aligned(16))) f16 Ks[AA_KT * LS];
   __shared__ __attribute__((aligned(16))) f16 Vs[AA_KT * LS];
-  const int qt = blockIdx.x % qtiles, bh = blockIdx.x / qtiles;
-  const int b = bh / heads, h = bh - b * heads;
-  const long p0 = (long)b * N;  // first token of the image
+  const int qt = blockIdx.x % qtiles, gh = blockIdx.x / qtiles;
+  const int gi = gh / heads, h = gh - gi * heads;
+  const long p0 = (long)gi * N;  // first token of the group
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
   const int n = (qt * 4 + wave) * 16 + r;  // this lane's query
   Vec8<f16> qf[NQS ? NQS : 1];
@@ -645,7 +458,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(int N, int heads, int q
   for (int cb = 0; cb < NCB; ++cb) acc[cb] = (f32x4)0.f;
   for (int t0 = 0; t0 < N; t0 += AA_KT) {
 #pragma unroll
-    for (int i = tid; i < AA_KT * OCT; i += 256) {  // staging: 64 keys x OCT vectors of K and of V
+    for (int i = tid; i < AA_KT * OCT; i += 256) {  // staging: 64 keys x OCT vectors of K and of V (HD 32: one K and one V vector per thread)
       const int skey = i / OCT, soct = i % OCT;
       Vec8<f16> a, c;
       if (t0 + skey < N) {
@@ -723,7 +536,118 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(int N, int heads, int q
   }
 }
 
-#define FA_VALU_MAX_TOKENS ((160 * 1024 / 4 - 4 * 64) / 4)  // area_attn_kernel keeps 4 fp32 score rows of N in LDS: 10176
+// VALU form (fp32, and f16 with head dims off the MFMA path or unaligned views): exact fp32 arithmetic in the reference's order -- scores
+// s_m = (q.k_m) * scale, e_m = exp(s_m - max), p_m = e_m / sum e, y = sum_m p_m v_m.  One wave per query at a time (4 per workgroup);
+// lanes stride over keys for the scores (kept in LDS), then over output channels.  hd <= 64.
+#define AA_VQ 16  // queries per workgroup
+template <typename T>
+__global__ __launch_bounds__(256) void area_attn_kernel(int Na, int heads, int hd, int qtiles, float scale, const T* __restrict__ q, int qCs,
+                                                         const T* __restrict__ k, int kCs, const T* __restrict__ v, int vCs, T* __restrict__ y, int yCs) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Qs = reinterpret_cast<float*>(smem);  // [4][64]
+  float* Sc = Qs + 4 * 64;                     // [4][Na]
+  const int qt = blockIdx.x % qtiles, gh = blockIdx.x / qtiles;
+  const int gi = gh / heads, h = gh - gi * heads;
+  const long p0 = (long)gi * Na;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* qs = Qs + wave * 64;
+  float* sc = Sc + (long)wave * Na;
+  const T* kb = k + p0 * kCs + h * hd;
+  const T* vb = v + p0 * vCs + h * hd;
+  const int n1 = min(Na, (qt + 1) * AA_VQ);
+  for (int n = qt * AA_VQ + wave; n < n1; n += 4) {
+    qs[lane] = lane < hd ? to_f(q[(p0 + n) * qCs + h * hd + lane]) : 0.f;
+    __builtin_amdgcn_wave_barrier();
+    float mx = -INFINITY;
+    for (int j = lane; j < Na; j += 64) {
+      const T* kr = kb + (long)j * kCs;
+      float a = 0.f;
+      for (int c = 0; c < hd; ++c) a = fmaf(qs[c], to_f(kr[c]), a);
+      a *= scale;
+      sc[j] = a;
+      mx = fmaxf(mx, a);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < Na; j += 64) {
+      const float e = expf(sc[j] - mx);
+      sc[j] = e;
+      sum += e;
+    }
+    sum = wave_sum(sum);
+    for (int j = lane; j < Na; j += 64) sc[j] = sc[j] / sum;  // (lanes own the keys they wrote)
+    __builtin_amdgcn_wave_barrier();
+    if (lane < hd) {
+      float o = 0.f;
+      for (int j = 0; j < Na; ++j) o = fmaf(sc[j], to_f(vb[(long)j * vCs + lane]), o);
+      y[(p0 + n) * yCs + h * hd + lane] = from_f<T>(o);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+#define FA_VALU_MAX_TOKENS ((160 * 1024 / 4 - 4 * 64) / 4)  // area_attn_kernel keeps 4 fp32 score rows of a group in LDS: 10176
+
+template <typename T>
+static int attn_valu_launch(const char* who, long gh, int Ng, int heads, int hd, float scale, const void* q, int q_cstride, const void* k, int k_cstride,
+                            const void* v, int v_cstride, void* y, int y_cstride, hipStream_t st) {
+  const size_t lds = (4 * 64 + 4 * (size_t)Ng) * sizeof(float);
+  const int qtiles = (Ng + AA_VQ - 1) / AA_VQ;
+  if (gh * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "%s: grid too large", who);
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
+  hipLaunchKernelGGL(area_attn_kernel<T>, dim3((unsigned)(gh * qtiles)), dim3(256), lds, st, Ng, heads, hd, qtiles, scale, (const T*)q, q_cstride,
+                     (const T*)k, k_cstride, (const T*)v, v_cstride, (T*)y, y_cstride);
+  return EY_OK;
+}
+
+// The launch behind both entry points, after their own argument checks: `groups` groups of Ng tokens.  mfma_hds: the head dims (16, 32
+// and 64 are their own bits) this caller sends to flash_attn_kernel when dtype and alignment allow; everything else runs the VALU kernel.
+// var_*: what ey_attention_last_variant() reports for the three kernels.
+static int attn_launch(const char* who, int dtype, long groups, int Ng, int heads, int hd, int mfma_hds, int var_mfma, int var_f16, int var_f32, float scale,
+                       const void* q, int q_cstride, const void* k, int k_cstride, const void* v, int v_cstride, void* y, int y_cstride, hipStream_t st) {
+  const long gh = groups * heads;
+  const bool mfma = dtype == EY_F16 && (hd == 16 || hd == 32 || hd == 64) && (mfma_hds & hd) && ey_aligned(q, 16) && ey_aligned(k, 16) && ey_aligned(v, 16) &&
+                    ey_aligned(y, 8) && q_cstride % 8 == 0 && k_cstride % 8 == 0 && v_cstride % 8 == 0 && y_cstride % 4 == 0;
+  if (mfma) {
+    const int qtiles = (Ng + 63) / 64;
+    if (gh * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "%s: grid too large", who);
+    const dim3 grid((unsigned)(gh * qtiles));
+    g_attn_variant = var_mfma;
+#define FLASH(HD)                                                                                                                                   \
+  hipLaunchKernelGGL(flash_attn_kernel<HD>, grid, dim3(256), 0, st, Ng, heads, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride, \
+                     (const f16*)v, v_cstride, (f16*)y, y_cstride)
+    if (hd == 16) FLASH(16);
+    else if (hd == 32) FLASH(32);
+    else FLASH(64);
+#undef FLASH
+  } else {
+    if (Ng > FA_VALU_MAX_TOKENS)
+      return ey_set_error(EY_EUNSUPPORTED, "%s: %d tokens per group exceed the %d-token limit of the VALU kernel (fp32, unaligned views, head dims off the MFMA path)",
+                          who, Ng, FA_VALU_MAX_TOKENS);
+    const int rc = dtype == EY_F16 ? attn_valu_launch<f16>(who, gh, Ng, heads, hd, scale, q, q_cstride, k, k_cstride, v, v_cstride, y, y_cstride, st)
+                                   : attn_valu_launch<float>(who, gh, Ng, heads, hd, scale, q, q_cstride, k, k_cstride, v, v_cstride, y, y_cstride, st);
+    if (rc != EY_OK) return rc;
+    g_attn_variant = dtype == EY_F16 ? var_f16 : var_f32;
+  }
+  EY_LAUNCH_CHECK(who);
+  return EY_OK;
+}
+
+extern "C" int ey_area_attention(int dtype, int B, int N, int area, int heads, int hd, float scale, const void* q, int q_cstride, const void* k,
+                                 int k_cstride, const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream) {
+  g_attn_variant = 0;
+  EY_CHECK(q && k && v && y, "area_attention: null pointer");
+  EY_CHECK(dtype == EY_F16 || dtype == EY_F32, "area_attention: bad dtype");
+  EY_CHECK(B > 0 && N > 0 && area > 0 && heads > 0 && hd > 0, "area_attention: B=%d N=%d area=%d heads=%d hd=%d", B, N, area, heads, hd);
+  if (N % area) return ey_set_error(EY_EINVAL, "area_attention: %d tokens do not split into %d equal areas", N, area);
+  if (hd > 64) return ey_set_error(EY_EUNSUPPORTED, "area_attention: head_dim %d > 64", hd);
+  EY_CHECK(q_cstride >= heads * hd && k_cstride >= heads * hd && v_cstride >= heads * hd && y_cstride >= heads * hd, "area_attention: cstride");
+  // hd 16 and 64 stay on the VALU kernel through this entry
+  return attn_launch("area_attention", dtype, (long)B * area, N / area, heads, hd, tune().areaattn_mfma ? 32 : 0, EY_ATTN_AREA_MFMA, EY_ATTN_AREA_F16,
+                     EY_ATTN_AREA_F32, scale, q, q_cstride, k, k_cstride, v, v_cstride, y, y_cstride, (hipStream_t)stream);
+}
+
 extern "C" int ey_flash_attention(int dtype, int B, int N, int heads, int hd, float scale, const void* q, int q_cstride, const void* k, int k_cstride,
                                   const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream) {
   g_attn_variant = 0;
@@ -732,46 +656,6 @@ extern "C" int ey_flash_attention(int dtype, int B, int N, int heads, int hd, fl
   EY_CHECK(B > 0 && N > 0 && heads > 0 && hd > 0, "flash_attention: B=%d N=%d heads=%d hd=%d", B, N, heads, hd);
   if (hd > 64) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: head_dim %d > 64", hd);
   EY_CHECK(q_cstride >= heads * hd && k_cstride >= heads * hd && v_cstride >= heads * hd && y_cstride >= heads * hd, "flash_attention: cstride");
-  const long groups = (long)B * heads;
-  hipStream_t st = (hipStream_t)stream;
-  const bool mfma = dtype == EY_F16 && (hd == 16 || hd == 32 || hd == 64) && ey_aligned(q, 16) && ey_aligned(k, 16) && ey_aligned(v, 16) && ey_aligned(y, 8) &&
-                    q_cstride % 8 == 0 && k_cstride % 8 == 0 && v_cstride % 8 == 0 && y_cstride % 4 == 0;
-  if (mfma) {
-    const int qtiles = (N + 63) / 64;
-    if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: grid too large");
-    const dim3 grid((unsigned)(groups * qtiles));
-    g_attn_variant = EY_ATTN_FLASH_MFMA + hd;
-#define FLASH(HD)                                                                                                                                  \
-  hipLaunchKernelGGL(flash_attn_kernel<HD>, grid, dim3(256), 0, st, N, heads, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride, \
-                     (const f16*)v, v_cstride, (f16*)y, y_cstride)
-    if (hd == 16) FLASH(16);
-    else if (hd == 32) FLASH(32);
-    else FLASH(64);
-#undef FLASH
-    EY_LAUNCH_CHECK("ey_flash_attention(mfma)");
-    return EY_OK;
-  }
-  // fp32, unaligned views, other head dims: the VALU area kernel with one area per image
-  if (N > FA_VALU_MAX_TOKENS)
-    return ey_set_error(EY_EUNSUPPORTED, "flash_attention: %d tokens exceed the %d-token limit of the VALU kernel (fp32, unaligned views, head_dim not 16/32/64)", N,
-                        FA_VALU_MAX_TOKENS);
-  const size_t lds = (4 * 64 + 4 * (size_t)N) * sizeof(float);
-  const int qtiles = (N + AA_VQ - 1) / AA_VQ;
-  if (groups * qtiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "flash_attention: grid too large");
-  const dim3 grid((unsigned)(groups * qtiles));
-  if (dtype == EY_F16) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
-    g_attn_variant = EY_ATTN_FLASH_F16;
-    hipLaunchKernelGGL(area_attn_kernel<f16>, grid, dim3(256), lds, st, N, heads, hd, qtiles, scale, (const f16*)q, q_cstride, (const f16*)k, k_cstride,
-                       (const f16*)v, v_cstride, (f16*)y, y_cstride);
-  } else {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)area_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return ey_set_error(EY_ELAUNCH, "cannot reserve %zu B of LDS", lds);
-    g_attn_variant = EY_ATTN_FLASH_F32;
-    hipLaunchKernelGGL(area_attn_kernel<float>, grid, dim3(256), lds, st, N, heads, hd, qtiles, scale, (const float*)q, q_cstride, (const float*)k,
-                       k_cstride, (const float*)v, v_cstride, (float*)y, y_cstride);
-  }
-  EY_LAUNCH_CHECK("ey_flash_attention");
-  return EY_OK;
+  return attn_launch("flash_attention", dtype, B, N, heads, hd, 16 | 32 | 64, EY_ATTN_FLASH_MFMA + hd, EY_ATTN_FLASH_F16, EY_ATTN_FLASH_F32, scale, q,
+                     q_cstride, k, k_cstride, v, v_cstride, y, y_cstride, (hipStream_t)stream);
 }

@@ -719,28 +719,37 @@ def softmax_attention(qkv, heads, kd, hd, scale, out=None):
     return out
 
 
-def area_attention(q, k, v, heads, area, scale, out=None):
-    """Area attention core (ey_area_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim -> (B,C,H,W).  The H*W tokens of an
-    image, row-major, are cut into `area` equal runs attended separately; N % area != 0 is refused like the reference's reshape."""
-    L.require_device(q, "area_attention")
-    _no_block("area attention")
+def _group_attention(name, q, k, v, heads, area, scale, out):
+    """Checks, output, trace record and call behind area_attention (ey_area_attention) and flash_attention (area None: ey_flash_attention)."""
+    L.require_device(q, name)
+    _no_block(name.replace("_", " "))
     q, k, v = L.as_nhwc(q), L.as_nhwc(k), L.as_nhwc(v)
     B, c, H, W = q.shape
     N = H * W
-    if N % area:
-        raise ValueError(f"area_attention: {H}x{W} = {N} tokens do not split into {area} equal areas")
+    if area and N % area:
+        raise ValueError(f"{name}: {H}x{W} = {N} tokens do not split into {area} equal areas")
     if c % heads or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"area_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, q.dtype, q.device)
+        raise ValueError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
+    out = _out_like(q, out, name)
     hd = c // heads
-    rec = _tr("area_attn_kernel", _nb(q, k, v, out), 4.0 * B * heads * N * (N // area) * hd, note=f"{H}x{W} area{area} h{heads}")
+    note = f"{H}x{W} area{area} h{heads}" if area else f"{H}x{W} h{heads} hd{hd}"
+    views = (float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(), L.cstride(k), v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream())
+    rec = _tr("area_attn_kernel", _nb(q, k, v, out), 4.0 * B * heads * N * (N // (area or 1)) * hd, note=note)
     with rec:
-        L.check(L.lib().ey_area_attention(L.dtype_code(q.dtype), B, N, area, heads, hd, float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(),
-                                          L.cstride(k), v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream()), "ey_area_attention")
-        if TRACE is not None and L.lib().ey_attention_last_variant() == L.ATTN_AREA_MFMA:
-            rec.kernel = "area_attn_mfma_kernel"
+        if area:
+            rc, mfma = L.lib().ey_area_attention(L.dtype_code(q.dtype), B, N, area, heads, hd, *views), L.ATTN_AREA_MFMA
+        else:
+            rc, mfma = L.lib().ey_flash_attention(L.dtype_code(q.dtype), B, N, heads, hd, *views), L.ATTN_FLASH_MFMA + hd
+        L.check(rc, "ey_" + name)
+        if TRACE is not None and L.lib().ey_attention_last_variant() == mfma:
+            rec.kernel = f"flash_attn_kernel<{hd}>"
     return out
+
+
+def area_attention(q, k, v, heads, area, scale, out=None):
+    """Area attention core (ey_area_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim -> (B,C,H,W).  The H*W tokens of an
+    image, row-major, are cut into `area` equal runs attended separately; N % area != 0 is refused like the reference's reshape."""
+    return _group_attention("area_attention", q, k, v, heads, area, scale, out)
 
 
 def scale_add_channels(x, gamma, t, out=None):
@@ -857,22 +866,7 @@ def _out_like(x, out, what, hw=None):
 
 def flash_attention(q, k, v, heads, scale, out=None):
     """Softmax attention over all H*W tokens of each image (ey_flash_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim."""
-    L.require_device(q, "flash_attention")
-    _no_block("flash attention")
-    q, k, v = L.as_nhwc(q), L.as_nhwc(k), L.as_nhwc(v)
-    B, c, H, W = q.shape
-    N = H * W
-    if c % heads or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"flash_attention: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
-    out = _out_like(q, out, "flash_attention")
-    hd = c // heads
-    rec = _tr("area_attn_kernel", _nb(q, k, v, out), 4.0 * B * heads * N * N * hd, note=f"{H}x{W} h{heads} hd{hd}")
-    with rec:
-        L.check(L.lib().ey_flash_attention(L.dtype_code(q.dtype), B, N, heads, hd, float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(), L.cstride(k),
-                                           v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream()), "ey_flash_attention")
-        if TRACE is not None and L.lib().ey_attention_last_variant() == L.ATTN_FLASH_MFMA + hd:
-            rec.kernel = f"flash_attn_kernel<{hd}>"
-    return out
+    return _group_attention("flash_attention", q, k, v, heads, None, scale, out)
 
 
 def dwconv_gate(mod, x, conv, mode, out=None, tag=""):

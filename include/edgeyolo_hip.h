@@ -361,11 +361,11 @@ int ey_flash_attention(int dtype, int B, int N, int heads, int hd, float scale, 
                        const void* v, int v_cstride, void* y, int y_cstride, ey_stream_t stream);
 
 /* Kernel the last ey_linear_attention / ey_softmax_attention / ey_area_attention / ey_flash_attention on this thread launched (tests); 0 = nothing launched.
- * Flash: EY_ATTN_FLASH_MFMA + hd (flash_attn_kernel<hd>, hd = 16, 32, 64), EY_ATTN_FLASH_F32 / _F16 (area_attn_kernel<T>, fp32 VALU).
+ * Flash: EY_ATTN_FLASH_MFMA + hd (flash_attn_kernel<hd>, hd = 16, 32, 64; a group is an image), EY_ATTN_FLASH_F32 / _F16 (area_attn_kernel<T>, fp32 VALU).
  * Linear: EY_ATTN_LIN_F32 / _F16 (linattn_kernel<T>, fp32 VALU), EY_ATTN_LIN_MFMA (linattn_mfma_kernel).
  * Softmax VALU: EY_ATTN_SOFT_VALU + 4 (f16) + 2 (K staged in LDS: K_LDS) + 1 (nsplit == 1: one query block per (image, head)).
  * Softmax MFMA: EY_ATTN_SOFT_MFMA + NKS (softattn_mfma_kernel<NKS>, NKS = 4, 8, 10, 13).
- * Area: EY_ATTN_AREA_F32 / _F16 (area_attn_kernel<T>, fp32 VALU), EY_ATTN_AREA_MFMA (area_attn_mfma_kernel). */
+ * Area: EY_ATTN_AREA_F32 / _F16 (area_attn_kernel<T>, fp32 VALU), EY_ATTN_AREA_MFMA (flash_attn_kernel<32>; a group is a run of an image). */
 enum { EY_ATTN_LIN_F32 = 101, EY_ATTN_LIN_F16 = 102, EY_ATTN_LIN_MFMA = 103, EY_ATTN_SOFT_VALU = 200, EY_ATTN_SOFT_MFMA = 300,
        EY_ATTN_AREA_F32 = 401, EY_ATTN_AREA_F16 = 402, EY_ATTN_AREA_MFMA = 403,
        EY_ATTN_FLASH_MFMA = 500, EY_ATTN_FLASH_F32 = 501, EY_ATTN_FLASH_F16 = 502 };

@@ -8,84 +8,26 @@ and the fp32 / f16 VALU kernels; each case asserts the kernel that ran (ey_atten
 * Bit-exact one-hot probe: per query one key scores -8 and every other real key scores below -800 (times scale), so softmax is a
   gather of one v row that every path must reproduce bit for bit; a zero-filled padded key would score 0 and win if the mask leaked.
 * Refusals: N % area != 0 launches nothing."""
-import math
-import zlib
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
 from gpu_util import tuned  # noqa: E402
+from group_attn_util import data as _data, groups, lib as _L, one_hot, ref, run, ulp as _ulp  # noqa: E402
 
 AREA_F32, AREA_F16, AREA_MFMA = 401, 402, 403
 WORST = {}
 
 
-def _gen(*key):
-    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _L():
-    from edge_yolo_amd import _lib as L
-    return L
-
-
-def _window(vals, off, pad, dtype):
-    """NHWC device view of logical (B, C, H, W) vals at channel offset `off` of a (off + C + pad)-channel NaN-filled buffer."""
-    B, C, H, W = vals.shape
-    buf = torch.full((B, H, W, off + C + pad), float("nan"), dtype=dtype, device="cuda")
-    buf[..., off:off + C] = vals.permute(0, 2, 3, 1).to(device="cuda", dtype=dtype)
-    return buf, buf.permute(0, 3, 1, 2)[:, off:off + C]
-
-
-def _run(q, k, v, heads, area, scale, dtype, yoff=8, ypad=8):
-    """-> (y logical (B,C,H,W) float64 cpu, y buffer)"""
+def _run(q, k, v, heads, area, scale, dtype):
+    """-> y logical (B,C,H,W) float64 cpu"""
     from edge_yolo_amd.nn import _ops
-    B, C, H, W = q.shape
-    qkbuf, _ = _window(torch.cat([q, k], 1), 8, 8, dtype)
-    qv = qkbuf.permute(0, 3, 1, 2)[:, 8:8 + C]
-    kv = qkbuf.permute(0, 3, 1, 2)[:, 8 + C:8 + 2 * C]
-    _, vv = _window(v, 16, 8, dtype)
-    ybuf = torch.full((B, H, W, yoff + C + ypad), float("nan"), dtype=dtype, device="cuda")
-    yv = ybuf.permute(0, 3, 1, 2)[:, yoff:yoff + C]
-    _ops.area_attention(qv, kv, vv, heads, area, scale, out=yv)
-    torch.cuda.synchronize()
-    assert torch.isnan(ybuf[..., :yoff]).all() and torch.isnan(ybuf[..., yoff + C:]).all(), "writes outside the output window"
-    return yv.double().cpu(), ybuf
-
-
-def _ref(q, k, v, heads, area, scale):
-    """float64: (y, P|v|, per-row max of the |score| terms) logical (B,C,H,W)."""
-    B, C, H, W = q.shape
-    hd, N = C // heads, H * W
-    Na = N // area
-
-    def rows(t):  # (B*area, heads, Na, hd)
-        return t.double().permute(0, 2, 3, 1).reshape(B * area, Na, heads, hd).transpose(1, 2)
-
-    qq, kk, vv = rows(q), rows(k), rows(v)
-    s = (qq @ kk.transpose(-1, -2)) * scale
-    P = torch.softmax(s, -1)
-    A = (qq.abs() @ kk.abs().transpose(-1, -2)) * scale  # |score| terms
-    y = P @ vv
-    Y = P @ vv.abs()
-
-    def back(t):
-        return t.transpose(1, 2).reshape(B, H, W, C).permute(0, 3, 1, 2)
-
-    return back(y), back(Y), back(A.amax(-1, keepdim=True).expand_as(y))
-
-
-def _ulp(v, dtype):
-    v = v.abs().to(dtype).double()
-    if dtype == torch.float16:
-        return torch.clamp(2.0 ** (torch.floor(torch.log2(torch.clamp(v, min=2.0 ** -14))) - 10), min=2.0 ** -24)
-    return torch.clamp(2.0 ** (torch.floor(torch.log2(torch.clamp(v, min=2.0 ** -126))) - 23), min=2.0 ** -149)
+    return run(lambda qv, kv, vv, yv: _ops.area_attention(qv, kv, vv, heads, area, scale, out=yv), q, k, v, dtype)
 
 
 def _check(case, got, q, k, v, heads, area, scale, dtype, mfma):
-    y, Y, Amax = _ref(q, k, v, heads, area, scale)
+    y, Y, Amax, _, _ = ref(q, k, v, heads, scale, area)
     Na = q.shape[2] * q.shape[3] // area
     u = 2.0 ** -24
     # score error: fp32 sums of hd exact products (2 hd u |s|), scale multiply; propagated through exp (relative) for every key
@@ -94,7 +36,7 @@ def _check(case, got, q, k, v, heads, area, scale, dtype, mfma):
     if mfma:
         rel = rel + 2.0 ** -11  # P rounded to f16 before the MFMA
     bnd = rel * Y * 1.25 + _ulp(y, dtype) + 2.0 ** -30  # (a whole ulp: the kernel's value may round across a binade boundary)
-    err = (got - y).abs()
+    err = (groups(got, heads, area) - y).abs()
     assert torch.isfinite(got).all(), f"{case}: non-finite output"
     r = float((err / bnd).max())
     print(f"[fp64] {case} max err/bound {r:.3f}")
@@ -120,13 +62,6 @@ CASES = [
 ]
 
 
-def _data(B, H, W, heads, hd, key):
-    g = _gen(*key)
-    C = heads * hd
-    f = lambda s: (torch.randn(B, C, H, W, generator=g) * s).half().float()  # noqa: E731  (f16-representable values)
-    return f(1.5), f(1.5), f(1.0)
-
-
 @pytest.mark.parametrize("B,H,W,area,heads", CASES)
 @pytest.mark.parametrize("path", ["mfma", "f32"])
 def test_area_attention_bounded(B, H, W, area, heads, path):
@@ -135,7 +70,7 @@ def test_area_attention_bounded(B, H, W, area, heads, path):
     q, k, v = _data(B, H, W, heads, hd, (B, H, W, area, heads))
     dtype = torch.float16 if path == "mfma" else torch.float32
     scale = hd ** -0.5
-    got, _ = _run(q, k, v, heads, area, scale, dtype)
+    got = _run(q, k, v, heads, area, scale, dtype)
     assert L.lib().ey_attention_last_variant() == (AREA_MFMA if path == "mfma" else AREA_F32)
     _check(f"{path} B{B} {H}x{W} area{area} h{heads}", got, q, k, v, heads, area, scale, dtype, path == "mfma")
 
@@ -146,32 +81,9 @@ def test_area_attention_f16_valu(hd, knob):
     B, H, W, area, heads = 2, 6, 10, 4, 2
     q, k, v = _data(B, H, W, heads, hd, ("valu", hd))
     with tuned(**(knob or {})):
-        got, _ = _run(q, k, v, heads, area, hd ** -0.5, torch.float16)
+        got = _run(q, k, v, heads, area, hd ** -0.5, torch.float16)
         assert L.lib().ey_attention_last_variant() == AREA_F16
     _check(f"f16 valu hd{hd}", got, q, k, v, heads, area, hd ** -0.5, torch.float16, False)
-
-
-def _one_hot(B, H, W, area, heads, hd=32):
-    """q, k, v whose softmax rows are exact one-hot gathers (module docstring); target(n) = (7 n + 3 + h) mod Na within the area."""
-    R = 20.0
-    C, N = heads * hd, H * W
-    Na = N // area
-    q = torch.zeros(B, N, C)
-    k = torch.zeros(B, N, C)
-    bits = 2.0 * ((torch.arange(Na).view(-1, 1) >> torch.arange(hd - 1).view(1, -1)) & 1).float() - 1.0  # (Na, 31) distinct +-1 codes
-    bias = R * R * (hd - 1) + 8.0  # best real score -8: a zero padded key (score 0) would win
-    for h in range(heads):
-        c0 = h * hd
-        tgt = (7 * torch.arange(Na) + 3 + h) % Na
-        for a in range(area):
-            sl = slice(a * Na, (a + 1) * Na)
-            q[:, sl, c0] = 1.0
-            q[:, sl, c0 + 1:c0 + hd] = R * bits[tgt]
-            k[:, sl, c0] = -bias
-            k[:, sl, c0 + 1:c0 + hd] = R * bits
-    v = (torch.randn(B, N, C, generator=_gen("onehot", B, H, W, area, heads)) * 4).half().float()
-    to4 = lambda t: t.view(B, H, W, C).permute(0, 3, 1, 2).contiguous()  # noqa: E731
-    return to4(q), to4(k), to4(v)
 
 
 @pytest.mark.parametrize("B,H,W,area,heads", [(1, 1, 1, 1, 1), (2, 6, 10, 4, 2), (1, 1, 17, 1, 3), (1, 5, 80, 1, 2), (1, 1, 401, 1, 1),
@@ -179,12 +91,13 @@ def _one_hot(B, H, W, area, heads, hd=32):
 @pytest.mark.parametrize("path", ["mfma", "f32", "f16valu"])
 def test_area_attention_one_hot_exact(B, H, W, area, heads, path):
     L = _L()
-    q, k, v = _one_hot(B, H, W, area, heads)
+    q, k, v = one_hot(B, H, W, heads, area, 32, ("onehot", B, H, W, area, heads))
     dtype = torch.float32 if path == "f32" else torch.float16
     with tuned(**({"areaattn_mfma": 0} if path == "f16valu" else {})):
-        got, _ = _run(q, k, v, heads, area, 32 ** -0.5, dtype)
+        got = _run(q, k, v, heads, area, 32 ** -0.5, dtype)
         assert L.lib().ey_attention_last_variant() == {"mfma": AREA_MFMA, "f32": AREA_F32, "f16valu": AREA_F16}[path]
-    y, _, _ = _ref(q, k, v, heads, area, 32 ** -0.5)
+    y = ref(q, k, v, heads, 32 ** -0.5, area)[0]
+    got = groups(got, heads, area)
     assert torch.equal(got, y.to(dtype).double()), f"{path}: one-hot gather not bit-exact (max diff {float((got - y).abs().max())})"
 
 

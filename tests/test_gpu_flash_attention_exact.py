@@ -11,86 +11,25 @@ kernels for head_dim 16 / 32 / 64 and the fp32 / f16 VALU fallback; each case as
   of one v row that every path must reproduce bit for bit; a zero-filled padded key would score 0 and win if the mask leaked.  Token
   counts 1, 17, 65, 401 leave a partly padded last key tile.
 * Refusals launch nothing."""
-import zlib
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+from group_attn_util import data as _data, groups as _tok_out, lib as _L, one_hot, one_hot_target, ref as _ref, run, ulp as _ulp  # noqa: E402
+
 FLASH_MFMA, FLASH_F32, FLASH_F16 = 500, 501, 502
 WORST = {}
-
-
-def _gen(*key):
-    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _L():
-    from edge_yolo_amd import _lib as L
-    return L
-
-
-def _window(vals, off, pad, dtype):
-    """NHWC device view of logical (B, C, H, W) vals at channel offset `off` of a (off + C + pad)-channel NaN-filled buffer."""
-    B, C, H, W = vals.shape
-    buf = torch.full((B, H, W, off + C + pad), float("nan"), dtype=dtype, device="cuda")
-    buf[..., off:off + C] = vals.permute(0, 2, 3, 1).to(device="cuda", dtype=dtype)
-    return buf, buf.permute(0, 3, 1, 2)[:, off:off + C]
 
 
 def _run(q, k, v, heads, scale, dtype, qoff=8, yoff=8, ypad=8):
     """-> y logical (B,C,H,W) float64 cpu"""
     from edge_yolo_amd.nn import _ops
-    B, C, H, W = q.shape
-    qkbuf, _ = _window(torch.cat([q, k], 1), qoff, 8, dtype)
-    qv = qkbuf.permute(0, 3, 1, 2)[:, qoff:qoff + C]
-    kv = qkbuf.permute(0, 3, 1, 2)[:, qoff + C:qoff + 2 * C]
-    _, vv = _window(v, 16, 8, dtype)
-    ybuf = torch.full((B, H, W, yoff + C + ypad), float("nan"), dtype=dtype, device="cuda")
-    yv = ybuf.permute(0, 3, 1, 2)[:, yoff:yoff + C]
-    _ops.flash_attention(qv, kv, vv, heads, scale, out=yv)
-    torch.cuda.synchronize()
-    assert torch.isnan(ybuf[..., :yoff]).all() and torch.isnan(ybuf[..., yoff + C:]).all(), "writes outside the output window"
-    assert not torch.isnan(ybuf[..., yoff:yoff + C]).any(), "NaN left inside the output window"
-    return yv.double().cpu()
-
-
-def _ref(q, k, v, heads, scale, rows=None):
-    """float64 on the queries `rows` (token indices; None = all): (y, sum P|v|, max |score| terms, sum exp(s - max), max |v|), each
-    (B, heads, len(rows), hd) or broadcastable to it."""
-    B, C, H, W = q.shape
-    hd, N = C // heads, H * W
-
-    def tok(t):  # (B, heads, N, hd)
-        return t.double().permute(0, 2, 3, 1).reshape(B, N, heads, hd).transpose(1, 2)
-
-    qq, kk, vv = tok(q), tok(k), tok(v)
-    if rows is not None:
-        qq = qq[:, :, rows]
-    s = (qq @ kk.transpose(-1, -2)) * scale
-    e = torch.exp(s - s.amax(-1, keepdim=True))
-    Lsum = e.sum(-1, keepdim=True)
-    P = e / Lsum
-    A = (qq.abs() @ kk.abs().transpose(-1, -2)) * scale
-    return P @ vv, P @ vv.abs(), A.amax(-1, keepdim=True), Lsum, vv.abs().amax(-2, keepdim=True)
-
-
-def _tok_out(got, heads, rows=None):
-    B, C, H, W = got.shape
-    t = got.permute(0, 2, 3, 1).reshape(B, H * W, heads, C // heads).transpose(1, 2)
-    return t if rows is None else t[:, :, rows]
-
-
-def _ulp(v, dtype):
-    v = v.abs().to(dtype).double()
-    if dtype == torch.float16:
-        return torch.clamp(2.0 ** (torch.floor(torch.log2(torch.clamp(v, min=2.0 ** -14))) - 10), min=2.0 ** -24)
-    return torch.clamp(2.0 ** (torch.floor(torch.log2(torch.clamp(v, min=2.0 ** -126))) - 23), min=2.0 ** -149)
+    return run(lambda qv, kv, vv, yv: _ops.flash_attention(qv, kv, vv, heads, scale, out=yv), q, k, v, dtype, qoff, yoff, ypad)
 
 
 def _check(case, got, q, k, v, heads, scale, dtype, mfma, rows=None):
-    y, Y, Amax, Lsum, vmax = _ref(q, k, v, heads, scale, rows)
+    y, Y, Amax, Lsum, vmax = _ref(q, k, v, heads, scale, rows=rows)
     N, hd = q.shape[2] * q.shape[3], q.shape[1] // heads
     u = 2.0 ** -24
     # score error: fp32 sums of hd exact products (2 hd u |s|), scale multiply; propagated through exp (relative) for every key
@@ -102,20 +41,13 @@ def _check(case, got, q, k, v, heads, scale, dtype, mfma, rows=None):
         # ... and a P below 2^-14 of its tile's running max is an f16 subnormal: absolute error 2^-25 per key, scaled by 1 / sum exp(s - max)
         extra = N * 2.0 ** -25 * vmax / Lsum
     bnd = rel * Y * 1.25 + extra + _ulp(y, dtype) + 2.0 ** -30  # (a whole ulp: the kernel's value may round across a binade boundary)
-    g = _tok_out(got, heads, rows)
+    g = _tok_out(got, heads, rows=rows)
     assert torch.isfinite(got).all(), f"{case}: non-finite output"
     r = float(((g - y).abs() / bnd).max())
     print(f"[fp64] {case} max err/bound {r:.3f}")
     fam = f"mfma hd{hd}" if mfma else ("f16 valu" if dtype == torch.float16 else "f32 valu")
     WORST[fam] = max(WORST.get(fam, (0.0, "")), (r, case))
     assert r <= 1.0, f"{case}: max err/bound {r:.3f}"
-
-
-def _data(B, H, W, heads, hd, key):
-    g = _gen(*key)
-    C = heads * hd
-    f = lambda s: (torch.randn(B, C, H, W, generator=g) * s).half().float()  # noqa: E731  (f16-representable values)
-    return f(1.5), f(1.5), f(1.0)
 
 
 # tokens -> (B, H, W)
@@ -176,41 +108,17 @@ def test_flash_attention_f16_valu(hd, qoff, yoff):
     _check(f"f16 valu hd{hd}", got, q, k, v, 2, hd ** -0.5, torch.float16, False)
 
 
-ONE_HOT_R = {16: 20.0, 32: 20.0, 64: 16.0}  # R^2 (hd - 1) + 8 must be an f16 number: 6008, 12408, 16136
-
-
-def _one_hot(B, H, W, heads, hd):
-    """q, k, v whose softmax rows are exact one-hot gathers (module docstring); target(n) = (7 n + 3 + h) mod N."""
-    R = ONE_HOT_R[hd]
-    C, N = heads * hd, H * W
-    q = torch.zeros(B, N, C)
-    k = torch.zeros(B, N, C)
-    bits = 2.0 * ((torch.arange(N).view(-1, 1) >> torch.arange(hd - 1).view(1, -1)) & 1).float() - 1.0  # (N, hd - 1) distinct +-1 codes
-    bias = R * R * (hd - 1) + 8.0  # best real score -8: a zero padded key (score 0) would win
-    assert float(torch.tensor(bias).half()) == bias
-    for h in range(heads):
-        c0 = h * hd
-        tgt = (7 * torch.arange(N) + 3 + h) % N
-        q[:, :, c0] = 1.0
-        q[:, :, c0 + 1:c0 + hd] = R * bits[tgt]
-        k[:, :, c0] = -bias
-        k[:, :, c0 + 1:c0 + hd] = R * bits
-    v = (torch.randn(B, N, C, generator=_gen("onehot", B, H, W, heads, hd)) * 4).half().float()
-    to4 = lambda t: t.view(B, H, W, C).permute(0, 3, 1, 2).contiguous()  # noqa: E731
-    return to4(q), to4(k), to4(v)
-
-
 @pytest.mark.parametrize("N,heads", [(1, 1), (17, 2), (64, 1), (65, 4), (401, 1), (1600, 2)])
 @pytest.mark.parametrize("hd", [16, 32, 64])
 @pytest.mark.parametrize("path", ["mfma", "f32"])
 def test_flash_attention_one_hot_exact(hd, N, heads, path):
     L = _L()
     B, H, W = MAPS[N]
-    q, k, v = _one_hot(B, H, W, heads, hd)
+    q, k, v = one_hot(B, H, W, heads, 1, hd, ("onehot", B, H, W, heads, hd))
     dtype = torch.float32 if path == "f32" else torch.float16
     got = _run(q, k, v, heads, hd ** -0.5, dtype)
     assert L.lib().ey_attention_last_variant() == (FLASH_MFMA + hd if path == "mfma" else FLASH_F32)
-    tgt = torch.stack([(7 * torch.arange(N) + 3 + h) % N for h in range(heads)])  # (heads, N)
+    tgt = torch.stack([one_hot_target(N, h) for h in range(heads)])  # (heads, N)
     vt = _tok_out(v.double(), heads)  # (B, heads, N, hd)
     want = torch.gather(vt, 2, tgt.view(1, heads, N, 1).expand(B, heads, N, hd))
     g = _tok_out(got, heads)

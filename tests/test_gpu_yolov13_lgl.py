@@ -118,7 +118,7 @@ def test_predict_graph_and_batches(E):
 
 def test_640_b2_f16_kernels(E):
     """A batch-2 640^2 f16 forward: no conv_direct launch, no VALU attention; one flash launch per LGL unit (six), the head_dim-16 kernel
-    (6400 tokens in layer 2) among them."""
+    (6400 tokens in layer 2) among them; the eight area-attention launches of the A2C2f layers run flash_attn_kernel<32> too."""
     from edge_yolo_amd import profiling
     m = _build(NAME.format("n"), torch.float16)
     x = synth.synth_images(2, 640, 640).cuda().half()
@@ -127,12 +127,14 @@ def test_640_b2_f16_kernels(E):
         y, _ = m(x)
     torch.cuda.synchronize()
     labels = [r[0] for r in t.records]
+    attn = [(r[0], r[5]) for r in t.records if "area_attn" in r[0] or "flash_attn" in r[0]]  # (kernel, trace note): area_attention's note names its area count
     assert torch.isfinite(y).all()
     assert not any("conv_direct" in k for k in labels), sorted(set(labels))
-    flash = [k for k in labels if k.startswith("flash_attn_kernel")]
+    flash = [k for k, note in attn if " area" not in note]  # the LGL units
     assert sorted(flash) == sorted(["flash_attn_kernel<16>", "flash_attn_kernel<32>", "flash_attn_kernel<64>", "flash_attn_kernel<32>",
                                     "flash_attn_kernel<64>", "flash_attn_kernel<64>"]), flash
-    assert labels.count("area_attn_kernel") == 0  # the VALU kernel (the A2C2f layers run area_attn_mfma_kernel)
+    assert [k for k, note in attn if " area" in note] == ["flash_attn_kernel<32>"] * 8, attn  # the A2C2f layers
+    assert labels.count("area_attn_kernel") == 0  # the VALU kernel
     assert labels.count("lgl_cmlp_kernel") == 6 and labels.count("lgl_unpool_ln_kernel") == 6 and labels.count("lgl_dw_kernel<9>") == 12
 
 

@@ -1,4 +1,5 @@
-"""Developer tool: time the area-attention core (ey_area_attention) on the shapes of YOLOv12 -- the MFMA flash kernel (f16), the VALU
+"""Developer tool: time the area-attention core (ey_area_attention) on the shapes of YOLOv12 -- the MFMA flash kernel (f16;
+flash_attn_kernel<32>, the kernel of ey_flash_attention, with one group per run), the VALU
 kernel (f16, areaattn_mfma=0) and torch's scaled_dot_product_attention on the same f16 data as a yardstick only -- each replayed
 from a hipGraph.  Prints one JSON line per shape.
 usage: area_attn_bench.py [reps]

@@ -1,7 +1,8 @@
 """Developer tool: time the flash attention core (ey_flash_attention) on the three attention shapes of yolov13n-DSC3K2_LGL at 640^2,
 batch 32 -- 6400 tokens x head_dim 16 (layer 2), 1600 x 32 (layers 4, 21), 400 x 64 (layers 17, 26; layer 30 is 100 x 64 x 2 heads) --
 against the VALU path the same shapes took before the flash kernel existed (ey_area_attention with one area: f16 VALU for head_dim 16 and
-64; head_dim 32 has its own MFMA kernel there, so the VALU form is forced with areaattn_mfma=0 and the MFMA form is listed too), each
+64; head_dim 32 runs flash_attn_kernel<32> through that entry too, so the VALU form is forced with areaattn_mfma=0 and the area entry's
+MFMA time is listed as a check that both entries cost the same), each
 replayed from a hipGraph.  Prints one JSON line per shape; mfma_peak_frac is against 2.5 PFLOP/s dense f16.
 usage: flash_attn_bench.py [reps]"""
 import json
