@@ -115,6 +115,7 @@ SIGNATURES = {
     "ey_cmlp": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_layernorm_channels": (_i, [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_unpool2_layernorm": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_dysample": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

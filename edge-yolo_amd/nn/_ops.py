@@ -786,6 +786,34 @@ def avgpool2(x, out=None):
     return out
 
 
+def dysample(mod, x, out=None):
+    """DySample x2 (ey_dysample): (B,C,H,W) -> (B,C,2H,2W), offsets and bilinear gather in one launch; `mod` supplies dense_weights(),
+    init_pos and groups.  out= may be a channel slot of a concat buffer."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "dysample")
+    _no_block("dysample")
+    B, c, H, W = x.shape
+    if c != mod.in_channels:
+        raise ValueError(f"dysample: input has {c} channels, the module was built for {mod.in_channels}")
+    dtype, dev = x.dtype, x.device
+
+    def build():
+        w, b, s = mod.dense_weights()
+        return (w.to(dev, dtype).contiguous(), b.to(dev).contiguous(), None if s is None else s.to(dev, dtype).contiguous(),
+                mod.init_pos.detach().to(dev, torch.float32).flatten().contiguous())
+
+    w, b, s, pos = mod._packed(_dev_key(x, "dysample"), build)
+    if out is None:
+        out = L.empty_nhwc(B, c, 2 * H, 2 * W, dtype, dev)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, 2 * H, 2 * W) or out.dtype != dtype:
+        raise ValueError(f"dysample: out= must be an NHWC view of shape {(B, c, 2 * H, 2 * W)} {dtype}")
+    flops = 2.0 * B * H * W * c * w.shape[0] * (2 if s is not None else 1) + 7.0 * out.numel()
+    with _tr("dysample_kernel", _nb(x, out), flops, note=f"C{c} G{mod.groups} {H}x{W}"):
+        L.check(L.lib().ey_dysample(L.dtype_code(dtype), B, H, W, c, mod.scale, mod.groups, x.data_ptr(), L.cstride(x), w.data_ptr(), b.data_ptr(),
+                                    None if s is None else s.data_ptr(), pos.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_dysample")
+    return out
+
+
 def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
     """Depthwise kxk, stride 2, pad k//2 (ey_dwconv_s2): the depthwise half of DSConv(c, c, k, 2)."""
     x = L.as_nhwc(as_tensor(x))

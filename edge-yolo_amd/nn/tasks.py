@@ -14,7 +14,7 @@ import yaml
 
 from . import _ops as ops
 from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, SPPF, Upsample)
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, SPPF, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
@@ -138,6 +138,9 @@ def parse_model(d, ch, verbose=False):
                 c2 = c1
         elif m is FullPAD_Tunnel:
             c2 = ch[f[0]]
+        elif m is DySample:  # reference tasks.py:1127-1130
+            c2 = c1 = ch[f]
+            args = [c1, *args]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m in _HEADS:
@@ -169,6 +172,8 @@ def _layer_down(m, down):
         src *= 2
     elif isinstance(m, Upsample):
         src /= 2
+    elif isinstance(m, DySample):
+        src /= m.scale
     return src
 
 
@@ -270,7 +275,7 @@ class BaseModel(nn.Module):
         return min(hi, hi_run)
 
     def _block_single_ok(self, i):
-        return not isinstance(self.model[i], (Concat, Upsample))
+        return not isinstance(self.model[i], (Concat, Upsample, DySample))
 
     def _run_block(self, lo, hi, x, y):
         """Layers [lo, hi) through one block program.  Inputs = the current x and the saved outputs of earlier layers the run reads;
@@ -419,9 +424,9 @@ class DetectionModel(BaseModel):
         self._block_of = {}
         i, n = 0, len(self.model) - 1  # (the head is handled inside Detect)
         while i < n:
-            if down[i] == top and not isinstance(self.model[i], Upsample):
+            if down[i] == top and not isinstance(self.model[i], (Upsample, DySample)):
                 j = i
-                while j < n and down[j] == top and not isinstance(self.model[j], Upsample):
+                while j < n and down[j] == top and not isinstance(self.model[j], (Upsample, DySample)):
                     j += 1
                 if j - i >= 2:
                     for q in range(i, j):

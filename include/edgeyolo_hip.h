@@ -302,6 +302,20 @@ int ey_layernorm_channels(int dtype, int B, int H, int W, int C, float eps, int 
 int ey_unpool2_layernorm(int dtype, int B, int Hs, int Ws, int H, int W, int C, float eps, const void* t, int t_cstride, const float* w_abc,
                          const float* gamma, const float* beta, void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- DySample (reference ultralytics/nn/modules/dysample.py), scale 2: offsets and bilinear gather in one kernel.
+ *   O[n] = (w_offset[n] . x[b,h,w,:] + bias[n]) * 0.25 + init_pos[n]                          (w_scope == NULL)
+ *   O[n] = (w_offset[n] . x[b,h,w,:] + bias[n]) * sigmoid(w_scope[n] . x[b,h,w,:]) * 0.5 + init_pos[n]
+ * for the 8 * groups offset channels n = xy * 4 groups + grp * 4 + i * 2 + j (xy 0: x, 1: y), then for group grp's channels
+ * [grp * C / groups, (grp + 1) * C / groups):   y[b, 2h+i, 2w+j, c] = bilinear sample of x[b, :, :, c] at column clamp(w + O_x, 0, W-1), row
+ * clamp(h + O_y, 0, H-1), the upper neighbour index clamped to the map (F.grid_sample, align_corners=False, padding_mode="border").
+ * w_offset / w_scope: DEVICE [8 groups][C] in `dtype`, 16-byte aligned (the 'pl' style is this form with a block-sparse weight);
+ * bias / init_pos: DEVICE fp32 [8 groups].  The GEMM accumulates in fp32 (f16: MFMA; fp32: the exact f32 MFMA); offsets, coordinates
+ * and the blend are fp32 in both storage types, the offset map stays in LDS.  x [B,H,W,*] and y [B,2H,2W,*] are channel windows of NHWC
+ * buffers; only y's window is written.  Any H, W >= 1, any C with C / groups a multiple of 8.  EY_EUNSUPPORTED (before anything is
+ * launched) for scale != 2, groups outside {2, 4, 8}, C / groups not a multiple of 8, x or y not 16-byte aligned windows. */
+int ey_dysample(int dtype, int B, int H, int W, int C, int scale, int groups, const void* x, int x_cstride, const void* w_offset, const float* bias,
+                const void* w_scope, const float* init_pos, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
