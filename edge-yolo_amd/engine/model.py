@@ -1,11 +1,11 @@
-"""`YOLO(...)` facade for the detect task, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
+"""`YOLO(...)` facade for the detect and segment tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
 `_new` :231-264, `_load` :266-302, `predict` :501-560) and models/yolo/model.py (:11-59)."""
 from pathlib import Path
 
 import torch
 
-from .predictor import DetectionPredictor
-from ..nn.tasks import DetectionModel, guess_model_task, torch_safe_load_state, yaml_model_load
+from .predictor import DetectionPredictor, SegmentationPredictor
+from ..nn.tasks import DetectionModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
 def _plain(o):
@@ -17,6 +17,10 @@ def _plain(o):
     if isinstance(o, (str, int, float, bool)) or o is None:
         return o
     return str(o)
+
+
+_TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor},
+             "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
 
 
 class Model(torch.nn.Module):
@@ -44,9 +48,11 @@ class Model(torch.nn.Module):
         # the reference raises NotImplementedError here for GFLHeadv2_uniH YAMLs unless task="detect" is passed
         # (engine/model.py:1096-1103 via tasks.py:1198-1210); the argument is accepted but not required
         self.task = task or guess_model_task(cfg_dict)
-        if self.task != "detect":
-            raise NotImplementedError(f"task '{self.task}': only 'detect' is built")
-        self.model = DetectionModel(cfg_dict, nc=nc, verbose=verbose)
+        if self.task not in self.task_map:
+            raise NotImplementedError(f"task '{self.task}': only {sorted(self.task_map)} are built")
+        self.model = self.task_map[self.task]["model"](cfg_dict, nc=nc, verbose=verbose)
+        if guess_model_task(self.model) != self.task:
+            raise ValueError(f"task '{self.task}' does not match the model's head ({type(self.model.model[-1]).__name__})")
         self.overrides["model"] = self.cfg
         self.overrides["task"] = self.task
         self.model.task = self.task
@@ -94,7 +100,7 @@ class Model(torch.nn.Module):
     @property
     def task_map(self):
         """task -> {model class, predictor class} (reference engine/model.py:1062-1064, models/yolo/model.py:24-59)."""
-        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor}}
+        return _TASK_MAP
 
     @property
     def names(self):
@@ -128,6 +134,9 @@ class Model(torch.nn.Module):
         if predictor is not None and not callable(predictor):
             raise TypeError(f"predict(predictor=...): expected a predictor class (constructed like DetectionPredictor), got {type(predictor).__name__}")
         args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None, "graph": True, "augment": False}
+        if self.task == "segment" and "retina_masks" in kwargs:  # (cfg/default.yaml `retina_masks`; masks come at the network-input resolution)
+            if kwargs.pop("retina_masks"):
+                raise NotImplementedError("retina_masks=True (masks at the original image resolution, ops.process_mask_native) is not built")
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "save", "mode"}
         if unknown:
             raise TypeError(f"predict() got unsupported arguments {sorted(unknown)}")
@@ -166,6 +175,8 @@ class Model(torch.nn.Module):
         The reference has no counterpart (its stream=True generator still runs one batch at a time)."""
         from .predictor import PipelinedRunner
         from ..utils import ops
+        if self.task != "detect":
+            raise NotImplementedError(f"predict_batches: pipelined throughput is built for the detect task only, not '{self.task}' (use predict())")
         args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None}
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "cuts"}
         if unknown:
@@ -278,4 +289,4 @@ class YOLO(Model):
 
     @property
     def task_map(self):
-        return {"detect": {"model": DetectionModel, "predictor": DetectionPredictor}}
+        return _TASK_MAP

@@ -287,13 +287,17 @@ class DetectionPredictor:
             with prof[0]:
                 im = self.preprocess(source)
             with prof[1]:
-                boxes, count, index, pred = self.runner(im)
+                out = self.runner(im)
             with prof[2]:
-                results = self.postprocess(boxes, count, im, source)
+                results = self._results(out, im, source)
             n = len(results)
             for r in results:
                 r.speed = {"preprocess": prof[0].dt * 1e3 / n, "inference": prof[1].dt * 1e3 / n, "postprocess": prof[2].dt * 1e3 / n}
             return results
+
+    def _results(self, out, im, source):
+        """device-step outputs -> list of Results (subclasses with more outputs than boxes override this)."""
+        return self.postprocess(out[0], out[1], im, source)
 
     def postprocess(self, boxes, count, img, source):
         """reference detect/predict.py:23-41: per image rows -> scale_boxes to the original shape -> Results."""
@@ -316,4 +320,51 @@ class DetectionPredictor:
                 r.orig_shape = tuple(img.shape[2:])
                 r.boxes.orig_shape = r.orig_shape
             results.append(r)
+        return results
+
+
+class SegmentationPredictor(DetectionPredictor):
+    """reference models/yolo/segment/predict.py:9-57.  The device step is DetectionPredictor's captured graph plus the Proto and cv4 launches
+    of the Segment head; `postprocess` assembles the masks of the whole batch with ONE ey_process_mask launch sized by the true number of
+    kept boxes (it runs after the count came back, outside the graph).  Masks are at the network-input resolution (retina_masks=False)."""
+
+    def __init__(self, model, device, *args, **kwargs):
+        super().__init__(model, device, *args, **kwargs)
+        if self.augment:  # SegmentationModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
+            import warnings
+            warnings.warn("SegmentationModel does not support 'augment=True', reverting to single-scale prediction.")
+            self.augment = False
+
+    def _device_step(self, im):
+        cand, (_, mcs, p) = self.model(im, head_nms={"conf": self.conf, "classes": self.classes, "keep_pred": self.keep_pred})
+        boxes, count, index = ops.nms_device(cand, self.conf, self.iou, self.classes, self.agnostic_nms, self.max_det)
+        return (boxes, count, index, getattr(cand, "pred", None), p, *mcs)
+
+    def _results(self, out, im, source):
+        boxes, count, index, _, p, *mcs = out
+        return self.postprocess(boxes, count, im, source, index=index, proto=p, coefs=mcs)
+
+    def postprocess(self, boxes, count, img, source, index=None, proto=None, coefs=None):
+        from ..nn import _ops
+        n = count.tolist()  # (the one host sync of the batch; everything below is sized by it)
+        B, max_det = index.shape
+        ih, iw = img.shape[2:]
+        mh, mw = proto.shape[2:]
+        s = ih // mh
+        if s * mh != ih or s * mw != iw:
+            raise NotImplementedError(f"SegmentationPredictor: input {ih}x{iw} over proto {mh}x{mw} is not one integer ratio")
+        total = sum(n)
+        masks = None
+        if total:
+            # rows (image, anchor) and boxes of the kept detections, image after image, built on the device from count and index
+            keep = torch.arange(max_det, device=index.device)[None, :] < count[:, None]
+            rows = torch.stack([torch.arange(B, dtype=torch.int32, device=index.device)[:, None].expand(B, max_det)[keep], index[keep]], 1).contiguous()
+            masks = _ops.process_mask(proto, coefs, rows, boxes[keep][:, :4].contiguous(), s)  # boxes in network-input pixels, before scale_boxes
+        results = super().postprocess(boxes, count, img, source)
+        off = 0
+        for i, r in enumerate(results):
+            if n[i]:
+                from .results import Masks
+                r.masks = Masks(masks[off:off + n[i]], r.orig_shape)
+            off += n[i]
         return results

@@ -1,5 +1,5 @@
-"""Minimal `Results` / `Boxes` containers with the attribute surface of the reference's engine/results.py
-(:187 Results, :938 Boxes) that predict() callers read.  Plotting/saving are out of scope."""
+"""Minimal `Results` / `Boxes` / `Masks` containers with the attribute surface of the reference's engine/results.py
+(:187 Results, :938 Boxes, :1093 Masks) that predict() callers read.  Plotting/saving are out of scope."""
 import torch
 
 
@@ -47,11 +47,46 @@ class Boxes:
         return len(self.data)
 
 
+class Masks:
+    """(n,h,w) instance masks at the network-input resolution.  `data` is torch.bool -- a view of the uint8 bytes ey_process_mask wrote (the
+    reference keeps the same 0 / 1 values as fp32).  Polygon extraction (`xy`, `xyn`) needs cv2.findContours and is not built."""
+
+    def __init__(self, masks, orig_shape):
+        if masks.ndim == 2:
+            masks = masks[None, :]
+        if torch.is_tensor(masks) and masks.dtype == torch.uint8:
+            masks = masks.view(torch.bool)
+        self.data = masks
+        self.orig_shape = orig_shape
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        raise NotImplementedError("Masks.xy: polygon extraction (cv2.findContours) is not built; use Masks.data")
+
+    @property
+    def xyn(self):
+        raise NotImplementedError("Masks.xyn: polygon extraction (cv2.findContours) is not built; use Masks.data")
+
+    def cpu(self):
+        return Masks(self.data.cpu(), self.orig_shape)
+
+    def numpy(self):
+        return Masks(self.data.cpu().numpy(), self.orig_shape)
+
+    def __len__(self):
+        return len(self.data)
+
+
 class Results:
-    def __init__(self, orig_img, path, names, boxes=None, speed=None):
+    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_img.shape[:2]) if orig_img is not None and hasattr(orig_img, "shape") and orig_img.ndim == 3 else None
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
+        self.masks = Masks(masks, self.orig_shape) if masks is not None else None
         self.names = names
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}

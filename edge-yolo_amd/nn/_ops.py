@@ -814,6 +814,70 @@ def dysample(mod, x, out=None):
     return out
 
 
+def deconv2x2(mod, x, deconv, out=None):
+    """Dense nn.ConvTranspose2d(Cin, Cout, 2, 2, 0, bias=True) (ey_deconv2x2): (B,Cin,H,W) -> (B,Cout,2H,2W) in one launch; `mod` caches the
+    packed weight, `deconv` holds the parameters (Proto.upsample, reference block.py:123)."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "deconv2x2")
+    _no_block("deconv2x2")
+    B, cin, H, W = x.shape
+    if (deconv.kernel_size != (2, 2) or deconv.stride != (2, 2) or deconv.groups != 1 or deconv.padding != (0, 0) or deconv.output_padding != (0, 0)
+            or deconv.dilation != (1, 1) or deconv.in_channels != cin):
+        raise NotImplementedError(f"deconv2x2: the kernel takes a dense ConvTranspose2d({cin}, Cout, 2, 2, 0), got {deconv}")
+    cout, dtype, dev = deconv.out_channels, x.dtype, x.device
+    if cin % 8 or cout % 8 or cin > 384 or cout > 384:
+        raise NotImplementedError(f"deconv2x2: Cin={cin} Cout={cout} (multiples of 8 up to 384 are built)")
+
+    def build():
+        code = L.dtype_code(dtype)
+        w = deconv.weight.detach().float().cpu().contiguous()
+        nbytes = L.lib().ey_deconv2x2_packed_bytes(code, cin, cout)
+        buf = torch.empty(nbytes, dtype=torch.uint8)
+        L.check(L.lib().ey_deconv2x2_pack_weight(code, cin, cout, w.data_ptr(), buf.data_ptr(), nbytes), "deconv2x2_pack_weight")
+        b = deconv.bias.detach().float() if deconv.bias is not None else torch.zeros(cout)
+        return buf.to(dev), b.to(dev).contiguous()
+
+    wp, bias = mod._packed(_dev_key(x, "deconv2x2"), build)
+    if out is None:
+        out = L.empty_nhwc(B, cout, 2 * H, 2 * W, dtype, dev)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, 2 * H, 2 * W) or out.dtype != dtype:
+        raise ValueError(f"deconv2x2: out= must be an NHWC view of shape {(B, cout, 2 * H, 2 * W)} {dtype}")
+    with _tr("deconv2x2_kernel", _nb(x, out) + wp.numel(), 8.0 * B * H * W * cin * cout, note=f"C{cin}->{cout} {H}x{W}"):
+        L.check(L.lib().ey_deconv2x2(L.dtype_code(dtype), B, H, W, cin, cout, x.data_ptr(), L.cstride(x), wp.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                     L.cstride(out), L.stream()), "ey_deconv2x2")
+    return out
+
+
+def process_mask(proto, coefs, rows, boxes, s, n=None, out=None):
+    """Mask assembly (ey_process_mask): proto logical (B,nm,mh,mw) NHWC view; coefs: list (<= 4) of logical (B,nm,H_l,W_l) NHWC views in
+    concatenated-anchor order; rows int32 (N,2) = (image, anchor); boxes fp32 (N,4) xyxy in network-input pixels; s = input / proto ratio.
+    -> uint8 (N, s*mh, s*mw), values 0 / 1.  n: number of leading rows to use (default all); out=: a contiguous uint8 buffer to fill."""
+    L.require_device(proto, "process_mask")
+    _no_block("process_mask")
+    if not L.is_nhwc_view(proto) or any(not L.is_nhwc_view(c) for c in coefs):
+        raise ValueError("process_mask: proto and the coefficient maps must be NHWC views")
+    B, nm, mh, mw = proto.shape
+    N = int(rows.shape[0]) if n is None else int(n)
+    if rows.dtype != torch.int32 or boxes.dtype != torch.float32 or not rows.is_contiguous() or not boxes.is_contiguous() or rows.shape[0] < N or boxes.shape[0] < N:
+        raise ValueError("process_mask: rows must be contiguous int32 (N,2) and boxes contiguous fp32 (N,4)")
+    if any(c.shape[0] != B or c.shape[1] != nm or c.dtype != coefs[0].dtype for c in coefs):
+        raise ValueError(f"process_mask: coefficient maps {[tuple(c.shape) for c in coefs]} do not match proto {tuple(proto.shape)}")
+    nl = len(coefs)
+    s = int(s)
+    if out is None:
+        out = torch.empty((N, s * mh, s * mw), dtype=torch.uint8, device=proto.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != (N, s * mh, s * mw):
+        raise ValueError(f"process_mask: out= must be a contiguous uint8 tensor of shape {(N, s * mh, s * mw)}")
+    IA, PA = ctypes.c_int * max(nl, 1), ctypes.c_void_p * max(nl, 1)
+    cp, cs = PA(*[c.data_ptr() for c in coefs]), IA(*[L.cstride(c) for c in coefs])
+    Hs, Ws = IA(*[c.shape[2] for c in coefs]), IA(*[c.shape[3] for c in coefs])
+    with _tr("process_mask_kernel", out.numel() + N * 24 + _nb(proto), 2.0 * N * mh * mw * nm, note=f"N{N} {mh}x{mw} s{s}"):
+        L.check(L.lib().ey_process_mask(L.dtype_code(proto.dtype), B, mh, mw, nm, proto.data_ptr(), L.cstride(proto), nl, cp,
+                                        L.dtype_code(coefs[0].dtype) if nl else L.F32, cs, Hs, Ws, N, rows.data_ptr(), boxes.data_ptr(), s, out.data_ptr(),
+                                        L.stream()), "ey_process_mask")
+    return out
+
+
 def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
     """Depthwise kxk, stride 2, pad k//2 (ey_dwconv_s2): the depthwise half of DSConv(c, c, k, 2)."""
     x = L.as_nhwc(as_tensor(x))

@@ -13,7 +13,7 @@ from .conv import Conv, DSConv, _Packed, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("DFL", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
+__all__ = ("DFL", "Proto", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
@@ -62,6 +62,21 @@ class DFL(nn.Module):
         self.conv = nn.Conv2d(c1, 1, 1, bias=False).requires_grad_(False)
         self.conv.weight.data[:] = torch.arange(c1, dtype=torch.float).view(1, c1, 1, 1)
         self.c1 = c1
+
+
+class Proto(_Packed):
+    """Mask prototypes of the Segment head (reference block.py:112-129): cv3(cv2(upsample(cv1(x)))).  `upsample` is an nn.ConvTranspose2d kept
+    as the parameter holder; it runs as ONE GEMM launch with a scatter epilogue (ey_deconv2x2)."""
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def forward(self, x, out=None):
+        return self.cv3(self.cv2(ops.deconv2x2(self, self.cv1(x), self.upsample)), out=out)
 
 
 class Bottleneck(nn.Module):

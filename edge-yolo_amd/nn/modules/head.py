@@ -1,4 +1,4 @@
-"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
+"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
@@ -9,12 +9,12 @@ import math
 import torch
 import torch.nn as nn
 
-from .block import DFL
+from .block import DFL, Proto
 from .conv import Conv, DWConv, _Packed, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+__all__ = ("Detect", "Segment", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
 
 
 class _Plain(_Packed):
@@ -411,6 +411,51 @@ class Detect(nn.Module):
                 a[-1].bias.data[:] = 1.0
                 b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / float(s)) ** 2)
         self._reset_caches()
+
+
+class Segment(Detect):
+    """YOLO Segment head (reference head.py:347-369): Detect plus the mask prototypes `proto` (block.py:112-129) and one coefficient tower
+    `cv4` per pyramid level.  Boxes and classes run through Detect.forward unchanged (fused decode and NMS candidates included); the
+    coefficient towers write one NHWC map per level, which ey_process_mask reads by anchor index -- nothing is concatenated on the
+    predict path."""
+
+    def __init__(self, nc=80, nm=32, npr=256, ch=()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+
+    def mask_maps(self, xs):
+        """-> (per-level coefficient maps [(B,nm,H_l,W_l) NHWC], p (B,nm,mh,mw) NHWC), all on the caller's stream."""
+        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        cpad = (self.nm + 7) // 8 * 8  # pixel stride kept 16-byte aligned for any nm
+        mcs = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.nm] for t in xs]
+        p = self.proto(xs[0])
+        for i, t in enumerate(xs):
+            c = self.cv4[i]
+            self._tail(c[2]).run(c[1](c[0](t)), mcs[i])
+        return mcs, p
+
+    def forward(self, x, nms=None):
+        """nms=None: the reference's eval-mode return (head.py:360-369): (cat([y, mc], 1) (B,4+nc+nm,A) fp32, (raw maps, mc (B,nm,A), p)).
+        nms=dict(...) (predict pipelines, see Detect.forward): (Candidates, (raw maps, [coefficient map per level], p))."""
+        if self.training:
+            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
+        if self.end2end:
+            raise NotImplementedError("Segment: end2end heads are not built")
+        xs = [L.as_nhwc(t) for t in x]
+        mcs, p = self.mask_maps(xs)
+        got = Detect.forward(self, list(xs), nms=nms)
+        if nms is not None:
+            if getattr(self, "defer_decode", False):
+                raise NotImplementedError("Segment: pipelined (deferred) decode is not built for the segment task")
+            cand, raw = got
+            return cand, (raw, mcs, p)
+        y, raw = got
+        mc = torch.cat([m.flatten(2) for m in mcs], 2)  # (layout only: the reference's view + cat, head.py:365)
+        return torch.cat([y, mc.to(y.dtype)], 1), (raw, mc, p)
 
 
 class GF2Detect(Detect):

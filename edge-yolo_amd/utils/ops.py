@@ -1,6 +1,7 @@
 """Post-processing of the detection path, mirroring the reference's ultralytics/utils/ops.py:
 `make_divisible` (:130-143), `non_max_suppression` (:167-316), `xywh2xyxy` (:416-433), `scale_boxes` (:92-127),
-`clip_boxes` (:319-338).  NMS runs in the HIP library (ey_nms); there is no torch/torchvision fallback."""
+`clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693).  NMS and mask assembly run in the HIP library (ey_nms,
+ey_process_mask); there is no torch/torchvision fallback."""
 import math
 
 import torch
@@ -97,11 +98,20 @@ def nms_device(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnost
     if prediction.shape[-1] == 6:
         return _end2end_filter(prediction, conf_thres, classes, max_det)
     nc = nc or (prediction.shape[1] - 4)
-    if prediction.shape[1] - nc - 4:
-        raise NotImplementedError("mask/keypoint channels (nm>0) are outside the detect path")
+    nm = prediction.shape[1] - nc - 4
+    if nm < 0:
+        raise ValueError(f"nms_device: nc={nc} but the prediction has {prediction.shape[1]} channels")
     if prediction.is_cuda and prediction.device.index != torch.cuda.current_device():
         with torch.cuda.device(prediction.device):  # launches go to the current device's stream (_lib.stream)
             return nms_device(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label)
+    if nm:
+        # mask coefficients ride behind the class scores (reference ops.py:232-234,257,266): suppression sees the first 4+nc channels, the
+        # kept rows get their nm coefficients appended, gathered by anchor index -> rows of 6+nm (zeros beyond `count`)
+        boxes, count, index = nms_device(prediction[:, :4 + nc], conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label)
+        ok = index >= 0
+        idx = index.clamp(min=0).long()[:, None, :].expand(-1, nm, -1)
+        coef = torch.gather(prediction[:, 4 + nc:].float(), 2, idx).transpose(1, 2) * ok[..., None]
+        return torch.cat([boxes, coef], 2), count, index
     p = prediction.float().contiguous()
     mask = None
     if classes is not None:
@@ -113,7 +123,8 @@ def nms_device(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnost
 
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, labels=(),
                         max_det=300, nc=0, max_time_img=0.05, max_nms=30000, max_wh=7680, in_place=True, rotated=False):
-    """Reference signature (ops.py:167-183); returns a list of (n_i, 6) tensors [x1,y1,x2,y2,conf,cls].
+    """Reference signature (ops.py:167-183); returns a list of (n_i, 6) tensors [x1,y1,x2,y2,conf,cls] -- (n_i, 6+nm) with the mask
+    coefficients appended when the prediction carries nm channels behind the nc classes (pass nc=).
     multi_label=True is the validation-mode variant (one candidate per (anchor, class) above conf, ops.py:270-272).
     Differences, all deliberate: no wall-clock abort (:238,:312-314 make the reference output timing dependent);
     the input tensor is not rewritten to xyxy in place; labels (autolabel) / rotated are not built and raise."""
@@ -124,3 +135,43 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     boxes, count, _ = nms_device(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label)
     n = count.tolist()  # one D2H sync for the whole batch
     return [boxes[i, : n[i]] for i in range(len(n))]
+
+
+def crop_mask(masks, boxes):
+    """masks [n,h,w] * (box indicator), boxes [n,4] xyxy in mask pixels (reference :644-660): column r is kept where r >= x1 and r < x2, row
+    c where c >= y1 and c < y2.  A tensor utility for callers that hold masks already; the predict path crops inside ey_process_mask."""
+    _, h, w = masks.shape
+    x1, y1, x2, y2 = torch.chunk(boxes[:, :, None], 4, 1)
+    r = torch.arange(w, device=masks.device, dtype=x1.dtype)[None, None, :]
+    c = torch.arange(h, device=masks.device, dtype=x1.dtype)[None, :, None]
+    return masks * ((r >= x1) * (r < x2) * (c >= y1) * (c < y2))
+
+
+def process_mask(protos, masks_in, bboxes, shape, upsample=False):
+    """Reference signature (:663-693): protos [nm,mh,mw], masks_in [n,nm], bboxes [n,4] xyxy in `shape` = (ih, iw) pixels -> [n,mh,mw], or
+    [n,ih,iw] with upsample=True, on ey_process_mask (coefficient product, crop, bilinear upsampling and the > 0 compare in one launch).
+    Returns uint8 0 / 1 where the reference returns the same values as fp32.  upsample=True needs ih/mh == iw/mw in {1, 2, 4, 8} and every
+    call nm a multiple of 8 up to 64 (NotImplementedError otherwise)."""
+    from ..nn import _ops
+    from .. import _lib as L
+    nm, mh, mw = protos.shape
+    ih, iw = int(shape[0]), int(shape[1])
+    n = int(masks_in.shape[0])
+    with torch.cuda.device(protos.device):
+        proto = L.as_nhwc(protos[None])
+        boxes = bboxes[:, :4].float()
+        if upsample:
+            s = ih // mh
+            if s * mh != ih or s * mw != iw:
+                raise NotImplementedError(f"process_mask: upsampling {mh}x{mw} -> {ih}x{iw} is not one integer ratio (1, 2, 4 and 8 are built)")
+            boxes = boxes.contiguous()
+        else:  # the crop happens on the low-resolution grid: scale the boxes exactly as the reference does (:681-688)
+            s = 1
+            boxes = boxes * torch.tensor([mw / iw, mh / ih, mw / iw, mh / ih], dtype=torch.float32, device=boxes.device)
+        if masks_in.dtype not in (torch.float16, torch.float32):
+            masks_in = masks_in.float()
+        coef = masks_in.contiguous().view(1, n, 1, nm).permute(0, 3, 1, 2)  # one level, one row per "anchor"
+        rows = torch.stack([torch.zeros(n, dtype=torch.int32, device=protos.device), torch.arange(n, dtype=torch.int32, device=protos.device)], 1).contiguous()
+        if n == 0:
+            return torch.empty((0, s * mh, s * mw), dtype=torch.uint8, device=protos.device)
+        return _ops.process_mask(proto, [coef], rows, boxes.contiguous(), s)

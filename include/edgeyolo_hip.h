@@ -316,6 +316,33 @@ int ey_unpool2_layernorm(int dtype, int B, int Hs, int Ws, int H, int W, int C, 
 int ey_dysample(int dtype, int B, int H, int W, int C, int scale, int groups, const void* x, int x_cstride, const void* w_offset, const float* bias,
                 const void* w_scope, const float* init_pos, void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- Instance segmentation: mask assembly (utils/ops.py:644-693 process_mask + crop_mask, called by models/yolo/segment/predict.py:50-57).
+ * For each of N kept detections (over the whole batch):
+ *   v[r][c]   = sum_k coef_n[k] * proto[img_n, r, c, k]        fp32, k ascending, on the low-resolution grid mh x mw
+ *   v[r][c]   = 0 unless  c >= x1/s, c < x2/s, r >= y1/s, r < y2/s   (crop_mask; the box scaled by 1/s in fp32)
+ *   out[n]    = bilinear_{align_corners=False}(v -> s mh x s mw) > 0        as uint8 0 / 1   (s = 1: v > 0, no interpolation)
+ * The interpolation reads source coordinate (dst + 0.5) / s - 0.5 clamped at 0, the upper neighbour clamped to the map (F.interpolate).
+ * proto: NHWC [B, mh, mw, nm] window in `dtype`.  Coefficients: `nlevels` NHWC maps [B, H[l], W[l], nm] in `coef_dtype` as the cv4 towers of
+ * Segment (nn/modules/head.py:358,365) write them; coef / coef_cstride / H / W are HOST arrays of length nlevels.  rows: DEVICE int32 [N][2] =
+ * (image, anchor index in the concatenated order of the levels); boxes: DEVICE fp32 [N][4] x1,y1,x2,y2 in network-input pixels.
+ * out: DEVICE uint8 [N][s mh][s mw]; every byte of it is written.  A row whose image or anchor is out of range gives an all-zero mask.
+ * Low-resolution products stay in LDS.  EY_EUNSUPPORTED (nothing launched, nothing written) unless s in {1, 2, 4, 8}, nm a multiple of 8 up
+ * to 64 and 1 <= nlevels <= 4.  N == 0 launches nothing. */
+int ey_process_mask(int dtype, int B, int mh, int mw, int nm, const void* proto, int proto_cstride, int nlevels, const void* const* coef,
+                    int coef_dtype, const int* coef_cstride, const int* H, const int* W, int N, const int* rows, const float* boxes, int s,
+                    uint8_t* out, ey_stream_t stream);
+
+/* ---- Dense transposed convolution k 2, s 2 with bias: Proto.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True) (nn/modules/block.py:123,129).
+ *   y[b, 2i+di, 2j+dj, co] = bias[co] + sum_ci x[b, i, j, ci] * W[ci][co][di][dj]
+ * as one GEMM [B H W x Cin] . [Cin x 4 Cout] whose epilogue scatters the four positions.  f16: MFMA with fp32 accumulation; fp32: the exact
+ * f32 MFMA (a k-ordered fmaf chain).  x [B,H,W,*] and y [B,2H,2W,*] are 16-byte aligned channel windows; Cin, Cout multiples of 8 up to 384
+ * (EY_EUNSUPPORTED otherwise).  bias: DEVICE fp32 [Cout].  w_packed: ey_deconv2x2_pack_weight's output on the device, 16-byte aligned. */
+size_t ey_deconv2x2_packed_bytes(int dtype, int Cin, int Cout);
+/* HOST: w_iohw fp32 [Cin][Cout][2][2] (the nn.ConvTranspose2d layout) -> dst (dst_bytes >= ey_deconv2x2_packed_bytes). */
+int ey_deconv2x2_pack_weight(int dtype, int Cin, int Cout, const float* w_iohw, void* dst, size_t dst_bytes);
+int ey_deconv2x2(int dtype, int B, int H, int W, int Cin, int Cout, const void* x, int x_cstride, const void* w_packed, const float* bias, void* y,
+                 int y_cstride, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
