@@ -15,6 +15,7 @@ ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
 ATTN_AREA_F32, ATTN_AREA_F16, ATTN_AREA_MFMA = 401, 402, 403  # ey_attention_last_variant of ey_area_attention
 ATTN_FLASH_MFMA, ATTN_FLASH_F32, ATTN_FLASH_F16 = 500, 501, 502  # ... of ey_flash_attention (MFMA: + head_dim)
 DWG_PLAIN, DWG_GATE, DWG_RESIDUAL = 0, 1, 2  # ey_dwconv_gate epilogues
+MASK_GT_STACK, MASK_GT_INDEX = 0, 1  # ey_mask_iou ground-truth forms
 
 
 class HipLibraryError(RuntimeError):
@@ -120,6 +121,8 @@ SIGNATURES = {
     "ey_deconv2x2_packed_bytes": (_sz, [_i, _i, _i]),
     "ey_deconv2x2_pack_weight": (_i, [_i, _i, _i, _vp, _vp, _sz]),
     "ey_deconv2x2": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ey_mask_iou_workspace_bytes": (_sz, [_i, _i, C.c_long, C.c_long]),
+    "ey_mask_iou": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

@@ -1,10 +1,11 @@
 """`YOLO(...)` facade for the detect and segment tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
-`_new` :231-264, `_load` :266-302, `predict` :501-560) and models/yolo/model.py (:11-59)."""
+`_new` :231-264, `_load` :266-302, `predict` :501-560, `val` :599-655) and models/yolo/model.py (:11-59)."""
 from pathlib import Path
 
 import torch
 
 from .predictor import DetectionPredictor, SegmentationPredictor
+from .validator import DetectionValidator, SegmentationValidator
 from ..nn.tasks import DetectionModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
@@ -19,8 +20,8 @@ def _plain(o):
     return str(o)
 
 
-_TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor},
-             "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor}}
+_TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "validator": DetectionValidator},
+             "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor, "validator": SegmentationValidator}}
 
 
 class Model(torch.nn.Module):
@@ -99,7 +100,7 @@ class Model(torch.nn.Module):
 
     @property
     def task_map(self):
-        """task -> {model class, predictor class} (reference engine/model.py:1062-1064, models/yolo/model.py:24-59)."""
+        """task -> {model class, predictor class, validator class} (reference engine/model.py:1062-1064, models/yolo/model.py:24-59)."""
         return _TASK_MAP
 
     @property
@@ -161,6 +162,33 @@ class Model(torch.nn.Module):
         return iter(results) if stream else results
 
     __call__ = predict
+
+    def val(self, dataloader=None, validator=None, **kwargs):
+        """Validate on an iterable of batches in the reference's collate format (engine/validator.py::DetectionValidator.__call__; the
+        segment task adds "masks", see SegmentationValidator) and return the results dict (reference engine/model.py:599-655 returns
+        validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml names): conf (default 0.001), iou,
+        max_det, half, single_cls, agnostic_nms, device, and for the segment task overlap_mask (True: one index map per image) plus
+        save_json / save_txt / plots, which are not built and raise when set.  validator: a validator CLASS to use instead of the task's."""
+        if dataloader is None:
+            raise ValueError("val() needs an iterable of batch dicts (see DetectionValidator.__call__); datasets are not part of this build")
+        args = {"conf": 0.001, "iou": 0.7, "max_det": 300, "half": False, "single_cls": False, "agnostic_nms": False, "device": None}
+        if self.task == "segment":
+            args.update({"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False})
+        unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "mode"}
+        if unknown:
+            raise TypeError(f"val() got unsupported arguments {sorted(unknown)}")
+        args.update({k: v for k, v in kwargs.items() if k in args})
+        device = self._select_device(args.pop("device"))
+        if self.predictor is not None:  # the model's dtype may change below: a captured predict graph must not outlive it
+            self.predictor.close()
+            self.predictor = None
+        m = self.model.to(device)
+        m.fuse()
+        m = (m.half() if args["half"] else m.float()).eval()
+        v = (validator or self.task_map[self.task]["validator"])(m, device=device, **args)
+        self.metrics = v(dataloader)
+        self.validator = v
+        return self.metrics
 
     def predict_batches(self, batches, stages=4, **kwargs):
         """Throughput form of predict(): a generator over an iterable of BCHW float tensors in [0,1] (all of one shape; host or device,

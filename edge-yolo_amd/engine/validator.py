@@ -5,7 +5,10 @@
 Device work = the forward on the HIP path + validation-mode NMS (conf 0.001, multi_label, iou 0.7, max_det 300: `ey_nms`); label
 scaling, TP matching at the 10 IoU thresholds and AP run on the host in numpy (the reference runs them on the CPU too), through
 `utils/metrics.py`.  Same predictions -> same statistics -> same mAP as the reference (pinned by tests/golden/validator_case.npz,
-produced by the reference's own update_metrics / get_stats / DetMetrics)."""
+produced by the reference's own update_metrics / get_stats / DetMetrics).
+
+`SegmentationValidator` below does the same for the segment task (models/yolo/segment/val.py): there the predicted masks and their IoU
+with the ground truth stay on the device (`ey_process_mask`, `ey_mask_iou`); pinned by tests/golden/segval_case.npz."""
 import numpy as np
 import torch
 
@@ -153,3 +156,218 @@ class DetectionValidator:
     def results(self):
         r = self.get_stats()
         return dict(mp=r[KEYS[0]], mr=r[KEYS[1]], map50=r[KEYS[2]], map75=r[KEYS[3]], map=r[KEYS[4]])
+
+
+class SegmentationValidator(DetectionValidator):
+    """Validation loop for the segment task, mirroring the reference's models/yolo/segment/val.py (`preprocess` :39-43, `postprocess` :71-84,
+    `_prepare_batch` :86-91, `_prepare_pred` :93-97, `update_metrics` :99-166, `_process_batch` :173-217) with SegmentMetrics.
+
+    Device work per batch: the forward, validation-mode NMS with the mask coefficients riding along (`nms_device`), the masks of ALL images
+    at proto resolution in one `ey_process_mask` launch (the reference's default `ops.process_mask(..., upsample=False)`: boxes scaled by
+    mw/iw, mh/ih in fp32, s = 1) and the mask IoU of ALL images in one `ey_mask_iou` call.  The masks never leave the device: the host gets the
+    kept rows (n, 6), and the [gt x pred] IoU matrices in one copy per batch; matching and AP run in numpy like the detect task.
+
+    batch["masks"]: overlap_mask=True (the reference's default) -> one index map per image, (B, h, w), instance m of an image = the pixels
+    equal to m + 1 (m = the label's position within its image), read by the kernel as it is; overlap_mask=False -> (M_total, h, w) 0/1, one
+    per label.  Ground truth of another resolution than the predicted masks is resized like the reference does (bilinear F.interpolate of the
+    expanded float masks, then > 0.5) with torch on the device before the kernel: a cold path -- the dataset produces masks at proto
+    resolution (mask_ratio 4) -- that does materialise the (nl, h, w) stack.
+
+    Host masks (numpy / CPU tensors, `update_metrics(..., pred_masks=[...])` with a validator on the CPU) go through the numpy restatement of
+    mask_iou: the route the CPU tests take.  save_json, save_txt, plots and process_mask_native (ops.process_mask_native) are not built."""
+
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, overlap_mask=True,
+                 save_json=False, save_txt=False, plots=False, process_mask_native=False):
+        for name, on in (("save_json", save_json), ("save_txt", save_txt), ("plots", plots), ("process_mask_native", process_mask_native)):
+            if on:
+                raise NotImplementedError(f"SegmentationValidator: {name}=True is not built (COCO json / txt export, plots and ops.process_mask_native)")
+        self.overlap_mask = bool(overlap_mask)
+        self.keep_outputs = False  # True: update_metrics appends (rows (n,6+nm), mask bits (n,mh,mw)) per image to self.kept, on the host
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+
+    # ---- reference segment/val.py:45-53
+    def init_metrics(self):
+        super().init_metrics()
+        self.metrics = metrics.SegmentMetrics()
+        self.stats = dict(tp_m=[], tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
+        self.results_dict = dict(zip(metrics.SEG_KEYS + ["fitness"], [0.0] * 11))
+        self.seg = None
+        self.kept = []
+
+    # ---- reference segment/val.py:39-43 (the masks stay integers: uint8 0/1 stacks, int32 index maps)
+    def preprocess(self, batch):
+        batch = super().preprocess(batch)
+        m = torch.as_tensor(batch["masks"]) if not torch.is_tensor(batch["masks"]) else batch["masks"]
+        m = m.to(self.device, non_blocking=True)
+        batch["masks"] = (m.to(torch.int32) if self.overlap_mask else (m != 0).to(torch.uint8)).contiguous()
+        return batch
+
+    # ---- reference segment/val.py:71-84: (rows (n_i, 6 + nm) per image, proto)
+    def postprocess(self, preds):
+        boxes, count, _ = ops.nms_device(preds[0], self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc, multi_label=True)
+        proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]
+        n = count.tolist()  # the one D2H sync of the NMS
+        return [boxes[i, :n[i]] for i in range(len(n))], proto
+
+    # ---- reference segment/val.py:86-91
+    def _prepare_batch(self, si, batch):
+        pbatch = super()._prepare_batch(si, batch)
+        masks = batch["masks"]
+        if self.overlap_mask:
+            pbatch["masks"] = masks[[si]]
+        else:
+            idx = _np(batch["batch_idx"]).reshape(-1) == si
+            pbatch["masks"] = masks[torch.as_tensor(idx, device=masks.device)] if torch.is_tensor(masks) else np.asarray(masks)[idx]
+        return pbatch
+
+    def _batch_pred_masks(self, rows, proto, imgsz):
+        """Masks of every image's kept rows at proto resolution, ONE ey_process_mask launch: (N_total, mh, mw) uint8 on the device.  The
+        padded row tensor serves as the coefficient "map" (one level, H = rows per image, W = 1, anchor = row number); boxes are in
+        network-input pixels (before scale_boxes), scaled to the proto grid like ops.process_mask does (reference ops.py:681-688)."""
+        from ..nn import _ops
+        from .. import _lib as L
+        B, nm, mh, mw = proto.shape
+        n = [int(r.shape[0]) for r in rows]
+        if sum(n) == 0:
+            return torch.empty((0, mh, mw), dtype=torch.uint8, device=proto.device)
+        pad = torch.nn.utils.rnn.pad_sequence([r.float() for r in rows], batch_first=True).contiguous()  # (B, max n, 6 + nm)
+        C = pad.shape[2]
+        coef = torch.as_strided(pad, (B, nm, pad.shape[1], 1), (pad.shape[1] * C, 1, C, C), pad.storage_offset() + 6)
+        dev = proto.device
+        idx = torch.tensor([[i, j] for i in range(B) for j in range(n[i])], dtype=torch.int32).to(dev)
+        ih, iw = imgsz
+        scale = torch.tensor([mw / iw, mh / ih, mw / iw, mh / ih], dtype=torch.float32, device=dev)
+        boxes = (torch.cat([r[:, :4].float() for r in rows], 0) * scale).contiguous()
+        return _ops.process_mask(L.as_nhwc(proto), [coef], idx, boxes, 1)
+
+    # ---- reference segment/val.py:93-97 (one image; update_metrics assembles the masks of the whole batch at once instead)
+    def _prepare_pred(self, pred, pbatch, proto):
+        predn = super()._prepare_pred(pred[:, :6], pbatch)
+        pred_masks = ops.process_mask(proto, pred[:, 6:], pred[:, :4], shape=pbatch["imgsz"])
+        return predn, pred_masks
+
+    @staticmethod
+    def _resize_gt(gt, shape):
+        """The reference's resize of float 0/1 ground truth to the predicted masks' shape (segment/val.py:210-212): torch plumbing, cold path."""
+        g = torch.as_tensor(gt).float()
+        g = torch.nn.functional.interpolate(g[None], tuple(shape), mode="bilinear", align_corners=False)[0]
+        return (g > 0.5).to(torch.uint8)
+
+    # ---- reference segment/val.py:173-217
+    def _process_batch(self, detections, gt_bboxes, gt_cls, pred_masks=None, gt_masks=None, overlap=False, masks=False, iou=None):
+        """masks=True: IoU of masks through metrics.mask_iou (device tensors: ey_mask_iou; host arrays: numpy), or `iou` when the caller
+        computed the batch's matrices in one launch already."""
+        if not masks:
+            return super()._process_batch(detections, gt_bboxes, gt_cls)
+        if iou is None:
+            nl = len(gt_cls)
+            if torch.is_tensor(gt_masks) and gt_masks.is_cuda:
+                if overlap:
+                    gt_masks = (gt_masks.view(1, *gt_masks.shape[-2:]) == torch.arange(1, nl + 1, device=gt_masks.device).view(nl, 1, 1)).to(torch.uint8)
+                if tuple(gt_masks.shape[1:]) != tuple(pred_masks.shape[1:]):
+                    gt_masks = self._resize_gt(gt_masks, pred_masks.shape[1:])
+                iou = _np(metrics.mask_iou(gt_masks.reshape(nl, -1), pred_masks.reshape(pred_masks.shape[0], -1)))
+            else:
+                g, p = _np(gt_masks), _np(pred_masks)
+                if overlap:
+                    g = metrics.expand_index_masks(g, nl)
+                if tuple(g.shape[1:]) != tuple(p.shape[1:]):
+                    g = self._resize_gt(g, p.shape[1:]).numpy()
+                iou = metrics.mask_iou(g.reshape(nl, -1), p.reshape(p.shape[0], -1))
+        return metrics.match_predictions(detections[:, 5], gt_cls, iou, self.iouv)
+
+    def _batch_mask_ious(self, pred_masks, n, batch, nl):
+        """[gt x pred] mask IoU of every image in ONE ey_mask_iou call and one copy to the host: list of (nl_i, n_i) arrays (None where
+        either side is empty).  pred_masks: (sum n, mh, mw) uint8 on the device."""
+        from ..nn import _ops
+        B = len(n)
+        gt = batch["masks"]
+        pred_off, gt_off = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(nl)])
+        if not any(a and b for a, b in zip(n, nl)):
+            return [None] * B
+        index = self.overlap_mask
+        if not index:  # one mask per label, image after image (the collate order); anything else is gathered into that order
+            bi = _np(batch["batch_idx"]).reshape(-1)
+            order = np.argsort(bi, kind="stable")
+            if not np.array_equal(order, np.arange(len(bi))):
+                gt = gt[torch.as_tensor(order, device=gt.device)]
+        if tuple(gt.shape[1:]) != tuple(pred_masks.shape[1:]):  # cold path, see the class docstring
+            if index:
+                gt = torch.cat([(gt[i:i + 1] == torch.arange(1, nl[i] + 1, device=gt.device).view(-1, 1, 1)) for i in range(B)], 0)
+                index = False
+            gt = self._resize_gt(gt, pred_masks.shape[1:])
+        iou, off, _ = _ops.mask_iou(pred_masks, pred_off, gt.contiguous(), gt_off, index=index)
+        host = iou.cpu().numpy()  # the one D2H copy of the batch's matrices
+        return [host[off[i]: off[i] + nl[i] * n[i]].reshape(nl[i], n[i]) if n[i] and nl[i] else None for i in range(B)]
+
+    # ---- reference segment/val.py:99-166
+    def update_metrics(self, preds, batch, pred_masks=None):
+        """preds: postprocess's (rows per image, proto).  pred_masks: optional list of per-image (n_i, h, w) 0/1 masks that replaces the
+        mask assembly (proto may then be None): host arrays take the numpy route."""
+        rows, proto = preds
+        B = len(rows)
+        n = [int(r.shape[0]) for r in rows]
+        bi = _np(batch["batch_idx"]).reshape(-1)
+        nl = [int((bi == si).sum()) for si in range(B)]
+        ious = [None] * B
+        on_device = pred_masks is None
+        if on_device:
+            imgsz = tuple(int(v) for v in batch["img"].shape[2:])
+            all_masks = self._batch_pred_masks(rows, proto, imgsz)
+            ious = self._batch_mask_ious(all_masks, n, batch, nl)
+            if self.keep_outputs:
+                host, off = all_masks.cpu().numpy(), np.concatenate([[0], np.cumsum(n)])
+                self.kept += [(_np(rows[i]).copy(), host[off[i]:off[i + 1]]) for i in range(B)]
+        for si, pred in enumerate(rows):
+            self.seen += 1
+            pred = _np(pred).astype(np.float32)
+            pred = pred.reshape(-1, pred.shape[-1] if pred.ndim == 2 else 6)
+            npr = pred.shape[0]
+            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), tp=np.zeros((npr, self.niou), bool), tp_m=np.zeros((npr, self.niou), bool))
+            pbatch = self._prepare_batch(si, batch)
+            cls, bbox = pbatch.pop("cls"), pbatch.pop("bbox")
+            stat["target_cls"] = cls
+            stat["target_img"] = np.unique(cls)
+            if npr == 0:
+                if nl[si]:
+                    for k in self.stats:
+                        self.stats[k].append(stat[k])
+                continue
+            gt_masks = pbatch.pop("masks")
+            if self.single_cls:
+                pred = pred.copy()
+                pred[:, 5] = 0
+            predn = DetectionValidator._prepare_pred(self, pred[:, :6], pbatch)
+            stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
+            if nl[si]:
+                stat["tp"] = self._process_batch(predn, bbox, cls)
+                stat["tp_m"] = self._process_batch(predn, bbox, cls, None if on_device else pred_masks[si], gt_masks, self.overlap_mask, masks=True, iou=ious[si])
+            for k in self.stats:
+                self.stats[k].append(stat[k])
+
+    # ---- reference detect/val.py:179-188 + SegmentMetrics.process / results_dict (metrics.py:949-1029)
+    def get_stats(self):
+        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k in ("tp", "tp_m") else 0)) for k, v in self.stats.items()}
+        self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc)
+        self.nt_per_image = np.bincount(stats["target_img"].astype(int), minlength=self.nc)
+        stats.pop("target_img", None)
+        if len(stats["tp"]) and stats["tp"].any():  # (the reference tests the box matches only, detect/val.py:186)
+            self.metrics.process(**stats)
+            self.box, self.seg = self.metrics.box, self.metrics.seg
+        self.results_dict = self.metrics.results_dict
+        return self.results_dict
+
+    @torch.no_grad()
+    def __call__(self, dataloader):
+        """dataloader: iterable of batch dicts in DetectionValidator's format plus "masks" (see the class docstring).  Returns the results
+        dict (reference SegmentMetrics.results_dict: five box keys, five mask keys, fitness)."""
+        self.init_metrics()
+        for batch in dataloader:
+            batch = self.preprocess(batch)
+            with torch.cuda.device(self.device):
+                preds = self.postprocess(self.model(batch["img"]))
+                self.update_metrics(preds, batch)
+        return self.get_stats()
+
+    def update(self, images, labels):
+        raise NotImplementedError("SegmentationValidator: the (images, labels) convenience of the detect task carries no masks; call it with batches")

@@ -878,6 +878,54 @@ def process_mask(proto, coefs, rows, boxes, s, n=None, out=None):
     return out
 
 
+def mask_iou(pred, pred_off, gt, gt_off, index=False, out_off=None, iou=None, inter=None, workspace=None):
+    """Mask IoU of a batch (ey_mask_iou): pred uint8 (N_total,H,W) 0/1 grouped by image through the host list pred_off (B+1 entries);
+    gt either a uint8 stack (M_total,H,W) grouped by gt_off, or with index=True one int32 map (B,H,W) per image whose instance m is the
+    pixels equal to m+1 (gt_off still gives the instance counts).  Image b's row-major [M_b][N_b] matrix lands at element out_off[b] of the
+    flat fp32 buffer `iou` (and of the int32 buffer `inter`, True = allocate one); by default the matrices are packed one after the other.
+    -> (iou, out_off, inter or None); the matrices: iou[out_off[b]: out_off[b] + M_b * N_b].view(M_b, N_b)."""
+    L.require_device(pred, "mask_iou")
+    _no_block("mask_iou")
+    pred_off, gt_off = [int(v) for v in pred_off], [int(v) for v in gt_off]
+    B = len(pred_off) - 1
+    if B < 0 or len(gt_off) != B + 1 or pred_off[0] != 0 or gt_off[0] != 0:
+        raise ValueError("mask_iou: pred_off and gt_off must have B+1 entries starting at 0")
+    if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_contiguous() or pred.shape[0] < pred_off[-1]:
+        raise ValueError(f"mask_iou: pred must be a contiguous uint8 (N,H,W) tensor with N >= {pred_off[-1]}, got {pred.dtype} {tuple(pred.shape)}")
+    H, W = int(pred.shape[1]), int(pred.shape[2])
+    want = (torch.int32, B) if index else (torch.uint8, gt_off[-1])
+    if gt.dim() != 3 or gt.dtype != want[0] or not gt.is_contiguous() or gt.device != pred.device or gt.shape[0] < want[1] or tuple(gt.shape[1:]) != (H, W):
+        raise ValueError(f"mask_iou: gt must be a contiguous {want[0]} ({want[1]},{H},{W}) tensor on {pred.device}, got {gt.dtype} {tuple(gt.shape)}")
+    sizes = [(gt_off[b + 1] - gt_off[b]) * (pred_off[b + 1] - pred_off[b]) for b in range(B)]
+    if out_off is None:
+        out_off = [0] * B
+        for b in range(1, B):
+            out_off[b] = out_off[b - 1] + sizes[b - 1]
+    out_off = [int(v) for v in out_off]
+    end = max([o + s for o, s in zip(out_off, sizes) if s] + [0])
+    if iou is None:
+        iou = torch.empty(end, dtype=torch.float32, device=pred.device)
+    if inter is True:
+        inter = torch.empty(iou.numel(), dtype=torch.int32, device=pred.device)
+    for name, t, dt in (("iou", iou, torch.float32), ("inter", inter, torch.int32)):
+        if t is not None and (t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or t.device != pred.device or t.numel() < end or len(out_off) != B
+                              or any(o < 0 for o, s in zip(out_off, sizes) if s)):
+            raise ValueError(f"mask_iou: {name} must be a flat contiguous {dt} buffer of at least {end} elements on {pred.device}")
+    nbytes = L.lib().ey_mask_iou_workspace_bytes(H, W, pred_off[-1], gt_off[-1])
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pred.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes or workspace.device != pred.device:
+        raise ValueError(f"mask_iou: workspace must be a contiguous uint8 buffer of at least {nbytes} bytes on {pred.device}")
+    IA, LA = ctypes.c_int * (B + 1), ctypes.c_long * max(B, 1)
+    words = (H * W + 63) // 64
+    with _tr("mask_iou_kernels", pred_off[-1] * H * W + gt.numel() * gt.element_size() + 8 * end, 2.0 * sum(sizes) * words,
+             note=f"B{B} N{pred_off[-1]} M{gt_off[-1]} {H}x{W}", kernels=3):
+        L.check(L.lib().ey_mask_iou(L.MASK_GT_INDEX if index else L.MASK_GT_STACK, B, H, W, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off),
+                                    LA(*out_off), iou.data_ptr(), None if inter is None else inter.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                    L.stream()), "ey_mask_iou")
+    return iou, out_off, inter
+
+
 def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
     """Depthwise kxk, stride 2, pad k//2 (ey_dwconv_s2): the depthwise half of DSConv(c, c, k, 2)."""
     x = L.as_nhwc(as_tensor(x))

@@ -2,7 +2,10 @@
 give the same mAP: `box_iou` (utils/metrics.py:52-72), `match_predictions` (engine/validator.py:222-262, the default
 non-scipy branch), `compute_ap` / `ap_per_class` (utils/metrics.py:505-623), `smooth` (:494-502), and the fitness-style
 summary of `DetMetrics` (:808).  The reference runs these on the CPU as well; only NMS (validation mode: conf 0.001,
-multi_label, models/yolo/detect/val.py:92-102) is device work and goes through `ey_nms`."""
+multi_label, models/yolo/detect/val.py:92-102) is device work and goes through `ey_nms`.
+
+Segment validation adds `mask_iou` (utils/metrics.py:137-153; device tensors run on `ey_mask_iou`, host arrays on a numpy restatement with
+the same bits), the host form of the overlap_mask expansion (models/yolo/segment/val.py:206-209) and `SegmentMetrics` (:909-1029)."""
 import numpy as np
 
 
@@ -111,3 +114,96 @@ class DetMetrics:
         ap = r["ap"]
         return dict(mp=float(r["p"].mean()) if len(r["p"]) else 0.0, mr=float(r["r"].mean()) if len(r["r"]) else 0.0,
                     map50=float(ap[:, 0].mean()) if len(ap) else 0.0, map=float(ap.mean()) if len(ap) else 0.0, per_class=r)
+
+
+def mask_iou_counts(inter, area1, area2, eps=1e-7):
+    """Integer counts -> the reference's fp32 expression, one rounding per operation (utils/metrics.py:151-153):
+    iou = fl(inter / fl(fl(fl(area1 + area2) - inter) + fl(eps))).  Counts up to 2^24 are exact in fp32."""
+    inter = np.asarray(inter).astype(np.float32)
+    union = (np.asarray(area1).astype(np.float32)[:, None] + np.asarray(area2).astype(np.float32)[None, :]) - inter
+    return inter / (union + np.float32(eps))
+
+
+def mask_iou(mask1, mask2, eps=1e-7):
+    """Reference signature (utils/metrics.py:137-153): mask1 (M, n) ground truth x mask2 (N, n) predictions, 0/1 -> (M, N) fp32 IoU.
+    Device tensors run on ey_mask_iou (bit-packed population counts) and return a device tensor; host arrays / CPU tensors take the
+    numpy restatement below -- integer counts, then the same fp32 expression -- and return an ndarray.  Both give the reference's bits."""
+    import torch
+    if torch.is_tensor(mask1) and mask1.is_cuda:
+        from ..nn import _ops
+        if abs(float(eps) - 1e-7) > 1e-20:
+            raise NotImplementedError("mask_iou: the kernel is built for the reference's eps=1e-7")
+        if not (torch.is_tensor(mask2) and mask2.device == mask1.device) or mask1.dim() != 2 or mask2.dim() != 2 or mask1.shape[1] != mask2.shape[1]:
+            raise ValueError("mask_iou: expected (M, n) and (N, n) tensors on one device")
+        M, n = mask1.shape
+        N = mask2.shape[0]
+        if M == 0 or N == 0 or n == 0:
+            return torch.zeros((M, N), dtype=torch.float32, device=mask1.device)
+        u8 = [m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8) for m in (mask1, mask2)]  # (layout only)
+        with torch.cuda.device(mask1.device):
+            iou, _, _ = _ops.mask_iou(u8[1].view(N, 1, n), [0, N], u8[0].view(M, 1, n), [0, M])
+        return iou.view(M, N)
+    g = (np.asarray(mask1.detach().cpu().numpy() if torch.is_tensor(mask1) else mask1) != 0).astype(np.float32)
+    p = (np.asarray(mask2.detach().cpu().numpy() if torch.is_tensor(mask2) else mask2) != 0).astype(np.float32)
+    if g.ndim != 2 or p.ndim != 2 or g.shape[1] != p.shape[1]:
+        raise ValueError("mask_iou: expected (M, n) and (N, n) masks")
+    if g.shape[1] > 1 << 24:
+        raise NotImplementedError("mask_iou: more than 2^24 pixels (the counts would not be exact in fp32)")
+    inter = g @ p.T  # 0/1 operands, sums below 2^24: the fp32 product is the exact count in any summation order
+    return mask_iou_counts(inter, g.sum(1), p.sum(1), eps)
+
+
+def expand_index_masks(index_map, nl):
+    """Host form of the reference's overlap_mask expansion (models/yolo/segment/val.py:206-209): one (h, w) index map ->
+    (nl, h, w) uint8, instance m = the pixels equal to m + 1.  (ey_mask_iou reads the map directly; this is for host masks.)"""
+    m = np.asarray(index_map)
+    m = m.reshape(m.shape[-2:])
+    return (m[None] == (np.arange(nl).reshape(nl, 1, 1) + 1)).astype(np.uint8)
+
+
+SEG_KEYS = ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP75(B)", "metrics/mAP50-95(B)",
+            "metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP75(M)", "metrics/mAP50-95(M)"]  # reference metrics.py:988-1001
+
+
+class Metric:
+    """Per-class results of one ap_per_class run and their means (reference Metric, metrics.py:626-761, with the fork's mAP75 column)."""
+
+    def __init__(self):
+        self.p, self.r, self.f1, self.all_ap, self.ap_class_index = [], [], [], [], []
+
+    def update(self, r):
+        self.p, self.r, self.f1, self.all_ap, self.ap_class_index = r["p"], r["r"], r["f1"], r["ap"], r["classes"]
+
+    def mean_results(self):
+        ap = self.all_ap
+        return [float(self.p.mean()) if len(self.p) else 0.0, float(self.r.mean()) if len(self.r) else 0.0,
+                float(ap[:, 0].mean()) if len(ap) else 0.0, float(ap[:, 5].mean()) if len(ap) else 0.0, float(ap.mean()) if len(ap) else 0.0]
+
+    def fitness(self):
+        return float((np.array(self.mean_results()) * [0.0, 0.0, 0.0, 0.0, 1.0]).sum())  # the fork weights only mAP50-95 (metrics.py:758-761)
+
+
+class SegmentMetrics:
+    """Box and mask metrics side by side (reference SegmentMetrics, metrics.py:909-1029): `box`, `seg`, `keys`, `fitness`, `results_dict`."""
+
+    def __init__(self):
+        self.box, self.seg = Metric(), Metric()
+
+    def process(self, tp, tp_m, conf, pred_cls, target_cls):
+        self.seg.update(ap_per_class(tp_m, conf, pred_cls, target_cls))
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls))
+
+    @property
+    def keys(self):
+        return list(SEG_KEYS)
+
+    def mean_results(self):
+        return self.box.mean_results() + self.seg.mean_results()
+
+    @property
+    def fitness(self):
+        return self.seg.fitness() + self.box.fitness()
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))

@@ -343,6 +343,28 @@ int ey_deconv2x2_pack_weight(int dtype, int Cin, int Cout, const float* w_iohw, 
 int ey_deconv2x2(int dtype, int B, int H, int W, int Cin, int Cout, const void* x, int x_cstride, const void* w_packed, const float* bias, void* y,
                  int y_cstride, ey_stream_t stream);
 
+/* ---- Segment validation: mask IoU (utils/metrics.py:137-153 mask_iou, with the ground-truth expansion of SegmentationValidator._process_batch,
+ * models/yolo/segment/val.py:204-213), for every image of a batch in one call.  For image b with N_b predictions and M_b instances:
+ *   inter[m][n] = #{pixels where gt m and prediction n are both set},  a_gt[m], a_pred[n] = #{set pixels}        exact integers
+ *   iou[m][n]   = fl(inter / fl(fl(fl(a_gt + a_pred) - inter) + 1e-7f))                                           fp32, one rounding per op
+ * (the reference's float matmul, sums and `union + eps`; no FMA contraction, IEEE division).  A union of 0 gives exactly 0.
+ * pred: DEVICE uint8 [pred_off[B]][H][W], 0 = clear, anything else = set (what ey_process_mask writes), image b's rows are
+ * pred_off[b] .. pred_off[b+1] - 1.  gt, by gt_mode:
+ *   EY_MASK_GT_STACK  DEVICE uint8 [gt_off[B]][H][W] like pred (the reference's overlap_mask=False layout);
+ *   EY_MASK_GT_INDEX  DEVICE int32 [B][H][W], instance m of image b = the pixels equal to m + 1 (overlap_mask=True: the reference repeats the
+ *                     map M_b times and compares; here the map is read, never repeated).  M_b comes from gt_off -- an instance that was
+ *                     painted over completely has area 0 -- and may exceed 255; other values (0, negative, > M_b) belong to no instance.
+ * pred_off / gt_off (B + 1 entries, [0] == 0, non-decreasing) and out_off (B entries) are HOST arrays.  Image b's row-major [M_b][N_b] matrix is
+ * written at iou + out_off[b] (and inter + out_off[b] when inter != NULL; int32); nothing else of iou / inter is touched, and an image
+ * with N_b == 0 or M_b == 0 has no matrix (its out_off is ignored).  B == 0 is valid.  workspace: DEVICE, 16-byte aligned,
+ * ey_mask_iou_workspace_bytes(H, W, pred_off[B], gt_off[B]) bytes: the bit-packed operands (64 pixels per word, one wave64 ballot each).
+ * Three launches (pack predictions, pack ground truth, pairs), no atomics: the same bytes run to run.  EY_EUNSUPPORTED -- before anything
+ * is launched -- for B > 128 or H * W > 2^24 (the areas must be exact in fp32); EY_EINVAL for bad arguments. */
+enum { EY_MASK_GT_STACK = 0, EY_MASK_GT_INDEX = 1 };
+size_t ey_mask_iou_workspace_bytes(int H, int W, long n_pred, long n_gt);
+int ey_mask_iou(int gt_mode, int B, int H, int W, const uint8_t* pred, const int* pred_off, const void* gt, const int* gt_off, const long* out_off,
+                float* iou, int* inter, void* workspace, size_t workspace_bytes, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
