@@ -146,6 +146,10 @@ SIGNATURES = {
     "ey_scale_img": (_i, [_i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "ey_tta_merge": (_i, [_i, _i, _i, _vp, _i, _i, _f, _i, _i, _i, _vp, C.c_long, _i, _vp]),
     "ey_nms": (_i, [_i, _i, _i, _vp, _f, _f, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_obb_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "ey_probiou": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "ey_nms_rotated_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ey_nms_rotated": (_i, [_i, _i, _i, _vp, _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,12 +1,12 @@
-"""`YOLO(...)` facade for the detect and segment tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
+"""`YOLO(...)` facade for the detect, segment and obb tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
 `_new` :231-264, `_load` :266-302, `predict` :501-560, `val` :599-655) and models/yolo/model.py (:11-59)."""
 from pathlib import Path
 
 import torch
 
-from .predictor import DetectionPredictor, SegmentationPredictor
+from .predictor import DetectionPredictor, OBBPredictor, SegmentationPredictor
 from .validator import DetectionValidator, SegmentationValidator
-from ..nn.tasks import DetectionModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
+from ..nn.tasks import DetectionModel, OBBModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
 def _plain(o):
@@ -22,6 +22,9 @@ def _plain(o):
 
 _TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "validator": DetectionValidator},
              "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor, "validator": SegmentationValidator}}
+# tasks served by predict() only: no validator yet, so they are not rows of `task_map` (model, predictor AND validator); an entry moves
+# there when its validator is built (obb: rotated mAP on ey_probiou, multi-label rotated NMS)
+_PREDICT_TASKS = {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
 
 
 class Model(torch.nn.Module):
@@ -49,9 +52,9 @@ class Model(torch.nn.Module):
         # the reference raises NotImplementedError here for GFLHeadv2_uniH YAMLs unless task="detect" is passed
         # (engine/model.py:1096-1103 via tasks.py:1198-1210); the argument is accepted but not required
         self.task = task or guess_model_task(cfg_dict)
-        if self.task not in self.task_map:
-            raise NotImplementedError(f"task '{self.task}': only {sorted(self.task_map)} are built")
-        self.model = self.task_map[self.task]["model"](cfg_dict, nc=nc, verbose=verbose)
+        if self.task not in self.task_map and self.task not in _PREDICT_TASKS:
+            raise NotImplementedError(f"task '{self.task}': only {sorted(self.task_map) + sorted(_PREDICT_TASKS)} are built")
+        self.model = self._task_entry()["model"](cfg_dict, nc=nc, verbose=verbose)
         if guess_model_task(self.model) != self.task:
             raise ValueError(f"task '{self.task}' does not match the model's head ({type(self.model.model[-1]).__name__})")
         self.overrides["model"] = self.cfg
@@ -103,6 +106,10 @@ class Model(torch.nn.Module):
         """task -> {model class, predictor class, validator class} (reference engine/model.py:1062-1064, models/yolo/model.py:24-59)."""
         return _TASK_MAP
 
+    def _task_entry(self):
+        """classes of this model's task: its `task_map` row, or the predict-only row (no "validator")."""
+        return self.task_map[self.task] if self.task in self.task_map else _PREDICT_TASKS[self.task]
+
     @property
     def names(self):
         return self.model.names
@@ -143,7 +150,7 @@ class Model(torch.nn.Module):
             raise TypeError(f"predict() got unsupported arguments {sorted(unknown)}")
         args.update({k: v for k, v in kwargs.items() if k in args})
         device = self._select_device(args["device"] if args["device"] is not None else (source.device if isinstance(source, torch.Tensor) and source.is_cuda else None))
-        pcls = predictor or self.task_map[self.task]["predictor"]
+        pcls = predictor or self._task_entry()["predictor"]
         key = tuple((k, str(v)) for k, v in sorted(args.items())) + (("dev", str(device)), ("predictor", pcls))
         if self.predictor is None or self._pred_key != key:
             if self.predictor is not None:  # options changed: release the old predictor's graphs before anything new is captured
@@ -169,6 +176,8 @@ class Model(torch.nn.Module):
         validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml names): conf (default 0.001), iou,
         max_det, half, single_cls, agnostic_nms, device, and for the segment task overlap_mask (True: one index map per image) plus
         save_json / save_txt / plots, which are not built and raise when set.  validator: a validator CLASS to use instead of the task's."""
+        if validator is None and "validator" not in self._task_entry():
+            raise NotImplementedError(f"val(): validation of the '{self.task}' task is not built (obb: rotated mAP and multi-label rotated NMS)")
         if dataloader is None:
             raise ValueError("val() needs an iterable of batch dicts (see DetectionValidator.__call__); datasets are not part of this build")
         args = {"conf": 0.001, "iou": 0.7, "max_det": 300, "half": False, "single_cls": False, "agnostic_nms": False, "device": None}
@@ -185,7 +194,7 @@ class Model(torch.nn.Module):
         m = self.model.to(device)
         m.fuse()
         m = (m.half() if args["half"] else m.float()).eval()
-        v = (validator or self.task_map[self.task]["validator"])(m, device=device, **args)
+        v = (validator or self._task_entry()["validator"])(m, device=device, **args)
         self.metrics = v(dataloader)
         self.validator = v
         return self.metrics

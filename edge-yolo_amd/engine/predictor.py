@@ -368,3 +368,37 @@ class SegmentationPredictor(DetectionPredictor):
                 r.masks = Masks(masks[off:off + n[i]], r.orig_shape)
             off += n[i]
         return results
+
+
+class OBBPredictor(DetectionPredictor):
+    """reference models/yolo/obb/predict.py:10-53.  The device step (forward, OBB decode, ey_nms_rotated) is one captured graph; after the one
+    read-back of the counts the kept rows are regularised (w >= h, angle in [0, pi)) and scaled to the original image as xywh.
+    Results carry `obb` rows [cx,cy,w,h,rotation,conf,cls]; `boxes` is None."""
+
+    def __init__(self, model, device, *args, **kwargs):
+        super().__init__(model, device, *args, **kwargs)
+        if self.augment:  # OBBModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
+            import warnings
+            warnings.warn("OBBModel does not support 'augment=True', reverting to single-scale prediction.")
+            self.augment = False
+
+    def _device_step(self, im):
+        pred = self.model(im)[0]
+        rows, count, index = ops.nms_device(pred, self.conf, self.iou, self.classes, self.agnostic_nms, self.max_det, nc=len(self.model.names), rotated=True)
+        return rows, count, index, pred
+
+    def postprocess(self, rows, count, img, source):
+        n = count.tolist()  # (the one host sync of the batch)
+        results = []
+        for i in range(len(n)):
+            det = rows[i, : n[i]]
+            orig = self._orig[i] if self._orig is not None else None
+            shape = tuple(orig.shape[:2]) if orig is not None else tuple(img.shape[2:])
+            rboxes = ops.regularize_rboxes(torch.cat([det[:, :4], det[:, -1:]], dim=-1))
+            rboxes[:, :4] = ops.scale_boxes(img.shape[2:], rboxes[:, :4], shape, xywh=True)
+            r = Results(orig, path=f"image{i}.jpg", names=self.model.names, obb=torch.cat([rboxes, det[:, 4:6]], dim=-1))
+            if orig is None:
+                r.orig_shape = shape
+                r.obb.orig_shape = shape
+            results.append(r)
+        return results

@@ -1,5 +1,6 @@
-"""Minimal `Results` / `Boxes` / `Masks` containers with the attribute surface of the reference's engine/results.py
-(:187 Results, :938 Boxes, :1093 Masks) that predict() callers read.  Plotting/saving are out of scope."""
+"""Minimal `Results` / `Boxes` / `Masks` / `OBB` containers with the attribute surface of the reference's engine/results.py
+(:187 Results, :938 Boxes, :1093 Masks, :1519 OBB) that predict() callers read.  Plotting/saving are out of scope."""
+import numpy as np
 import torch
 
 
@@ -81,15 +82,73 @@ class Masks:
         return len(self.data)
 
 
+class OBB:
+    """(n,7) rows [cx,cy,w,h,rotation,conf,cls] in original-image pixels (reference :1519; track ids are not built)."""
+
+    def __init__(self, boxes, orig_shape):
+        if boxes.ndim == 1:
+            boxes = boxes[None, :]
+        assert boxes.shape[-1] == 7, f"expected 7 values but got {boxes.shape[-1]}"
+        self.data = boxes
+        self.orig_shape = orig_shape
+
+    @property
+    def xywhr(self):
+        return self.data[:, :5]
+
+    @property
+    def conf(self):
+        return self.data[:, -2]
+
+    @property
+    def cls(self):
+        return self.data[:, -1]
+
+    @property
+    def xyxyxyxy(self):
+        """(n,4,2) corner points."""
+        from ..utils import ops
+        return ops.xywhr2xyxyxyxy(self.xywhr)
+
+    @property
+    def xyxyxyxyn(self):
+        p = self.xyxyxyxy
+        p = p.clone() if isinstance(p, torch.Tensor) else np.copy(p)
+        p[..., 0] /= self.orig_shape[1]
+        p[..., 1] /= self.orig_shape[0]
+        return p
+
+    @property
+    def xyxy(self):
+        """(n,4) axis-aligned boxes enclosing the corner points."""
+        p = self.xyxyxyxy
+        x, y = p[..., 0], p[..., 1]
+        if isinstance(x, torch.Tensor):
+            return torch.stack([x.amin(1), y.amin(1), x.amax(1), y.amax(1)], -1)
+        return np.stack([x.min(1), y.min(1), x.max(1), y.max(1)], -1)
+
+    def cpu(self):
+        return self if isinstance(self.data, np.ndarray) else OBB(self.data.cpu(), self.orig_shape)
+
+    def numpy(self):
+        return self if isinstance(self.data, np.ndarray) else OBB(self.data.cpu().numpy(), self.orig_shape)
+
+    def __len__(self):
+        return len(self.data)
+
+
 class Results:
-    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None):
+    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None, obb=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_img.shape[:2]) if orig_img is not None and hasattr(orig_img, "shape") and orig_img.ndim == 3 else None
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
         self.masks = Masks(masks, self.orig_shape) if masks is not None else None
+        self.obb = OBB(obb, self.orig_shape) if obb is not None else None
         self.names = names
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
 
     def __len__(self):
-        return len(self.boxes) if self.boxes is not None else 0
+        if self.boxes is not None:
+            return len(self.boxes)
+        return len(self.obb) if self.obb is not None else 0

@@ -1333,3 +1333,58 @@ def nms(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, class_m
                                class_mask.data_ptr() if class_mask is not None else None, boxes.data_ptr(), count.data_ptr(), index.data_ptr(),
                                ws.data_ptr(), nbytes, L.stream()), "ey_nms")
     return (boxes, count, index, ws) if return_workspace else (boxes, count, index)
+
+
+def obb_decode_levels(levels, pred):
+    """levels: list (<= 4) of (box, cls, angle, stride, a_off) NHWC views -> pred (B, 4+nc+1, A) fp32: DFL expectation, dist2rbox, class
+    sigmoids and the angle row of the OBB head, every level in ONE launch (ey_obb_decode_levels)."""
+    n = len(levels)
+    box0, cls0 = levels[0][0], levels[0][1]
+    L.require_device(box0, "obb_decode")
+    _no_block("obb decode")
+    B, nc = box0.shape[0], cls0.shape[1]
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[0] != B or pred.shape[1] != 4 + nc + 1:
+        raise ValueError(f"obb_decode: pred must be a contiguous float32 (B, 4+nc+1, A) tensor, got {tuple(pred.shape)} {pred.dtype}")
+    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
+    Hs, Ws = IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels])
+    st = FA(*[float(lv[3]) for lv in levels])
+    ptr = [PA(*[lv[j].data_ptr() for lv in levels]) for j in range(3)]
+    cs = [IA(*[L.cstride(lv[j]) for lv in levels]) for j in range(3)]
+    offs = IA(*[int(lv[4]) for lv in levels])
+    nbytes = sum(_nb(lv[0], lv[1], lv[2]) for lv in levels) + _nb(pred)
+    with _tr("obb_decode_kernel", nbytes, sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * 220 for lv in levels), note=f"{n} levels"):
+        L.check(L.lib().ey_obb_decode_levels(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, ptr[0], cs[0], ptr[1], cs[1], ptr[2], cs[2], nc, pred.data_ptr(), pred.shape[2],
+                                             offs, L.stream()), "ey_obb_decode_levels")
+    return pred
+
+
+def probiou(obb1, obb2):
+    """(N,5), (M,5) xywhr fp32 device tensors -> the (N,M) fp32 ProbIoU matrix (ey_probiou)."""
+    L.require_device(obb1, "probiou")
+    o1, o2 = obb1.float().contiguous(), obb2.float().contiguous()
+    if o1.dim() != 2 or o2.dim() != 2 or o1.shape[1] != 5 or o2.shape[1] != 5:
+        raise ValueError(f"probiou: expected (N,5) and (M,5) xywhr tensors, got {tuple(obb1.shape)} and {tuple(obb2.shape)}")
+    out = torch.empty((o1.shape[0], o2.shape[0]), dtype=torch.float32, device=o1.device)
+    with _tr("obb_probiou_kernel", _nb(o1, o2, out), 60.0 * out.numel()):
+        L.check(L.lib().ey_probiou(o1.shape[0], o2.shape[0], o1.data_ptr(), o2.data_ptr(), out.data_ptr(), L.stream()), "ey_probiou")
+    return out
+
+
+def nms_rotated(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, class_mask=None):
+    """pred fp32 (B,4+nc+1,A) contiguous (xywh, scores, angle) -> (rows (B,max_det,7) fp32 = x,y,w,h,conf,cls,angle, count (B,) int32,
+    index (B,max_det) int32): fast-NMS on ProbIoU (ey_nms_rotated), single label."""
+    L.require_device(pred, "nms_rotated")
+    if pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise ValueError("nms_rotated: pred must be a contiguous float32 (B,4+nc+1,A) tensor")
+    B, no, A = pred.shape
+    dev = pred.device
+    rows = torch.empty((B, max_det, 7), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    index = torch.empty((B, max_det), dtype=torch.int32, device=dev)
+    nbytes = L.lib().ey_nms_rotated_workspace_bytes(B, A, int(max_nms))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _tr("nms_rotated(init+score+rank+pair+resolve)", _nb(pred, rows), kernels=5):
+        L.check(L.lib().ey_nms_rotated(B, no - 5, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh), int(bool(agnostic)),
+                                       class_mask.data_ptr() if class_mask is not None else None, rows.data_ptr(), count.data_ptr(), index.data_ptr(),
+                                       ws.data_ptr(), nbytes, L.stream()), "ey_nms_rotated")
+    return rows, count, index

@@ -1,4 +1,4 @@
-"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
+"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
@@ -14,7 +14,7 @@ from .conv import Conv, DWConv, _Packed, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "Segment", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+__all__ = ("Detect", "Segment", "OBB", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
 
 
 class _Plain(_Packed):
@@ -165,8 +165,9 @@ class Detect(nn.Module):
     def _quality_params(self, i, device):
         return None
 
-    def forward(self, x, nms=None):
-        """nms=None: returns (pred (B,4+nc,A) fp32, raw per-level maps) like the reference.  nms=dict(conf=, classes=None, keep_pred=False)
+    def forward(self, x, nms=None, towers_only=False):
+        """towers_only (subclasses that decode themselves, OBB): stop behind the towers and return (levels, raw maps) as `defer_decode` does.
+        nms=None: returns (pred (B,4+nc,A) fp32, raw per-level maps) like the reference.  nms=dict(conf=, classes=None, keep_pred=False)
         (predict pipelines): the decode also builds the NMS candidates for that confidence threshold / class filter in the same pass
         and returns (_ops.Candidates, raw maps) -- `utils.ops.nms_device` takes it in place of `pred`, which is then neither written nor
         re-read (keep_pred=True still writes it, as Candidates.pred).  Where the head has the standard shape (f16, 64-channel box
@@ -182,7 +183,7 @@ class Detect(nn.Module):
             return self._forward_end2end(x, xs)
         B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
         A = sum(t.shape[2] * t.shape[3] for t in xs)
-        want_pred = nms is None or nms.get("keep_pred") or not (len(xs) <= 4 and self.nc > 1)
+        want_pred = not towers_only and (nms is None or nms.get("keep_pred") or not (len(xs) <= 4 and self.nc > 1))
         pred = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev) if want_pred else None
         a_off = 0
         if getattr(self, "_stride_f", None) is None:
@@ -236,7 +237,7 @@ class Detect(nn.Module):
         if fork:
             for side in self._side:
                 cur.wait_stream(side)
-        if getattr(self, "defer_decode", False):
+        if towers_only or getattr(self, "defer_decode", False):
             # two-stage pipelines (engine/predictor.py::PipelinedRunner) put the decode into the post-processing stage, next to the
             # NMS: the next batch's backbone then starts as soon as the towers are done instead of behind the decode launch
             return levels, x
@@ -456,6 +457,47 @@ class Segment(Detect):
         y, raw = got
         mc = torch.cat([m.flatten(2) for m in mcs], 2)  # (layout only: the reference's view + cat, head.py:365)
         return torch.cat([y, mc.to(y.dtype)], 1), (raw, mc, p)
+
+
+class OBB(Detect):
+    """YOLO OBB head (reference head.py:372-399): Detect plus one angle tower `cv4` per pyramid level (`ne` = 1 output channel).  The box and
+    class towers run through Detect.forward(towers_only=True); the angle towers write one NHWC map per level; ey_obb_decode_levels then decodes
+    all levels in one launch (DFL expectation, dist2rbox with the anchor's angle, class sigmoids, the angle row)."""
+
+    def __init__(self, nc=80, ne=1, ch=()):
+        super().__init__(nc, ch)
+        self.ne = ne
+        c4 = max(ch[0] // 4, self.ne)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.ne, 1)) for x in ch)
+
+    def angle_maps(self, xs):
+        """-> per-level angle logit maps [(B,ne,H_l,W_l) NHWC, pixel stride padded to 8 channels], on the caller's stream."""
+        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        cpad = (self.ne + 7) // 8 * 8  # pixel stride kept 16-byte aligned
+        maps = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.ne] for t in xs]
+        for i, t in enumerate(xs):
+            c = self.cv4[i]
+            self._tail(c[2]).run(c[1](c[0](t)), maps[i])
+        return maps
+
+    def forward(self, x, nms=None):
+        """The reference's eval-mode return (head.py:383-395): (cat([y, angle], 1) (B,4+nc+1,A) fp32, (raw maps, angle (B,1,A))) with
+        angle = (sigmoid(logit) - 0.25) * pi; rows 0-3 of y are the rotated box (cx, cy, w, h) in input pixels."""
+        if self.training:
+            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
+        if self.end2end:
+            raise NotImplementedError("OBB: end2end heads are not built")
+        if self.ne != 1:
+            raise NotImplementedError(f"OBB: ne={self.ne} (the decode kernel is built for one angle channel)")
+        if nms is not None:
+            raise NotImplementedError("OBB: the fused NMS candidate build is axis-aligned; run utils.ops.nms_device(pred, rotated=True) on the prediction")
+        xs = [L.as_nhwc(t) for t in x]
+        angs = self.angle_maps(xs)
+        levels, raw = Detect.forward(self, list(xs), towers_only=True)
+        B, A = xs[0].shape[0], sum(t.shape[2] * t.shape[3] for t in xs)
+        pred = torch.empty((B, 4 + self.nc + 1, A), dtype=torch.float32, device=xs[0].device)
+        ops.obb_decode_levels([(box, cls, angs[i], st, off) for i, (box, cls, st, _, off) in enumerate(levels)], pred)
+        return pred if self.export else (pred, (raw, pred[:, 4 + self.nc:]))
 
 
 class GF2Detect(Detect):

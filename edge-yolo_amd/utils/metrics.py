@@ -5,7 +5,9 @@ summary of `DetMetrics` (:808).  The reference runs these on the CPU as well; on
 multi_label, models/yolo/detect/val.py:92-102) is device work and goes through `ey_nms`.
 
 Segment validation adds `mask_iou` (utils/metrics.py:137-153; device tensors run on `ey_mask_iou`, host arrays on a numpy restatement with
-the same bits), the host form of the overlap_mask expansion (models/yolo/segment/val.py:206-209) and `SegmentMetrics` (:909-1029)."""
+the same bits), the host form of the overlap_mask expansion (models/yolo/segment/val.py:206-209) and `SegmentMetrics` (:909-1029).
+
+`batch_probiou` (utils/metrics.py:244-275) is the pairwise ProbIoU of oriented boxes on `ey_probiou` (device tensors only)."""
 import numpy as np
 
 
@@ -151,6 +153,21 @@ def mask_iou(mask1, mask2, eps=1e-7):
         raise NotImplementedError("mask_iou: more than 2^24 pixels (the counts would not be exact in fp32)")
     inter = g @ p.T  # 0/1 operands, sums below 2^24: the fp32 product is the exact count in any summation order
     return mask_iou_counts(inter, g.sum(1), p.sum(1), eps)
+
+
+def batch_probiou(obb1, obb2, eps=1e-7):
+    """(N,5) x (M,5) xywhr -> (N,M) fp32 ProbIoU (https://arxiv.org/pdf/2106.06072v1.pdf) on ey_probiou.  Device tensors; numpy arrays and
+    host tensors are moved to the current device and the result comes back where the first operand was.  eps is the kernel's 1e-7."""
+    import torch
+    from ..nn import _ops
+    if eps != 1e-7:
+        raise NotImplementedError(f"batch_probiou: eps={eps} (the kernel is built for the reference's 1e-7)")
+    o1 = torch.from_numpy(obb1) if isinstance(obb1, np.ndarray) else obb1
+    o2 = torch.from_numpy(obb2) if isinstance(obb2, np.ndarray) else obb2
+    dev = o1.device if o1.is_cuda else (o2.device if o2.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    with torch.cuda.device(dev):
+        out = _ops.probiou(o1.to(dev), o2.to(dev))
+    return out if o1.is_cuda else out.to(o1.device)
 
 
 def expand_index_masks(index_map, nl):

@@ -1,7 +1,8 @@
 """Post-processing of the detection path, mirroring the reference's ultralytics/utils/ops.py:
 `make_divisible` (:130-143), `non_max_suppression` (:167-316), `xywh2xyxy` (:416-433), `scale_boxes` (:92-127),
-`clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693).  NMS and mask assembly run in the HIP library (ey_nms,
-ey_process_mask); there is no torch/torchvision fallback."""
+`clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693), `nms_rotated` (:146-164), `xywhr2xyxyxyxy` (:556-584),
+`regularize_rboxes` (:775-790).  NMS and mask assembly run in the HIP library (ey_nms, ey_nms_rotated, ey_process_mask); there is no
+torch/torchvision fallback."""
 import math
 
 import torch
@@ -74,14 +75,71 @@ def _end2end_filter(prediction, conf_thres, classes, max_det):
     return boxes, keep.sum(1).to(torch.int32), index
 
 
+_CLASS_MASKS = {}
+
+
+def _class_mask(classes, nc, device):
+    """uint8 [nc] class-filter mask on `device`, uploaded once per (classes, nc, device): the first, eager, call of a predictor builds it, so
+    nothing is copied from the host inside a captured graph (as `_CLASS_TENSORS` above and Detect._class_mask)."""
+    if classes is None:
+        return None
+    key = (tuple(classes), int(nc), device)
+    if key not in _CLASS_MASKS:
+        mask = torch.zeros(nc, dtype=torch.uint8)
+        mask[torch.as_tensor(list(classes), dtype=torch.long)] = 1
+        _CLASS_MASKS[key] = mask.to(device)
+    return _CLASS_MASKS[key]
+
+
+def _nms_device_rotated(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label):
+    """nms_device(rotated=True): (B,4+nc+1,A) predictions of an OBB head (xywh, class scores, angle) -> (rows (B,max_det,7) = x,y,w,h,conf,
+    cls,angle, count (B,), index (B,max_det)) on ey_nms_rotated (fast-NMS on ProbIoU, reference ops.py:146-164,289-293)."""
+    from ..nn import _ops
+    assert 0 <= conf_thres <= 1, f"Invalid Confidence threshold {conf_thres}, valid values are between 0.0 and 1.0"
+    assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
+    if isinstance(prediction, _ops.Candidates):
+        raise ValueError("nms_device(rotated=True) takes the prediction tensor; fused candidates are axis-aligned")
+    if not nc:
+        # the reference's default, nc = channels - 4 (ops.py:231), scores the angle row as one more class; its OBB predictor and validator
+        # always pass nc (obb/predict.py:38).  That nc-less form is not built
+        raise NotImplementedError("rotated NMS needs nc= (the number of classes: the prediction is 4 + nc + 1 angle channels)")
+    if prediction.shape[1] - nc - 4 != 1:
+        raise ValueError(f"nms_device(rotated=True): nc={nc} but the prediction has {prediction.shape[1]} channels (4 + nc + 1 angle expected)")
+    if multi_label and nc > 1:
+        raise NotImplementedError("rotated NMS with multi_label=True (the validation regime, one candidate per (anchor, class)) is not built; "
+                                  "single-label (predict) mode is")
+    with torch.cuda.device(prediction.device):  # launches go to the current device's stream (_lib.stream)
+        p = prediction.float().contiguous()
+        return _ops.nms_rotated(p, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, _class_mask(classes, nc, p.device))
+
+
+def nms_rotated(boxes, scores, threshold=0.45):
+    """Reference signature (ops.py:146-164): boxes (N,5) xywhr, scores (N,) -> indices of the kept boxes in descending score order
+    (equal scores: lower index first), fast-NMS on ProbIoU through ey_nms_rotated.  Device tensors; one host read of the count."""
+    n = int(boxes.shape[0])
+    if n == 0:
+        return torch.empty((0,), dtype=torch.long, device=boxes.device)
+    # one image of one class whose anchors are the boxes in descending score order (stable: equal scores keep the lower index first); the
+    # kernel's own ranking then reproduces that order whatever the scores are: a strictly decreasing stand-in score, ties by anchor
+    order = torch.argsort(scores, descending=True, stable=True)
+    b = boxes.float()[order]
+    s = 0.75 - 0.5 * torch.arange(n, device=b.device, dtype=torch.float64) / n
+    pred = torch.cat([b[:, :4].t(), s.float()[None], b[:, 4:5].t()], 0)[None].contiguous()
+    _, count, index = _nms_device_rotated(pred, 0.0, threshold, None, True, n, 1, n, 0.0, False)
+    return order[index[0, : int(count[0])].long()]
+
+
 def nms_device(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, max_det=300, nc=0, max_nms=30000, max_wh=7680,
-               multi_label=False):
+               multi_label=False, rotated=False):
     """Batched NMS on the device, fixed-size outputs (graph-capturable): returns (boxes (B,max_det,6), count (B,),
     index (B,max_det)).  `prediction` is (B,4+nc,A); fp16 input is promoted to fp32 first (the reference promotes inside
-    NMS, ops.py:275; this build keeps head outputs in fp32 end to end)."""
+    NMS, ops.py:275; this build keeps head outputs in fp32 end to end).  rotated=True: (B,4+nc+1,A) predictions of an OBB head ->
+    rows (B,max_det,7) = x,y,w,h,conf,cls,angle (see _nms_device_rotated)."""
     from ..nn import _ops
     if isinstance(prediction, (list, tuple)):
         prediction = prediction[0]
+    if rotated:
+        return _nms_device_rotated(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label)
     if isinstance(prediction, _ops.Candidates):  # built by the fused head decode for (conf, classes): selection + suppression only
         c = prediction
         assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
@@ -126,13 +184,15 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     """Reference signature (ops.py:167-183); returns a list of (n_i, 6) tensors [x1,y1,x2,y2,conf,cls] -- (n_i, 6+nm) with the mask
     coefficients appended when the prediction carries nm channels behind the nc classes (pass nc=).
     multi_label=True is the validation-mode variant (one candidate per (anchor, class) above conf, ops.py:270-272).
+    rotated=True: predictions of an OBB head (B,4+nc+1,A) -> (n_i, 7) rows [x,y,w,h,conf,cls,angle], single label only (multi_label=True
+    raises NotImplementedError, and so does the reference's nc-less default, which would score the angle row as a class: pass nc=).
     Differences, all deliberate: no wall-clock abort (:238,:312-314 make the reference output timing dependent);
-    the input tensor is not rewritten to xyxy in place; labels (autolabel) / rotated are not built and raise."""
-    if (labels and len(labels)) or rotated:
-        raise NotImplementedError("autolabel / rotated NMS variants are not part of the built path")
+    the input tensor is not rewritten to xyxy in place; labels (autolabel) is not built and raises."""
+    if labels and len(labels):
+        raise NotImplementedError("the autolabel NMS variant is not part of the built path")
     if isinstance(prediction, (list, tuple)):
         prediction = prediction[0]
-    boxes, count, _ = nms_device(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label)
+    boxes, count, _ = nms_device(prediction, conf_thres, iou_thres, classes, agnostic, max_det, nc, max_nms, max_wh, multi_label, rotated=rotated)
     n = count.tolist()  # one D2H sync for the whole batch
     return [boxes[i, : n[i]] for i in range(len(n))]
 
@@ -175,3 +235,29 @@ def process_mask(protos, masks_in, bboxes, shape, upsample=False):
         if n == 0:
             return torch.empty((0, s * mh, s * mw), dtype=torch.uint8, device=protos.device)
         return _ops.process_mask(proto, [coef], rows, boxes.contiguous(), s)
+
+
+_CORNER_SIGNS = ((1.0, 1.0), (1.0, -1.0), (-1.0, -1.0), (-1.0, 1.0))  # (along w, along h) of the four corners, in the reference's order
+
+
+def xywhr2xyxyxyxy(x):
+    """(..., 5) [cx, cy, w, h, rotation] -> (..., 4, 2) corner points; torch tensors or numpy arrays.  Corner k is the centre plus the
+    half extents (sw_k w/2, sh_k h/2) turned by the rotation: x = cx + sw w/2 cos - sh h/2 sin, y = cy + sw w/2 sin + sh h/2 cos, summed in
+    that order (the reference's :556-584 adds the w edge vector first, then the h one)."""
+    import numpy as np
+    xp = torch if isinstance(x, torch.Tensor) else np
+    c, s = xp.cos(x[..., 4]), xp.sin(x[..., 4])
+    hw, hh = x[..., 2] / 2, x[..., 3] / 2
+    ux, uy, vx, vy = hw * c, hw * s, -hh * s, hh * c  # half edge vectors along w and along h
+    pts = [xp.stack([(x[..., 0] + ux * sw) + vx * sh, (x[..., 1] + uy * sw) + vy * sh], -1) for sw, sh in _CORNER_SIGNS]
+    return xp.stack(pts, -2)
+
+
+def regularize_rboxes(rboxes):
+    """(N,5) xywhr -> the same rectangles with the long side first and the angle in [0, pi) (reference :775-790): where h >= w the sides
+    swap and the angle advances by pi/2; every angle is then reduced modulo pi."""
+    swap = ~(rboxes[..., 2] > rboxes[..., 3])
+    turned = torch.stack([rboxes[..., 0], rboxes[..., 1], rboxes[..., 3], rboxes[..., 2], rboxes[..., 4] + math.pi / 2], -1)
+    out = torch.where(swap[..., None], turned, rboxes)
+    out[..., 4] = out[..., 4] % math.pi
+    return out

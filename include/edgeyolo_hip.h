@@ -571,6 +571,29 @@ int ey_nms(int B, int nc, int A, const float* pred, float conf_thres, float iou_
            float max_wh, int agnostic, int multi_label, const uint8_t* class_mask, float* out_boxes, int32_t* out_count,
            int32_t* out_index, void* workspace, size_t workspace_bytes, ey_stream_t stream);
 
+/* ---- Oriented boxes (csrc/obb.hip).
+ * ey_obb_decode_levels: eval-mode OBB head (ultralytics/nn/modules/head.py:383-399 with Detect._inference :117-148, DFL block.py:87-90,
+ *   dist2rbox utils/tal.py:366-385) for up to 4 pyramid levels in ONE launch.  Per level NHWC maps of `dtype`: box [B,H,W,64] logits,
+ *   cls [B,H,W,nc] logits, angle [B,H,W,1] logits, each with its pixel stride.  pred fp32 [B, 4+nc+1, A_total]: rows 0-3 = the rotated box
+ *   (cx, cy, w, h) * stride, rows 4.. = sigmoid(cls), last row = the angle (sigmoid(a) - 0.25) * pi, unscaled.
+ * ey_probiou: utils/metrics.py::batch_probiou (:244-275, eps = 1e-7): obb1 [N,5], obb2 [M,5] xywhr fp32 -> out [N,M] fp32.
+ * ey_nms_rotated: non_max_suppression(rotated=True) in single-label mode (utils/ops.py:230-297 with nms_rotated :146-164: fast-NMS on
+ *   ProbIoU).  pred fp32 [B, 4+nc+1, A] as written by ey_obb_decode_levels, NOT modified.  Candidates: best class score > conf_thres
+ *   (strict; conf_thres >= 0, EY_EINVAL otherwise) and class_mask (uint8 [nc] or NULL); the max_nms best by score, ordered by descending score, equal scores by ascending
+ *   anchor; pair input (x + c max_wh, y + c max_wh, w, h, r), c = class (0 when agnostic), summed in fp32; column j is kept iff
+ *   max(0, max_{i before j} probiou(i, j)) < iou_thres.  out_rows fp32 [B,max_det,7] = x,y,w,h,conf,cls,angle copied from pred, the first
+ *   max_det kept columns in score order (zeros beyond the count); out_count int32 [B]; out_index int32 [B,max_det] = anchor of each row, -1
+ *   beyond the count (may be NULL).  workspace: ey_nms_rotated_workspace_bytes(B, A, max_nms) bytes, 256-byte aligned.  No host
+ *   synchronisation, no allocation: graph-capturable.  Exact at every candidate count up to max_nms. */
+int ey_obb_decode_levels(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box, const int* box_cstride,
+                         const void* const* cls, const int* cls_cstride, const void* const* angle, const int* angle_cstride, int nc, float* pred,
+                         int A_total, const int* a_off, ey_stream_t stream);
+int ey_probiou(int N, int M, const float* obb1, const float* obb2, float* out, ey_stream_t stream);
+size_t ey_nms_rotated_workspace_bytes(int B, int A, int max_nms);
+int ey_nms_rotated(int B, int nc, int A, const float* pred, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
+                   const uint8_t* class_mask, float* out_rows, int32_t* out_count, int32_t* out_index, void* workspace, size_t workspace_bytes,
+                   ey_stream_t stream);
+
 /* ---- Test-time augmentation (DetectionModel._predict_augment, nn/tasks.py:372-408; reached by predict(augment=True)).
  * ey_scale_img = `scale_img(x.flip(3) if flip_lr else x, ratio, gs)` (utils/torch_utils.py:423-432): bilinear resize
  * (align_corners=False, ATen source-index rule) of the planar NCHW image x [B,C,H,W] to hs x ws = int(H*r) x int(W*r), written into the
