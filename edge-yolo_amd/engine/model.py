@@ -1,12 +1,12 @@
-"""`YOLO(...)` facade for the detect, segment and obb tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
+"""`YOLO(...)` facade for the detect, segment, obb and pose tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
 `_new` :231-264, `_load` :266-302, `predict` :501-560, `val` :599-655) and models/yolo/model.py (:11-59)."""
 from pathlib import Path
 
 import torch
 
-from .predictor import DetectionPredictor, OBBPredictor, SegmentationPredictor
-from .validator import DetectionValidator, SegmentationValidator
-from ..nn.tasks import DetectionModel, OBBModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
+from .predictor import DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
+from .validator import DetectionValidator, PoseValidator, SegmentationValidator
+from ..nn.tasks import DetectionModel, OBBModel, PoseModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
 def _plain(o):
@@ -22,9 +22,10 @@ def _plain(o):
 
 _TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "validator": DetectionValidator},
              "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor, "validator": SegmentationValidator}}
-# tasks served by predict() only: no validator yet, so they are not rows of `task_map` (model, predictor AND validator); an entry moves
-# there when its validator is built (obb: rotated mAP on ey_probiou, multi-label rotated NMS)
-_PREDICT_TASKS = {"obb": {"model": OBBModel, "predictor": OBBPredictor}}
+# tasks outside `task_map` (whose key set is pinned to the two tasks above): `_task_entry()` falls back to this table.  A row without a
+# "validator" is served by predict() only and val() refuses it (obb: rotated mAP on ey_probiou and multi-label rotated NMS are not built)
+_PREDICT_TASKS = {"obb": {"model": OBBModel, "predictor": OBBPredictor},
+                  "pose": {"model": PoseModel, "predictor": PosePredictor, "validator": PoseValidator}}
 
 
 class Model(torch.nn.Module):
@@ -107,7 +108,7 @@ class Model(torch.nn.Module):
         return _TASK_MAP
 
     def _task_entry(self):
-        """classes of this model's task: its `task_map` row, or the predict-only row (no "validator")."""
+        """classes of this model's task: its `task_map` row, or its row of the side table (which may lack a "validator")."""
         return self.task_map[self.task] if self.task in self.task_map else _PREDICT_TASKS[self.task]
 
     @property
@@ -172,7 +173,7 @@ class Model(torch.nn.Module):
 
     def val(self, dataloader=None, validator=None, **kwargs):
         """Validate on an iterable of batches in the reference's collate format (engine/validator.py::DetectionValidator.__call__; the
-        segment task adds "masks", see SegmentationValidator) and return the results dict (reference engine/model.py:599-655 returns
+        segment task adds "masks", see SegmentationValidator; the pose task "keypoints", see PoseValidator) and return the results dict (reference engine/model.py:599-655 returns
         validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml names): conf (default 0.001), iou,
         max_det, half, single_cls, agnostic_nms, device, and for the segment task overlap_mask (True: one index map per image) plus
         save_json / save_txt / plots, which are not built and raise when set.  validator: a validator CLASS to use instead of the task's."""
@@ -183,6 +184,8 @@ class Model(torch.nn.Module):
         args = {"conf": 0.001, "iou": 0.7, "max_det": 300, "half": False, "single_cls": False, "agnostic_nms": False, "device": None}
         if self.task == "segment":
             args.update({"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False})
+        if self.task == "pose":
+            args.update({"save_json": False, "save_txt": False, "plots": False})
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "mode"}
         if unknown:
             raise TypeError(f"val() got unsupported arguments {sorted(unknown)}")

@@ -402,3 +402,51 @@ class OBBPredictor(DetectionPredictor):
                 r.obb.orig_shape = shape
             results.append(r)
         return results
+
+
+class PosePredictor(DetectionPredictor):
+    """reference models/yolo/pose/predict.py:8-56.  The device step is DetectionPredictor's captured graph (fused head decode, candidate NMS)
+    plus the cv4 launches of the Pose head and ONE ey_kpts_decode_rows launch that decodes the keypoints of the kept rows by anchor index:
+    a fixed (B, max_det, K, ndim) tensor, nothing is decoded for the anchors NMS dropped.  After the one read-back of the counts the boxes
+    are scaled and rounded (pose/predict.py:50; detect does not round) and the keypoints go through scale_coords."""
+
+    def __init__(self, model, device, *args, **kwargs):
+        super().__init__(model, device, *args, **kwargs)
+        if self.augment:  # PoseModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
+            import warnings
+            warnings.warn("PoseModel does not support 'augment=True', reverting to single-scale prediction.")
+            self.augment = False
+
+    def _device_step(self, im):
+        from ..nn import _ops
+        head = self.model.model[-1]
+        cand, (_, maps) = self.model(im, head_nms={"conf": self.conf, "classes": self.classes, "keep_pred": self.keep_pred})
+        boxes, count, index = ops.nms_device(cand, self.conf, self.iou, self.classes, self.agnostic_nms, self.max_det)
+        kpts = _ops.kpts_decode_rows(head.kpt_levels(maps), head.kpt_shape, index, count)
+        return boxes, count, index, getattr(cand, "pred", None), kpts
+
+    def _results(self, out, im, source):
+        return self.postprocess(out[0], out[1], im, source, kpts=out[4])
+
+    def postprocess(self, boxes, count, img, source, kpts=None):
+        n = count.tolist()  # (the one host sync of the batch)
+        boxes, kpts = boxes.clone(), kpts.clone()
+        names = self.model.names
+        results = []
+        same = self._orig is None or all(tuple(o.shape[:2]) == tuple(img.shape[2:]) for o in self._orig)
+        if same:  # gain 1, pad 0: one clip (and one rounding of the boxes) over the whole batch
+            ops.clip_boxes(boxes, img.shape[2:])
+            boxes[..., :4] = boxes[..., :4].round()
+            ops.clip_coords(kpts, img.shape[2:])
+        for i in range(len(n)):
+            det, kp = boxes[i, : n[i]], kpts[i, : n[i]]
+            orig = self._orig[i] if self._orig is not None else None
+            if not same:
+                det[:, :4] = ops.scale_boxes(img.shape[2:], det[:, :4], orig.shape).round()
+                kp = ops.scale_coords(img.shape[2:], kp, orig.shape)
+            r = Results(orig, path=f"image{i}.jpg", names=names, boxes=det, keypoints=kp)
+            if orig is None:
+                r.orig_shape = tuple(img.shape[2:])
+                r.boxes.orig_shape = r.keypoints.orig_shape = r.orig_shape
+            results.append(r)
+        return results

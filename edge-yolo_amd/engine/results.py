@@ -137,13 +137,57 @@ class OBB:
         return len(self.data)
 
 
+class Keypoints:
+    """(n,K,2) or (n,K,3) keypoints [x, y(, confidence)] in original-image pixels (reference :1254-1375).  Points whose confidence is below
+    0.5 get x = y = 0, in the tensor handed in (the reference's constructor writes in place too)."""
+
+    def __init__(self, keypoints, orig_shape):
+        if keypoints.ndim == 2:
+            keypoints = keypoints[None, :]
+        if keypoints.shape[2] == 3:  # x, y, conf
+            mask = keypoints[..., 2] < 0.5  # points with conf < 0.5 (not visible)
+            keypoints[..., :2][mask] = 0
+        self.data = keypoints
+        self.orig_shape = orig_shape
+        self.has_visible = self.data.shape[-1] == 3
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        return self.data[..., :2]
+
+    @property
+    def xyn(self):
+        xy = self.xy.clone() if isinstance(self.xy, torch.Tensor) else np.copy(self.xy)
+        xy[..., 0] /= self.orig_shape[1]
+        xy[..., 1] /= self.orig_shape[0]
+        return xy
+
+    @property
+    def conf(self):
+        return self.data[..., 2] if self.has_visible else None
+
+    def cpu(self):
+        return self if isinstance(self.data, np.ndarray) else Keypoints(self.data.cpu(), self.orig_shape)
+
+    def numpy(self):
+        return self if isinstance(self.data, np.ndarray) else Keypoints(self.data.cpu().numpy(), self.orig_shape)
+
+    def __len__(self):
+        return len(self.data)
+
+
 class Results:
-    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None, obb=None):
+    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None, obb=None, keypoints=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_img.shape[:2]) if orig_img is not None and hasattr(orig_img, "shape") and orig_img.ndim == 3 else None
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
         self.masks = Masks(masks, self.orig_shape) if masks is not None else None
         self.obb = OBB(obb, self.orig_shape) if obb is not None else None
+        self.keypoints = Keypoints(keypoints, self.orig_shape) if keypoints is not None else None
         self.names = names
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}

@@ -371,3 +371,185 @@ class SegmentationValidator(DetectionValidator):
 
     def update(self, images, labels):
         raise NotImplementedError("SegmentationValidator: the (images, labels) convenience of the detect task carries no masks; call it with batches")
+
+
+class PoseValidator(DetectionValidator):
+    """Validation loop for the pose task, mirroring the reference's models/yolo/pose/val.py (`init_metrics` :77-84, `_prepare_batch` :86-96,
+    `_prepare_pred` :98-104, `update_metrics` :106-157, `_process_batch` :159-197) with PoseMetrics.
+
+    Device work per batch: the forward WITHOUT the (B, nk, A) keypoint decode (Pose.forward(decode_kpts=False)), validation-mode multi-label
+    NMS on the boxes and classes, the keypoints of the kept rows by anchor index (`ey_kpts_decode_rows`), their scaling to the original
+    images as one expression over the batch, and the OKS of ALL images in one `ey_kpt_iou` call.  The host gets the kept rows and the
+    [gt x pred] matrices in one copy each; matching and AP run in numpy like the detect task.
+
+    batch["keypoints"]: (M_total, K, ndim) normalised to the network input, gathered per image through batch_idx.  sigma = OKS_SIGMA for
+    kpt_shape [17, 3], else 1/K; kpt_shape comes from the model's head (datasets are not part of this build).  Host predictions
+    (`update_metrics((rows, kpts), batch)` with numpy arrays / CPU tensors) go through the numpy restatement of kpt_iou: the route the CPU
+    tests take.  save_json, save_txt and plots are not built."""
+
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, save_json=False, save_txt=False,
+                 plots=False):
+        for name, on in (("save_json", save_json), ("save_txt", save_txt), ("plots", plots)):
+            if on:
+                raise NotImplementedError(f"PoseValidator: {name}=True is not built (COCO json / txt export and plots)")
+        self.keep_outputs = False  # True: update_metrics appends (rows (n,6), keypoints (n,K,ndim) in input pixels) per image to self.kept, on the host
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+
+    # ---- reference pose/val.py:77-84
+    def init_metrics(self):
+        super().init_metrics()
+        self.kpt_shape = [int(v) for v in self.model.model[-1].kpt_shape]
+        nkpt = self.kpt_shape[0]
+        self.sigma = metrics.OKS_SIGMA if self.kpt_shape == [17, 3] else np.ones(nkpt) / nkpt
+        self.metrics = metrics.PoseMetrics()
+        self.stats = dict(tp_p=[], tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
+        self.results_dict = dict(zip(metrics.POSE_KEYS + ["fitness"], [0.0] * 11))
+        self.pose = None
+        self.kept = []
+
+    # ---- reference pose/val.py:64-75 + the keypoints of the kept rows: (rows (n_i, 6) per image, keypoints (B, max_det, K, ndim) in input pixels)
+    def postprocess(self, preds):
+        from ..nn import _ops
+        y, (_, maps) = preds
+        head = self.model.model[-1]
+        boxes, count, index = ops.nms_device(y, self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc, multi_label=True)
+        kpts = _ops.kpts_decode_rows(head.kpt_levels(maps), head.kpt_shape, index, count)
+        n = count.tolist()  # the one D2H sync of the NMS
+        return [boxes[i, :n[i]] for i in range(len(n))], kpts
+
+    def _forward(self, img):
+        head = self.model.model[-1]
+        was = head.decode_kpts
+        head.decode_kpts = False
+        try:
+            return self.model(img)
+        finally:
+            head.decode_kpts = was
+
+    # ---- reference pose/val.py:86-96
+    def _prepare_batch(self, si, batch):
+        pbatch = super()._prepare_batch(si, batch)
+        idx = _np(batch["batch_idx"]).reshape(-1) == si
+        kpts = torch.as_tensor(_np(batch["keypoints"]), dtype=torch.float32)[torch.as_tensor(idx)].clone()
+        h, w = pbatch["imgsz"]
+        kpts[..., 0] *= w
+        kpts[..., 1] *= h
+        pbatch["kpts"] = ops.scale_coords(pbatch["imgsz"], kpts, pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"]).numpy()
+        return pbatch
+
+    # ---- reference pose/val.py:159-197
+    def _process_batch(self, detections, gt_bboxes, gt_cls, pred_kpts=None, gt_kpts=None, iou=None):
+        """pred_kpts / gt_kpts given: OKS through metrics.kpt_iou (host arrays: numpy), or `iou` when the caller computed the batch's matrices
+        in one launch already; otherwise box IoU."""
+        if pred_kpts is None and gt_kpts is None and iou is None:
+            return super()._process_batch(detections, gt_bboxes, gt_cls)
+        if iou is None:
+            area = (ops.xyxy2xywh(torch.as_tensor(gt_bboxes))[:, 2:].prod(1) * 0.53).numpy()  # 0.53: the COCO keypoint evaluation's box-to-area factor
+            iou = _np(metrics.kpt_iou(gt_kpts, pred_kpts, area, self.sigma))
+        return metrics.match_predictions(detections[:, 5], gt_cls, iou, self.iouv)
+
+    def _scale_pred_kpts(self, kpts, pbatches):
+        """pose/val.py:98-104 for every image at once, on the tensor's device: (B, max_det, K, ndim) input pixels -> original-image pixels
+        (scale_coords per image: - pad, / gain, clip), one expression over the batch."""
+        B = kpts.shape[0]
+        geo = np.zeros((B, 5), np.float32)
+        for i, pb in enumerate(pbatches):
+            if pb["ratio_pad"] is None:
+                gain = min(pb["imgsz"][0] / pb["ori_shape"][0], pb["imgsz"][1] / pb["ori_shape"][1])
+                pad = (pb["imgsz"][1] - pb["ori_shape"][1] * gain) / 2, (pb["imgsz"][0] - pb["ori_shape"][0] * gain) / 2
+            else:
+                gain, pad = pb["ratio_pad"][0][0], pb["ratio_pad"][1]
+            geo[i] = [pad[0], pad[1], gain, pb["ori_shape"][1], pb["ori_shape"][0]]
+        g = torch.from_numpy(geo).to(kpts.device).view(B, 5, 1, 1)
+        out = kpts.clone()
+        zero = torch.zeros((), dtype=torch.float32, device=kpts.device)
+        out[..., 0] = torch.minimum(torch.maximum((kpts[..., 0] - g[:, 0]) / g[:, 2], zero), g[:, 3])
+        out[..., 1] = torch.minimum(torch.maximum((kpts[..., 1] - g[:, 1]) / g[:, 2], zero), g[:, 4])
+        return out
+
+    # ---- reference pose/val.py:106-157
+    def update_metrics(self, preds, batch):
+        """preds: postprocess's (rows per image, keypoints).  keypoints: a (B, max_det, K, ndim) tensor (device: the one-launch route) or a
+        list of per-image (n_i, K, ndim) host arrays, in network-input pixels."""
+        from ..nn import _ops
+        rows, kpts = preds
+        B = len(rows)
+        n = [int(r.shape[0]) for r in rows]
+        pbatches = [self._prepare_batch(si, batch) for si in range(B)]
+        nl = [len(pb["cls"]) for pb in pbatches]
+        K = self.kpt_shape[0]
+        areas = [(ops.xyxy2xywh(torch.from_numpy(pb["bbox"]))[:, 2:].prod(1) * 0.53).numpy() if nl[i] else np.zeros(0, np.float32) for i, pb in enumerate(pbatches)]
+        on_device = torch.is_tensor(kpts) and kpts.is_cuda
+        ious = [None] * B
+        if on_device:
+            scaled = self._scale_pred_kpts(kpts, pbatches)
+            if self.keep_outputs:
+                host = kpts.cpu().numpy()
+                self.kept += [(_np(rows[i]).copy(), host[i, :n[i]]) for i in range(B)]
+            if any(a and b for a, b in zip(n, nl)):
+                dev = kpts.device
+                keep = torch.arange(kpts.shape[1], device=dev)[None, :] < torch.tensor(n, device=dev)[:, None]
+                pk = scaled[keep].contiguous()  # (sum n, K, ndim), image after image
+                gk = torch.from_numpy(np.concatenate([pb["kpts"].reshape(-1, K, 3) for pb in pbatches], 0)).to(dev)
+                ar = torch.from_numpy(np.concatenate(areas).astype(np.float32)).to(dev)
+                sg = torch.from_numpy(np.asarray(self.sigma, np.float32)).to(dev)
+                pred_off, gt_off = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(nl)])
+                out, off = _ops.kpt_iou(pk, pred_off, gk, gt_off, ar, sg)
+                host = out.cpu().numpy()  # the one D2H copy of the batch's matrices
+                ious = [host[off[i]: off[i] + nl[i] * n[i]].reshape(nl[i], n[i]) if n[i] and nl[i] else None for i in range(B)]
+        for si, pred in enumerate(rows):
+            self.seen += 1
+            pred = _np(pred).astype(np.float32).reshape(-1, 6)
+            npr = pred.shape[0]
+            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), tp=np.zeros((npr, self.niou), bool), tp_p=np.zeros((npr, self.niou), bool))
+            pbatch = pbatches[si]
+            cls, bbox = pbatch["cls"], pbatch["bbox"]
+            stat["target_cls"] = cls
+            stat["target_img"] = np.unique(cls)
+            if npr == 0:
+                if nl[si]:
+                    for k in self.stats:
+                        self.stats[k].append(stat[k])
+                continue
+            if self.single_cls:
+                pred = pred.copy()
+                pred[:, 5] = 0
+            predn = DetectionValidator._prepare_pred(self, pred, pbatch)
+            stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
+            if nl[si]:
+                stat["tp"] = self._process_batch(predn, bbox, cls)
+                if on_device:
+                    stat["tp_p"] = self._process_batch(predn, bbox, cls, iou=ious[si])
+                else:
+                    pk = torch.as_tensor(_np(kpts[si]), dtype=torch.float32)[:npr].reshape(npr, K, -1).clone()
+                    ops.scale_coords(pbatch["imgsz"], pk, pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"])
+                    stat["tp_p"] = self._process_batch(predn, bbox, cls, pk.numpy(), pbatch["kpts"])
+            for k in self.stats:
+                self.stats[k].append(stat[k])
+
+    # ---- reference detect/val.py:179-188 + PoseMetrics.process / results_dict
+    def get_stats(self):
+        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k in ("tp", "tp_p") else 0)) for k, v in self.stats.items()}
+        self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc)
+        self.nt_per_image = np.bincount(stats["target_img"].astype(int), minlength=self.nc)
+        stats.pop("target_img", None)
+        if len(stats["tp"]) and stats["tp"].any():  # (the reference tests the box matches only, detect/val.py:186)
+            self.metrics.process(**stats)
+            self.box, self.pose = self.metrics.box, self.metrics.pose
+        self.results_dict = self.metrics.results_dict
+        return self.results_dict
+
+    @torch.no_grad()
+    def __call__(self, dataloader):
+        """dataloader: iterable of batch dicts in DetectionValidator's format plus "keypoints" (see the class docstring).  Returns the results
+        dict (reference PoseMetrics.results_dict: five box keys, five pose keys, fitness)."""
+        self.init_metrics()
+        for batch in dataloader:
+            batch = self.preprocess(batch)
+            with torch.cuda.device(self.device):
+                preds = self.postprocess(self._forward(batch["img"]))
+                self.update_metrics(preds, batch)
+        return self.get_stats()
+
+    def update(self, images, labels):
+        raise NotImplementedError("PoseValidator: the (images, labels) convenience of the detect task carries no keypoints; call it with batches")

@@ -1388,3 +1388,90 @@ def nms_rotated(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic,
                                        class_mask.data_ptr() if class_mask is not None else None, rows.data_ptr(), count.data_ptr(), index.data_ptr(),
                                        ws.data_ptr(), nbytes, L.stream()), "ey_nms_rotated")
     return rows, count, index
+
+
+def _kpt_levels(levels, kpt_shape, what):
+    """levels: list of (kpt map (B,nk,H,W) NHWC view, stride, a_off) -> the ctypes arrays both keypoint decode kernels take."""
+    n = len(levels)
+    m0 = levels[0][0]
+    L.require_device(m0, what)
+    _no_block(what)
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    for lv in levels:
+        if lv[0].dim() != 4 or lv[0].shape[1] != nkpt * ndim or lv[0].dtype != m0.dtype or lv[0].shape[0] != m0.shape[0]:
+            raise ValueError(f"{what}: every level must be a (B, {nkpt * ndim}, H, W) map of one dtype, got {tuple(lv[0].shape)} {lv[0].dtype}")
+    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
+    return (L.dtype_code(m0.dtype), m0.shape[0], n, IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels]), FA(*[float(lv[1]) for lv in levels]),
+            PA(*[lv[0].data_ptr() for lv in levels]), IA(*[L.cstride(lv[0]) for lv in levels]), nkpt, ndim), IA(*[int(lv[2]) for lv in levels])
+
+
+def kpts_decode_levels(levels, kpt_shape, out):
+    """levels: list (<= 4) of (kpt logits (B,nk,H,W) NHWC view, stride, a_off); out: fp32 (B, nk, A) view whose rows are contiguous (e.g.
+    pred[:, 4+nc:] of the prediction tensor) -> the decoded keypoint rows of every level in ONE launch (ey_kpts_decode_levels)."""
+    head, offs = _kpt_levels(levels, kpt_shape, "kpts_decode_levels")
+    B, nk = head[1], head[8] * head[9]
+    if out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != B or out.shape[1] != nk or out.stride(2) != 1 or out.stride(1) != out.shape[2] or (
+            B > 1 and out.stride(0) < nk * out.shape[2]):
+        raise ValueError(f"kpts_decode_levels: out must be a float32 (B, {nk}, A) tensor with contiguous rows, got {tuple(out.shape)} {out.dtype} strides {out.stride()}")
+    A = out.shape[2]
+    with _tr("kpts_decode_levels_kernel", sum(_nb(lv[0]) for lv in levels) + 4 * B * nk * A, 3.0 * B * nk * A, note=f"{len(levels)} levels"):
+        L.check(L.lib().ey_kpts_decode_levels(*head, out.data_ptr(), out.stride(0) if B > 1 else nk * A, A, offs, L.stream()), "ey_kpts_decode_levels")
+    return out
+
+
+def kpts_decode_rows(levels, kpt_shape, index, count, A=None, out=None):
+    """The keypoints of the rows NMS kept (ey_kpts_decode_rows): levels as for kpts_decode_levels, index int32 (B,max_det) anchors, count
+    int32 (B,) -> fp32 (B, max_det, nkpt, ndim) (`out`, or a new tensor); rows beyond the count or without a valid anchor are zeros.  A: the
+    anchor count of the prediction (default: the end of the last level).  No host synchronisation."""
+    head, offs = _kpt_levels(levels, kpt_shape, "kpts_decode_rows")
+    B, nkpt, ndim = head[1], head[8], head[9]
+    dev = levels[0][0].device
+    if index.dtype != torch.int32 or count.dtype != torch.int32 or index.dim() != 2 or index.shape[0] != B or tuple(count.shape) != (B,) or not index.is_contiguous() \
+            or not count.is_contiguous() or index.device != dev or count.device != dev or index.shape[1] < 1:
+        raise ValueError(f"kpts_decode_rows: index must be a contiguous int32 (B, max_det) tensor and count int32 (B,) on {dev}")
+    if A is None:
+        A = max(int(lv[2]) + lv[0].shape[2] * lv[0].shape[3] for lv in levels)
+    max_det = index.shape[1]
+    if out is None:
+        out = torch.empty((B, max_det, nkpt, ndim), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, max_det, nkpt, ndim) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"kpts_decode_rows: out must be a contiguous float32 {(B, max_det, nkpt, ndim)} tensor on {dev}")
+    with _tr("kpts_decode_rows_kernel", _nb(index, out), 3.0 * out.numel()):
+        L.check(L.lib().ey_kpts_decode_rows(*head, int(A), offs, max_det, index.data_ptr(), count.data_ptr(), out.data_ptr(), L.stream()), "ey_kpts_decode_rows")
+    return out
+
+
+def kpt_iou(pred, pred_off, gt, gt_off, area, sigma, out_off=None, out=None):
+    """OKS of a batch (ey_kpt_iou): pred fp32 (N_total,K,ndim) and gt fp32 (M_total,K,3) grouped by image through the host lists pred_off /
+    gt_off (B+1 entries from 0), area fp32 (M_total,), sigma fp32 (K,).  Image b's row-major [M_b][N_b] matrix lands at element out_off[b] of
+    the flat fp32 buffer `out` (packed one after the other by default).  -> (out, out_off)."""
+    L.require_device(pred, "kpt_iou")
+    _no_block("kpt_iou")
+    pred_off, gt_off = [int(v) for v in pred_off], [int(v) for v in gt_off]
+    B = len(pred_off) - 1
+    if B < 0 or len(gt_off) != B + 1 or pred_off[0] != 0 or gt_off[0] != 0:
+        raise ValueError("kpt_iou: pred_off and gt_off must have B+1 entries starting at 0")
+    dev = pred.device
+    if pred.dim() != 3 or gt.dim() != 3 or gt.shape[2] != 3 or pred.shape[1] != gt.shape[1] or pred.shape[0] < pred_off[-1] or gt.shape[0] < gt_off[-1]:
+        raise ValueError(f"kpt_iou: expected pred (N,K,ndim) and gt (M,K,3) with N >= {pred_off[-1]}, M >= {gt_off[-1]}, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    K, ndim = int(pred.shape[1]), int(pred.shape[2])
+    for name, t, n in (("pred", pred, None), ("gt", gt, None), ("area", area, gt_off[-1]), ("sigma", sigma, K)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or (n is not None and (t.dim() != 1 or t.shape[0] < n)):
+            raise ValueError(f"kpt_iou: {name} must be a contiguous float32 tensor on {dev}" + (f" with {n} entries" if n is not None else ""))
+    sizes = [(gt_off[b + 1] - gt_off[b]) * (pred_off[b + 1] - pred_off[b]) for b in range(B)]
+    if out_off is None:
+        out_off = [0] * B
+        for b in range(1, B):
+            out_off[b] = out_off[b - 1] + sizes[b - 1]
+    out_off = [int(v) for v in out_off]
+    end = max([o + s for o, s in zip(out_off, sizes) if s] + [0])
+    if out is None:
+        out = torch.empty(end, dtype=torch.float32, device=dev)
+    if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < end or len(out_off) != B \
+            or any(o < 0 for o, s in zip(out_off, sizes) if s):
+        raise ValueError(f"kpt_iou: out must be a flat contiguous float32 buffer of at least {end} elements on {dev}")
+    IA, LA = ctypes.c_int * (B + 1), ctypes.c_long * max(B, 1)
+    with _tr("kpt_iou_kernel", _nb(pred, gt) + 4 * sum(sizes), 12.0 * K * sum(sizes), note=f"B{B} N{pred_off[-1]} M{gt_off[-1]} K{K}"):
+        L.check(L.lib().ey_kpt_iou(B, K, ndim, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off), area.data_ptr(), sigma.data_ptr(), LA(*out_off),
+                                   out.data_ptr(), L.stream()), "ey_kpt_iou")
+    return out, out_off

@@ -1,4 +1,4 @@
-"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
+"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `Pose` (:402-451), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
@@ -10,11 +10,11 @@ import torch
 import torch.nn as nn
 
 from .block import DFL, Proto
-from .conv import Conv, DWConv, _Packed, fold_bn
+from .conv import Conv, DWConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "Segment", "OBB", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+__all__ = ("Detect", "Segment", "OBB", "Pose", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
 
 
 class _Plain(_Packed):
@@ -498,6 +498,95 @@ class OBB(Detect):
         pred = torch.empty((B, 4 + self.nc + 1, A), dtype=torch.float32, device=xs[0].device)
         ops.obb_decode_levels([(box, cls, angs[i], st, off) for i, (box, cls, st, _, off) in enumerate(levels)], pred)
         return pred if self.export else (pred, (raw, pred[:, 4 + self.nc:]))
+
+
+class Pose(Detect):
+    """YOLO Pose head (reference head.py:402-451): Detect plus one keypoint tower `cv4` per pyramid level (`nk` = nkpt * ndim channels).
+    Boxes and classes run through Detect.forward unchanged (fused decode and NMS candidates included); the keypoint towers write one NHWC
+    map per level.  Predict and validation decode the keypoints of the rows NMS kept (ey_kpts_decode_rows reads the maps by anchor index);
+    the reference's eval-mode return decodes every anchor with one ey_kpts_decode_levels launch."""
+
+    def __init__(self, nc=80, kpt_shape=(17, 3), ch=()):
+        super().__init__(nc, ch)
+        self.kpt_shape = kpt_shape  # number of keypoints, number of dims (2 for x,y or 3 for x,y,visible)
+        self.nk = kpt_shape[0] * kpt_shape[1]
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+
+    def kpt_maps(self, xs):
+        """-> per-level keypoint logit maps [(B,nk,H_l,W_l) NHWC, pixel stride padded to a multiple of 8 channels], on the caller's stream."""
+        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        cpad = (self.nk + 7) // 8 * 8  # pixel stride kept 16-byte aligned for any nk
+        maps = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.nk] for t in xs]
+        for i, t in enumerate(xs):
+            self._kpt_tower(self.cv4[i], t, maps[i])
+        return maps
+
+    def _kpt_tower(self, c, t, out):
+        """Conv(x, c4, 3) -> Conv(c4, c4, 3) -> nn.Conv2d(c4, nk, 1) with c4 = max(x // 4, nk).  The MFMA conv reads sources whose channel
+        count is a multiple of 8; c4 = 51 is not, and the second and third conv would take the generic direct kernel (measured 8.8 ms
+        instead of 0.06 ms for the 80x80 level at batch 32).  So the tower runs on c4 rounded up to a multiple of 8: the weights are
+        packed with zero rows / zero input columns for the extra channels, which therefore hold SiLU(0) = 0 and add 0 to every sum."""
+        c4 = c[0].conv.out_channels
+        pad = -c4 % 8
+        plain = all(isinstance(m, Conv) and m.conv.kernel_size == (3, 3) and m.conv.stride == (1, 1) and m.conv.padding == (1, 1) and m.conv.groups == 1
+                    and m.conv.dilation == (1, 1) for m in (c[0], c[1]))
+        if not pad or not plain or c[2].kernel_size != (1, 1) or c[2].groups != 1:
+            return self._tail(c[2]).run(c[1](c[0](t)), out)
+        F = nn.functional
+
+        def padded(fn, po, pi):  # (w (O,I,k,k), b (O,)) -> po zero output channels, pi zero input channels appended
+            w, b = fn()
+            return F.pad(w, (0, 0, 0, 0, 0, pi, 0, po)), F.pad(b, (0, po))
+
+        h = ops.conv2d(c[0], [t], lambda: padded(c[0].folded, pad, 0), 3, 1, 1, _act_code(c[0].act), tag="kpad")
+        h = ops.conv2d(c[1], [h], lambda: padded(c[1].folded, pad, pad), 3, 1, 1, _act_code(c[1].act), tag="kpad")
+        return ops.conv2d(self._tail(c[2]), [h], lambda: padded(lambda: fold_bn(c[2].weight, c[2].bias, None), 0, pad), 1, 1, 0, L.ACT_NONE, out=out, tag="kpad")
+
+    def kpt_levels(self, maps):
+        """the keypoint maps as the level list of _ops.kpts_decode_levels / kpts_decode_rows: [(map, stride, first anchor)]."""
+        if getattr(self, "_stride_f", None) is None:
+            self._stride_f = [float(s) for s in self.stride]
+        levels, a_off = [], 0
+        for i, m in enumerate(maps):
+            levels.append((m, self._stride_f[i], a_off))
+            a_off += m.shape[2] * m.shape[3]
+        return levels
+
+    decode_kpts = True  # instance attribute (or forward keyword): False leaves the (B,nk,A) decode out of the nms=None return, see forward
+
+    def forward(self, x, nms=None, decode_kpts=None):
+        """nms=None: the reference's eval-mode return (head.py:414-422): (cat([y, pred_kpt], 1) (B,4+nc+nk,A) fp32, (raw maps, kpt (B,nk,A)
+        logits)); the keypoint rows are decoded straight into the prediction tensor.  decode_kpts=False (validation; keyword, or the head
+        attribute of that name): (y (B,4+nc,A), (raw maps, [keypoint map per level])) -- the (B,nk,A) decode is left out,
+        ey_kpts_decode_rows serves the kept rows.
+        nms=dict(...) (predict pipelines, see Detect.forward): (Candidates, (raw maps, [keypoint map per level]))."""
+        if self.training:
+            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
+        if self.end2end:
+            raise NotImplementedError("Pose: end2end heads are not built")
+        if self.kpt_shape[1] not in (2, 3) or self.nk > 256 or len(x) > 4:
+            raise NotImplementedError(f"Pose: kpt_shape={tuple(self.kpt_shape)} on {len(x)} levels (the keypoint kernels are built for ndim 2 or 3, nk <= 256, <= 4 levels)")
+        if getattr(self, "defer_decode", False):
+            raise NotImplementedError("Pose: pipelined (deferred) decode is not built for the pose task")
+        xs = [L.as_nhwc(t) for t in x]
+        maps = self.kpt_maps(xs)
+        if nms is not None:
+            cand, raw = Detect.forward(self, list(xs), nms=nms)
+            return cand, (raw, maps)
+        if not (self.decode_kpts if decode_kpts is None else decode_kpts):
+            y, raw = Detect.forward(self, list(xs))
+            return y, (raw, maps)
+        levels, raw = Detect.forward(self, list(xs), towers_only=True)
+        B, A, no = xs[0].shape[0], sum(t.shape[2] * t.shape[3] for t in xs), 4 + self.nc
+        pred = torch.empty((B, no + self.nk, A), dtype=torch.float32, device=xs[0].device)
+        if B == 1:  # the box / class rows of one image are contiguous: the Detect decode writes them in place
+            self._decode(levels, pred[:, :no])
+        else:
+            pred[:, :no].copy_(self._decode(levels, torch.empty((B, no, A), dtype=torch.float32, device=pred.device)))
+        ops.kpts_decode_levels(self.kpt_levels(maps), self.kpt_shape, pred[:, no:])
+        kpt = torch.cat([m.flatten(2) for m in maps], 2)  # (layout only: the reference's view + cat of the logits, head.py:417)
+        return pred if self.export else (pred, (raw, kpt))
 
 
 class GF2Detect(Detect):

@@ -1,6 +1,6 @@
 """YAML -> model graph and the graph executor, mirroring the reference's ultralytics/nn/tasks.py for the detect
 path: `parse_model` (:958-1147), `yaml_model_load` (:1150-1163), `guess_model_scale` (:1166-1181),
-`guess_model_task` (:1184-1255), `BaseModel._predict_once/fuse` (:152-242), `DetectionModel` (:320-370), `OBBModel` (:416-428), `SegmentationModel` (:472-480).
+`guess_model_task` (:1184-1255), `BaseModel._predict_once/fuse` (:152-242), `DetectionModel` (:320-370), `OBBModel` (:416-428), `PoseModel` (:440-451), `SegmentationModel` (:472-480).
 """
 import ast
 import contextlib
@@ -14,7 +14,7 @@ import yaml
 
 from . import _ops as ops
 from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, SPPF, Segment, Upsample)
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
@@ -23,7 +23,7 @@ from ..utils.ops import make_divisible
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
 _CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
 _REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
-_HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB}
+_HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose}
 
 
 def guess_model_scale(model_path):
@@ -51,7 +51,8 @@ def yaml_model_load(path):
 def guess_model_task(model):
     """Reference tasks.py:1184-1255 reduced to this build's scope.  The reference only recognises heads whose
     lower-cased name contains 'detect' and raises for GFLHeadv2_uniH YAMLs unless task='detect' is passed
-    (SURVEY §3 quirk); here every registered head but Segment ("segment", reference :1206-1207) and OBB ("obb", :1210-1211) is a detect head."""
+    (SURVEY §3 quirk); here every registered head but Segment ("segment", reference :1206-1207) OBB ("obb", :1210-1211) and Pose ("pose", :1208-1209)
+    is a detect head."""
     cfg = model if isinstance(model, dict) else None
     if cfg is None and isinstance(model, (str, Path)):
         with contextlib.suppress(Exception):
@@ -62,14 +63,18 @@ def guess_model_task(model):
             return "segment"
         if m == "OBB":
             return "obb"
+        if m == "Pose":
+            return "pose"
         if m in {h.__name__ for h in _HEADS}:
             return "detect"
-        raise NotImplementedError(f"head '{m}': only the detect, segment and obb tasks are built")
+        raise NotImplementedError(f"head '{m}': only the detect, segment, obb and pose tasks are built")
     if isinstance(model, nn.Module):  # reference :1226-1240: look at the modules
         if any(isinstance(mod, Segment) for mod in model.modules()):
             return "segment"
         if any(isinstance(mod, OBB) for mod in model.modules()):
             return "obb"
+        if any(isinstance(mod, Pose) for mod in model.modules()):
+            return "pose"
     return "detect"
 
 
@@ -78,7 +83,7 @@ def parse_model(d, ch, verbose=False):
     legacy = True
     max_channels = float("inf")
     nc, act, scales = (d.get(x) for x in ("nc", "activation", "scales"))
-    depth, width = (d.get(x, 1.0) for x in ("depth_multiple", "width_multiple"))
+    depth, width, kpt_shape = (d.get(x, 1.0) for x in ("depth_multiple", "width_multiple", "kpt_shape"))  # (kpt_shape: a Pose row names it, reference :966)
     scale = d.get("scale")
     if scales:
         if not scale:
@@ -505,6 +510,19 @@ class OBBModel(DetectionModel):
 
     def __init__(self, cfg="yolo11n-obb.yaml", ch=3, nc=None, verbose=False):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+
+
+class PoseModel(DetectionModel):
+    """Pose model built from a YAML (reference tasks.py:440-451); data_kpt_shape overrides the YAML's kpt_shape.  augment=True warns and runs
+    single-scale, as for SegmentationModel."""
+
+    def __init__(self, cfg="yolo11n-pose.yaml", ch=3, nc=None, data_kpt_shape=(None, None), verbose=False):
+        if not isinstance(cfg, dict):
+            cfg = yaml_model_load(cfg)
+        if any(data_kpt_shape) and list(data_kpt_shape) != list(cfg["kpt_shape"]):
+            cfg["kpt_shape"] = data_kpt_shape
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        self.kpt_shape = self.model[-1].kpt_shape  # (the reference's AutoBackend exposes it as model.kpt_shape: pose/predict.py:51)
 
 
 def torch_safe_load_state(path):

@@ -7,7 +7,10 @@ multi_label, models/yolo/detect/val.py:92-102) is device work and goes through `
 Segment validation adds `mask_iou` (utils/metrics.py:137-153; device tensors run on `ey_mask_iou`, host arrays on a numpy restatement with
 the same bits), the host form of the overlap_mask expansion (models/yolo/segment/val.py:206-209) and `SegmentMetrics` (:909-1029).
 
-`batch_probiou` (utils/metrics.py:244-275) is the pairwise ProbIoU of oriented boxes on `ey_probiou` (device tensors only)."""
+`batch_probiou` (utils/metrics.py:244-275) is the pairwise ProbIoU of oriented boxes on `ey_probiou` (device tensors only).
+
+Pose validation adds `OKS_SIGMA` (:17-20), `kpt_iou` (:156-175; device tensors on `ey_kpt_iou`, host operands on a numpy restatement) and
+`PoseMetrics` (:1051-1176)."""
 import numpy as np
 
 
@@ -170,6 +173,41 @@ def batch_probiou(obb1, obb2, eps=1e-7):
     return out if o1.is_cuda else out.to(o1.device)
 
 
+# per-keypoint falloff constants of the COCO keypoint evaluation (reference utils/metrics.py:17-20)
+OKS_SIGMA = np.array([0.26, 0.25, 0.25, 0.35, 0.35, 0.79, 0.79, 0.72, 0.72, 0.62, 0.62, 1.07, 1.07, 0.87, 0.87, 0.89, 0.89]) / 10.0
+
+
+def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
+    """Object keypoint similarity, reference signature (utils/metrics.py:156-175): kpt1 (N,K,3) ground truth, kpt2 (M,K,2 or 3) predictions,
+    area (N,) of the ground-truth boxes, sigma (K,) -> (N,M) fp32.  Device tensors run one ey_kpt_iou call and return a device tensor; host
+    arrays / CPU tensors take the numpy restatement below (the reference's fp32 expression, operation by operation) and return an ndarray."""
+    import torch
+    if torch.is_tensor(kpt1) and kpt1.is_cuda:
+        from ..nn import _ops
+        if abs(float(eps) - 1e-7) > 1e-20:
+            raise NotImplementedError("kpt_iou: the kernel is built for the reference's eps=1e-7")
+        dev = kpt1.device
+        N, M = kpt1.shape[0], kpt2.shape[0]
+        if N == 0 or M == 0:
+            return torch.zeros((N, M), dtype=torch.float32, device=dev)
+        sg = torch.as_tensor(np.asarray(_host(sigma), np.float32)).to(dev) if not (torch.is_tensor(sigma) and sigma.is_cuda) else sigma.float().contiguous()
+        with torch.cuda.device(dev):
+            out, _ = _ops.kpt_iou(kpt2.to(dev).float().contiguous(), [0, M], kpt1.float().contiguous(), [0, N], torch.as_tensor(area).to(dev).float().contiguous(), sg)
+        return out.view(N, M)
+    g, p, a = (np.asarray(_host(t), np.float32) for t in (kpt1, kpt2, area))
+    sg = np.asarray(_host(sigma), np.float32)
+    if g.ndim != 3 or p.ndim != 3 or g.shape[2] != 3 or p.shape[2] < 2 or g.shape[1] != p.shape[1] or sg.shape != (g.shape[1],) or a.shape != (g.shape[0],):
+        raise ValueError(f"kpt_iou: expected (N,K,3), (M,K,2|3), (N,), (K,), got {g.shape}, {p.shape}, {a.shape}, {sg.shape}")
+    d = (g[:, None, :, 0] - p[None, :, :, 0]) ** 2 + (g[:, None, :, 1] - p[None, :, :, 1]) ** 2  # (N, M, K)
+    vis = g[..., 2] != 0
+    e = d / ((np.float32(2) * sg) ** 2 * (a[:, None, None] + np.float32(eps)) * np.float32(2))
+    return ((np.exp(-e) * vis[:, None].astype(np.float32)).sum(-1, dtype=np.float32) / (vis.sum(-1)[:, None].astype(np.float32) + np.float32(eps))).astype(np.float32)
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else t
+
+
 def expand_index_masks(index_map, nl):
     """Host form of the reference's overlap_mask expansion (models/yolo/segment/val.py:206-209): one (h, w) index map ->
     (nl, h, w) uint8, instance m = the pixels equal to m + 1.  (ey_mask_iou reads the map directly; this is for host masks.)"""
@@ -224,3 +262,25 @@ class SegmentMetrics:
     @property
     def results_dict(self):
         return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))
+
+
+POSE_KEYS = SEG_KEYS[:5] + [k.replace("(M)", "(P)") for k in SEG_KEYS[5:]]  # reference metrics.py:1130-1144
+
+
+class PoseMetrics(SegmentMetrics):
+    """Box and pose metrics side by side (reference PoseMetrics, metrics.py:1051-1176): SegmentMetrics with `pose` in the place of `seg`."""
+
+    def __init__(self):
+        self.box, self.pose = Metric(), Metric()
+
+    @property
+    def seg(self):
+        return self.pose
+
+    def process(self, tp, tp_p, conf, pred_cls, target_cls):
+        self.pose.update(ap_per_class(tp_p, conf, pred_cls, target_cls))
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls))
+
+    @property
+    def keys(self):
+        return list(POSE_KEYS)

@@ -48,6 +48,47 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xyw
     return clip_boxes(boxes, img0_shape)
 
 
+def xyxy2xywh(x):
+    """(..., 4) x1,y1,x2,y2 -> centre x, centre y, width, height (reference utils/ops.py:384-402)."""
+    y = torch.empty_like(x) if isinstance(x, torch.Tensor) else x.copy()
+    y[..., 0] = (x[..., 0] + x[..., 2]) / 2
+    y[..., 1] = (x[..., 1] + x[..., 3]) / 2
+    y[..., 2] = x[..., 2] - x[..., 0]
+    y[..., 3] = x[..., 3] - x[..., 1]
+    return y
+
+
+def clip_coords(coords, shape):
+    """Clip point coordinates (..., >= 2) to the image (h, w), in place (reference utils/ops.py:341-358)."""
+    if isinstance(coords, torch.Tensor):
+        coords[..., 0] = coords[..., 0].clamp(0, shape[1])
+        coords[..., 1] = coords[..., 1].clamp(0, shape[0])
+    else:  # numpy
+        coords[..., 0] = coords[..., 0].clip(0, shape[1])
+        coords[..., 1] = coords[..., 1].clip(0, shape[0])
+    return coords
+
+
+def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None, normalize=False, padding=True):
+    """Rescale point coordinates (x, y in the first two entries of the last axis) from img1_shape to img0_shape, in place (reference
+    utils/ops.py:740-772; unlike scale_boxes the padding is not rounded)."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    else:
+        gain, pad = ratio_pad[0][0], ratio_pad[1]
+    if padding:
+        coords[..., 0] -= pad[0]
+        coords[..., 1] -= pad[1]
+    coords[..., 0] /= gain
+    coords[..., 1] /= gain
+    coords = clip_coords(coords, img0_shape)
+    if normalize:
+        coords[..., 0] /= img0_shape[1]
+        coords[..., 1] /= img0_shape[0]
+    return coords
+
+
 _CLASS_TENSORS = {}
 
 

@@ -594,6 +594,33 @@ int ey_nms_rotated(int B, int nc, int A, const float* pred, float conf_thres, fl
                    const uint8_t* class_mask, float* out_rows, int32_t* out_count, int32_t* out_index, void* workspace, size_t workspace_bytes,
                    ey_stream_t stream);
 
+/* ---- Pose estimation (csrc/pose.hip).  Levels are described as for ey_obb_decode_levels: per level an NHWC map kpt [B,H,W,nkpt*ndim] of
+ *   `dtype` (logits of the cv4 towers) with its pixel stride, the level's stride and its first anchor a_off.  ndim is 2 (x, y) or 3
+ *   (x, y, visibility), nkpt*ndim <= 256, 1 to 4 levels: anything else is EY_EUNSUPPORTED before any launch.  Windows that are not 16-byte
+ *   aligned are read with scalar loads.
+ * ey_kpts_decode_levels: Pose.kpts_decode (ultralytics/nn/modules/head.py:446-451) for every level in ONE launch.  out fp32: rows
+ *   [nkpt*ndim][A_total] per image, images out_bstride elements apart (so it can write rows 4+nc.. of the prediction tensor in place).
+ *   Anchor with grid cell (gx, gy): x = (v*2 + gx) * stride, y = (v*2 + gy) * stride -- one rounding, bit for bit the reference's fp32
+ *   (v*2.0 + (anchor - 0.5)) * stride -- and sigmoid(v) for the third value.
+ * ey_kpts_decode_rows: the same decode for the rows NMS kept.  index int32 [B,max_det] = anchor of each row (as ey_nms / the candidate
+ *   NMS write it), count int32 [B]; out fp32 [B,max_det,nkpt,ndim].  Row r < count[b] with 0 <= index < A_total inside a level: that
+ *   pixel's channels, bit-identical to ey_kpts_decode_levels; every other row (beyond the count, negative index, index outside every level:
+ *   checked in the kernel before an address is formed) is zeros.  No host synchronisation, no allocation, no atomics: graph-capturable
+ *   and the same bytes run to run.
+ * ey_kpt_iou: utils/metrics.py::kpt_iou (:156-175, eps = 1e-7) for every image of a batch in ONE launch.  gt fp32 [gt_off[B]][K][3],
+ *   area fp32 [gt_off[B]], pred fp32 [pred_off[B]][K][ndim] (x and y are read), sigma fp32 [K]; pred_off / gt_off (B+1 entries from 0) and
+ *   out_off (B entries, in elements) are HOST arrays as for ey_mask_iou.  Image b's row-major [M_b][N_b] matrix (ground truth x prediction)
+ *   goes to out + out_off[b]; nothing else is written; images with M_b == 0 or N_b == 0 have none; B == 0 is valid.  fp32 in the reference's
+ *   order: d = dx^2 + dy^2, e = d / ((2 sigma)^2 * (area + eps) * 2), sum_k exp(-e) * (gt_v != 0) / (#visible + eps); a ground truth without a
+ *   visible keypoint gives exactly 0.  K <= 64, B <= 128, otherwise EY_EUNSUPPORTED. */
+int ey_kpts_decode_levels(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* kpt, const int* kpt_cstride,
+                          int nkpt, int ndim, float* out, long out_bstride, int A_total, const int* a_off, ey_stream_t stream);
+int ey_kpts_decode_rows(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* kpt, const int* kpt_cstride,
+                        int nkpt, int ndim, int A_total, const int* a_off, int max_det, const int32_t* index, const int32_t* count, float* out,
+                        ey_stream_t stream);
+int ey_kpt_iou(int B, int K, int ndim, const float* pred, const int* pred_off, const float* gt, const int* gt_off, const float* area, const float* sigma,
+               const long* out_off, float* out, ey_stream_t stream);
+
 /* ---- Test-time augmentation (DetectionModel._predict_augment, nn/tasks.py:372-408; reached by predict(augment=True)).
  * ey_scale_img = `scale_img(x.flip(3) if flip_lr else x, ratio, gs)` (utils/torch_utils.py:423-432): bilinear resize
  * (align_corners=False, ATen source-index rule) of the planar NCHW image x [B,C,H,W] to hs x ws = int(H*r) x int(W*r), written into the
