@@ -153,6 +153,9 @@ SIGNATURES = {
     "ey_kpts_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_long, _i, _vp, _vp]),
     "ey_kpts_decode_rows": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ey_kpt_iou": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_classify_pool": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ey_classify_linear_softmax": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_classify_transform": (_i, [_i, _vp, _i, _i, _i, _i, C.c_long, _vp, _i, _i, _vp]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Inference-time pre-transform: `LetterBox` with the reference's constructor and geometry (ultralytics/data/augment.py:1477-1591),
-executed on the GPU.  The reference letterboxes on the host with cv2 (resize INTER_LINEAR + copyMakeBorder 114) and then
+executed on the GPU, and `ClassifyTransform`, the classify task's `classify_transforms(size)` (:2346-2402).  The reference letterboxes on the host with cv2 (resize INTER_LINEAR + copyMakeBorder 114) and then
 `BasePredictor.preprocess` (engine/predictor.py:123-133) stacks, flips BGR->RGB, transposes to BCHW, uploads the float batch
 and divides by 255.  Here the raw uint8 image is uploaded (1/2 - 1/4 of the bytes of the float batch) and ONE kernel per image
 (`ey_letterbox`) does resize + pad + channel flip + layout + normalisation straight into the NCHW batch tensor."""
@@ -101,3 +101,56 @@ class LetterBox:
             raise L.HipLibraryError("LetterBox runs on the HIP path only and no ROCm GPU is visible")
         t = self.batch([image], torch.device("cuda", torch.cuda.current_device()), torch.float32, swap_rb=False)[0]
         return torch.round(t * 255).to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+
+
+class ClassifyTransform:
+    """classify_transforms(size) of the reference (ultralytics/data/augment.py:2346-2402 with mean 0, std 1, crop_fraction 1: torchvision
+    Resize(size) -> CenterCrop(size) -> ToTensor) plus ClassificationPredictor.preprocess's BGR -> RGB (models/yolo/classify/predict.py:45-47),
+    as ONE kernel (`ey_classify_transform`) on the raw uint8 image: antialiased bilinear resize (Pillow's filter) of the crop's pixels only,
+    channel flip, CHW, /255.  A uint8 (B,h,w,3) tensor takes one launch; a list of ndarrays (shapes may differ) one launch per image."""
+
+    def __init__(self, size=224):
+        if isinstance(size, (tuple, list)):
+            if len(size) != 2 or size[0] != size[1]:
+                raise NotImplementedError(f"ClassifyTransform: size={size}; only square crops (an int, or (s, s)) are built")
+            size = size[0]
+        self.size = int(size)
+
+    @staticmethod
+    def resized(h, w, size):
+        """(new_h, new_w) of torchvision's Resize(size): the shorter side becomes `size`."""
+        return (int(size * h / w), size) if w <= h else (size, int(size * w / h))
+
+    @staticmethod
+    def crop_origin(n, size):
+        """first row / column of torchvision's CenterCrop(size) in an axis of n >= size pixels."""
+        return int(round((n - size) / 2.0))
+
+    def batch_tensor(self, images, dtype, out=None, swap_rb=True):
+        from ..nn import _ops
+        with torch.cuda.device(images.device):
+            return _ops.classify_transform(images, self.size, dtype, out=out, swap_rb=swap_rb)
+
+    def batch(self, images, device, dtype=torch.float32, swap_rb=True):
+        """list of HWC uint8 BGR images (ndarray or tensor) -> (B,3,size,size) `dtype` RGB in [0,1] on `device`."""
+        from ..nn import _ops
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise L.HipLibraryError("ClassifyTransform.batch runs on the HIP path only: device must be a ROCm GPU")
+        out = torch.empty((len(images), 3, self.size, self.size), dtype=dtype, device=device)
+        with torch.cuda.device(device):
+            for i, a in enumerate(images):
+                if a.ndim != 3 or a.shape[2] != 3:
+                    raise ValueError(f"ClassifyTransform: expected HWC images with 3 channels, got {tuple(a.shape)}")
+                t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+                if t.dtype != torch.uint8:
+                    raise TypeError("ClassifyTransform: images must be uint8")
+                t = t.contiguous().to(device, non_blocking=True)
+                _ops.classify_transform(t[None], self.size, dtype, out=out[i:i + 1], swap_rb=swap_rb)
+        return out
+
+    def __call__(self, image):
+        """one HWC uint8 RGB image (the reference's transform takes a PIL RGB image) -> (3,size,size) fp32 tensor in [0,1] on the host."""
+        if not torch.cuda.is_available():
+            raise L.HipLibraryError("ClassifyTransform runs on the HIP path only and no ROCm GPU is visible")
+        return self.batch([np.asarray(image)], torch.device("cuda", torch.cuda.current_device()), torch.float32, swap_rb=False)[0].cpu()

@@ -1,12 +1,12 @@
-"""`YOLO(...)` facade for the detect, segment, obb and pose tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
+"""`YOLO(...)` facade for the detect, segment, obb, pose and classify tasks, mirroring the reference's engine/model.py (`Model.__init__` :84-151,
 `_new` :231-264, `_load` :266-302, `predict` :501-560, `val` :599-655) and models/yolo/model.py (:11-59)."""
 from pathlib import Path
 
 import torch
 
-from .predictor import DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
-from .validator import DetectionValidator, PoseValidator, SegmentationValidator
-from ..nn.tasks import DetectionModel, OBBModel, PoseModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
+from .predictor import ClassificationPredictor, DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
+from .validator import ClassificationValidator, DetectionValidator, PoseValidator, SegmentationValidator
+from ..nn.tasks import ClassificationModel, DetectionModel, OBBModel, PoseModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
 def _plain(o):
@@ -25,7 +25,8 @@ _TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor
 # tasks outside `task_map` (whose key set is pinned to the two tasks above): `_task_entry()` falls back to this table.  A row without a
 # "validator" is served by predict() only and val() refuses it (obb: rotated mAP on ey_probiou and multi-label rotated NMS are not built)
 _PREDICT_TASKS = {"obb": {"model": OBBModel, "predictor": OBBPredictor},
-                  "pose": {"model": PoseModel, "predictor": PosePredictor, "validator": PoseValidator}}
+                  "pose": {"model": PoseModel, "predictor": PosePredictor, "validator": PoseValidator},
+                  "classify": {"model": ClassificationModel, "predictor": ClassificationPredictor, "validator": ClassificationValidator}}
 
 
 class Model(torch.nn.Module):
@@ -165,7 +166,9 @@ class Model(torch.nn.Module):
             self.predictor = pcls(m, device, half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
                                   agnostic_nms=args["agnostic_nms"], classes=args["classes"], graph=args["graph"], augment=args["augment"])
             self._pred_key = key
-        self.predictor.imgsz = kwargs.get("imgsz", 640)  # letterbox target for ndarray sources (reference cfg default 640)
+        # letterbox target for ndarray sources (reference cfg default 640); classify: the crop size of ClassifyTransform, default 224 (the
+        # reference's 640 only holds until a checkpoint's train args override it: every released -cls checkpoint says 224)
+        self.predictor.imgsz = kwargs.get("imgsz", 224 if self.task == "classify" else 640)
         results = self.predictor(source)
         return iter(results) if stream else results
 
@@ -186,6 +189,8 @@ class Model(torch.nn.Module):
             args.update({"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False})
         if self.task == "pose":
             args.update({"save_json": False, "save_txt": False, "plots": False})
+        if self.task == "classify":
+            args.update({"plots": False})
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "mode"}
         if unknown:
             raise TypeError(f"val() got unsupported arguments {sorted(unknown)}")
@@ -216,7 +221,8 @@ class Model(torch.nn.Module):
         from .predictor import PipelinedRunner
         from ..utils import ops
         if self.task != "detect":
-            raise NotImplementedError(f"predict_batches: pipelined throughput is built for the detect task only, not '{self.task}' (use predict())")
+            raise NotImplementedError(f"predict_batches: pipelined throughput is built for the detect task only, not '{self.task}' (use predict(); "
+                                      "built tasks: detect, segment, obb, pose, classify)")
         args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None}
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "cuts"}
         if unknown:

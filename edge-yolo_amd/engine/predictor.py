@@ -450,3 +450,68 @@ class PosePredictor(DetectionPredictor):
                 r.boxes.orig_shape = r.keypoints.orig_shape = r.orig_shape
             results.append(r)
         return results
+
+
+class ClassificationPredictor(DetectionPredictor):
+    """reference models/yolo/classify/predict.py:12-60.  Float BCHW tensors in [0,1] go to the network as they are (any H, W: the model has
+    no stride constraint); ndarray sources (HWC uint8 BGR) and uint8 (B,h,w,3) tensors go through ClassifyTransform(imgsz) on the device.  The
+    device step -- for uint8 tensors the transform too -- is one captured graph: backbone, ey_classify_pool, ey_classify_linear_softmax.
+    Results carry `probs` only; its top-5 comes from the head's kernel.  conf, iou, max_det, classes and agnostic_nms are accepted and
+    ignored, as in the reference; augment=True raises."""
+
+    def __init__(self, model, device, half=False, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, classes=None, graph=True, validate_input=None, keep_pred=False,
+                 augment=False):
+        if augment:
+            raise NotImplementedError("ClassificationPredictor: augment=True (test-time augmentation) is not built for the classify task")
+        super().__init__(model, device, half=half, conf=conf, iou=iou, max_det=max_det, agnostic_nms=agnostic_nms, classes=classes, graph=graph,
+                         validate_input=validate_input, keep_pred=keep_pred, augment=False)
+        self.imgsz = 224
+
+    def _device_step(self, im):
+        if im.dtype == torch.uint8:  # a decoded batch: the transform is part of the captured graph
+            from ..data.augment import ClassifyTransform
+            im = ClassifyTransform(self._u8_size).batch_tensor(im, torch.float16 if self.half else torch.float32)
+        probs, logits = self.model(im)
+        topi, topp = self.model.model[-1].top5
+        return probs, logits, topi, topp
+
+    def preprocess(self, im):
+        from ..data.augment import ClassifyTransform
+        size = getattr(self, "imgsz", 224)
+        if isinstance(im, torch.Tensor) and im.dtype == torch.uint8:
+            if im.dim() != 4 or im.shape[3] != 3:
+                raise ValueError(f"uint8 tensor sources must be (B,h,w,3) BGR image stacks, got {tuple(im.shape)}")
+            if getattr(self, "_u8_size", size) != size and hasattr(self.runner, "graphs"):
+                self.runner.graphs.clear()  # the crop size is baked into the captured transform
+            self._u8_size = size
+            self._orig = [a for a in im.cpu().numpy()]
+            return im.contiguous().to(self.device, non_blocking=True)
+        if not isinstance(im, torch.Tensor):
+            ims = im if isinstance(im, (list, tuple)) else [im]
+            self._orig = [np.asarray(a) for a in ims]
+            return ClassifyTransform(size).batch(self._orig, self.device, torch.float16 if self.half else torch.float32)
+        if im.dim() == 3:
+            im = im[None]
+        if im.dim() != 4:
+            raise ValueError(f"input tensor should be BCHW, got {tuple(im.shape)}")
+        if not im.is_floating_point():
+            raise TypeError("tensor sources must be floating point images in [0,1] or uint8 (B,h,w,3) BGR stacks")
+        im = im.to(self.device, non_blocking=True)
+        return (im.half() if self.half else im.float()).contiguous()
+
+    def _results(self, out, im, source):
+        return self.postprocess(out[0], im, source, top=(out[2], out[3]))
+
+    def postprocess(self, probs, img, source, top=None):
+        """reference classify/predict.py:51-60: one Results with `probs` per image.  One D2H copy each of the probabilities and the top-5."""
+        from .results import Probs
+        probs = probs.clone()
+        top = tuple(t.clone() for t in top) if top is not None else None
+        results = []
+        for i in range(probs.shape[0]):
+            orig = self._orig[i] if self._orig is not None else None
+            r = Results(orig, path=f"image{i}.jpg", names=self.model.names, probs=Probs(probs[i], top=None if top is None else (top[0][i], top[1][i])))
+            if orig is None:
+                r.orig_shape = tuple(img.shape[2:])
+            results.append(r)
+        return results

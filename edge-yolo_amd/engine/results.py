@@ -1,5 +1,5 @@
-"""Minimal `Results` / `Boxes` / `Masks` / `OBB` containers with the attribute surface of the reference's engine/results.py
-(:187 Results, :938 Boxes, :1093 Masks, :1519 OBB) that predict() callers read.  Plotting/saving are out of scope."""
+"""Minimal `Results` / `Boxes` / `Masks` / `OBB` / `Keypoints` / `Probs` containers with the attribute surface of the reference's engine/results.py
+(:187 Results, :938 Boxes, :1093 Masks, :1254 Keypoints, :1378 Probs, :1519 OBB) that predict() callers read.  Plotting/saving are out of scope."""
 import numpy as np
 import torch
 
@@ -180,14 +180,62 @@ class Keypoints:
         return len(self.data)
 
 
+class Probs:
+    """(nc,) class probabilities of one image (reference :1378-1516).  top1 / top5 / top1conf / top5conf are the reference's expressions
+    (argmax; (-data).argsort(0)[:5]) unless the head's own top-5 came along (`top`: (index int32 (k,), probability (k,)) from
+    ey_classify_linear_softmax, k = min(nc, 5)); those rank equal probabilities by the lower class index."""
+
+    def __init__(self, probs, orig_shape=None, top=None):
+        self.data = probs
+        self.orig_shape = orig_shape
+        self._top = top
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def top1(self):
+        if self._top is not None:
+            return int(self._top[0][0])
+        return int(self.data.argmax())
+
+    @property
+    def top5(self):
+        if self._top is not None:
+            return [int(v) for v in self._top[0]]
+        return (-self.data).argsort(0)[:5].tolist()  # this way works with both torch and numpy.
+
+    @property
+    def top1conf(self):
+        return self.data[self.top1]
+
+    @property
+    def top5conf(self):
+        return self.data[self.top5]
+
+    def _like(self, f):
+        return Probs(f(self.data), self.orig_shape, None if self._top is None else tuple(f(t) for t in self._top))
+
+    def cpu(self):
+        return self if isinstance(self.data, np.ndarray) else self._like(lambda t: t.cpu())
+
+    def numpy(self):
+        return self if isinstance(self.data, np.ndarray) else self._like(lambda t: t.cpu().numpy())
+
+    def __len__(self):
+        return len(self.data)
+
+
 class Results:
-    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None, obb=None, keypoints=None):
+    def __init__(self, orig_img, path, names, boxes=None, masks=None, speed=None, obb=None, keypoints=None, probs=None):
         self.orig_img = orig_img
         self.orig_shape = tuple(orig_img.shape[:2]) if orig_img is not None and hasattr(orig_img, "shape") and orig_img.ndim == 3 else None
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None else None
         self.masks = Masks(masks, self.orig_shape) if masks is not None else None
         self.obb = OBB(obb, self.orig_shape) if obb is not None else None
         self.keypoints = Keypoints(keypoints, self.orig_shape) if keypoints is not None else None
+        self.probs = (probs if isinstance(probs, Probs) else Probs(probs)) if probs is not None else None
         self.names = names
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
@@ -195,4 +243,6 @@ class Results:
     def __len__(self):
         if self.boxes is not None:
             return len(self.boxes)
+        if self.probs is not None:
+            return len(self.probs)
         return len(self.obb) if self.obb is not None else 0

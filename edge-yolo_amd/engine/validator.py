@@ -553,3 +553,72 @@ class PoseValidator(DetectionValidator):
 
     def update(self, images, labels):
         raise NotImplementedError("PoseValidator: the (images, labels) convenience of the detect task carries no keypoints; call it with batches")
+
+
+class ClassificationValidator:
+    """Validation loop for the classify task, mirroring the reference's models/yolo/classify/val.py (`init_metrics` :41-47, `preprocess`
+    :49-54, `update_metrics` :56-60, `postprocess` :74-76, `get_stats` :78-81) with ClassifyMetrics.
+
+    Batches are {"img": (B,3,H,W) float in [0,1] or uint8 0..255, "cls": (B,) class indices}.  Device work per batch: the forward; the top
+    min(nc, 5) classes come from the head's kernel (ey_classify_linear_softmax; equal probabilities rank the lower class first, where the
+    reference's argsort is unspecified) and reach the host as ONE copy of a (B, 5) int32 tensor.  Host predictions (`update_metrics(probs,
+    batch)` with a numpy array / CPU tensor of probabilities) are ranked by the same rule on the host: the route the CPU tests take.
+    plots=True raises; the confusion matrix is not built."""
+
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, plots=False):
+        if plots:
+            raise NotImplementedError("ClassificationValidator: plots=True is not built (confusion matrix and sample plots)")
+        self.model = getattr(model, "model", model) if not hasattr(model, "forward_layers") else model
+        self.half = half
+        self.device = torch.device(device) if device is not None else next(self.model.parameters()).device
+        self.metrics = metrics.ClassifyMetrics()
+        self.init_metrics()
+
+    def init_metrics(self):
+        self.names = self.model.names
+        self.nc = len(self.names)
+        self.pred, self.targets = [], []
+        self.results_dict = dict(zip(self.metrics.keys + ["fitness"], [0.0] * 3))
+
+    def preprocess(self, batch):
+        img = batch["img"].to(self.device, non_blocking=True)
+        scale = 255.0 if img.dtype == torch.uint8 else 1.0
+        img = img.half() if self.half else img.float()
+        batch = dict(batch)
+        batch["img"] = (img / scale if scale != 1.0 else img).contiguous()
+        return batch
+
+    def postprocess(self, preds):
+        """-> the (B, min(nc, 5)) int32 top classes of the forward that just ran (device tensor)."""
+        return self.model.model[-1].top5[0]
+
+    @staticmethod
+    def rank(probs, n5):
+        """host form of the kernel's ranking: descending probability, equal probabilities by ascending class index -> (B, n5) int32."""
+        p = _np(probs).astype(np.float32)
+        return np.argsort(-p, axis=1, kind="stable")[:, :n5].astype(np.int32)
+
+    def update_metrics(self, preds, batch):
+        n5 = min(self.nc, 5)
+        if torch.is_tensor(preds) and preds.dtype == torch.int32:
+            top = preds[:, :n5].cpu().numpy()  # the one D2H copy of the batch
+        else:
+            top = self.rank(preds[0] if isinstance(preds, (list, tuple)) else preds, n5)
+        self.pred.append(top)
+        self.targets.append(_np(batch["cls"]).reshape(-1).astype(np.int32))
+
+    def get_stats(self):
+        self.metrics.process(self.targets, self.pred)
+        self.results_dict = self.metrics.results_dict
+        return self.results_dict
+
+    @torch.no_grad()
+    def __call__(self, dataloader):
+        self.init_metrics()
+        for batch in dataloader:
+            batch = self.preprocess(batch)
+            with torch.cuda.device(self.device):
+                self.model(batch["img"])
+                top = self.postprocess(None)
+            self.update_metrics(top, batch)
+        return self.get_stats()

@@ -1475,3 +1475,70 @@ def kpt_iou(pred, pred_off, gt, gt_off, area, sigma, out_off=None, out=None):
         L.check(L.lib().ey_kpt_iou(B, K, ndim, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off), area.data_ptr(), sigma.data_ptr(), LA(*out_off),
                                    out.data_ptr(), L.stream()), "ey_kpt_iou")
     return out, out_off
+
+
+def classify_pool(x, w, bias, act, out=None):
+    """Classify.conv + pool + flatten (ey_classify_pool): x logical (B, C1, H, W) NHWC view, w (Cout, C1) in x's dtype (BN folded), bias fp32
+    (Cout,) -> fp32 (B, Cout) = mean over the pixels of act(conv1x1(x) + bias).  The (B, Cout, H, W) map is never written."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "classify_pool")
+    _no_block("classify_pool")
+    B, C1, H, W = x.shape
+    Cout = int(w.shape[0])
+    if w.dim() != 2 or w.shape[1] != C1 or w.dtype != x.dtype or not w.is_contiguous() or w.device != x.device:
+        raise ValueError(f"classify_pool: w must be a contiguous {x.dtype} (Cout, {C1}) tensor on {x.device}, got {w.dtype} {tuple(w.shape)}")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.device != x.device:
+        raise ValueError(f"classify_pool: bias must be a contiguous float32 ({Cout},) tensor on {x.device}")
+    if out is None:
+        out = torch.empty((B, Cout), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Cout) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"classify_pool: out must be a contiguous float32 {(B, Cout)} tensor on {x.device}")
+    with _tr("classify_pool_kernel", _nb(x, w, bias, out), 2.0 * B * H * W * C1 * Cout):
+        L.check(L.lib().ey_classify_pool(L.dtype_code(x.dtype), B, H * W, C1, Cout, int(act), x.data_ptr(), L.cstride(x), w.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                         L.stream()), "ey_classify_pool")
+    return out
+
+
+def classify_linear_softmax(pooled, w, bias):
+    """Classify.linear + softmax + top-k (ey_classify_linear_softmax): pooled fp32 (B, K), w (nc, K) f16 or fp32, bias fp32 (nc,) ->
+    (logits (B, nc), probs (B, nc), top index int32 (B, min(nc, 5)), top probability (B, min(nc, 5))), all fp32 but the index.  Equal
+    probabilities rank the lower class index first."""
+    L.require_device(pooled, "classify_linear_softmax")
+    _no_block("classify_linear_softmax")
+    if pooled.dim() != 2 or pooled.dtype != torch.float32 or not pooled.is_contiguous():
+        raise ValueError(f"classify_linear_softmax: pooled must be a contiguous float32 (B, K) tensor, got {pooled.dtype} {tuple(pooled.shape)}")
+    B, K = pooled.shape
+    nc = int(w.shape[0])
+    dev = pooled.device
+    if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous() or w.device != dev:
+        raise ValueError(f"classify_linear_softmax: w must be a contiguous (nc, {K}) tensor on {dev}, got {tuple(w.shape)}")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (nc,) or not bias.is_contiguous() or bias.device != dev:
+        raise ValueError(f"classify_linear_softmax: bias must be a contiguous float32 ({nc},) tensor on {dev}")
+    k5 = min(nc, 5)
+    logits = torch.empty((B, nc), dtype=torch.float32, device=dev)
+    probs = torch.empty((B, nc), dtype=torch.float32, device=dev)
+    topi = torch.empty((B, k5), dtype=torch.int32, device=dev)
+    topp = torch.empty((B, k5), dtype=torch.float32, device=dev)
+    with _tr("classify_linear_softmax_kernel", _nb(pooled, w, bias, logits, probs, topi, topp), 2.0 * B * K * nc):
+        L.check(L.lib().ey_classify_linear_softmax(L.dtype_code(w.dtype), B, K, nc, pooled.data_ptr(), w.data_ptr(), bias.data_ptr(), logits.data_ptr(), probs.data_ptr(),
+                                                   topi.data_ptr(), topp.data_ptr(), L.stream()), "ey_classify_linear_softmax")
+    return logits, probs, topi, topp
+
+
+def classify_transform(images, size, dtype, out=None, swap_rb=True):
+    """classify_transforms(size) on the device (ey_classify_transform): images = contiguous uint8 (B, h, w, 3) device tensor (BGR like cv2)
+    -> (B, 3, size, size) `dtype` RGB in [0, 1]: Resize(size) (Pillow's antialiased bilinear) + CenterCrop(size) + ToTensor in one launch."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous()):
+        raise ValueError("classify_transform: expected a contiguous uint8 device tensor of shape (B, h, w, 3)")
+    L.require_device(images, "classify_transform")
+    _no_block("classify_transform")
+    B, h, w, _ = images.shape
+    S = int(size)
+    if out is None:
+        out = torch.empty((B, 3, S, S), dtype=dtype, device=images.device)
+    elif tuple(out.shape) != (B, 3, S, S) or out.dtype != dtype or not out.is_contiguous() or out.device != images.device:
+        raise ValueError(f"classify_transform: out must be a contiguous {dtype} tensor of shape {(B, 3, S, S)} on {images.device}")
+    with _tr("classify_transform_kernel", _nb(images, out)):
+        L.check(L.lib().ey_classify_transform(L.dtype_code(dtype), images.data_ptr(), B, h, w, 3 * w, 3 * w * h, out.data_ptr(), S, int(swap_rb), L.stream()),
+                "ey_classify_transform")
+    return out

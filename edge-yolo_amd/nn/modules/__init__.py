@@ -6,9 +6,9 @@ from .block import (DFL, Proto, SPPF, C2f, C3, C3k, C3k2, Bottleneck, Attention,
                     AdaHGComputation, C3AH, FuseModule, HyperACE, DownsampleConv, FullPAD_Tunnel)
 from .conv import Conv, DWConv, DSConv, Concat, Upsample, autopad
 from .dysample import DySample
-from .head import Detect, E2EDetect, GF2Detect, GFLHeadv2_uniH, OBB, Pose, Segment
+from .head import Classify, Detect, E2EDetect, GF2Detect, GFLHeadv2_uniH, OBB, Pose, Segment
 
 __all__ = ("Conv", "DWConv", "DSConv", "Concat", "Upsample", "autopad", "DFL", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention",
            "PSABlock", "C2PSA", "LinearAttention", "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k",
            "DSC3K2_Wavelet", "DSC3K2", "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv",
-           "FullPAD_Tunnel", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "DSC3K2_LGL", "DySample", "Detect", "Segment", "OBB", "Pose", "Proto", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+           "FullPAD_Tunnel", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "DSC3K2_LGL", "DySample", "Detect", "Segment", "OBB", "Pose", "Classify", "Proto", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")

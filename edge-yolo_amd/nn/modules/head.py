@@ -1,4 +1,4 @@
-"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `Pose` (:402-451), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
+"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `Pose` (:402-451), `Classify` (:454-476), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
@@ -14,7 +14,7 @@ from .conv import Conv, DWConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "Segment", "OBB", "Pose", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+__all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
 
 
 class _Plain(_Packed):
@@ -653,3 +653,47 @@ class GFLHeadv2_uniH(GF2Detect):
         self.reg_conf = nn.ModuleList(
             nn.Sequential(nn.Conv2d(in_stat, self.reg_channels, 1, bias=True), nn.ReLU(inplace=True), nn.Conv2d(self.reg_channels, 1, 1, bias=True),
                           nn.Sigmoid()) for _ in ch)
+
+
+class Classify(_Packed):
+    """YOLO classification head (reference head.py:454-476): x (B, c1, H, W) -> (probabilities, logits), both (B, c2) fp32.  Same attribute
+    names and state_dict keys (conv.conv.weight, conv.bn.*, linear.weight, linear.bias); `pool` and `drop` hold no tensors and are never
+    called.  The eval forward is two launches: ey_classify_pool (the 1x1 conv to 1280 channels with the folded BatchNorm, SiLU and the mean
+    over the pixels: the 1280-channel map never exists) and ey_classify_linear_softmax (linear, softmax and the top-5 classes).  The top-5
+    indices and probabilities of the last forward are kept in `top5` for the validator and `Probs` (fixed-size device tensors)."""
+
+    export = False
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1):
+        super().__init__()
+        if k != 1 or s != 1 or g != 1:
+            raise NotImplementedError(f"Classify(k={k}, s={s}, g={g}): only the 1x1, stride-1, dense conv of the shipped YAMLs is built")
+        c_ = 1280  # efficientnet_b0 size
+        self.conv = Conv(c1, c_, k, s, p, g)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.drop = nn.Dropout(p=0.0, inplace=True)
+        self.linear = nn.Linear(c_, c2)
+        self.top5 = None
+
+    def _weights(self, dtype, device):
+        def build():
+            w, b = self.conv.folded()
+            return (w.reshape(w.shape[0], -1).to(device=device, dtype=dtype).contiguous(), b.to(device=device, dtype=torch.float32).contiguous(),
+                    self.linear.weight.detach().to(device=device, dtype=dtype).contiguous(), self.linear.bias.detach().to(device=device, dtype=torch.float32).contiguous())
+        return self._packed(("cls", dtype, device), build)
+
+    def forward(self, x):
+        if self.training:
+            raise NotImplementedError("Classify: the training forward (logits only) is outside the built inference path")
+        if self.linear.out_features > 8192:
+            raise NotImplementedError(f"Classify: nc={self.linear.out_features} (1 to 8192 classes are built)")
+        if isinstance(x, list):
+            x = ops.concat(x)
+        x = ops.as_tensor(x)
+        if hasattr(self.conv, "bn") and self.conv.bn.training:
+            raise NotImplementedError("Classify: BatchNorm in training mode")
+        wc, bc, wl, bl = self._weights(x.dtype, x.device)
+        pooled = ops.classify_pool(x, wc, bc, _act_code(self.conv.act))
+        logits, probs, topi, topp = ops.classify_linear_softmax(pooled, wl, bl)
+        self.top5 = (topi, topp)
+        return probs if self.export else (probs, logits)

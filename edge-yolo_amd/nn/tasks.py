@@ -1,6 +1,6 @@
 """YAML -> model graph and the graph executor, mirroring the reference's ultralytics/nn/tasks.py for the detect
 path: `parse_model` (:958-1147), `yaml_model_load` (:1150-1163), `guess_model_scale` (:1166-1181),
-`guess_model_task` (:1184-1255), `BaseModel._predict_once/fuse` (:152-242), `DetectionModel` (:320-370), `OBBModel` (:416-428), `PoseModel` (:440-451), `SegmentationModel` (:472-480).
+`guess_model_task` (:1184-1255), `BaseModel._predict_once/fuse` (:152-242), `DetectionModel` (:320-370), `OBBModel` (:416-428), `PoseModel` (:440-451), `ClassificationModel` (:457-500), `SegmentationModel` (:472-480).
 """
 import ast
 import contextlib
@@ -13,7 +13,7 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
+from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
                       DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
@@ -21,7 +21,7 @@ from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
 _REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
 _HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose}
 
@@ -51,14 +51,17 @@ def yaml_model_load(path):
 def guess_model_task(model):
     """Reference tasks.py:1184-1255 reduced to this build's scope.  The reference only recognises heads whose
     lower-cased name contains 'detect' and raises for GFLHeadv2_uniH YAMLs unless task='detect' is passed
-    (SURVEY §3 quirk); here every registered head but Segment ("segment", reference :1206-1207) OBB ("obb", :1210-1211) and Pose ("pose", :1208-1209)
-    is a detect head."""
+    (SURVEY §3 quirk); here every registered head but Segment ("segment", reference :1206-1207) OBB ("obb", :1210-1211), Pose ("pose", :1208-1209)
+    and Classify ("classify", :1204-1205) is a detect head.  A string that is no model YAML is matched by name like the reference does
+    (:1200-1210: classify, classifier, cls, fc -> "classify")."""
     cfg = model if isinstance(model, dict) else None
     if cfg is None and isinstance(model, (str, Path)):
         with contextlib.suppress(Exception):
             cfg = yaml_model_load(model)
     if cfg is not None:
         m = cfg["head"][-1][-2]
+        if m == "Classify" or str(m).lower() in {"classify", "classifier", "cls", "fc"}:
+            return "classify"
         if m == "Segment":
             return "segment"
         if m == "OBB":
@@ -67,8 +70,12 @@ def guess_model_task(model):
             return "pose"
         if m in {h.__name__ for h in _HEADS}:
             return "detect"
-        raise NotImplementedError(f"head '{m}': only the detect, segment, obb and pose tasks are built")
+        raise NotImplementedError(f"head '{m}': only the detect, segment, obb, pose and classify tasks are built")
+    if isinstance(model, str) and model.lower() in {"classify", "classifier", "cls", "fc"}:
+        return "classify"
     if isinstance(model, nn.Module):  # reference :1226-1240: look at the modules
+        if any(isinstance(mod, Classify) for mod in model.modules()):
+            return "classify"
         if any(isinstance(mod, Segment) for mod in model.modules()):
             return "segment"
         if any(isinstance(mod, OBB) for mod in model.modules()):
@@ -523,6 +530,46 @@ class PoseModel(DetectionModel):
             cfg["kpt_shape"] = data_kpt_shape
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
         self.kpt_shape = self.model[-1].kpt_shape  # (the reference's AutoBackend exposes it as model.kpt_shape: pose/predict.py:51)
+
+
+class ClassificationModel(BaseModel):
+    """Classification model built from a YAML (reference tasks.py:457-500): no stride constraint (stride = [1]), nc from the YAML or the
+    argument (one of them is required), names {i: str(i)}.  The backbone runs on the same kernels as the detect models; the Classify head is
+    two launches (nn/modules/head.py)."""
+
+    def __init__(self, cfg="yolo11n-cls.yaml", ch=3, nc=None, verbose=False):
+        super().__init__()
+        self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        ch = self.yaml["ch"] = self.yaml.get("ch", ch)
+        if nc and nc != self.yaml.get("nc"):
+            self.yaml["nc"] = nc
+        elif not nc and not self.yaml.get("nc", None):
+            raise ValueError("nc not specified. Must specify nc in model.yaml or function arguments.")
+        self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
+        self.stride = torch.Tensor([1])  # no stride constraints
+        self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
+        self.inplace = self.yaml.get("inplace", True)
+        self.end2end = False
+        self.register_load_state_dict_post_hook(lambda m, _keys: m.__dict__.__setitem__("_block_caches", {}))
+        # (no initialize_weights here: the reference's ClassificationModel does not call it, so its BatchNorm layers keep torch's eps = 1e-5
+        # where the detect-family models have 1e-3)
+        self.eval()
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("edge-yolo_amd builds the inference forward path only")
+        return super().train(False)
+
+    @staticmethod
+    def reshape_outputs(model, nc):
+        """Give the model's Classify head `nc` outputs if it has another count (reference tasks.py:481-500, the Classify case; torchvision
+        models are not part of this build)."""
+        name, m = list((model.model if hasattr(model, "model") else model).named_children())[-1]
+        if not isinstance(m, Classify):
+            raise NotImplementedError(f"reshape_outputs: the last module is {type(m).__name__}; only the Classify head is built")
+        if m.linear.out_features != nc:
+            m.linear = nn.Linear(m.linear.in_features, nc)
+            m._cache = {}
 
 
 def torch_safe_load_state(path):

@@ -284,3 +284,41 @@ class PoseMetrics(SegmentMetrics):
     @property
     def keys(self):
         return list(POSE_KEYS)
+
+
+class ClassifyMetrics:
+    """top-1 / top-5 accuracy of the classify task (reference utils/metrics.py:1184-1237)."""
+
+    def __init__(self):
+        self.top1 = 0
+        self.top5 = 0
+        self.speed = {"preprocess": 0.0, "inference": 0.0, "loss": 0.0, "postprocess": 0.0}
+        self.task = "classify"
+
+    def process(self, targets, pred):
+        """targets: list of (n_i,) int32 class tensors; pred: list of (n_i, k) int32 top-k class tensors, best first."""
+        pred, targets = np.concatenate([np.asarray(_host(p)) for p in pred]), np.concatenate([np.asarray(_host(t)).reshape(-1) for t in targets])
+        correct = (targets[:, None] == pred).astype(np.float32)
+        acc = np.stack((correct[:, 0], correct.max(1)), axis=1)  # (top1, top5) accuracy
+        n = np.float32(len(acc))
+        self.top1, self.top5 = (float(np.float32(v) / n) for v in acc.sum(0, dtype=np.float64))  # fp32 mean of 0 / 1 values: exact sum, one division
+
+    @property
+    def fitness(self):
+        return (self.top1 + self.top5) / 2
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], [self.top1, self.top5, self.fitness]))
+
+    @property
+    def keys(self):
+        return ["metrics/accuracy_top1", "metrics/accuracy_top5"]
+
+    @property
+    def curves(self):
+        return []
+
+    @property
+    def curves_results(self):
+        return []

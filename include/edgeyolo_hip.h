@@ -621,6 +621,34 @@ int ey_kpts_decode_rows(int dtype, int B, int nlevels, const int* H, const int* 
 int ey_kpt_iou(int B, int K, int ndim, const float* pred, const int* pred_off, const float* gt, const int* gt_off, const float* area, const float* sigma,
                const long* out_off, float* out, ey_stream_t stream);
 
+/* ---- Image classification (csrc/classify.hip).
+ * ey_classify_pool: Classify.conv + AdaptiveAvgPool2d(1) + flatten (ultralytics/nn/modules/head.py:463-472) in ONE launch:
+ *   out[b][co] = ( sum_p act( bias[co] + sum_ci x[b][p][ci] * w[co][ci] ) ) / (float)HW        p over the HW pixels of image b
+ *   x: NHWC window [B, HW, *] of `dtype` with pixel stride x_cstride >= C1 (only the C1 channels are read; a window that is not 16-byte
+ *   aligned is read with scalar loads); w: DEVICE [Cout][C1] in `dtype`, 16-byte aligned (the BN-folded 1x1 weight, row-major); bias: DEVICE
+ *   fp32 [Cout]; out: DEVICE fp32 [B][Cout].  The (B, Cout, H, W) map is never written.  f16: MFMA with fp32 accumulation, Cout a multiple of
+ *   16; fp32: a k-ordered fmaf chain per output, any Cout.  Any HW >= 1 (pixel tiles accumulate the per-channel sums of the activated values
+ *   in fp32; the mean is that sum followed by one IEEE division), C1 a multiple of 8 up to 2016: EY_EUNSUPPORTED before any launch otherwise.
+ * ey_classify_linear_softmax: Classify.linear + softmax(1) (head.py:472-475) + the top-min(nc, 5) classes in ONE launch, all outputs of fixed
+ *   size (graph-capturable, no atomics, the same bytes run to run).  pooled: DEVICE fp32 [B][K]; w: DEVICE [nc][K] in `dtype`, 16-byte aligned;
+ *   bias fp32 [nc].  logits / probs: fp32 [B][nc] (accumulation and everything behind it in fp32; softmax subtracts the row maximum);
+ *   topk_index int32 / topk_prob fp32 [B][min(nc, 5)]: classes by descending probability, EQUAL PROBABILITIES BY ASCENDING CLASS INDEX (the
+ *   reference's argsort is not stable; this is the rule here).  A row whose probabilities are NaN gets index -1, probability 0.
+ *   1 <= nc <= 8192 and K a multiple of 8 up to 4096: EY_EUNSUPPORTED before any launch otherwise.
+ * ey_classify_transform: classify_transforms(size) of the reference (ultralytics/data/augment.py:2346: torchvision Resize(S) ->
+ *   CenterCrop(S) -> ToTensor, mean 0, std 1, crop fraction 1) for B uint8 HWC images of ONE shape (image i at src_hwc + i * src_image_bytes)
+ *   -> [B][3][S][S] of out_dtype in [0, 1], channels reversed when swap_rb (BGR -> RGB).  Resized size: shorter side S, longer side
+ *   int(S * long / short); crop origin int(round((n - S) / 2.0)) with round-half-to-even; filter: Pillow's antialiased BILINEAR per axis
+ *   (scale = in / out, fs = max(scale, 1), center = (i + 0.5) scale, taps [max(int(center - fs + 0.5), 0), min(int(center + fs + 0.5), in)),
+ *   weight max(0, 1 - |(x - center + 0.5) / fs|) normalised to sum 1), both axes applied in one pass with fp32 pixel sums and no uint8
+ *   intermediate; only the pixels inside the crop are computed. */
+int ey_classify_pool(int dtype, int B, int HW, int C1, int Cout, int act, const void* x, int x_cstride, const void* w, const float* bias, float* out,
+                     ey_stream_t stream);
+int ey_classify_linear_softmax(int dtype, int B, int K, int nc, const float* pooled, const void* w, const float* bias, float* logits, float* probs,
+                               int32_t* topk_index, float* topk_prob, ey_stream_t stream);
+int ey_classify_transform(int out_dtype, const uint8_t* src_hwc, int B, int src_h, int src_w, int src_row_bytes, long src_image_bytes, void* dst_chw, int S,
+                          int swap_rb, ey_stream_t stream);
+
 /* ---- Test-time augmentation (DetectionModel._predict_augment, nn/tasks.py:372-408; reached by predict(augment=True)).
  * ey_scale_img = `scale_img(x.flip(3) if flip_lr else x, ratio, gs)` (utils/torch_utils.py:423-432): bilinear resize
  * (align_corners=False, ATen source-index rule) of the planar NCHW image x [B,C,H,W] to hs x ws = int(H*r) x int(W*r), written into the
