@@ -9,4 +9,4 @@ The directory is called `edge-yolo_amd`; import it as `edge_yolo_amd` (see `edge
 """
 __version__ = "0.1.0"
 
-from .engine.model import YOLO  # noqa: E402,F401
+from .engine.model import YOLO, YOLOWorld  # noqa: E402,F401

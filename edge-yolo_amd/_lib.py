@@ -16,6 +16,7 @@ ATTN_AREA_F32, ATTN_AREA_F16, ATTN_AREA_MFMA = 401, 402, 403  # ey_attention_las
 ATTN_FLASH_MFMA, ATTN_FLASH_F32, ATTN_FLASH_F16 = 500, 501, 502  # ... of ey_flash_attention (MFMA: + head_dim)
 DWG_PLAIN, DWG_GATE, DWG_RESIDUAL = 0, 1, 2  # ey_dwconv_gate epilogues
 MASK_GT_STACK, MASK_GT_INDEX = 0, 1  # ey_mask_iou ground-truth forms
+MSA_MAX_TEXTS = 4096  # EY_MSA_MAX_TEXTS: the most texts ey_max_sigmoid_attn takes
 
 
 class HipLibraryError(RuntimeError):
@@ -155,6 +156,7 @@ SIGNATURES = {
     "ey_kpt_iou": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ey_classify_pool": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ey_classify_linear_softmax": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ey_max_sigmoid_attn": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_classify_transform": (_i, [_i, _vp, _i, _i, _i, _i, C.c_long, _vp, _i, _i, _vp]),
 }
 

@@ -6,7 +6,7 @@ import torch
 
 from .predictor import ClassificationPredictor, DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
 from .validator import ClassificationValidator, DetectionValidator, PoseValidator, SegmentationValidator
-from ..nn.tasks import ClassificationModel, DetectionModel, OBBModel, PoseModel, SegmentationModel, guess_model_task, torch_safe_load_state, yaml_model_load
+from ..nn.tasks import ClassificationModel, DetectionModel, OBBModel, PoseModel, SegmentationModel, WorldModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
 def _plain(o):
@@ -83,6 +83,7 @@ class Model(torch.nn.Module):
             missing = sorted(set(self.model.state_dict()) - set(ck["state_dict"]))[:5]
             raise ValueError(f"{weights}: only {loaded} of {own} model tensors were found in the checkpoint (e.g. missing {missing}); "
                              "was it saved from a different YAML / nc, or fused without the 'fused' flag?")
+        self._restore_extra(ck)
         self.ckpt_path = weights
 
     def save(self, filename):
@@ -94,7 +95,14 @@ class Model(torch.nn.Module):
         # would only reload where a file of that name exists under cfg/models and still describes the same graph
         cfg = _plain(m.yaml) if isinstance(self.cfg, dict) else self.cfg
         torch.save({"yaml": cfg, "nc": int(m.yaml["nc"]),
-                    "fused": bool(m.convs_folded()), "state_dict": sd}, filename)
+                    "fused": bool(m.convs_folded()), "state_dict": sd, **self._checkpoint_extra()}, filename)
+
+    def _checkpoint_extra(self):
+        """Further checkpoint entries of a subclass (YOLOWorld: the class names); none here, so other checkpoints keep their exact content."""
+        return {}
+
+    def _restore_extra(self, ck):
+        """Counterpart of _checkpoint_extra, called by _load behind the state_dict."""
 
     def load(self, weights):
         """Load a flat state_dict (dict or tensor-only file) keyed like the reference's `model.N....` entries."""
@@ -336,3 +344,45 @@ class YOLO(Model):
     @property
     def task_map(self):
         return _TASK_MAP
+
+
+_WORLD_TASK_MAP = {"detect": {"model": WorldModel, "predictor": DetectionPredictor, "validator": DetectionValidator}}
+
+
+class YOLOWorld(Model):
+    """YOLO-World open-vocabulary detect model (reference models/yolo/model.py:62-111).  predict(), val(), save() and loading work as for any
+    detect model; `set_classes` chooses the vocabulary at run time.  The CLIP text encoder is not part of the build, so `set_classes` takes the
+    embeddings of the class names next to the names."""
+
+    def __init__(self, model="yolov8s-worldv2.yaml", verbose=False):
+        super().__init__(model=model, task="detect", verbose=verbose)
+
+    @property
+    def task_map(self):
+        return _WORLD_TASK_MAP
+
+    def set_classes(self, classes, txt_feats=None):
+        """classes: the class names; txt_feats: their embeddings (n, 512) or (1, n, 512) (required: WorldModel.set_classes).  A " " background
+        entry keeps its embedding and is removed from the names, as in the reference (:102-106).  A live predictor is closed: its captured
+        graphs were recorded for the old vocabulary."""
+        classes = list(classes)
+        self.model.set_classes(classes, txt_feats)
+        background = " "
+        if background in classes:
+            classes.remove(background)
+        self.model.names = dict(enumerate(classes))
+        if self.predictor is not None:
+            self.predictor.model.names = self.model.names
+            self.predictor.close()
+            self.predictor = None
+
+    def _checkpoint_extra(self):
+        return {"names": [str(self.model.names[i]) for i in sorted(self.model.names)]}
+
+    def _restore_extra(self, ck):
+        if ck.get("names") is not None:
+            self.model.names = dict(enumerate(str(n) for n in ck["names"]))
+
+    def predict_batches(self, batches, stages=4, **kwargs):
+        raise NotImplementedError("predict_batches: the pipelined stages are built and verified for fixed-vocabulary detect models only; a YOLOWorld model, "
+                                  "whose neck and head depend on the vocabulary set at run time, runs through predict()")

@@ -814,6 +814,31 @@ def dysample(mod, x, out=None):
     return out
 
 
+def max_sigmoid_attn(e, p, guide, bias, scale, nh, out=None):
+    """Max-sigmoid attention gate of YOLO-World's C2fAttn (ey_max_sigmoid_attn): e, p (B,C,H,W) NHWC views with C = 32 nh, guide (Bg, n, C)
+    dense in e's dtype with Bg = 1 or B, bias fp32 (nh,), scale fp32 (nh,) or None (1.0) -> p * sigmoid(max_n(e . guide) / sqrt(32) + bias)
+    * scale per pixel and head.  out= may be a channel slot of a concat buffer."""
+    e, p = L.as_nhwc(as_tensor(e)), L.as_nhwc(as_tensor(p))
+    L.require_device(e, "max_sigmoid_attn")
+    _no_block("max_sigmoid_attn")
+    B, c, H, W = e.shape
+    dtype, dev = e.dtype, e.device
+    if tuple(p.shape) != (B, c, H, W) or p.dtype != dtype:
+        raise ValueError(f"max_sigmoid_attn: p is {tuple(p.shape)} {p.dtype}, e is {(B, c, H, W)} {dtype}")
+    if guide.dim() != 3 or guide.shape[2] != c or guide.shape[0] not in (1, B) or guide.dtype != dtype or not guide.is_contiguous() or guide.device != dev:
+        raise ValueError(f"max_sigmoid_attn: guide must be a contiguous (1 or {B}, n, {c}) {dtype} tensor on {dev}, got {tuple(guide.shape)} {guide.dtype}")
+    if out is None:
+        out = L.empty_nhwc(B, c, H, W, dtype, dev)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H, W) or out.dtype != dtype:
+        raise ValueError(f"max_sigmoid_attn: out= must be an NHWC view of shape {(B, c, H, W)} {dtype}")
+    n = guide.shape[1]
+    with _tr("max_sigmoid_attn_kernel", _nb(e, p, out, guide), 2.0 * B * H * W * c * n, note=f"C{c} n{n} {H}x{W}"):
+        L.check(L.lib().ey_max_sigmoid_attn(L.dtype_code(dtype), B, H * W, nh, c // nh if nh else 0, c, n, guide.shape[0], e.data_ptr(), L.cstride(e), p.data_ptr(),
+                                            L.cstride(p), guide.data_ptr(), bias.data_ptr(), None if scale is None else scale.data_ptr(), out.data_ptr(),
+                                            L.cstride(out), L.stream()), "ey_max_sigmoid_attn")
+    return out
+
+
 def deconv2x2(mod, x, deconv, out=None):
     """Dense nn.ConvTranspose2d(Cin, Cout, 2, 2, 0, bias=True) (ey_deconv2x2): (B,Cin,H,W) -> (B,Cout,2H,2W) in one launch; `mod` caches the
     packed weight, `deconv` holds the parameters (Proto.upsample, reference block.py:123)."""

@@ -7,13 +7,13 @@ import math
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F  # only for softplus/tanh on 4+1 scalar parameters at pack time
+import torch.nn.functional as F  # pack time only: softplus/tanh on 4+1 scalar parameters, the text projection of a vocabulary
 
 from .conv import Conv, DSConv, _Packed, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("DFL", "Proto", "SPPF", "C2f", "C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
+__all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNContrastiveHead","C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
@@ -172,6 +172,92 @@ class C3k2(C2f):
     def __init__(self, c1, c2, n=1, c3k=False, e=0.5, g=1, shortcut=True):
         super().__init__(c1, c2, n, shortcut, g, e)
         self.m = nn.ModuleList(C3k(self.c, self.c, 2, shortcut, g) if c3k else Bottleneck(self.c, self.c, shortcut, g) for _ in range(n))
+
+
+class MaxSigmoidAttnBlock(_Packed):
+    """Max-sigmoid attention of YOLO-World (reference block.py:544-576): x = proj_conv(x) gated per pixel and head by
+    sigmoid(max_n(embed . gl(text)) / sqrt(hc) + bias) * scale.  The projected guide gl(text) is constant for a vocabulary: it is computed
+    once (torch, fp32, rounded once to the storage type) and cached per (vocabulary, dtype, device); the gate is ONE launch
+    (ey_max_sigmoid_attn).  The module holds its text (`set_text`); the graph executor never passes it.  Built: no embed conv (c1 == ec,
+    which the parse rule gives every C2fAttn of the worldv2 YAML) and head width hc = 32."""
+
+    def __init__(self, c1, c2, nh=1, ec=128, gc=512, scale=False):
+        super().__init__()
+        self.nh = nh
+        self.hc = c2 // nh
+        if c1 != ec:
+            raise NotImplementedError(f"MaxSigmoidAttnBlock: c1={c1} != ec={ec} needs the embed conv `ec`, which is not built (the worldv2 YAML never has one)")
+        if self.hc != 32 or self.hc * nh != c2:
+            raise NotImplementedError(f"MaxSigmoidAttnBlock: c2={c2} with nh={nh} gives head width hc={c2 / nh:g}; the kernel is built for hc=32")
+        if ec != c2:
+            raise ValueError(f"MaxSigmoidAttnBlock: ec={ec} must equal nh * hc = {c2}")
+        self.ec = None
+        self.gl = nn.Linear(gc, ec)
+        self.bias = nn.Parameter(torch.zeros(nh))
+        self.proj_conv = Conv(c1, c2, k=3, s=1, act=False)
+        self.scale = nn.Parameter(torch.ones(1, nh, 1, 1)) if scale else 1.0
+        self.__dict__["_txt"] = None
+
+    def set_text(self, txt):
+        """txt: (Bg, n, gc) text embeddings (any device / float dtype), Bg = 1 or the batch size; drops the cached guide."""
+        self.__dict__["_txt"] = txt
+        self._cache = {}
+
+    def guide(self, dtype, device):
+        """(Bg, n, nh * hc) projected text in `dtype` on `device`, cached until the text or the parameters change."""
+        txt = self.__dict__.get("_txt")
+        if txt is None:
+            raise RuntimeError("MaxSigmoidAttnBlock: no text set (WorldModel.set_classes / set_text supply it)")
+        if not 1 <= txt.shape[1] <= L.MSA_MAX_TEXTS:
+            raise NotImplementedError(f"MaxSigmoidAttnBlock: {txt.shape[1]} texts; the kernel takes 1 to {L.MSA_MAX_TEXTS}")
+
+        def build():
+            w, b = self.gl.weight.detach().to(device).float(), self.gl.bias.detach().to(device).float()
+            g = F.linear(txt.detach().to(device).float(), w, b).to(dtype).contiguous()
+            sc = self.scale.detach().to(device).float().flatten().contiguous() if torch.is_tensor(self.scale) else None
+            return g, self.bias.detach().to(device).float().contiguous(), sc
+
+        return self._packed(("guide", dtype, device), build)
+
+    def forward(self, x, out=None):
+        x = L.as_nhwc(ops.as_tensor(x))
+        g, bias, sc = self.guide(x.dtype, x.device)
+        if g.shape[0] not in (1, x.shape[0]):
+            raise ValueError(f"MaxSigmoidAttnBlock: text for {g.shape[0]} images, batch of {x.shape[0]}")
+        return ops.max_sigmoid_attn(x, self.proj_conv(x), g, bias, sc, self.nh, out=out)
+
+
+class C2fAttn(C2f):
+    """C2f with a max-sigmoid attention branch on its last hidden map (reference block.py:579-596): one more slot in the concat buffer,
+    (3 + n) c channels.  cv1 writes the first two slots, each Bottleneck its own, proj_conv a scratch map, ey_max_sigmoid_attn the last slot;
+    cv2 reads the buffer."""
+
+    def __init__(self, c1, c2, n=1, ec=128, nh=1, gc=512, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.cv2 = Conv((3 + n) * self.c, c2, 1)
+        self.attn = MaxSigmoidAttnBlock(self.c, self.c, gc=gc, ec=ec, nh=nh)
+
+    def forward(self, x, out=None):
+        B, _, H, W = x.shape  # x may be a VirtualCat (upsample+concat folded into cv1)
+        c, n = self.c, len(self.m)
+        buf = L.empty_nhwc(B, (3 + n) * c, H, W, x.dtype, x.device)
+        self.cv1(x, out=buf[:, :2 * c])
+        for i, m in enumerate(self.m):
+            m(_slot(buf, 1 + i, c), out=_slot(buf, 2 + i, c))
+        self.attn(_slot(buf, 1 + n, c), out=_slot(buf, 2 + n, c))
+        return self.cv2(buf, out=out)
+
+
+class BNContrastiveHead(nn.Module):
+    """Region-text similarity head of WorldDetect (reference block.py:670-692): exp(logit_scale) * <BatchNorm(x), normalize(w)> + bias.
+    Parameter holder: for a fixed vocabulary the whole expression is affine in the class tower's hidden map and WorldDetect folds it into
+    the tower's closing 1x1 conv."""
+
+    def __init__(self, embed_dims):
+        super().__init__()
+        self.norm = nn.BatchNorm2d(embed_dims)
+        self.bias = nn.Parameter(torch.tensor([-10.0]))
+        self.logit_scale = nn.Parameter(-1.0 * torch.ones([]))
 
 
 class SPPF(nn.Module):

@@ -1,4 +1,4 @@
-"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `Pose` (:402-451), `Classify` (:454-476), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
+"""Detection heads, HIP-backed: `Detect` (reference head.py:38-189), `Segment` (:347-369), `OBB` (:372-399), `Pose` (:402-451), `Classify` (:454-476), `WorldDetect` (:479-521), `GF2Detect` (:194-345), `E2EDetect` (:799-824),
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
@@ -14,7 +14,7 @@ from .conv import Conv, DWConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH")
+__all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH", "WorldDetect")
 
 
 class _Plain(_Packed):
@@ -457,6 +457,88 @@ class Segment(Detect):
         y, raw = got
         mc = torch.cat([m.flatten(2) for m in mcs], 2)  # (layout only: the reference's view + cat, head.py:365)
         return torch.cat([y, mc.to(y.dtype)], 1), (raw, mc, p)
+
+
+class WorldDetect(Detect):
+    """YOLO-World head (reference head.py:479-521): Detect whose class tower ends in an `embed`-channel map that a contrastive head `cv4`
+    (BNContrastiveHead, block.py:670-692) compares with the text embeddings.  For a fixed vocabulary of n texts that tail is affine in the
+    tower's hidden map h:
+        logits = s W^ (A (W3 h + b3) + d) + beta = (s W^ A W3) h + (s W^ (A b3 + d) + beta)
+    with W^ the row-normalised text matrix, A / d the eval-mode BatchNorm's scale / shift, s = exp(logit_scale), beta the head bias.  The
+    (n x c3) weight and the bias are computed per level in float64 on the host, once per vocabulary, and run as the class tower's closing 1x1
+    conv: from there on this is a Detect head with nc = n, decode and NMS candidate kernels unchanged.  `set_text` supplies the vocabulary;
+    `nc` and `no` follow it.  with_bn=False (ContrastiveHead: a per-pixel L2 norm, not affine) is not built."""
+
+    max_vocab = 252  # classes the head-decode kernel's LDS tile takes in fp32 storage (ey_head_decode_levels: 128 anchors x (64 + nc) logits in 160 KiB)
+
+    def __init__(self, nc=80, embed=512, with_bn=False, ch=()):
+        super().__init__(nc, ch)
+        if not with_bn:
+            raise NotImplementedError("WorldDetect(with_bn=False): ContrastiveHead (per-pixel L2 normalisation, yolov8-world.yaml) is not built; "
+                                      "the worldv2 YAML uses with_bn=True")
+        from .block import BNContrastiveHead
+        c3 = max(ch[0], min(self.nc, 100))
+        self.embed = embed
+        self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, embed, 1)) for x in ch)
+        self.cv4 = nn.ModuleList(BNContrastiveHead(embed) for _ in ch)
+        self.__dict__["_txt"] = None
+
+    def set_text(self, txt):
+        """txt: (1, n, embed) text embeddings (the model's original text, not one an ImagePoolingAttn refined); sets nc / no and drops the folds."""
+        if txt.dim() != 3 or txt.shape[0] != 1 or txt.shape[2] != self.embed:
+            raise ValueError(f"WorldDetect: text must be (1, n, {self.embed}), got {tuple(txt.shape)}")
+        n = int(txt.shape[1])
+        if not 1 <= n <= self.max_vocab:
+            raise NotImplementedError(f"WorldDetect: a vocabulary of {n} texts; the head decode and NMS kernels take 1 to {self.max_vocab} classes")
+        self.__dict__["_txt"] = txt
+        self.nc = n
+        self.no = n + self.reg_max * 4
+        self._reset_caches()
+        self.__dict__["_mask_key"] = None
+
+    def folded_tail(self, i):
+        """fp32 (weight (n, c3, 1, 1), bias (n,)) of level i's class tail folded over the current vocabulary (float64 arithmetic)."""
+        txt = self.__dict__.get("_txt")
+        if txt is None:
+            raise RuntimeError("WorldDetect: no text set (WorldModel.set_classes / set_text supply it)")
+        conv, head = self.cv3[i][2], self.cv4[i]
+        bn = head.norm
+        dev = conv.weight.device
+        f = lambda t: t.detach().to(dev).double()  # noqa: E731
+        w3, b3 = f(conv.weight).flatten(1), f(conv.bias)
+        a = f(bn.weight) / torch.sqrt(f(bn.running_var) + bn.eps)
+        d = f(bn.bias) - f(bn.running_mean) * a
+        wn = nn.functional.normalize(f(txt)[0], dim=-1, p=2)
+        s = torch.exp(f(head.logit_scale))
+        w = s * ((wn * a) @ w3)
+        b = s * (wn @ (a * b3 + d)) + f(head.bias)
+        return w.float().view(*w.shape, 1, 1), b.float()
+
+    def _fold(self, i):
+        t = self._tails.get(("fold", i))
+        if t is None:
+            t = self._tails[("fold", i)] = _Packed()
+        return t
+
+    def _cls_tower(self, i, x, raw, out=None):
+        """class logits of the current vocabulary -> raw[:, 64:] (or `out`): two 3x3 convs, then the folded tail as a 1x1 conv."""
+        c = self.cv3[i]
+        if out is None:
+            out = raw[:, 4 * self.reg_max:]
+        ops.conv2d(self._fold(i), [c[1](c[0](x))], lambda: self.folded_tail(i), 1, 1, 0, L.ACT_NONE, out=out)
+
+    def forward(self, x, nms=None, towers_only=False):
+        if self.__dict__.get("_txt") is None:
+            raise RuntimeError("WorldDetect: no text set (WorldModel.set_classes / set_text supply it)")
+        if self.end2end:
+            raise NotImplementedError("WorldDetect: end2end heads are not built")
+        return super().forward(x, nms=nms, towers_only=towers_only)
+
+    def bias_init(self):
+        """reference head.py:523-530: only the box towers' biases (the class logits' offset is the contrastive head's bias)."""
+        for a in self.cv2:
+            a[-1].bias.data[:] = 1.0
+        self._reset_caches()
 
 
 class OBB(Detect):

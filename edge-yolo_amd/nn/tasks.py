@@ -13,17 +13,17 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample)
+from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
-_REPEAT_MODULES = {C2f, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
-_HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
+_REPEAT_MODULES = {C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
+_HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
 
 
 def guess_model_scale(model_path):
@@ -124,6 +124,9 @@ def parse_model(d, ch, verbose=False):
             c1, c2 = ch[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
+            if m is C2fAttn:  # embed channels and head count scale with the width (reference tasks.py:1037-1041)
+                args[1] = make_divisible(min(args[1], max_channels // 2) * width, 8)
+                args[2] = int(max(round(min(args[2], max_channels // 2 // 32)) * width, 1) if args[2] > 1 else args[2])
             args = [c1, c2, *args[1:]]
             if m in _REPEAT_MODULES:
                 args.insert(2, n)
@@ -530,6 +533,87 @@ class PoseModel(DetectionModel):
             cfg["kpt_shape"] = data_kpt_shape
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
         self.kpt_shape = self.model[-1].kpt_shape  # (the reference's AutoBackend exposes it as model.kpt_shape: pose/predict.py:51)
+
+
+class WorldModel(DetectionModel):
+    """YOLO-World v2 model built from a YAML (reference tasks.py:624-695): open-vocabulary detection, the classes are text embeddings chosen at
+    run time.  `txt_feats` (1, n, 512) is a persistent buffer, so it travels in state_dict and in tensor-only checkpoints; its initial value is
+    seeded.  The text is constant between two `set_classes` calls, so it lives in the modules that use it (every C2fAttn's projected guide,
+    WorldDetect's folded class tail) and the graph executor runs the model like any detect model.  The CLIP text encoder is not part of the
+    build: `set_classes` takes the embeddings."""
+
+    def __init__(self, cfg="yolov8s-worldv2.yaml", ch=3, nc=None, verbose=False):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        gen = torch.Generator().manual_seed(0)
+        self.register_buffer("txt_feats", torch.randn(1, self.yaml["nc"], 512, generator=gen), persistent=True)  # features placeholder
+        self.clip_model = None
+        self._push_text(self.txt_feats)
+        self.register_load_state_dict_post_hook(lambda m, _keys: m._push_text(m.txt_feats))
+
+    def _text_modules(self):
+        return [m for m in self.model if isinstance(m, (C2fAttn, WorldDetect))]
+
+    def _push_text(self, txt):
+        """Hand `txt` (1, n, 512) to every C2fAttn (the current text) and to WorldDetect (the original text; equal, as no ImagePoolingAttn is
+        built); each drops what it derived from the old one."""
+        for m in self._text_modules():
+            (m.attn if isinstance(m, C2fAttn) else m).set_text(txt)
+        self.__dict__["_block_caches"] = {}
+
+    def _apply(self, fn, *args, **kwargs):
+        self = super()._apply(fn, *args, **kwargs)
+        if "txt_feats" in self._buffers:  # (moved / converted with the parameters: the modules hold the old tensor)
+            self._push_text(self.txt_feats)
+        return self
+
+    def _store_text(self, txt):
+        old = self.txt_feats
+        self._buffers["txt_feats"] = txt.detach().to(device=old.device, dtype=old.dtype).contiguous()
+        self._push_text(self.txt_feats)  # (yaml["nc"] stays the constructed class count: the towers' width c3 depends on it)
+
+    def set_classes(self, text, txt_feats=None):
+        """Set the vocabulary: `text` the n class names, `txt_feats` their embeddings, (n, 512) or (1, n, 512), as the CLIP ViT-B/32 text
+        encoder gives them.  They are L2-normalised as the reference does behind CLIP (tasks.py:650), stored, and pushed to the modules;
+        model[-1].nc and `names` follow.  Without embeddings: NotImplementedError (no text encoder in this build)."""
+        text = list(text)
+        if txt_feats is None:
+            raise NotImplementedError("WorldModel.set_classes: the CLIP text encoder is not part of the build; pass the embeddings of the class names "
+                                      "as txt_feats=(n, 512)")
+        t = torch.as_tensor(txt_feats).detach().float()
+        if t.dim() == 3 and t.shape[0] != 1:
+            raise NotImplementedError(f"WorldModel.set_classes: per-image vocabularies {tuple(t.shape)} are not built (one vocabulary for the batch)")
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() != 3 or t.shape[2] != self.txt_feats.shape[2] or t.shape[1] != len(text):
+            raise ValueError(f"WorldModel.set_classes: {len(text)} names need embeddings of shape ({len(text)}, {self.txt_feats.shape[2]}), got {tuple(txt_feats.shape)}")
+        t = t / t.norm(p=2, dim=-1, keepdim=True)
+        self._store_text(t)
+        self.names = dict(enumerate(text))
+
+    def load(self, weights, verbose=False):
+        """BaseModel.load; a checkpoint's `txt_feats` of another vocabulary size replaces the buffer first (stored as saved, not re-normalised)."""
+        sd = weights["state_dict"] if isinstance(weights, dict) and "state_dict" in weights else weights
+        t = sd.get("txt_feats")
+        if t is not None and t.dim() == 3 and t.shape[0] == 1 and t.shape[2] == self.txt_feats.shape[2] and t.shape[1] != self.txt_feats.shape[1]:
+            self._store_text(t)
+            self.names = {i: f"{i}" for i in range(t.shape[1])}
+        return super().load(weights, verbose=verbose)
+
+    def predict(self, x, profile=False, visualize=False, txt_feats=None, augment=False, embed=None, head_nms=None):
+        """txt_feats: a (1, n, 512) override of the stored text for this call, n = the current vocabulary size (used as given, as the
+        reference's predict does, tasks.py:669).  A per-image (B, n, 512) text is not built at this level (ey_max_sigmoid_attn takes one)."""
+        if txt_feats is None:
+            return super().predict(x, profile=profile, visualize=visualize, augment=augment, embed=embed, head_nms=head_nms)
+        t = torch.as_tensor(txt_feats)
+        if t.dim() != 3 or t.shape[1:] != self.txt_feats.shape[1:]:
+            raise ValueError(f"WorldModel.predict: txt_feats must be (1, {self.txt_feats.shape[1]}, {self.txt_feats.shape[2]}), got {tuple(t.shape)}")
+        if t.shape[0] != 1:
+            raise NotImplementedError(f"WorldModel.predict: per-image text {tuple(t.shape)} is not built at the model level (one vocabulary for the batch)")
+        self._push_text(t.detach())
+        try:
+            return super().predict(x, profile=profile, visualize=visualize, augment=augment, embed=embed, head_nms=head_nms)
+        finally:
+            self._push_text(self.txt_feats)
 
 
 class ClassificationModel(BaseModel):

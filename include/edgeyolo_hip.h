@@ -316,6 +316,21 @@ int ey_unpool2_layernorm(int dtype, int B, int Hs, int Ws, int H, int W, int C, 
 int ey_dysample(int dtype, int B, int H, int W, int C, int scale, int groups, const void* x, int x_cstride, const void* w_offset, const float* bias,
                 const void* w_scope, const float* init_pos, void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- YOLO-World: max-sigmoid attention of C2fAttn (reference ultralytics/nn/modules/block.py:558-576, behind the `gl` linear and proj_conv).
+ *   aw[b,m,p]     = sigmoid( max_n( sum_c e[b,p,m*hc+c] * g[bg,n,m*hc+c] ) / sqrt(hc) + bias[m] ) * scale[m]
+ *   y[b,p,m*hc+c] = p[b,p,m*hc+c] * aw[b,m,p]
+ * e, p, y: channel windows [B,HW,*] of NHWC buffers in `dtype` with their pixel strides, C = nh * hc channels used; only y's window is
+ * written and nothing outside e's and p's windows is read.  g: DEVICE [Bg][n][C] in `dtype`, dense; Bg = 1 (one vocabulary for the batch,
+ * bg = 0) or Bg = B (bg = b).  bias: DEVICE fp32 [nh]; scale: DEVICE fp32 [nh] or NULL (1.0).  The dot accumulates in fp32 (f16: one
+ * mfma_f32_16x16x32_f16 per 16 pixels x 16 texts; fp32: an fmaf chain), the division is by the fp32 value of sqrt(hc), the tail is
+ * fp32 and rounds once to storage.  1 <= n <= EY_MSA_MAX_TEXTS; text tiles past n repeat text n-1, so padding never enters the maximum.
+ * No atomics and no workspace: deterministic and graph-capturable.  EY_EINVAL for a null pointer, n < 1 or a Bg other than 1 or B;
+ * EY_EUNSUPPORTED (before anything is launched) for hc != 32, C != 32 * nh, n > EY_MSA_MAX_TEXTS, e / p / y / g not 16-byte aligned
+ * windows, or a view of 2 GiB and more. */
+#define EY_MSA_MAX_TEXTS 4096
+int ey_max_sigmoid_attn(int dtype, int B, int HW, int nh, int hc, int C, int n, int Bg, const void* e, int e_cstride, const void* p, int p_cstride,
+                        const void* g, const float* bias, const float* scale, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- Instance segmentation: mask assembly (utils/ops.py:644-693 process_mask + crop_mask, called by models/yolo/segment/predict.py:50-57).
  * For each of N kept detections (over the whole batch):
  *   v[r][c]   = sum_k coef_n[k] * proto[img_n, r, c, k]        fp32, k ascending, on the low-resolution grid mh x mw

@@ -2,6 +2,7 @@
 """Weight bridge, REFERENCE side: turn a checkpoint written by the reference trainer (a pickled module object,
 engine/trainer.py:513-546; read back by nn/tasks.py:815-955) into the tensor-only format `edge_yolo_amd.YOLO(path)` loads with
 `torch.load(weights_only=True)`:  {"yaml": <model yaml dict>, "nc": int, "fused": bool, "state_dict": {reference keys: fp32 tensors}}.
+A YOLO-World checkpoint also gets its text embeddings (state_dict key `txt_feats`) and a `names` list (`edge_yolo_amd.YOLOWorld(path)`).
 
 Run it where the reference package (`ultralytics`, this fork) is importable -- unpickling a reference checkpoint executes its module
 code, which is why edge-yolo_amd never does it:
@@ -50,7 +51,13 @@ def export(src, dst):
     first_conv = next(k for k in sd if k.endswith("conv.weight"))
     fused = first_conv.replace("conv.weight", "bn.weight") not in sd  # BaseModel.fuse() deleted the BatchNorms (tasks.py:214-242)
     _record_wavelet_kwargs(model, cfg)
-    torch.save({"yaml": cfg, "nc": int(cfg["nc"]), "fused": bool(fused), "state_dict": sd}, dst)
+    extra = {}
+    if type(model).__name__ == "WorldModel":  # YOLO-World: the text is a plain attribute there (tasks.py:629,651); edge-yolo_amd keeps it as the buffer `txt_feats`
+        t = model.txt_feats.detach().float()
+        sd["txt_feats"] = t.reshape(1, -1, t.shape[-1]).clone()
+        names = getattr(model, "names", None) or {}
+        extra["names"] = [str(names[i]) for i in sorted(names)] if isinstance(names, dict) else [str(n) for n in names]
+    torch.save({"yaml": cfg, "nc": int(cfg["nc"]), "fused": bool(fused), "state_dict": sd, **extra}, dst)
     return len(sd), fused
 
 
