@@ -60,6 +60,12 @@ class BlockStage(C.Structure):
     ]
 
 
+class CBFuseSrc(C.Structure):
+    """ey_cbfuse_src (include/edgeyolo_hip.h): one source map of ey_cbfuse."""
+    _fields_ = [("ptr", C.c_void_p), ("cstride", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32)]
+
+
+CBFUSE_MAX = 6  # EY_CBFUSE_MAX: the most sources ey_cbfuse takes
 BLK_CONV, BLK_DW, BLK_DWT, BLK_POOL, BLK_LINATTN = range(5)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 # name -> (restype, argtypes): every symbol include/edgeyolo_hip.h declares
@@ -157,6 +163,8 @@ SIGNATURES = {
     "ey_classify_pool": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ey_classify_linear_softmax": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ey_max_sigmoid_attn": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_adown_pool": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_cbfuse": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "ey_classify_transform": (_i, [_i, _vp, _i, _i, _i, _i, C.c_long, _vp, _i, _i, _vp]),
 }
 

@@ -231,6 +231,9 @@ class Model(torch.nn.Module):
         if self.task != "detect":
             raise NotImplementedError(f"predict_batches: pipelined throughput is built for the detect task only, not '{self.task}' (use predict(); "
                                       "built tasks: detect, segment, obb, pose, classify)")
+        if isinstance(self.model.model[0], torch.nn.Identity):
+            raise NotImplementedError("predict_batches: layer 0 of this model is nn.Identity, not a conv (yolov9e): a later layer reads the input image itself "
+                                      "and the CBLinear layers hand tuples on, which the pipeline stages' static buffers do not carry; use predict()")
         args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None}
         unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "cuts"}
         if unknown:

@@ -786,6 +786,70 @@ def avgpool2(x, out=None):
     return out
 
 
+def _slot_view(t, what, shape, dtype):
+    """`t` must be an NHWC view of `shape` and `dtype` whose channel window starts on a 16-byte boundary with a 16-byte pixel stride."""
+    if not L.is_nhwc_view(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+        raise ValueError(f"{what} must be an NHWC view of shape {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
+    es = t.element_size()
+    if t.shape[1] % 8 or (L.cstride(t) * es) % 16 or t.data_ptr() % 16:
+        raise ValueError(f"{what}: {t.shape[1]} channels at pixel stride {L.cstride(t)}: channel counts, slot offsets and strides must be multiples of 8 elements")
+    return t
+
+
+def adown_pool(x, c_avg=None, a=None, m=None):
+    """Pooling front end of ADown / AConv (ey_adown_pool): A = avg_pool2d(x, 2, 1, 0); returns (a, m) with a = A[:, :c_avg] (B,c_avg,H-1,W-1)
+    and m = max_pool2d(A[:, c_avg:], 3, 2, 1) (B,C-c_avg,H//2,W//2), m None when c_avg == C (the default, AConv).  x, a= and m= may be
+    channel slots of larger NHWC buffers."""
+    B, c, H, W = x.shape
+    c_avg = c if c_avg is None else int(c_avg)
+    if H < 2 or W < 2:
+        raise ValueError(f"adown_pool: a {H}x{W} map has no 2x2 window")
+    if c % 8 or c_avg % 8 or not 0 < c_avg <= c:
+        raise ValueError(f"adown_pool: C={c}, c_avg={c_avg}: channel counts and the split must be multiples of 8 with 0 < c_avg <= C")
+    L.require_device(x, "adown_pool")
+    _no_block("adown pool")
+    x = L.as_nhwc(as_tensor(x))
+    _slot_view(x, "adown_pool: x", x.shape, x.dtype)
+    a = L.empty_nhwc(B, c_avg, H - 1, W - 1, x.dtype, x.device) if a is None else _slot_view(a, "adown_pool: a=", (B, c_avg, H - 1, W - 1), x.dtype)
+    if c_avg == c:
+        if m is not None:
+            raise ValueError("adown_pool: m= given but c_avg == C leaves no channels to max-pool")
+    else:
+        m = (L.empty_nhwc(B, c - c_avg, H // 2, W // 2, x.dtype, x.device) if m is None
+             else _slot_view(m, "adown_pool: m=", (B, c - c_avg, H // 2, W // 2), x.dtype))
+    with _tr("adown_kernel", _nb(x, a, m), 4.0 * a.numel() + (13.0 * m.numel() if m is not None else 0.0), note=f"C{c} split{c_avg} {H}x{W}"):
+        L.check(L.lib().ey_adown_pool(L.dtype_code(x.dtype), B, H, W, c, c_avg, x.data_ptr(), L.cstride(x), a.data_ptr(), L.cstride(a),
+                                      m.data_ptr() if m is not None else None, L.cstride(m) if m is not None else 0, L.stream()), "ey_adown_pool")
+    return a, m
+
+
+def cbfuse(xs, out=None):
+    """CBFuse (ey_cbfuse): every map of `xs` (1 to 6 NHWC views with equal batch and channel counts) nearest-resized to the LAST one's size and
+    summed in fp32 in list order, one rounding -> (B,C,H,W).  The maps may be channel slices of larger buffers (CBLinear's outputs)."""
+    xs = list(xs)
+    if not 1 <= len(xs) <= L.CBFUSE_MAX:
+        raise ValueError(f"cbfuse: {len(xs)} sources; the kernel takes 1 to {L.CBFUSE_MAX}")
+    if xs[-1].shape[1] % 8:
+        raise ValueError(f"cbfuse: C={xs[-1].shape[1]} must be a multiple of 8")
+    L.require_device(xs[-1], "cbfuse")
+    _no_block("cbfuse")
+    xs = [L.as_nhwc(as_tensor(t)) for t in xs]
+    B, c, H, W = xs[-1].shape
+    dt = xs[-1].dtype
+    for i, t in enumerate(xs):
+        if t.shape[0] != B or t.shape[1] != c or t.dtype != dt:
+            raise ValueError(f"cbfuse: source {i} is {tuple(t.shape)} {t.dtype}, the target {tuple(xs[-1].shape)} {dt}")
+        _slot_view(t, f"cbfuse: source {i}", t.shape, dt)
+    out = L.empty_nhwc(B, c, H, W, dt, xs[-1].device) if out is None else _slot_view(out, "cbfuse: out=", (B, c, H, W), dt)
+    srcs = (L.CBFuseSrc * len(xs))()
+    for s, t in zip(srcs, xs):
+        s.ptr, s.cstride, s.Hi, s.Wi = t.data_ptr(), L.cstride(t), t.shape[2], t.shape[3]
+    with _tr("cbfuse_kernel", _nb(*xs, out), float(len(xs) - 1) * out.numel(), note=f"C{c} {H}x{W} n{len(xs)}"):
+        L.check(L.lib().ey_cbfuse(L.dtype_code(dt), B, H, W, c, len(xs), ctypes.cast(srcs, ctypes.c_void_p), out.data_ptr(), L.cstride(out), L.stream()),
+                "ey_cbfuse")
+    return out
+
+
 def dysample(mod, x, out=None):
     """DySample x2 (ey_dysample): (B,C,H,W) -> (B,C,2H,2W), offsets and bilinear gather in one launch; `mod` supplies dense_weights(),
     init_pos and groups.  out= may be a channel slot of a concat buffer."""

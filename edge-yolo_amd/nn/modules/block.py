@@ -9,14 +9,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F  # pack time only: softplus/tanh on 4+1 scalar parameters, the text projection of a vocabulary
 
-from .conv import Conv, DSConv, _Packed, fold_bn
+from .conv import Conv, DSConv, RepConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
 __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNContrastiveHead","C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
-           "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel")
+           "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
+           "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse")
 
 
 def _slot(buf, i, c):
@@ -1181,3 +1182,232 @@ class FullPAD_Tunnel(_Packed):
         C = t.shape[1]
         gamma = self._packed(("gate", t.dtype, t.device, C), lambda: self.gate.detach().to(t.dtype).float().expand(C).to(t.device).contiguous())
         return ops.scale_add_channels(a, gamma, t, out=out)
+
+
+# ----------------------------------------------------------------------------------------------- YOLOv9 (GELAN)
+def _ceil8(c):
+    return (c + 7) // 8 * 8
+
+
+def _pad_folded(fn, out_segs, in_segs):
+    """The (BN-folded) weights of `fn()` re-laid on padded channel segments: out_segs / in_segs = [(true width, padded width), ...] in channel
+    order; the pad rows, pad columns and pad biases are zero.  yolov9m's hidden widths (60, 90, 180) are no multiples of 8, which the MFMA conv
+    and 16-byte channel slots need: its maps carry zero channels at the end of every slot instead (SiLU(0) = 0, so they stay exactly zero and
+    add exactly nothing downstream)."""
+    def build():
+        w, b = fn()
+        wp = w.new_zeros((sum(p for _, p in out_segs), sum(p for _, p in in_segs)) + tuple(w.shape[2:]))
+        bp = b.new_zeros(wp.shape[0])
+        ro = so = 0
+        for to, po in out_segs:
+            ci = si = 0
+            for ti, pi in in_segs:
+                wp[ro:ro + to, ci:ci + ti] = w[so:so + to, si:si + ti]
+                ci, si = ci + pi, si + ti
+            bp[ro:ro + to] = b[so:so + to]
+            ro, so = ro + po, so + to
+        return wp, bp
+    return build
+
+
+def _conv_padded(conv, x, out, res=None):
+    """A Conv / RepConv whose input and output channels are zero-padded at the end to the widths of `x` and `out`."""
+    c = conv.conv if hasattr(conv, "conv") else conv.conv1.conv
+    k = c.kernel_size[0]
+    return ops.conv2d(conv, [x], _pad_folded(conv.folded, [(c.out_channels, out.shape[1])], [(c.in_channels, x.shape[1])]), k, 1, k // 2, _act_code(conv.act),
+                      out=out, res=res, tag=f"pad{x.shape[1]}_{out.shape[1]}")
+
+
+class RepBottleneck(Bottleneck):
+    """reference block.py:695-702: a Bottleneck whose first conv is a RepConv."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
+        super().__init__(c1, c2, shortcut, g, k, e)
+        c_ = int(c2 * e)
+        self.cv1 = RepConv(c1, c_, k[0], 1)
+
+
+class RepCSP(C3):
+    """reference block.py:705-712: C3 over RepBottlenecks (same slot scheme as C3: the chain rewrites slot 0 in place)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(RepBottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)))
+
+    def forward(self, x, out=None, cv12=None):
+        c1, c_, c2 = self.cv1.conv.in_channels, self.cv1.conv.out_channels, self.cv3.conv.out_channels
+        if c_ % 8 == 0 and x.shape[1] == c1 and (out is None or out.shape[1] == c2):
+            return super().forward(x, out=out, cv12=cv12)
+        # zero-padded widths (see _pad_folded): x and out may carry pad channels at the end, the hidden width is padded to a multiple of 8
+        if out is None:
+            raise NotImplementedError(f"RepCSP: hidden width {c_} is no multiple of 8; built inside RepNCSPELAN4, which supplies the padded output")
+        x = L.as_nhwc(x)
+        B, xin, H, W = x.shape
+        cp = _ceil8(c_)
+        buf = ops.conv2d(self, [x], _pad_folded(self._cv12, [(c_, cp), (c_, cp)], [(c1, xin)]), 1, 1, 0, L.ACT_SILU, tag=f"cv12pad{xin}")
+        slot = buf[:, :cp]
+        for b in self.m:
+            h = _conv_padded(b.cv1, slot, L.empty_nhwc(B, cp, H, W, x.dtype, x.device))
+            _conv_padded(b.cv2, h, slot, res=slot if b.add else None)
+        return ops.conv2d(self.cv3, [buf], _pad_folded(self.cv3.folded, [(c2, out.shape[1])], [(c_, cp), (c_, cp)]), 1, 1, 0, L.ACT_SILU, out=out,
+                          tag=f"pad{out.shape[1]}")
+
+
+class RepNCSPELAN4(nn.Module):
+    """CSP-ELAN (reference block.py:715-737).  One concat buffer of c3 + 2 c4 channels: cv1 writes the first two slots (c3), cv2 reads the
+    second of them and writes the next c4 channels, cv3 reads those and writes the last c4, cv4 reads the buffer in place."""
+
+    def __init__(self, c1, c2, c3, c4, n=1):
+        super().__init__()
+        self.c = c3 // 2
+        self.cv1 = Conv(c1, c3, 1, 1)
+        self.cv2 = nn.Sequential(RepCSP(c3 // 2, c4, n), Conv(c4, c4, 3, 1))
+        self.cv3 = nn.Sequential(RepCSP(c4, c4, n), Conv(c4, c4, 3, 1))
+        self.cv4 = Conv(c3 + (2 * c4), c2, 1, 1)
+
+    @staticmethod
+    def _branch(m, x, out):
+        if not isinstance(m, nn.Sequential):
+            return m(x, out=out)
+        B, _, H, W = x.shape  # (RepCSP gets its output buffer: a hidden width that is no multiple of 8 pads inside it, see _pad_folded)
+        return m[1](m[0](x, out=L.empty_nhwc(B, m[0].cv3.conv.out_channels, H, W, x.dtype, x.device)), out=out)
+
+    def forward(self, x, out=None):
+        B, _, H, W = x.shape  # x may be a VirtualCat (upsample+concat folded into cv1)
+        c3 = self.cv1.conv.out_channels
+        c, c4 = self.c, (self.cv4.conv.in_channels - c3) // 2
+        if c % 8 or c4 % 8:
+            return self._forward_padded(x, out, c, c4)
+        buf = L.empty_nhwc(B, c3 + 2 * c4, H, W, x.dtype, x.device)
+        self.cv1(x, out=buf[:, :c3])
+        self._branch(self.cv2, buf[:, c3 - self.c:c3], buf[:, c3:c3 + c4])
+        self._branch(self.cv3, buf[:, c3:c3 + c4], buf[:, c3 + c4:])
+        return self.cv4(buf, out=out)
+
+    def _forward_padded(self, x, out, c, c4):
+        """Widths that are no multiples of 8 (yolov9m: 180 | 180 | 180 | 180): every slot of the buffer is padded with zero channels to the next
+        multiple of 8 (see _pad_folded); cv4's weights skip them."""
+        B, _, H, W = x.shape
+        hp, qp = _ceil8(c), _ceil8(c4)
+        buf = L.empty_nhwc(B, 2 * hp + 2 * qp, H, W, x.dtype, x.device)
+        c1 = self.cv1.conv.in_channels
+        ops.conv2d(self.cv1, [x], _pad_folded(self.cv1.folded, [(c, hp), (c, hp)], [(c1, c1)]), 1, 1, 0, _act_code(self.cv1.act), out=buf[:, :2 * hp], tag="pad")
+        src = buf[:, hp:2 * hp]
+        for i, m in enumerate((self.cv2, self.cv3)):
+            dst = buf[:, 2 * hp + i * qp:2 * hp + (i + 1) * qp]
+            if isinstance(m, nn.Sequential):
+                _conv_padded(m[1], m[0](src, out=L.empty_nhwc(B, qp, H, W, x.dtype, x.device)), dst)
+            else:
+                _conv_padded(m, src, dst)
+            src = dst
+        c2 = self.cv4.conv.out_channels
+        return ops.conv2d(self.cv4, [buf], _pad_folded(self.cv4.folded, [(c2, c2)], [(c, hp), (c, hp), (c4, qp), (c4, qp)]), 1, 1, 0, _act_code(self.cv4.act),
+                          out=out, tag="pad")
+
+    forward_split = forward
+
+
+class ELAN1(RepNCSPELAN4):
+    """reference block.py:740-750: RepNCSPELAN4 whose two branches are plain 3x3 convs."""
+
+    def __init__(self, c1, c2, c3, c4):
+        super().__init__(c1, c2, c3, c4)
+        self.c = c3 // 2
+        self.cv1 = Conv(c1, c3, 1, 1)
+        self.cv2 = Conv(c3 // 2, c4, 3, 1)
+        self.cv3 = Conv(c4, c4, 3, 1)
+        self.cv4 = Conv(c3 + (2 * c4), c2, 1, 1)
+
+
+class AConv(nn.Module):
+    """reference block.py:753-764: avg_pool2d(x, 2, 1, 0) (ey_adown_pool, AConv mode) -> 3x3 stride-2 conv."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 3, 2, 1)
+
+    def forward(self, x, out=None):
+        a, _ = ops.adown_pool(x)
+        return self.cv1(a, out=out)
+
+
+class ADown(nn.Module):
+    """reference block.py:767-784.  ONE ey_adown_pool launch gives the averaged first half and the averaged-then-max-pooled second half (the
+    averaged second half is never written); cv1 (3x3 stride 2) and cv2 (1x1) write the two halves of the output buffer."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.c = c2 // 2
+        self.cv1 = Conv(c1 // 2, self.c, 3, 2, 1)
+        self.cv2 = Conv(c1 // 2, self.c, 1, 1, 0)
+
+    def forward(self, x, out=None):
+        B, c1, H, W = x.shape
+        a, m = ops.adown_pool(x, c1 // 2)
+        if out is None:
+            out = L.empty_nhwc(B, 2 * self.c, H // 2, W // 2, x.dtype, x.device)
+        self.cv1(a, out=out[:, :self.c])
+        self.cv2(m, out=out[:, self.c:])
+        return out
+
+
+class SPPELAN(nn.Module):
+    """reference block.py:787-804: cv1 -> three chained 5x5 max-pools (ONE ey_sppf_pool launch into slots 1-3 of a 4 c3 buffer) -> cv5.
+    cv2-cv4 are the reference's nn.MaxPool2d children (no parameters; never called)."""
+
+    def __init__(self, c1, c2, c3, k=5):
+        super().__init__()
+        if k != 5:
+            raise NotImplementedError("SPPELAN pooling kernel is built for k=5 (the only value the YAMLs use)")
+        self.c = c3
+        self.cv1 = Conv(c1, c3, 1, 1)
+        self.cv2 = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
+        self.cv3 = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
+        self.cv4 = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
+        self.cv5 = Conv(4 * c3, c2, 1, 1)
+
+    def forward(self, x, out=None):
+        x = L.as_nhwc(x)
+        B, _, H, W = x.shape
+        c = self.c
+        buf = L.empty_nhwc(B, 4 * c, H, W, x.dtype, x.device)
+        self.cv1(x, out=buf[:, :c])
+        ops.sppf_pool(_slot(buf, 0, c), _slot(buf, 1, c), _slot(buf, 2, c), _slot(buf, 3, c))
+        return self.cv5(buf, out=out)
+
+
+class CBLinear(_Packed):
+    """reference block.py:807-818: ONE 1x1 conv with bias (no BatchNorm, no activation); the outputs are channel-slice views of it."""
+
+    def __init__(self, c1, c2s, k=1, s=1, p=None, g=1):
+        super().__init__()
+        if k != 1 or s != 1 or g != 1:
+            raise NotImplementedError(f"CBLinear(k={k}, s={s}, g={g}): only the pointwise form (k=1, s=1, g=1) of the YOLOv9 YAMLs is built")
+        self.c2s = list(c2s)
+        self.conv = nn.Conv2d(c1, sum(c2s), k, s, k // 2 if p is None else p, groups=g, bias=True)
+
+    def _folded(self):
+        return fold_bn(self.conv.weight, self.conv.bias, None)
+
+    def forward(self, x):
+        y = ops.conv2d(self, [x], self._folded, 1, 1, 0, L.ACT_NONE)
+        outs, o = [], 0
+        for c in self.c2s:
+            outs.append(y[:, o:o + c])
+            o += c
+        return tuple(outs)
+
+
+class CBFuse(nn.Module):
+    """reference block.py:821-833: sum of xs[i][idx[i]] nearest-resized to the last input's size, plus that input -- ONE ey_cbfuse launch
+    (fp32 sum in list order, one rounding)."""
+
+    def __init__(self, idx):
+        super().__init__()
+        self.idx = idx
+
+    def forward(self, xs):
+        if len(xs) > L.CBFUSE_MAX:
+            raise NotImplementedError(f"CBFuse: {len(xs)} inputs; ey_cbfuse takes at most {L.CBFUSE_MAX}")
+        return ops.cbfuse([x[self.idx[i]] for i, x in enumerate(xs[:-1])] + [xs[-1]])

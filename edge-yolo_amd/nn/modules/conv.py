@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Conv", "DWConv", "DSConv", "Concat", "Upsample", "autopad")
+__all__ = ("Conv", "DWConv", "DSConv", "RepConv", "Concat", "Upsample", "autopad")
 
 
 def autopad(k, p=None, d=1):
@@ -137,6 +137,65 @@ class DWConv(Conv):
 
     def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
+
+
+class RepConv(_Packed):
+    """RepVGG-style conv of the YOLOv9 RepBottleneck (reference conv.py:196-297): act(conv1 3x3 + conv2 1x1 [+ bn identity]), each branch a
+    Conv(act=False).  The three branches are linear in x, so the HIP path always runs ONE 3x3 conv on the reference's
+    `get_equivalent_kernel_bias` weights, folded in fp32 when they are packed -- before `fuse_convs()` (from conv1 / conv2 / bn) and after it
+    (from the single `conv` it leaves)."""
+
+    default_act = nn.SiLU()
+
+    def __init__(self, c1, c2, k=3, s=1, p=1, g=1, d=1, act=True, bn=False, deploy=False):
+        super().__init__()
+        assert k == 3 and p == 1
+        self.g, self.c1, self.c2 = g, c1, c2
+        self.act = self.default_act if act is True else act if isinstance(act, nn.Module) else nn.Identity()
+        self.bn = nn.BatchNorm2d(num_features=c1) if bn and c2 == c1 and s == 1 else None
+        self.conv1 = Conv(c1, c2, k, s, p=p, g=g, act=False)
+        self.conv2 = Conv(c1, c2, 1, s, p=(p - k // 2), g=g, act=False)
+
+    def get_equivalent_kernel_bias(self):
+        """3x3 kernel + zero-padded 1x1 kernel + identity kernel, and the sum of their biases, BatchNorms folded, in fp32 (reference :228-269)."""
+        k3, b3 = self.conv1.folded()
+        k1, b1 = self.conv2.folded()
+        k, b = k3 + nn.functional.pad(k1, [1, 1, 1, 1]), b3 + b1
+        if getattr(self, "bn", None) is not None:
+            cg = self.c1 // self.g
+            kid = torch.zeros((self.c1, cg, 3, 3), dtype=torch.float32, device=k.device)
+            kid[torch.arange(self.c1), torch.arange(self.c1) % cg, 1, 1] = 1.0
+            kid, bid = fold_bn(kid, None, self.bn)
+            k, b = k + kid, b + bid
+        return k, b
+
+    def folded(self):
+        if hasattr(self, "conv"):
+            return self.conv.weight.detach().float(), self.conv.bias.detach().float()
+        return self.get_equivalent_kernel_bias()
+
+    def fuse_convs(self):
+        """Leave a single `conv` with bias and drop conv1, conv2 and bn (reference :271-297)."""
+        if hasattr(self, "conv"):
+            return
+        with torch.no_grad():
+            kernel, bias = self.get_equivalent_kernel_bias()
+        c, dt = self.conv1.conv, self.conv1.conv.weight.dtype
+        self.conv = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True).requires_grad_(False)
+        self.conv.weight.data = kernel.to(dt)
+        self.conv.bias.data = bias.to(dt)
+        for name in ("conv1", "conv2", "nm", "bn", "id_tensor"):
+            if hasattr(self, name):
+                delattr(self, name)
+        self._cache = {}
+
+    def forward(self, x, out=None, res=None):
+        if self.g != 1:
+            raise NotImplementedError("RepConv with groups != 1 is outside the built path (the YOLOv9 YAMLs never use it)")
+        c = self.conv if hasattr(self, "conv") else self.conv1.conv
+        return ops.conv2d(self, [x], self.folded, 3, c.stride[0], 1, _act_code(self.act), out=out, res=res)
+
+    forward_fuse = forward
 
 
 class DSConv(_Packed):

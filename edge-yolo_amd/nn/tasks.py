@@ -13,7 +13,7 @@ import torch.nn as nn
 import yaml
 
 from . import _ops as ops
-from .modules import (A2C2f, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
+from .modules import (A2C2f, AConv, ADown, CBFuse, CBLinear, ELAN1, RepConv, RepNCSPELAN4, SPPELAN, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
                       DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
@@ -21,7 +21,7 @@ from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN}
 _REPEAT_MODULES = {C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
 _HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
 
@@ -106,6 +106,8 @@ def parse_model(d, ch, verbose=False):
         args = list(args)
         if m == "nn.Upsample":
             m = Upsample
+        elif m == "nn.Identity" and i == 0:  # yolov9e: layer 0 hands the image on, so that a later stem can read it (`from 0`)
+            m = nn.Identity
         elif isinstance(m, str) and m.startswith("nn."):
             raise NotImplementedError(f"torch module '{m}' is not on the built detection path")
         else:
@@ -167,6 +169,12 @@ def parse_model(d, ch, verbose=False):
             args = [c1, *args]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
+        elif m is CBLinear:  # reference tasks.py:1100-1103: c2 is the list of slice widths
+            c2 = args[0]
+            c1 = ch[f]
+            args = [c1, c2, *args[1:]]
+        elif m is CBFuse:  # reference tasks.py:1104-1105
+            c2 = ch[f[-1]]
         elif m in _HEADS:
             args.append([ch[x] for x in f])
             if m is Segment:  # reference tasks.py:1094-1095
@@ -188,13 +196,13 @@ def parse_model(d, ch, verbose=False):
 
 def _layer_down(m, down):
     """Downsampling factor of layer m's output, given those of the layers before it (`down`)."""
-    f = m.f if isinstance(m.f, int) else m.f[1 if isinstance(m, HyperACE) else 0]  # HyperACE works at its middle input's resolution
+    f = m.f if isinstance(m.f, int) else m.f[1 if isinstance(m, HyperACE) else -1 if isinstance(m, CBFuse) else 0]  # HyperACE works at its middle input's resolution, CBFuse at its last's
     src = 1.0 if m.i == 0 else (down[f] if f != -1 else down[-1])
     if isinstance(m, Conv):
         src *= m.conv.stride[0]
     elif isinstance(m, DSConv):
         src *= m.dw.stride[0]
-    elif isinstance(m, DownsampleConv):
+    elif isinstance(m, (DownsampleConv, ADown, AConv)):
         src *= 2
     elif isinstance(m, Upsample):
         src /= 2
@@ -357,6 +365,8 @@ class BaseModel(nn.Module):
             for m in self.model.modules():
                 if isinstance(m, Conv) and hasattr(m, "bn"):
                     m.fuse_bn()
+                if isinstance(m, RepConv):  # (reference :234-236; visited before its conv1 / conv2, which it removes)
+                    m.fuse_convs()
         return self
 
     def convs_folded(self):
@@ -393,6 +403,8 @@ class DetectionModel(BaseModel):
     def __init__(self, cfg="yolo11n.yaml", ch=3, nc=None, verbose=False):
         super().__init__()
         self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        if self.yaml["backbone"][0][2] == "Silence":  # YOLOv9's deprecated name for it (reference tasks.py:327-332)
+            self.yaml["backbone"][0][2] = "nn.Identity"
         ch = self.yaml["ch"] = self.yaml.get("ch", ch)
         if nc and nc != self.yaml["nc"]:
             self.yaml["nc"] = nc
@@ -426,7 +438,7 @@ class DetectionModel(BaseModel):
                 consumers.setdefault((m.i + j) if j < 0 else j, []).append(m)
 
         def takes_virtual(m):
-            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f)):
+            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f, RepNCSPELAN4)):
                 return True
             return isinstance(m, Conv) and m.conv.kernel_size == (1, 1) and m.conv.groups == 1
 

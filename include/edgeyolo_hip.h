@@ -331,6 +331,30 @@ int ey_dysample(int dtype, int B, int H, int W, int C, int scale, int groups, co
 int ey_max_sigmoid_attn(int dtype, int B, int HW, int nh, int hc, int C, int n, int Bg, const void* e, int e_cstride, const void* p, int p_cstride,
                         const void* g, const float* bias, const float* scale, void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- YOLOv9 (GELAN): the pooling front end of ADown / AConv (reference ultralytics/nn/modules/block.py:753-784) in one launch.
+ *   A = avg_pool2d(x, 2, 1, 0)                 [B, H-1, W-1, C]; each window summed in fp32 as ((x00 + x01) + x10) + x11, times 0.25f, rounded
+ *                                               once to `dtype` (bit-identical to torch's CPU avg_pool2d)
+ *   a = A[..., :c_avg]                          [B, H-1, W-1, c_avg], the input of the 3x3 stride-2 conv
+ *   m = max_pool2d(A[..., c_avg:], 3, 2, 1)     [B, H/2, W/2, C - c_avg], the maximum over the ROUNDED A values; window positions outside A are
+ *                                               skipped.  These A values are never written to memory.
+ * x, a, m: channel windows of NHWC buffers with their pixel strides.  c_avg == C is the AConv mode (m unused, may be NULL); c_avg == 0 is
+ * refused.  H, W >= 2.  No atomics, no workspace: deterministic and graph-capturable.  EY_EINVAL unless C, c_avg and the strides are multiples
+ * of 8 elements and the pointers 16-byte aligned; EY_EUNSUPPORTED when three rows of A of 8 channels exceed 64 KiB of LDS. */
+int ey_adown_pool(int dtype, int B, int H, int W, int C, int c_avg, const void* x, int x_cstride, void* a, int a_cstride, void* m, int m_cstride,
+                  ey_stream_t stream);
+
+/* CBFuse (block.py:821-833): y[b,r,q,c] = sum_i src_i[b, ri(r), qi(q), c], every source resized to H x W with PyTorch's mode="nearest" rule
+ *   ri(r) = min((int)floorf(r * ((float)Hi / (float)H)), Hi - 1),   qi(q) likewise from Wi and W   (any ratio; Hi == H reads at the identity).
+ * The sum is fp32 in list order starting from source 0 and rounds once to `dtype`.  srcs: HOST array of n descriptors, 1 <= n <=
+ * EY_CBFUSE_MAX, each a C-channel window [B, Hi, Wi, *] of an NHWC buffer with its pixel stride; they travel to the kernel by value.
+ * EY_EINVAL unless C and all strides are multiples of 8 elements and all pointers 16-byte aligned. */
+#define EY_CBFUSE_MAX 6
+typedef struct ey_cbfuse_src {
+  const void* ptr;
+  int cstride, Hi, Wi;
+} ey_cbfuse_src;
+int ey_cbfuse(int dtype, int B, int H, int W, int C, int n, const ey_cbfuse_src* srcs, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- Instance segmentation: mask assembly (utils/ops.py:644-693 process_mask + crop_mask, called by models/yolo/segment/predict.py:50-57).
  * For each of N kept detections (over the whole batch):
  *   v[r][c]   = sum_k coef_n[k] * proto[img_n, r, c, k]        fp32, k ascending, on the low-resolution grid mh x mw
