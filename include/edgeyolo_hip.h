@@ -534,6 +534,7 @@ int ey_nms_candidates(int B, int nc, int A, void* candidates, size_t candidates_
  * ey_e2e_topk: Detect.postprocess (head.py:167-189) on that tensor: out_rows [B, k, 6] fp32 = the k best (anchor, class) pairs of each
  *   image in descending score order, row = x1,y1,x2,y2,score,class; k = min(max_det, A) is the caller's; out_index [B, k] (anchor of
  *   each row) or NULL.  Equal scores: lower anchor, then lower class first (torch.topk leaves that order unspecified).
+ *   1 <= k <= min(A, 1611): the LDS bound of the selection workgroup, see ey_nms.
  *   workspace: ey_e2e_topk_workspace_bytes(B, nc, A) bytes, 16-byte aligned. */
 int ey_head_decode_levels_xyxy(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box,
                                const int* box_cstride, const void* const* cls, const int* cls_cstride, int nc, const float* const* q_w1,
@@ -603,7 +604,12 @@ int ey_block_run_timed(const void* program_dev, int nstages, int B, const void* 
  * pred fp32 [B,4+nc,A] (xywh + scores), NOT modified.
  * out_boxes fp32 [B,max_det,6] = x1,y1,x2,y2,conf,cls in kept (descending score) order; out_count int32 [B];
  * out_index int32 [B,max_det] = anchor index of each kept row (may be NULL); class_mask uint8 [nc] or NULL
- * (the `classes=` filter).  workspace: ey_nms_workspace_bytes(B, A) bytes. */
+ * (the `classes=` filter).  workspace: ey_nms_workspace_bytes(B, A) bytes.
+ * max_det (ey_nms, ey_nms_candidates) and k (ey_e2e_topk) are bounded by the LDS of the one workgroup that selects an image: its fixed
+ * state (82416 B) plus, per kept box, the class-offset box, the result row and the index (48 B; 80 B with the per-owner rank lists of
+ * the class-partitioned greedy, which only runs for max_det <= 512) plus 4096 B of reserve must fit 160 KiB, i.e.
+ * 82416 + 48 * max_det + 4096 <= 163840: 1 <= max_det <= 1611.  From 1612 up the call returns EY_EINVAL ("nms: max_det=1612 needs
+ * 159792 B of LDS") before the selection is launched; nothing is written to the outputs. */
 size_t ey_nms_workspace_bytes(int B, int A);
 size_t ey_nms_workspace_bytes_ml(int B, int nc, int A);
 int ey_nms(int B, int nc, int A, const float* pred, float conf_thres, float iou_thres, int max_det, int max_nms,
