@@ -49,6 +49,8 @@ struct EyTune {
   long pw3 = 1;                 // closing 1x1 of a block + the 64 -> 64 stride-2 3x3 behind it as one kernel (0 = two launches)
   long pw3_skew = 8;            // ... start delay of the second half of the grid in units of 1024 clocks (anti-phase the two workgroups of a CU)
   long pw3_min_px = 100000;     // ... on maps with at least this many pixels (B x H x W)
+  long scdown = 1;              // SCDown (1x1 + SiLU, depthwise 3x3 stride 2) as one kernel, the map between them in LDS (0 = two launches)
+  long scdown_min_px = 0;       // ... on maps with at least this many pixels (B x H x W)
   long stem_mfma = 1;           // MFMA stem kernel (0 = VALU stem)
   long linattn_mfma = 1;        // MFMA linear-attention kernel (0 = fp32 VALU kernel)
   long softattn_mfma = 1;       // MFMA softmax-attention kernel (0 = fp32 VALU kernel)

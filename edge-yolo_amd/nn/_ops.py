@@ -396,6 +396,50 @@ def pw_conv3s2(cv2, conv3, srcs, out=None):
     return out
 
 
+def scdown(cv1, cv2, x, out=None):
+    """SCDown (reference block.py:1174-1206) as one launch (ey_scdown): cv1 = pointwise Conv + activation, cv2 = depthwise 3x3 stride-2 Conv; the
+    full-resolution map between them stays in LDS.  Bit-identical to ops.conv2d + ops.dwconv_s2.  x may be a channel slice of a wider NHWC
+    buffer, out= a slot of one.  Returns None (nothing launched) outside the fused kernel's shapes: the caller runs the two launches."""
+    if RECORD is not None or isinstance(x, VirtualCat) or not torch.is_tensor(x) or x.dim() != 4:
+        return None
+    L.require_device(x, "scdown")
+    if x.dtype != torch.float16:
+        return None
+    from .modules.conv import _act_code
+    x = L.as_nhwc(x)
+    B, c1n, H, W = x.shape
+    c1, c2 = cv1.conv, cv2.conv
+    k = c2.kernel_size[0]
+    cout = c2.out_channels
+    if (c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.groups != 1 or c1.in_channels != c1n or c1.out_channels != cout or c2.kernel_size != (k, k)
+            or k != 3 or c2.stride != (2, 2) or c2.padding != (k // 2, k // 2) or c2.dilation != (1, 1) or not c2.groups == c2.in_channels == cout
+            or c1n % 8 or cout % 64 or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16):
+        return None
+    act1, act2 = _act_code(cv1.act), _act_code(cv2.act)
+    w1, b1 = _conv_pack(cv1, x, c1n, 1)[:2]
+
+    def build():  # (the cache slot and layout ops.dwconv_s2 uses for cv2)
+        w, b = cv2.folded()
+        wk = w.view(cout, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)
+        return wk, (b.to(x.device).float().contiguous() if b is not None else None)
+
+    w2, b2 = cv2._packed(_dev_key(x, "dw2"), build)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = L.empty_nhwc(B, cout, Ho, Wo, x.dtype, x.device)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != x.dtype:
+        raise ValueError(f"scdown: out= must be an NHWC view of shape {(B, cout, Ho, Wo)} {x.dtype}")
+    if (L.cstride(out) * 2) % 16 or out.data_ptr() % 16:
+        return None
+    try:
+        with _tr("scdown_kernel", _nb(x, out) + (cout * c1n + 9 * cout) * 2, 2.0 * B * (H * W * cout * c1n + Ho * Wo * cout * k * k), note=f"{c1n}->{cout} k1 -> dw k{k}s2 {H}x{W}"):
+            L.check(L.lib().ey_scdown(L.dtype_code(x.dtype), B, H, W, c1n, cout, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), b1.data_ptr() if b1 is not None else None, act1,
+                                      w2.data_ptr(), b2.data_ptr() if b2 is not None else None, act2, out.data_ptr(), L.cstride(out), L.stream()), "ey_scdown")
+    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+        return None
+    return out
+
+
 def stem_pair(m0, m1, x, out=None):
     """Layers 0 + 1 (Conv 3->16 k3 s2 + Conv 16->32 k3 s2, both BN + SiLU; reference conv.py:41-59) as one launch from the NCHW-contiguous f16
     image: the stem's output -- the largest tensor of the forward, with one consumer -- stays in LDS.  Bit-identical to the two launches.

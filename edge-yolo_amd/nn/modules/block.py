@@ -17,7 +17,7 @@ __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNC
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
-           "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse")
+           "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA")
 
 
 def _slot(buf, i, c):
@@ -1411,3 +1411,123 @@ class CBFuse(nn.Module):
         if len(xs) > L.CBFUSE_MAX:
             raise NotImplementedError(f"CBFuse: {len(xs)} inputs; ey_cbfuse takes at most {L.CBFUSE_MAX}")
         return ops.cbfuse([x[self.idx[i]] for i, x in enumerate(xs[:-1])] + [xs[-1]])
+
+
+# ----------------------------------------------------------------------------------------------- YOLOv10
+class SCDown(nn.Module):
+    """Spatial-channel decoupled downsampling of YOLOv10 (reference block.py:1174-1206): cv2(cv1(x)), cv1 a pointwise Conv + SiLU, cv2 a
+    depthwise k x k stride-s Conv without activation.  Stride 2 runs as ONE kernel where the shape allows (ops.scdown: the full-resolution
+    c2-channel map stays in LDS), else as ey_conv2d + ey_dwconv_s2 -- the same bits either way.  `out=` may be a slot of a concat buffer."""
+
+    def __init__(self, c1, c2, k, s):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.cv2 = Conv(c2, c2, k=k, s=s, g=c2, act=False)
+
+    def forward(self, x, out=None):
+        c = self.cv2.conv
+        k = c.kernel_size[0]
+        if c.stride == (2, 2) and k in (3, 5, 7) and c.kernel_size == (k, k) and c.padding == (k // 2, k // 2) and c.dilation == (1, 1):
+            y = ops.scdown(self.cv1, self.cv2, x, out=out)
+            if y is not None:
+                return y
+            return ops.dwconv_s2(self.cv2, self.cv1(x), self.cv2.folded, k, _act_code(self.cv2.act), out=out)
+        return self.cv2(self.cv1(x), out=out)
+
+
+class RepVGGDW(_Packed):
+    """Re-parameterised depthwise block of the YOLOv10 CIB (reference block.py:879-938): SiLU(conv 7x7 dw (x) + conv1 3x3 dw (x)), both
+    Conv(act=False).  The two branches are linear in x, so the HIP path always runs ONE depthwise 7x7 on the sum of the 7x7 kernel and the
+    3x3 kernel padded to 7x7 (biases added), BatchNorms folded in fp32 when the weights are packed -- before `fuse()` (from conv / conv1) and
+    after it (from the single `conv` with bias it leaves)."""
+
+    def __init__(self, ed):
+        super().__init__()
+        self.conv = Conv(ed, ed, 7, 1, 3, g=ed, act=False)
+        self.conv1 = Conv(ed, ed, 3, 1, 1, g=ed, act=False)
+        self.dim = ed
+        self.act = nn.SiLU()
+
+    def folded(self):
+        """(7x7 depthwise kernel (ed,1,7,7), bias) equal to both branches, in fp32 (reference :921-932)."""
+        if not hasattr(self, "conv1"):
+            return self.conv.weight.detach().float(), self.conv.bias.detach().float()
+        k7, b7 = self.conv.folded()
+        k3, b3 = self.conv1.folded()
+        return k7 + F.pad(k3, [2, 2, 2, 2]), b7 + b3
+
+    @torch.no_grad()
+    def fuse(self):
+        """Leave a single `conv` (nn.Conv2d with bias) and drop conv1 (reference :914-938)."""
+        if not hasattr(self, "conv1"):
+            return
+        w, b = self.folded()
+        c, dt = self.conv.conv, self.conv.conv.weight.dtype
+        conv = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True).requires_grad_(False)
+        conv = conv.to(w.device)
+        conv.weight.data = w.to(dt)
+        conv.bias.data = b.to(dt)
+        self.conv = conv
+        del self.conv1
+        self._cache = {}
+
+    def forward(self, x, out=None):
+        return ops.dwconv(self, x, self.folded, 7, _act_code(self.act), out=out)
+
+    forward_fuse = forward
+
+
+class CIB(nn.Module):
+    """Compact inverted block of YOLOv10 (reference block.py:941-977): dw 3x3 -> pw (c1 -> 2c_) -> dw 3x3 (RepVGGDW 7x7 with lk) -> pw
+    (2c_ -> c2) -> dw 3x3, every stage + SiLU, plus x when shortcut and c1 == c2.  Five launches on the depthwise and MFMA pointwise
+    kernels; the last stage is a depthwise kernel, which has no residual input, so the add is ey_cbfuse on two maps (x + y in fp32, one
+    rounding)."""
+
+    def __init__(self, c1, c2, shortcut=True, e=0.5, lk=False):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = nn.Sequential(
+            Conv(c1, c1, 3, g=c1),
+            Conv(c1, 2 * c_, 1),
+            RepVGGDW(2 * c_) if lk else Conv(2 * c_, 2 * c_, 3, g=2 * c_),
+            Conv(2 * c_, c2, 1),
+            Conv(c2, c2, 3, g=c2),
+        )
+        self.add = shortcut and c1 == c2
+
+    def forward(self, x, out=None):
+        m = self.cv1
+        t = m[3](m[2](m[1](m[0](x))))
+        if not self.add:
+            return m[4](t, out=out)
+        return ops.cbfuse([x, m[4](t)], out=out)
+
+
+class C2fCIB(C2f):
+    """C2f with CIB blocks in place of the bottlenecks (reference block.py:980-997)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, lk=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(CIB(self.c, self.c, shortcut, e=1.0, lk=lk) for _ in range(n))
+
+
+class PSA(nn.Module):
+    """Partial self-attention of YOLOv10 (reference block.py:1057-1097): cv1 splits into (a, b); b = b + attn(b); b = b + ffn(b);
+    cv2(cat(a, b)).  Both residual adds ride in conv epilogues and b is updated in its half of cv1's buffer: no split, add or cat kernel.
+    c // 64 heads of head_dim 64 / key_dim 32 where c is a multiple of 64 (2 at n, 5 at x); 4 heads of 72 / 36 at the m scale (c = 288)."""
+
+    def __init__(self, c1, c2, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.attn = Attention(self.c, attn_ratio=0.5, num_heads=self.c // 64)
+        self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
+
+    def forward(self, x, out=None):
+        t = self.cv1(x)
+        b = t[:, self.c:]
+        b = self.attn(b, res=b)
+        self.ffn[1](self.ffn[0](b), out=t[:, self.c:], res=b)
+        return self.cv2(t, out=out)

@@ -14,7 +14,7 @@ from .conv import Conv, DWConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH", "WorldDetect")
+__all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH", "WorldDetect", "v10Detect")
 
 
 class _Plain(_Packed):
@@ -708,6 +708,23 @@ class E2EDetect(GF2Detect):
     class tower is the depthwise structure whatever `legacy` says (:812-822)."""
 
     end2end = True
+
+    def __init__(self, nc=80, ch=()):
+        super().__init__(nc, ch)
+        c3 = max(ch[0], min(self.nc, 100))
+        self.cv3 = nn.ModuleList(
+            nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), nn.Conv2d(c3, self.nc, 1))
+            for x in ch)
+        self.one2one_cv3 = copy.deepcopy(self.cv3)
+
+
+class v10Detect(Detect):
+    """YOLOv10 head (reference head.py:764-797): Detect with end2end = True and the light class tower (depthwise 3x3 -> 1x1 -> depthwise 3x3 ->
+    1x1 -> nn.Conv2d) whatever `legacy` says; one2one_cv3 is a deep copy of it.  The one2one towers, the x1y1x2y2 decode and the top-k
+    selection (ey_e2e_topk) are Detect's end2end path."""
+
+    end2end = True
+    legacy = False  # parse_model does not assign it (reference tasks.py:1096): the class default stays visible
 
     def __init__(self, nc=80, ch=()):
         super().__init__(nc, ch)

@@ -14,16 +14,16 @@ import yaml
 
 from . import _ops as ops
 from .modules import (A2C2f, AConv, ADown, CBFuse, CBLinear, ELAN1, RepConv, RepNCSPELAN4, SPPELAN, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect)
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN}
-_REPEAT_MODULES = {C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
-_HEADS = {Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN, SCDown, PSA, C2fCIB}
+_REPEAT_MODULES = {C2f, C2fCIB, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
+_HEADS = {Detect, v10Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
 
 
 def guess_model_scale(model_path):
@@ -179,7 +179,8 @@ def parse_model(d, ch, verbose=False):
             args.append([ch[x] for x in f])
             if m is Segment:  # reference tasks.py:1094-1095
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
-            m.legacy = legacy
+            if m is not v10Detect:  # (the reference leaves v10Detect's class default, tasks.py:1096)
+                m.legacy = legacy
         else:
             c2 = ch[f]
         m_ = nn.Sequential(*(m(*args, **kw) for _ in range(n))) if n > 1 else m(*args, **kw)
@@ -202,6 +203,8 @@ def _layer_down(m, down):
         src *= m.conv.stride[0]
     elif isinstance(m, DSConv):
         src *= m.dw.stride[0]
+    elif isinstance(m, SCDown):
+        src *= m.cv2.conv.stride[0]
     elif isinstance(m, (DownsampleConv, ADown, AConv)):
         src *= 2
     elif isinstance(m, Upsample):
@@ -367,6 +370,8 @@ class BaseModel(nn.Module):
                     m.fuse_bn()
                 if isinstance(m, RepConv):  # (reference :234-236; visited before its conv1 / conv2, which it removes)
                     m.fuse_convs()
+                if isinstance(m, RepVGGDW):  # (reference :237-239; modules() yields it before its conv / conv1, which still carry their bn here)
+                    m.fuse()
         return self
 
     def convs_folded(self):
@@ -438,7 +443,7 @@ class DetectionModel(BaseModel):
                 consumers.setdefault((m.i + j) if j < 0 else j, []).append(m)
 
         def takes_virtual(m):
-            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f, RepNCSPELAN4)):
+            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f, RepNCSPELAN4, SCDown, PSA)):
                 return True
             return isinstance(m, Conv) and m.conv.kernel_size == (1, 1) and m.conv.groups == 1
 

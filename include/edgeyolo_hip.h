@@ -236,6 +236,16 @@ int ey_sppf_pool(int dtype, int B, int H, int W, int C, const void* x, int x_cst
 int ey_scale_add_channels(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, const float* gamma, const void* t, int t_cstride,
                           void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- SCDown of YOLOv10 (reference block.py:1174-1206) as one kernel (f16, k = 3):
+ *     y = act2( DWConv_{3x3, s2, pad 1}( round_f16( act1( Conv1x1_{C1->C2}(x) + bias1 ) ) ) + bias2 ),   Ho = (H-1)/2 + 1
+ * x and y are channel windows of NHWC buffers (x may be a slice, y a slot of a concat buffer).  w1: ey_conv_pack_weight(EY_F16, C2, C1, 1);
+ * w2: [3][3][C2] f16 as ey_dwconv_s2 takes it; biases fp32, bias2 may be NULL.  The (B,C2,H,W) map between the two convs stays in LDS, rounded
+ * to f16 as ey_conv2d stores it; taps outside the map are skipped as ey_dwconv_s2 skips them: bit-identical to ey_conv2d + ey_dwconv_s2.
+ * Takes C1 % 8 == 0, C2 % 64 == 0, act1 none / ReLU / SiLU, act2 none / ReLU, 16-byte aligned views, any H, W >= 1; no workspace, no atomics.
+ * EY_EUNSUPPORTED (before anything is launched) for everything else: the caller runs the two launches. */
+int ey_scdown(int dtype, int B, int H, int W, int C1, int C2, int k, const void* x, int x_cstride, const void* w1_packed, const float* bias1, int act1,
+              const void* w2_kkc, const float* bias2, int act2, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- YOLOv13 (HyperACE / FullPAD, reference block.py:1564-2008, conv.py:87-104) --------------------------------------------------------
  * AvgPool2d(2) (FuseModule.downsample / DownsampleConv.downsample, block.py:1858,1985): y[b,i,j,c] = mean of the 2x2 window at (2i, 2j),
  * floor semantics (Ho = H/2, Wo = W/2; an odd last row / column is dropped), summed in fp32 in row-major order and rounded once.  x and y
