@@ -51,6 +51,9 @@ struct EyTune {
   long pw3_min_px = 100000;     // ... on maps with at least this many pixels (B x H x W)
   long scdown = 1;              // SCDown (1x1 + SiLU, depthwise 3x3 stride 2) as one kernel, the map between them in LDS (0 = two launches)
   long scdown_min_px = 0;       // ... on maps with at least this many pixels (B x H x W)
+  long ghost = 1;               // GhostConv (1x1, depthwise 5x5, concat, optional residual) as one kernel, the 1x1's output in LDS (0 = compose)
+  long ghost_min_px = 0;        // ... on maps with at least this many pixels (B x H x W)
+  long ghost_sb = 0;            // ... 16-channel blocks per slab: 0 = by the work (at most 4, halved while tiles x slabs < 2 per CU), 1 / 2 / 4 = at most this
   long stem_mfma = 1;           // MFMA stem kernel (0 = VALU stem)
   long linattn_mfma = 1;        // MFMA linear-attention kernel (0 = fp32 VALU kernel)
   long softattn_mfma = 1;       // MFMA softmax-attention kernel (0 = fp32 VALU kernel)

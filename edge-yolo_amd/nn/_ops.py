@@ -440,6 +440,62 @@ def scdown(cv1, cv2, x, out=None):
     return out
 
 
+def ghost_conv(cv1, cv2, x, out=None, res=None):
+    """GhostConv(c1, c2, 1, 1) (reference conv.py:180-193) as one launch (ey_ghost_conv): cv1 = pointwise Conv, cv2 = depthwise 5x5 Conv on
+    cv1's output, both with the same activation; out = cat(cv1(x), cv2(cv1(x))) [+ res, an f16 add -- the shortcut of a GhostBottleneck].
+    cv1's output stays in LDS.  Where the hidden width is a multiple of 8, bit-identical to ops.conv2d + ops.dwconv (+ the add).  x may be a
+    channel slice of a wider NHWC buffer, out= a slot of one, and out= may be res itself.  Returns None (nothing launched) outside the fused
+    kernel's shapes: the caller composes."""
+    if RECORD is not None or isinstance(x, VirtualCat) or not torch.is_tensor(x) or x.dim() != 4:
+        return None
+    L.require_device(x, "ghost_conv")
+    if x.dtype != torch.float16:
+        return None
+    from .modules.conv import _act_code
+    x = L.as_nhwc(x)
+    B, c1n, H, W = x.shape
+    c1, c2 = cv1.conv, cv2.conv
+    k = c2.kernel_size[0]
+    ch = c1.out_channels
+    act = _act_code(cv1.act)
+    if (c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.groups != 1 or c1.in_channels != c1n or c2.kernel_size != (k, k) or k != 5
+            or c2.stride != (1, 1) or c2.padding != (k // 2, k // 2) or c2.dilation != (1, 1) or not c2.groups == c2.in_channels == c2.out_channels == ch
+            or c1n % 8 or ch % 4 or act != _act_code(cv2.act) or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16):
+        return None
+    va = 8 if ch % 8 else 16
+    if out is not None:
+        if not L.is_nhwc_view(out) or tuple(out.shape) != (B, 2 * ch, H, W) or out.dtype != x.dtype:
+            raise ValueError(f"ghost_conv: out= must be an NHWC view of shape {(B, 2 * ch, H, W)} {x.dtype}")
+        if (L.cstride(out) * 2) % va or out.data_ptr() % va:
+            return None
+    if res is not None:
+        res = L.as_nhwc(res)
+        if tuple(res.shape) != (B, 2 * ch, H, W) or res.dtype != x.dtype:
+            raise ValueError("ghost_conv: residual shape/dtype mismatch")
+        if (L.cstride(res) * 2) % va or res.data_ptr() % va:
+            return None
+    w1, b1 = _conv_pack(cv1, x, c1n, 1)[:2]
+
+    def build():  # (the cache slot and layout ops.dwconv uses for cv2)
+        w, b = cv2.folded()
+        wk = w.view(ch, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)
+        return wk, (b.to(x.device).contiguous() if b is not None else None)
+
+    w2, b2 = cv2._packed(_dev_key(x, "dw"), build)
+    fresh = out is None
+    if fresh:
+        out = L.empty_nhwc(B, 2 * ch, H, W, x.dtype, x.device)
+    try:
+        with _tr("ghost_conv_kernel", _nb(x, out, res) + (ch * c1n + k * k * ch) * 2, 2.0 * B * H * W * ch * (c1n + k * k),
+                 note=f"{c1n}->{ch} k1 -> dw k{k} {H}x{W}{' +res' if res is not None else ''}"):
+            L.check(L.lib().ey_ghost_conv(L.dtype_code(x.dtype), B, H, W, c1n, ch, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), b1.data_ptr() if b1 is not None else None,
+                                          w2.data_ptr(), b2.data_ptr() if b2 is not None else None, act, res.data_ptr() if res is not None else None,
+                                          L.cstride(res) if res is not None else 0, out.data_ptr(), L.cstride(out), L.stream()), "ey_ghost_conv")
+    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+        return None
+    return out
+
+
 def stem_pair(m0, m1, x, out=None):
     """Layers 0 + 1 (Conv 3->16 k3 s2 + Conv 16->32 k3 s2, both BN + SiLU; reference conv.py:41-59) as one launch from the NCHW-contiguous f16
     image: the stem's output -- the largest tensor of the forward, with one consumer -- stays in LDS.  Bit-identical to the two launches.

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F  # pack time only: softplus/tanh on 4+1 scalar parameters, the text projection of a vocabulary
 
-from .conv import Conv, DSConv, RepConv, _Packed, _act_code, fold_bn
+from .conv import Conv, DSConv, DWConv, GhostConv, RepConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
 
@@ -17,7 +17,8 @@ __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNC
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
-           "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA")
+           "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA",
+           "C2", "GhostBottleneck", "C3Ghost")
 
 
 def _slot(buf, i, c):
@@ -1531,3 +1532,58 @@ class PSA(nn.Module):
         b = self.attn(b, res=b)
         self.ffn[1](self.ffn[0](b), out=t[:, self.c:], res=b)
         return self.cv2(t, out=out)
+
+
+# ----------------------------------------------------------------------------------------------- YOLOv8 (P6 heads) and YOLOv8-ghost
+class C2(nn.Module):
+    """CSP bottleneck with two convolutions (reference block.py:339-354): cv2(cat(m(a), b)) with (a, b) = cv1(x).chunk(2), m a chain of
+    3x3 + 3x3 Bottlenecks -- the head blocks of yolov8-p6.yaml.  The chain rewrites a's half of cv1's buffer in place (a Bottleneck's
+    closing conv reads a temporary and adds its input pixel by pixel as the residual), so there is no chunk and no cat."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        self.c = int(c2 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c2, 1)
+        self.m = nn.Sequential(*(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n)))
+
+    def forward(self, x, out=None):
+        buf = self.cv1(x)  # x may be a VirtualCat (upsample + concat folded into cv1)
+        a = buf[:, :self.c]
+        for m in self.m:
+            m(a, out=a)
+        return self.cv2(buf, out=out)
+
+
+class GhostBottleneck(nn.Module):
+    """Ghost bottleneck (reference block.py:446-464): conv(x) + shortcut(x), conv = GhostConv(c1, c2 / 2) -> [DWConv k x k stride 2] ->
+    GhostConv(c2 / 2, c2, act=False).  Stride 1 (every shipped YAML): the shortcut is x itself and rides in the closing GhostConv's kernel
+    (`res=`), so the block is two launches, and `out=` may be x (C3Ghost's in-place chain).  Stride 2: the shortcut is DWConv stride 2 ->
+    Conv 1x1, composed from the existing kernels."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(
+            GhostConv(c1, c_, 1, 1),
+            DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+            GhostConv(c_, c2, 1, 1, act=False),
+        )
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+    def forward(self, x, out=None):
+        t = self.conv[0](x)
+        if isinstance(self.shortcut, nn.Identity):
+            if t.shape[1] * 2 != x.shape[1]:
+                raise ValueError(f"GhostBottleneck: the stride-1 block adds its input, which needs c1 == c2 (got {x.shape[1]} and {t.shape[1] * 2})")
+            return self.conv[2](t, out=out, res=x)
+        return self.conv[2](self.conv[1](t), out=out, res=self.shortcut[1](self.shortcut[0](x)))
+
+
+class C3Ghost(C3):
+    """C3 with GhostBottlenecks (reference block.py:436-443), on C3's concat buffer: the chain rewrites slot 0 in place."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))

@@ -16,7 +16,7 @@ import torch.nn as nn
 from .. import _ops as ops
 from ... import _lib as L
 
-__all__ = ("Conv", "DWConv", "DSConv", "RepConv", "Concat", "Upsample", "autopad")
+__all__ = ("Conv", "DWConv", "DSConv", "RepConv", "GhostConv", "Concat", "Upsample", "autopad")
 
 
 def autopad(k, p=None, d=1):
@@ -137,6 +137,50 @@ class DWConv(Conv):
 
     def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
+
+
+class GhostConv(nn.Module):
+    """Ghost convolution (reference conv.py:180-193): cat(y, cv2(y)) with y = cv1(x), cv1 = Conv(c1, c2 / 2, k, s, g=g), cv2 a depthwise 5x5 Conv
+    on y, both with the same activation.  The pointwise form (k = s = g = 1) on f16 is ONE launch (ops.ghost_conv: y stays in LDS, the concat
+    is two channel windows of one store pass, and `res=` -- the shortcut of a GhostBottleneck -- is added in the same pass).  Every other form
+    -- fp32, the 3x3 stride-2 downsampling layers, a shape the kernel refuses, the tunable ghost = 0 -- writes cv1 straight into the first
+    half of the output buffer and runs cv2 from there into the second half on the existing kernels: no cat.  `out=` may be a slot of a concat
+    buffer and may be `res` itself."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act=act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act=act)
+
+    def _cv2_folded_f16(self):
+        w, b = self.cv2.folded()
+        return w.half().float(), b
+
+    def forward(self, x, out=None, res=None):
+        c = self.cv1.conv
+        c_ = c.out_channels
+        if c.kernel_size == (1, 1) and c.stride == (1, 1) and c.groups == 1:
+            y = ops.ghost_conv(self.cv1, self.cv2, x, out=out, res=res)
+            if y is not None:
+                return y
+        B, _, H, W = x.shape  # x may be a VirtualCat
+        k, s, p = c.kernel_size[0], c.stride[0], c.padding[0]
+        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        if out is not None and (not L.is_nhwc_view(out) or tuple(out.shape) != (B, 2 * c_, Ho, Wo) or out.dtype != x.dtype):
+            raise ValueError(f"GhostConv: out= must be an NHWC view of shape {(B, 2 * c_, Ho, Wo)} {x.dtype}")
+        # with a residual the two halves go to a buffer of their own: out= may be res, and cv2 reads cv1's output before anything is added
+        t = out if out is not None and res is None else L.empty_nhwc(B, 2 * c_, Ho, Wo, x.dtype, x.device)
+        self.cv1(x, out=t[:, :c_])
+        if x.dtype == torch.float16 and c_ % 8:
+            # a hidden width ey_dwconv does not take (4, 12, 20 ...): the generic direct kernel, with the depthwise weights rounded to f16 as
+            # ey_dwconv and ey_ghost_conv hold them -- the same sums in the same order, so the f16 result does not depend on the path
+            ops.conv2d_direct(self.cv2, t[:, :c_], self._cv2_folded_f16, 5, 1, 2, c_, _act_code(self.cv2.act), out=t[:, c_:], tag="f16w")
+        else:
+            self.cv2(t[:, :c_], out=t[:, c_:])
+        if res is None:
+            return t
+        return ops.cbfuse([t, res], out=out)  # fp32 sum of the two maps, one rounding (= an f16 add)
 
 
 class RepConv(_Packed):

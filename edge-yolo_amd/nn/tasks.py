@@ -14,15 +14,15 @@ import yaml
 
 from . import _ops as ops
 from .modules import (A2C2f, AConv, ADown, CBFuse, CBLinear, ELAN1, RepConv, RepNCSPELAN4, SPPELAN, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect)
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect, C2, GhostConv, GhostBottleneck, C3Ghost)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN, SCDown, PSA, C2fCIB}
-_REPEAT_MODULES = {C2f, C2fCIB, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN, SCDown, PSA, C2fCIB, C2, GhostConv, GhostBottleneck, C3Ghost}
+_REPEAT_MODULES = {C2f, C2, C3Ghost, C2fCIB, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
 _HEADS = {Detect, v10Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
 
 
@@ -205,6 +205,8 @@ def _layer_down(m, down):
         src *= m.dw.stride[0]
     elif isinstance(m, SCDown):
         src *= m.cv2.conv.stride[0]
+    elif isinstance(m, GhostConv):
+        src *= m.cv1.conv.stride[0]
     elif isinstance(m, (DownsampleConv, ADown, AConv)):
         src *= 2
     elif isinstance(m, Upsample):
@@ -443,7 +445,7 @@ class DetectionModel(BaseModel):
                 consumers.setdefault((m.i + j) if j < 0 else j, []).append(m)
 
         def takes_virtual(m):
-            if isinstance(m, (C2f, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f, RepNCSPELAN4, SCDown, PSA)):
+            if isinstance(m, (C2f, C2, DSC3K2_Wavelet, C2PSA, C2PSA_LinearAttention, A2C2f, RepNCSPELAN4, SCDown, PSA)):
                 return True
             return isinstance(m, Conv) and m.conv.kernel_size == (1, 1) and m.conv.groups == 1
 

@@ -246,6 +246,19 @@ int ey_scale_add_channels(int dtype, int B, int H, int W, int C, const void* x, 
 int ey_scdown(int dtype, int B, int H, int W, int C1, int C2, int k, const void* x, int x_cstride, const void* w1_packed, const float* bias1, int act1,
               const void* w2_kkc, const float* bias2, int act2, void* y, int y_cstride, ey_stream_t stream);
 
+/* ---- GhostConv(c1, 2 Ch, 1, 1) of the YOLOv8-ghost models (reference conv.py:180-193) as one kernel (f16, k = 5):
+ *     y1 = round_f16( act( Conv1x1_{C1->Ch}(x) + bias1 ) ),   y2 = round_f16( act( DWConv_{5x5, s1, pad 2}(y1) + bias2 ) )
+ *     y[:, 0:Ch] = y1, y[:, Ch:2Ch] = y2;   with res:  y = round_f16( f32(cat(y1, y2)) + f32(res) )   (an f16 add; y may be res itself)
+ * x, y and res are channel windows of NHWC buffers (slices or slots of a concat buffer, each with its own pixel stride).
+ * w1: ey_conv_pack_weight(EY_F16, Ch, C1, 1); w2: [5][5][Ch] f16 as ey_dwconv takes it; biases fp32, bias2 may be NULL; act (both convs) none,
+ * ReLU or SiLU.  y1 stays in LDS, rounded to f16 as ey_conv2d stores it; the depthwise stage is ey_dwconv's arithmetic (sum started from the
+ * bias, taps in (ky, kx) order, taps outside the map skipped): where Ch % 8 == 0 the result is bit-identical to ey_conv2d + ey_dwconv (+ the
+ * f16 add).  Takes C1 % 8 == 0 (C1 <= 832), Ch % 4 == 0, any H, W >= 1; x 16-byte aligned, y and res 16-byte aligned, 8-byte where
+ * Ch % 8 == 4; no workspace, no atomics.  EY_EUNSUPPORTED (before anything is launched) for everything else, f32 and k != 5 included: the
+ * caller composes. */
+int ey_ghost_conv(int dtype, int B, int H, int W, int C1, int Ch, int k, const void* x, int x_cstride, const void* w1_packed, const float* bias1,
+                  const void* w2_kkc, const float* bias2, int act, const void* res, int res_cstride, void* y, int y_cstride, ey_stream_t stream);
+
 /* ---- YOLOv13 (HyperACE / FullPAD, reference block.py:1564-2008, conv.py:87-104) --------------------------------------------------------
  * AvgPool2d(2) (FuseModule.downsample / DownsampleConv.downsample, block.py:1858,1985): y[b,i,j,c] = mean of the 2x2 window at (2i, 2j),
  * floor semantics (Ho = H/2, Wo = W/2; an odd last row / column is dropped), summed in fp32 in row-major order and rounded once.  x and y
