@@ -87,6 +87,9 @@ SIGNATURES = {
     "ey_conv_pw_chain": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_conv2d_direct": (_i, [C.POINTER(ConvDirectDesc), _vp]),
     "ey_stem_conv": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_stem_conv_ks": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_stem_conv_ks_last_variant": (_i, []),
+    "ey_maxpool2d": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ey_dwconv": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_dsconv": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_dsconv_toeplitz_bytes": (_sz, [_i, _i]),

@@ -346,6 +346,64 @@ def stem_conv(mod, x, folded_fn, act, out_dtype, out=None):
     return out
 
 
+STEM_KS = {(6, 2, 2): "stem6", (3, 1, 1): "stem3s1"}  # (k, s, p) of ey_stem_conv_ks -> trace label stem
+
+
+def stem_conv_ks(mod, x, folded_fn, k, s, p, act, out_dtype, out=None):
+    """The image stems that are not 3x3 stride 2, straight from the NCHW-contiguous image (ey_stem_conv_ks): (k, s, p) = (6, 2, 2) of YOLOv5
+    and (3, 1, 1) of YOLOv3.  out= may be a channel slot of a wider NHWC buffer."""
+    L.require_device(x, "stem_conv_ks")
+    _no_block("stem conv")
+    B, cin, H, W = x.shape
+
+    def build():
+        w, b = folded_fn()
+        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
+
+    w, bias = mod._packed(("stem", x.device), build)
+    cout = w.shape[0]
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"stem_conv_ks: a {H}x{W} image has no {k}x{k} window at padding {p}")
+    if out is None:
+        out = L.empty_nhwc(B, cout, Ho, Wo, out_dtype, x.device)
+    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != out_dtype:
+        raise ValueError(f"stem_conv_ks: out= must be an NHWC view of shape {(B, cout, Ho, Wo)} {out_dtype}")
+    stem = STEM_KS.get((k, s, p), f"stem_k{k}s{s}p{p}")
+    rec = _tr(stem + "_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * cin * k * k, note=f"{cin}->{cout} k{k}s{s} {H}x{W}")
+    with rec:
+        L.check(L.lib().ey_stem_conv_ks(L.dtype_code(x.dtype), L.dtype_code(out_dtype), B, cin, H, W, cout, k, s, p, act, x.data_ptr(), w.data_ptr(),
+                                        bias.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_stem_conv_ks")
+        if rec is not _NT and L.lib().ey_stem_conv_ks_last_variant() == 1:
+            rec.kernel = stem + "_mfma_kernel"
+    return out
+
+
+def maxpool2d(x, k, s, pad=(0, 0, 0, 0), out=None):
+    """nn.MaxPool2d(k, s) behind nn.ZeroPad2d(pad), pad = (left, right, top, bottom) (ey_maxpool2d): the padded cells are ZEROS that take part in
+    the maximum.  k = 2 with s = 1 or 2; k = 1, s = 1 is the zero-padded copy.  x and out= may be channel slots of wider NHWC buffers."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "maxpool2d")
+    _no_block("max pool")
+    B, c, H, W = x.shape
+    pl, pr, pt, pb = (int(v) for v in pad)
+    if (k, s) not in ((2, 1), (2, 2), (1, 1)):
+        raise NotImplementedError(f"maxpool2d: k={k} stride={s}: a 2x2 window with stride 1 or 2 is built (and k = 1, the zero-padded copy)")
+    if min(pl, pr, pt, pb) < 0:
+        raise NotImplementedError(f"maxpool2d: negative padding {tuple(pad)} (cropping) is not built")
+    if c % 8:
+        raise NotImplementedError(f"maxpool2d: C={c} must be a multiple of 8")
+    Ho, Wo = (H + pt + pb - k) // s + 1, (W + pl + pr - k) // s + 1
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"maxpool2d: a {H}x{W} map padded by {tuple(pad)} has no {k}x{k} window")
+    _slot_view(x, "maxpool2d: x", x.shape, x.dtype)
+    out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device) if out is None else _slot_view(out, "maxpool2d: out=", (B, c, Ho, Wo), x.dtype)
+    with _tr("maxpool_kernel" if k > 1 else "zeropad_kernel", _nb(x, out), float(k * k * out.numel()), note=f"C{c} k{k}s{s} pad{(pl, pr, pt, pb)} {H}x{W}"):
+        L.check(L.lib().ey_maxpool2d(L.dtype_code(x.dtype), B, H, W, c, k, s, pl, pr, pt, pb, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out),
+                                     L.stream()), "ey_maxpool2d")
+    return out
+
+
 def _conv_pack(mod, x0, cin, k, tag=""):
     """Packed MFMA weights + fp32 bias of a plain Conv module, under the cache key (and with the tuple layout) ops.conv2d uses."""
     def build():

@@ -5,8 +5,9 @@ from .block import (DFL, Proto, SPPF, C2f, C2fAttn, MaxSigmoidAttnBlock, BNContr
                     Mlp, CMlp, LocalAgg, GlobalSparseAttn, SelfAttn, LGLBlock, DSC3K2_LGL,
                     AdaHGComputation, C3AH, FuseModule, HyperACE, DownsampleConv, FullPAD_Tunnel,
                     RepBottleneck, RepCSP, RepNCSPELAN4, ELAN1, SPPELAN, AConv, ADown, CBLinear, CBFuse,
-                    SCDown, RepVGGDW, CIB, C2fCIB, PSA, C2, GhostBottleneck, C3Ghost)
+                    SCDown, RepVGGDW, CIB, C2fCIB, PSA, C2, GhostBottleneck, C3Ghost, SPP)
 from .conv import Conv, DWConv, DSConv, RepConv, GhostConv, Concat, Upsample, autopad
+from .classic import ConvTranspose2d, MaxPool2d, ZeroPad2d
 from .dysample import DySample
 from .head import Classify, Detect, E2EDetect, GF2Detect, GFLHeadv2_uniH, OBB, Pose, Segment, WorldDetect, v10Detect
 
@@ -16,4 +17,5 @@ __all__ = ("Conv", "DWConv", "DSConv", "Concat", "Upsample", "autopad", "DFL", "
            "FullPAD_Tunnel", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "DSC3K2_LGL", "DySample", "Detect", "Segment", "OBB", "Pose", "Classify", "Proto", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH",
            "C2fAttn", "MaxSigmoidAttnBlock", "BNContrastiveHead", "WorldDetect",
            "RepConv", "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "SPPELAN", "AConv", "ADown", "CBLinear", "CBFuse",
-           "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA", "v10Detect", "C2", "GhostConv", "GhostBottleneck", "C3Ghost")
+           "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA", "v10Detect", "C2", "GhostConv", "GhostBottleneck", "C3Ghost",
+           "SPP", "MaxPool2d", "ZeroPad2d", "ConvTranspose2d")

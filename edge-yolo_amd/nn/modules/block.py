@@ -18,7 +18,7 @@ __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNC
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
            "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA",
-           "C2", "GhostBottleneck", "C3Ghost")
+           "C2", "GhostBottleneck", "C3Ghost", "SPP")
 
 
 def _slot(buf, i, c):
@@ -133,6 +133,13 @@ class C3(_Packed):
         (w1, b1), (w2, b2) = self.cv1.folded(), self.cv2.folded()
         return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
 
+    def _cv12_act(self):
+        """The one activation code of the stacked launch: cv1 and cv2 carry the same activation (the model's: SiLU, or the YAML's `activation:`)."""
+        a1, a2 = _act_code(self.cv1.act), _act_code(self.cv2.act)
+        if a1 != a2:
+            raise NotImplementedError("C3: cv1 and cv2 with different activations cannot share the stacked launch")
+        return a1
+
     def forward(self, x, out=None, cv12=None):
         """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (chained into the producer of x)."""
         x = L.as_nhwc(x)
@@ -140,7 +147,7 @@ class C3(_Packed):
         c_ = self.cv1.conv.out_channels
         # buf = [cv1(x) -> m(.) in place | cv2(x)]: the bottleneck chain rewrites slot 0 in place (its last conv reads a
         # temporary and adds slot 0 pixel-by-pixel as the residual), so cat() never happens
-        buf = cv12 if cv12 is not None else ops.conv2d(self, [x], self._cv12, 1, 1, 0, L.ACT_SILU, tag="cv12")
+        buf = cv12 if cv12 is not None else ops.conv2d(self, [x], self._cv12, 1, 1, 0, self._cv12_act(), tag="cv12")
         slot, t, spare = buf[:, :c_], buf[:, :c_], None
         for m in self.m:
             if isinstance(m, DSBottleneck):
@@ -155,7 +162,7 @@ class C3(_Packed):
             else:
                 t = m(t, out=slot)
         if t.data_ptr() != slot.data_ptr():  # odd DSBottleneck count: the chain ended in the spare buffer -> cv3 reads [spare | cv2(x)] as a virtual concat
-            return ops.conv2d(self.cv3, [t, buf[:, c_:]], self.cv3.folded, 1, 1, 0, L.ACT_SILU, out=out)
+            return ops.conv2d(self.cv3, [t, buf[:, c_:]], self.cv3.folded, 1, 1, 0, _act_code(self.cv3.act), out=out)
         return self.cv3(buf, out=out)
 
 
@@ -276,6 +283,30 @@ class SPPF(nn.Module):
     def forward(self, x, out=None, cv12=None):
         """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (chained into the producer of x)."""
         x = L.as_nhwc(x)
+        B, _, H, W = x.shape
+        c_ = self.cv1.conv.out_channels
+        buf = L.empty_nhwc(B, 4 * c_, H, W, x.dtype, x.device)
+        self.cv1(x, out=buf[:, :c_])
+        ops.sppf_pool(_slot(buf, 0, c_), _slot(buf, 1, c_), _slot(buf, 2, c_), _slot(buf, 3, c_))
+        return self.cv2(buf, out=out)
+
+
+class SPP(nn.Module):
+    """Spatial pyramid pooling of YOLOv3-SPP (reference block.py:186-201): cv2(cat(y, m5(y), m9(y), m13(y))), y = cv1(x).  A 5x5 max-pool
+    applied twice is the 9x9 pool and applied three times the 13x13 one (stride 1, -inf padding), so k = (5, 9, 13) runs on the SPPF chain kernel
+    (ey_sppf_pool) bit for bit; no other k is built.  `m` keeps the reference's pooling modules (no parameters; never called)."""
+
+    def __init__(self, c1, c2, k=(5, 9, 13)):
+        super().__init__()
+        if tuple(k) != (5, 9, 13):
+            raise NotImplementedError(f"SPP: k={tuple(k)}; the pooling kernel is built for k=(5, 9, 13), the chain of three 5x5 pools")
+        c_ = c1 // 2
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_ * (len(k) + 1), c2, 1, 1)
+        self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])
+
+    def forward(self, x, out=None):
+        x = L.as_nhwc(ops.as_tensor(x))
         B, _, H, W = x.shape
         c_ = self.cv1.conv.out_channels
         buf = L.empty_nhwc(B, 4 * c_, H, W, x.dtype, x.device)
@@ -741,7 +772,7 @@ class DSC3K2_Wavelet(nn.Module):
         buf = L.empty_nhwc(B, (1 + n) * c, H, W, x.dtype, x.device)  # [wave(b) | m_0 | ...]
         pre = None
         if n and isinstance(self.m[0], C3):  # the DSC3k behind the enhancer starts with a 1x1 over the enhancer's output: chained into its tail conv
-            _, pre = self.wave(t[:, c:], out=_slot(buf, 0, c), then=dict(mod=self.m[0], folded_fn=self.m[0]._cv12, act=L.ACT_SILU, tag="cv12"))
+            _, pre = self.wave(t[:, c:], out=_slot(buf, 0, c), then=dict(mod=self.m[0], folded_fn=self.m[0]._cv12, act=self.m[0]._cv12_act(), tag="cv12"))
         else:
             self.wave(t[:, c:], out=_slot(buf, 0, c))
         for i, m in enumerate(self.m):
@@ -752,8 +783,8 @@ class DSC3K2_Wavelet(nn.Module):
         # cat(a, wave(b), m...) is never built: cv2 reads the two buffers as one virtual concat
         if tail is not None:
             y = ops.pw_conv3s2(self.cv2, tail, [t[:, :c], buf])
-            return y if y is not None else tail(ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, L.ACT_SILU))
-        return ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, L.ACT_SILU, out=out)
+            return y if y is not None else tail(ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, _act_code(self.cv2.act)))
+        return ops.conv2d(self.cv2, [t[:, :c], buf], self.cv2.folded, 1, 1, 0, _act_code(self.cv2.act), out=out)
 
 
 # ----------------------------------------------------------------------------------------------- YOLOv13: HyperACE / FullPAD
@@ -1246,12 +1277,12 @@ class RepCSP(C3):
         x = L.as_nhwc(x)
         B, xin, H, W = x.shape
         cp = _ceil8(c_)
-        buf = ops.conv2d(self, [x], _pad_folded(self._cv12, [(c_, cp), (c_, cp)], [(c1, xin)]), 1, 1, 0, L.ACT_SILU, tag=f"cv12pad{xin}")
+        buf = ops.conv2d(self, [x], _pad_folded(self._cv12, [(c_, cp), (c_, cp)], [(c1, xin)]), 1, 1, 0, self._cv12_act(), tag=f"cv12pad{xin}")
         slot = buf[:, :cp]
         for b in self.m:
             h = _conv_padded(b.cv1, slot, L.empty_nhwc(B, cp, H, W, x.dtype, x.device))
             _conv_padded(b.cv2, h, slot, res=slot if b.add else None)
-        return ops.conv2d(self.cv3, [buf], _pad_folded(self.cv3.folded, [(c2, out.shape[1])], [(c_, cp), (c_, cp)]), 1, 1, 0, L.ACT_SILU, out=out,
+        return ops.conv2d(self.cv3, [buf], _pad_folded(self.cv3.folded, [(c2, out.shape[1])], [(c_, cp), (c_, cp)]), 1, 1, 0, _act_code(self.cv3.act), out=out,
                           tag=f"pad{out.shape[1]}")
 
 

@@ -105,6 +105,10 @@ class Conv(_Packed):
                 and torch.is_tensor(x) and x.dim() == 4 and x.is_contiguous() and not L.is_nhwc_view(x)):
             # network stem: read the planar NCHW image directly, write NHWC
             return ops.stem_conv(self, x, self.folded, act, x.dtype, out=out)
+        if (g == 1 and (k, s, p) in ops.STEM_KS and c.in_channels <= 4 and c.out_channels % 16 == 0 and res is None
+                and torch.is_tensor(x) and x.dim() == 4 and x.is_contiguous() and not L.is_nhwc_view(x)):
+            # the stems of YOLOv5 (6x6 stride 2, pad 2) and YOLOv3 (3x3 stride 1): planar NCHW image in, NHWC out, as above
+            return ops.stem_conv_ks(self, x, self.folded, k, s, p, act, x.dtype, out=out)
         if g == 1:
             return ops.conv2d(self, [x], self.folded, k, s, p, act, out=out, res=res)
         if g == c.in_channels == c.out_channels and s == 1 and k in (3, 5, 7) and p == k // 2 and res is None:

@@ -14,14 +14,17 @@ import yaml
 
 from . import _ops as ops
 from .modules import (A2C2f, AConv, ADown, CBFuse, CBLinear, ELAN1, RepConv, RepNCSPELAN4, SPPELAN, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
-                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect, C2, GhostConv, GhostBottleneck, C3Ghost)
+                      DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect, C2, GhostConv, GhostBottleneck, C3Ghost,
+                      Bottleneck, SPP, MaxPool2d, ZeroPad2d, ConvTranspose2d)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
 from ..utils.ops import make_divisible
 
 CFG_DIR = Path(__file__).resolve().parent.parent / "cfg" / "models"
-_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN, SCDown, PSA, C2fCIB, C2, GhostConv, GhostBottleneck, C3Ghost}
+_CH_MODULES = {Classify, Conv, SPPF, C2PSA, C2PSA_LinearAttention, DWConv, C2f, C2fAttn, C3k2, DSC3K2_Wavelet, C3, DSConv, A2C2f, DSC3K2, DSC3K2_LGL, RepNCSPELAN4, ELAN1, ADown, AConv, SPPELAN, SCDown, PSA, C2fCIB, C2, GhostConv, GhostBottleneck, C3Ghost,
+               Bottleneck, SPP, ConvTranspose2d}  # (ConvTranspose2d: its channels scale with the width like a Conv's, reference tasks.py:1021)
+_TORCH_ROWS = {"nn.MaxPool2d": MaxPool2d, "nn.ZeroPad2d": ZeroPad2d, "nn.ConvTranspose2d": ConvTranspose2d}  # torch rows with a device path: subclasses of the torch modules
 _REPEAT_MODULES = {C2f, C2, C3Ghost, C2fCIB, C2fAttn, C3k2, DSC3K2_Wavelet, C3, C2PSA, C2PSA_LinearAttention, A2C2f, DSC3K2, DSC3K2_LGL}
 _HEADS = {Detect, v10Detect, GF2Detect, E2EDetect, GFLHeadv2_uniH, Segment, OBB, Pose, WorldDetect}
 
@@ -86,7 +89,16 @@ def guess_model_task(model):
 
 
 def parse_model(d, ch, verbose=False):
-    """YAML dict -> (nn.Sequential, savelist).  Channel/repeat rewriting as reference tasks.py:958-1147."""
+    """YAML dict -> (nn.Sequential, savelist).  Channel/repeat rewriting as reference tasks.py:958-1147.  A YAML's `activation:` (YOLOv6:
+    nn.ReLU()) is the default activation of the Convs of THIS model: Conv.default_act is put back when the build returns or raises."""
+    saved_act = Conv.default_act
+    try:
+        return _parse_model(d, ch, verbose)
+    finally:
+        Conv.default_act = saved_act
+
+
+def _parse_model(d, ch, verbose=False):
     legacy = True
     max_channels = float("inf")
     nc, act, scales = (d.get(x) for x in ("nc", "activation", "scales"))
@@ -108,6 +120,8 @@ def parse_model(d, ch, verbose=False):
             m = Upsample
         elif m == "nn.Identity" and i == 0:  # yolov9e: layer 0 hands the image on, so that a later stem can read it (`from 0`)
             m = nn.Identity
+        elif m in _TORCH_ROWS:
+            m = _TORCH_ROWS[m]
         elif isinstance(m, str) and m.startswith("nn."):
             raise NotImplementedError(f"torch module '{m}' is not on the built detection path")
         else:
@@ -184,7 +198,10 @@ def parse_model(d, ch, verbose=False):
         else:
             c2 = ch[f]
         m_ = nn.Sequential(*(m(*args, **kw) for _ in range(n))) if n > 1 else m(*args, **kw)
-        t = f"{m.__module__}.{m.__name__}".replace("edge_yolo_amd", "ultralytics") if m is not Upsample else "torch.nn.modules.upsampling.Upsample"
+        if m in _TORCH_ROWS.values():  # the reference builds the torch module itself: its name is the type
+            t = f"{m.__mro__[1].__module__}.{m.__name__}"
+        else:
+            t = f"{m.__module__}.{m.__name__}".replace("edge_yolo_amd", "ultralytics") if m is not Upsample else "torch.nn.modules.upsampling.Upsample"
         m_.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t
         save.extend(x % i for x in ([f] if isinstance(f, int) else f) if x != -1)
@@ -209,7 +226,9 @@ def _layer_down(m, down):
         src *= m.cv1.conv.stride[0]
     elif isinstance(m, (DownsampleConv, ADown, AConv)):
         src *= 2
-    elif isinstance(m, Upsample):
+    elif isinstance(m, MaxPool2d):  # (ZeroPad2d: x 1, like every row not listed here)
+        src *= m.stride if isinstance(m.stride, int) else m.stride[0]
+    elif isinstance(m, (Upsample, ConvTranspose2d)):
         src /= 2
     elif isinstance(m, DySample):
         src /= m.scale
@@ -456,6 +475,10 @@ class DetectionModel(BaseModel):
             if isinstance(m, Upsample) and m.i not in self.save:
                 cs = consumers.get(m.i, [])
                 m.lazy = bool(cs) and all(isinstance(c, Concat) and c.lazy for c in cs)
+        for m in self.model:  # a ZeroPad2d read only by the MaxPool2d on the next row (yolov3-tiny rows 11-12): the pool pads in its own launch
+            if isinstance(m, ZeroPad2d) and m.i not in self.save:
+                cs = consumers.get(m.i, [])
+                m.lazy = len(cs) == 1 and isinstance(cs[0], MaxPool2d) and cs[0].i == m.i + 1 and cs[0].f == -1
 
     def _plan_blocks(self):
         """Runs of >= 2 consecutive non-head layers at the coarsest stride (layers 7-10 and 20-22 of the 24-layer YAMLs): candidates for

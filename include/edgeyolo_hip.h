@@ -133,6 +133,22 @@ int ey_conv2d_direct(const ey_conv_direct_desc* d, ey_stream_t stream);
  * x: [B,Cin,H,W] contiguous, x_dtype EY_F16|EY_F32; w: fp32 [Cout][Cin][3][3] device; Cin<=4, Cout%16==0. */
 int ey_stem_conv(int x_dtype, int y_dtype, int B, int Cin, int H, int W, int Cout, int act, const void* x_nchw,
                  const float* w_oihw, const float* bias, void* y, int y_cstride, ey_stream_t stream);
+/* The same contract for the other image stems: (k, stride, pad) = (6, 2, 2) (YOLOv5's Conv(3, c, 6, 2, 2)) and (3, 1, 1) (YOLOv3's
+ * Conv(3, c, 3, 1)); w: fp32 [Cout][Cin][k][k] device.  Ho = (H + 2 pad - k) / stride + 1: the 6x6 window of output o covers the input
+ * columns 2o - 2 ... 2o + 3.  f16 -> f16 with Cin = 3, W % 8 == 0, a 16-byte aligned image and Cout <= 80 runs on the MFMA (weights rounded to
+ * f16); everything else on the exact fp32 VALU form.  EY_EUNSUPPORTED (before anything is launched) for every other (k, stride, pad).
+ * ey_stem_conv_ks_last_variant: 1 when the last launch took the MFMA form, 0 for the VALU form (developer tools, tests). */
+int ey_stem_conv_ks(int x_dtype, int y_dtype, int B, int Cin, int H, int W, int Cout, int k, int stride, int pad, int act, const void* x_nchw,
+                    const float* w_oihw, const float* bias, void* y, int y_cstride, ey_stream_t stream);
+int ey_stem_conv_ks_last_variant(void);
+
+/* ---- nn.MaxPool2d(k, stride) behind an explicit nn.ZeroPad2d((pad_l, pad_r, pad_t, pad_b)) (yolov3-tiny): the padded cells take part in the
+ * maximum with value 0 -- not -inf -- so an all-negative border gives 0.  k = 2 with stride 1 or 2; k = 1, stride 1 is the zero-padded copy
+ * (a lone ZeroPad2d).  Ho = (H + pad_t + pad_b - k) / stride + 1 (floor: an odd last row / column is dropped at stride 2).  x and y are
+ * 16-byte aligned channel windows of NHWC buffers, C a multiple of 8.  Bit-identical to torch's max_pool2d of the padded map for finite
+ * inputs.  EY_EUNSUPPORTED for every other (k, stride). */
+int ey_maxpool2d(int dtype, int B, int H, int W, int C, int k, int stride, int pad_l, int pad_r, int pad_t, int pad_b, const void* x, int x_cstride,
+                 void* y, int y_cstride, ey_stream_t stream);
 
 /* ---- two chained 1x1 convs as one launch (f16, 64 or 128 channels, small maps): `second` must read exactly what `first` writes
  * (second->src[0] == first->y, same cstride, one source each; `first` may carry bias / addz / activation / out_scale / residual, `second`
