@@ -67,6 +67,7 @@ class CBFuseSrc(C.Structure):
 
 CBFUSE_MAX = 6  # EY_CBFUSE_MAX: the most sources ey_cbfuse takes
 BLK_CONV, BLK_DW, BLK_DWT, BLK_POOL, BLK_LINATTN = range(5)
+BLK_RAN_IMAGE, BLK_RAN_TILE, BLK_RAN_CHAIN = 1, 2, 3  # ey_block_last_variant
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 # name -> (restype, argtypes): every symbol include/edgeyolo_hip.h declares
 SIGNATURES = {
@@ -147,6 +148,10 @@ SIGNATURES = {
     "ey_block_run": (_i, [_vp, _i, _i, C.POINTER(C.c_void_p), _i, _vp]),
     "ey_block_tileable": (_i, [C.POINTER(BlockStage), _i]),
     "ey_block_run_tiles": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_void_p), _i, _vp]),
+    "ey_block_fast_plan_bytes": (_sz, []),
+    "ey_block_fast_plan": (_i, [C.POINTER(BlockStage), _i, _vp, _sz]),
+    "ey_block_run_chain": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_void_p), _i, _vp]),
+    "ey_block_last_variant": (_i, []),
     "ey_block_run_timed": (_i, [_vp, _i, _i, C.POINTER(C.c_void_p), _i, _vp, _vp]),
     "ey_nms_candidates_bytes": (_sz, [_i, _i]),
     "ey_head_tail_decode_levels_nms": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i,

@@ -11,7 +11,9 @@
 // accumulation (v_mfma_f32_16x16x32_f16), fp32 epilogues; the K order of every contraction is (ky, kx, source, channel) like
 // ey_conv2d.  f16 only (the fp32 parity mode keeps the per-layer kernels).
 #include "common.h"
+#include "tune.h"
 #include "linattn_mfma.inc.h"
+#include <string.h>
 
 #define BLK_THREADS 1024
 #define BLK_WAVES 16
@@ -522,6 +524,180 @@ __global__ __launch_bounds__(256) void block_tile_kernel(const BlkStage* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- register-weight chains
+// The same pointwise chains with the roles of conv_pwn_kernel: a 512-thread workgroup owns FAST_PX = 64 consecutive pixels of one image
+// (4 MFMA pixel blocks); in every stage wave w owns the 16-row output blocks w, w + 8, ... and keeps ITS weight fragments in registers,
+// so a fragment is read once per workgroup and feeds 4 MFMAs (block_tile_kernel: once per 32 pixels, 2 MFMAs).  No weight load waits
+// for data: the fragments of stage 0 are requested first thing, those of stage s + 1 before stage s multiplies.  Every global tensor the
+// chain reads (sources, residuals) and every bias is requested before the first barrier and goes to LDS once; a stage reads its pixel
+// fragments and its residual there and writes its output there (dead tensors are aliased), from where a lane copies what the caller
+// sees to global memory; ONE LDS-only barrier separates two stages.  Fragment counts index registers, so they are compile-time: a chain runs here when its
+// (k-steps, row blocks per wave) list is one of FAST_CHAINS below (ey_block_fast_plan decides; everything else keeps block_tile_kernel).
+// Arithmetic is tile_conv's: source 0 then source 1 in ascending 32-channel steps, one fp32 chain per output, blk_epilogue.
+#define FAST_PX 64
+#define FAST_WAVES 8
+#define FAST_MAX_STAGES 4
+#define FAST_MAX_JOBS 4
+#define FAST_MAX_SLOTS 8               // 512-vector rounds of the preload (<= 4096 16-byte vectors per tile)
+#define FAST_LDS_MAX (96 * 1024)
+
+struct FJob {     // one 512-vector round of a global tensor tile -> LDS (C channels of the tile's pixels); unused rounds: nv = 0, nothing is read
+  int64_t addr, img;     // (ext, addr) as in the program; the launch turns addr into the absolute address
+  int32_t ext, cs, C, cv, inv, nv, lds, pitch, v0, bytes;  // cv = C / 8 vectors per pixel, inv = ceil(2^20 / cv), nv = 64 * cv, lds / pitch in elements, v0 = first vector of the round, bytes = extent of an image's view
+};
+struct FStage {
+  const f16* w; const float* bias;
+  int64_t y, y_img;
+  int32_t y_ext, y_cs, y_glob, y_lds, y_pitch;   // y_glob: the caller sees the output (written to global memory behind its LDS slot)
+  int32_t res_lds, res_pitch;                    // residual (always LDS-resident), -1 = none
+  int32_t src_lds[2], src_pitch[2], nks0;        // nks0 = 32-channel steps of source 0
+  int32_t bias_lds, bias_bytes;                  // fp32 index into the bias area (at bias_base elements), -1 = no bias; 4 * Cout or 0
+  int32_t kpad, nt, nrb, Cout, act;
+  float out_scale;
+};
+struct FPlan {
+  int32_t sig, nstages, njobs, nslot, lds_bytes, M, bias_base, pad_;
+  FJob slot[FAST_MAX_SLOTS];
+  FStage st[FAST_MAX_STAGES];
+};
+
+typedef __attribute__((address_space(1))) f16 gf16;
+typedef __attribute__((address_space(1))) f16x4 gf16x4;
+template <int KS, int NRW> struct FS { static constexpr int ks = KS, nrw = NRW, nf = KS * NRW, code = KS * 8 + NRW; };
+template <class A, class... R> struct FFirst { typedef A type; };
+
+template <class S>
+__device__ __forceinline__ void fast_wload(Vec8<f16> (&wf)[S::nf], const FStage& t) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  const __amdgpu_buffer_rsrc_t rw = ey_rsrc(t.w, (unsigned)((long)t.nrb * 16 * t.kpad * 2));
+#pragma unroll
+  for (int i = 0; i < S::nrw; ++i) {
+    const int rb = wave + FAST_WAVES * i;
+    const unsigned off = rb < t.nrb ? (unsigned)(((rb * 16 + r) * t.kpad + 8 * g) * 2) : EY_OOB;
+#pragma unroll
+    for (int ks = 0; ks < S::ks; ++ks) BufLoad8<f16>::load(wf[ks * S::nrw + i], rw, off, ks * 64);
+  }
+}
+
+template <class S>
+__device__ __forceinline__ void fast_stage(const FStage& t, const Vec8<f16> (&wf)[S::nf], f16* lds, const float* lbias, int b, int m0, int M) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  if (wave >= t.nrb) return;  // (fewer row blocks than waves: this wave owns none)
+  f32x4 acc[S::nrw][4][1];
+#pragma unroll
+  for (int i = 0; i < S::nrw; ++i)
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) acc[i][pb][0] = (f32x4)0.f;
+  const int nks0 = t.nks0, p0 = t.src_pitch[0], p1 = t.src_pitch[1];
+  const int o0 = t.src_lds[0] + r * p0 + 8 * g, o1 = t.src_lds[1] + r * p1 + 8 * g;
+#pragma unroll
+  for (int ks = 0; ks < S::ks; ++ks) {
+    const bool s1 = ks >= nks0;  // (wave-uniform)
+    const int o = s1 ? o1 + (ks - nks0) * 32 : o0 + ks * 32, pit = s1 ? p1 : p0;
+    Vec8<f16> bq[4];
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) bq[pb].load(lds + o + pb * 16 * pit);
+#pragma unroll
+    for (int i = 0; i < S::nrw; ++i)
+#pragma unroll
+      for (int pb = 0; pb < 4; ++pb) acc[i][pb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ks * S::nrw + i].v, bq[pb].v, acc[i][pb][0], 0, 0, 0);
+  }
+  // ---- epilogue: lane (r, g) holds 4 consecutive channels of pixel 16 pb + r per row block (ey_conv_pack_weight's row permutation)
+#pragma unroll
+  for (int i = 0; i < S::nrw; ++i) {
+    const int rb = wave + FAST_WAVES * i;
+    if (rb >= t.nrb) break;
+    const int nb = rb / t.nt, j = rb - nb * t.nt;
+    const int ch0 = (nb * 16 + 4 * g) * t.nt + 4 * j;
+    BlkEpi e;
+    e.bias = t.bias_lds >= 0 ? lbias + t.bias_lds + ch0 : nullptr;
+    e.z = nullptr; e.addz_cs = 0; e.Hz = 0; e.Wz = 0; e.zsy = 0.f; e.zsx = 0.f;
+    e.act = t.act; e.out_scale = t.out_scale; e.nq = 1;
+    e.res = t.res_lds >= 0 ? lds + t.res_lds + ch0 : nullptr;
+    e.res_cs = t.res_pitch;
+    gf16* yg = t.y_glob ? (gf16*)(reinterpret_cast<f16*>(t.y) + (long)b * t.y_img + ch0) : nullptr;
+    // Always through LDS (a slot of its own, aliased over dead tensors, when no later stage reads the output): blk_epilogue's stores
+    // are then LDS writes, and the lane copies its own 4 halves out with a GLOBAL store.  Through a generic pointer both would be
+    // flat stores, which count as LDS traffic as well: every later LDS wait (bias, residual, the stage barrier) would wait for them.
+    f16* yl = lds + t.y_lds + ch0;
+    e.y = yl; e.y_cs = t.y_pitch;
+#pragma unroll
+    for (int pb = 0; pb < 4; ++pb) {
+      const int row = pb * 16 + r, m = m0 + row;
+      if (m >= M) continue;
+      blk_epilogue<1>(e, acc[i][pb], m, 0, 0, row, row);
+      if (t.y_glob) *reinterpret_cast<gf16x4*>(yg + (long)m * t.y_cs) = *reinterpret_cast<const f16x4*>(yl + row * t.y_pitch);
+    }
+  }
+}
+
+template <int SI, class Pre, class S0, class... Rest>
+__device__ __forceinline__ void fast_run(const FPlan& p, const Vec8<f16> (&wf)[S0::nf], const Pre& pre, f16* lds, const float* lbias, int b, int m0) {
+  if constexpr (sizeof...(Rest) > 0) {
+    typedef typename FFirst<Rest...>::type S1;
+    Vec8<f16> wn[S1::nf];
+    fast_wload<S1>(wn, p.st[SI + 1]);  // in flight while this stage multiplies
+    if constexpr (SI == 0) pre();
+    fast_stage<S0>(p.st[SI], wf, lds, lbias, b, m0, p.M);
+    ey_lds_barrier();  // this stage's LDS output is complete, its LDS inputs are free
+    fast_run<SI + 1, Pre, Rest...>(p, wn, pre, lds, lbias, b, m0);
+  } else {
+    if constexpr (SI == 0) pre();
+    fast_stage<S0>(p.st[SI], wf, lds, lbias, b, m0, p.M);
+  }
+}
+
+template <class... S>
+__global__ __launch_bounds__(512) void block_chain_kernel(FPlan p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  f16* lds = reinterpret_cast<f16*>(smem);
+  float* lbias = reinterpret_cast<float*>(lds + p.bias_base);
+  typedef typename FFirst<S...>::type S0;
+  const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * FAST_PX, M = p.M;
+  Vec8<f16> w0[S0::nf];
+  fast_wload<S0>(w0, p.st[0]);
+  // ---- every global tile and bias of the chain: all requests first, LDS stores behind the next stage's weight requests
+  // (branch-free: the plan carries one descriptor per round, an unused round or a missing bias is an empty buffer and reads nothing)
+  Vec8<f16> pv[FAST_MAX_SLOTS];
+  int pdst[FAST_MAX_SLOTS];
+#pragma unroll
+  for (int u = 0; u < FAST_MAX_SLOTS; ++u) {
+    const FJob& jb = p.slot[u];
+    const int v = tid + jb.v0;
+    const int px = (int)(((unsigned)v * (unsigned)jb.inv) >> 20), c8 = v - px * jb.cv;  // v / cv, exact for v < 4096 (cv < 256)
+    const unsigned goff = (unsigned)(((m0 + px) * jb.cs + c8 * 8) * 2);
+    const int ldst = jb.lds + px * jb.pitch + c8 * 8;
+    const bool in = v < jb.nv, ok = in & (m0 + px < M);  // (selects, no control flow: a branch here puts a wait for ALL loads in flight between two rounds)
+    const __amdgpu_buffer_rsrc_t rs = ey_rsrc(reinterpret_cast<const f16*>(jb.addr) + (long)b * jb.img, (unsigned)jb.bytes);
+    BufLoad8<f16>::load(pv[u], rs, ok ? goff : EY_OOB);
+    pdst[u] = in ? ldst : -1;
+  }
+  float bv[FAST_MAX_STAGES];
+#pragma unroll
+  for (int s = 0; s < FAST_MAX_STAGES; ++s) {
+    const FStage& t = p.st[s];  // (beyond nstages: zero-filled, bias_lds = -1)
+    const __amdgpu_buffer_rsrc_t rb = ey_rsrc(t.bias, (unsigned)t.bias_bytes);
+    bv[s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, tid * 4, 0, 0));
+  }
+  auto pre = [&]() {
+#pragma unroll
+    for (int u = 0; u < FAST_MAX_SLOTS; ++u)
+      if (pdst[u] >= 0) pv[u].store(lds + pdst[u]);
+#pragma unroll
+    for (int s = 0; s < FAST_MAX_STAGES; ++s)
+      if (p.st[s].bias_lds >= 0 && tid < p.st[s].Cout) lbias[p.st[s].bias_lds + tid] = bv[s];
+    ey_lds_barrier();
+  };
+  fast_run<0, decltype(pre), S...>(p, w0, pre, lds, lbias, b, m0);
+}
+
+// the instantiated chains: (k-steps, row blocks per wave) per stage
+#define FAST_CHAINS(X)                                \
+  X(FS<4, 1>, FS<4, 2>, FS<8, 1>, FS<8, 2>) /* C2PSA tail at c = 128: proj 128->128, ffn 128->256->128, cv2 256->256 */ \
+  X(FS<8, 2>, FS<4, 3>)                     /* C2PSA head at c = 128: cv1 256->256, qkv 128->384 */                     \
+  X(FS<2, 1>, FS<2, 1>, FS<4, 1>, FS<4, 1>) /* C2PSA tail at c = 64 */                                                  \
+  X(FS<4, 1>, FS<2, 2>)                     /* C2PSA head at c = 64 */
+
 // ---------------------------------------------------------------------------------------------------------------- host side
 static const int kMT[3] = {1, 2, 4};
 
@@ -663,6 +839,10 @@ extern "C" int ey_block_compile(const ey_block_stage* st, int nstages, void* out
   return EY_OK;
 }
 
+// which executor the last launch on this thread took (EY_BLK_RAN_*): a fallback is visible to tools and tests
+static thread_local int g_blk_last_variant = 0;
+extern "C" int ey_block_last_variant(void) { return g_blk_last_variant; }
+
 static int block_launch(const void* program_dev, int nstages, int B, const void* const* ext_ptrs_host, int next, long long* tstamps, ey_stream_t stream) {
   EY_CHECK(program_dev && nstages > 0 && B > 0, "block_run: null / empty program");
   EY_CHECK(next >= 0 && next <= BLK_MAX_EXT && (next == 0 || ext_ptrs_host), "block_run: %d external tensors (0..%d)", next, BLK_MAX_EXT);
@@ -679,6 +859,7 @@ static int block_launch(const void* program_dev, int nstages, int B, const void*
   }
   hipLaunchKernelGGL(block_kernel, dim3(B), dim3(BLK_THREADS), BLK_LDS_BYTES, (hipStream_t)stream, (const BlkStage*)program_dev, nstages, ext, tstamps);
   EY_LAUNCH_CHECK("ey_block_run");
+  g_blk_last_variant = EY_BLK_RAN_IMAGE;
   return EY_OK;
 }
 
@@ -710,6 +891,263 @@ extern "C" int ey_block_run_tiles(const void* program_dev, int nstages, int B, i
   const size_t lds = TILE_MAX_STAGES * sizeof(TStage) + (size_t)lds_bytes;
   hipLaunchKernelGGL(block_tile_kernel, dim3((unsigned)mtiles, (unsigned)B), dim3(256), lds, (hipStream_t)stream, (const BlkStage*)program_dev, nstages, ext);
   EY_LAUNCH_CHECK("ey_block_run_tiles");
+  g_blk_last_variant = EY_BLK_RAN_TILE;
+  return EY_OK;
+}
+// ---- register-weight chains (block_chain_kernel): plan on the host, where the stage list is known
+template <class... S>
+static constexpr uint32_t fast_sig() {
+  uint32_t sig = 0;
+  int sh = 0;
+  ((sig |= (uint32_t)S::code << sh, sh += 8), ...);
+  return sig;
+}
+static bool fast_sig_known(uint32_t sig) {
+#define EY_X(...) if (sig == fast_sig<__VA_ARGS__>()) return true;
+  FAST_CHAINS(EY_X)
+#undef EY_X
+  return false;
+}
+static int fast_pitch(int C) {  // LDS pixel pitch (elements): 2 (mod 4) 16-byte units, conflict-free fragment reads (as pwn_launch)
+  int units = C >> 3;
+  while ((units & 3) != 2) ++units;
+  return units * 8;
+}
+
+extern "C" size_t ey_block_fast_plan_bytes(void) { return sizeof(FPlan); }
+
+// Eligibility + lowering of a compiled, tileable program for block_chain_kernel.  1: plan_host holds the plan; 0: not eligible (the
+// program keeps block_tile_kernel).  Pure host function of the stage list.
+extern "C" int ey_block_fast_plan(const ey_block_stage* cs, int nstages, void* plan_host, size_t plan_bytes) {
+  if (!cs || !plan_host || plan_bytes < sizeof(FPlan) || nstages > FAST_MAX_STAGES || !ey_block_tileable(cs, nstages)) return 0;
+  FPlan p;
+  memset(&p, 0, sizeof(p));
+  p.nstages = nstages;
+  p.M = cs[0].Ho * cs[0].Wo;
+  for (int u = 0; u < FAST_MAX_SLOTS; ++u) { p.slot[u].ext = -1; p.slot[u].cv = 1; }  // unused rounds: an empty buffer
+  for (int i = 0; i < FAST_MAX_STAGES; ++i) p.st[i].bias_lds = -1;
+  // ---- shapes: pointwise, no addz, 32-channel sources, whole packed block tiles, an instantiated (k-steps, row blocks per wave) list
+  uint32_t sig = 0;
+  for (int i = 0; i < nstages; ++i) {
+    const ey_block_stage& s = cs[i];
+    if (s.k != 1 || s.stride != 1 || s.ngroup != 1 || s.has_addz || s.Cout > 512 || s.Cout % (16 * s.nt_pack)) return 0;
+    int K = 0;
+    for (int j = 0; j < s.nsrc; ++j) {
+      if (s.src_C[j] % 32) return 0;
+      K += s.src_C[j];
+    }
+    const int ks = K / 32, nrw = (s.Cout / 16 + FAST_WAVES - 1) / FAST_WAVES;
+    if (ks > 31 || nrw > 7) return 0;
+    sig |= (uint32_t)(ks * 8 + nrw) << (8 * i);
+  }
+  if (!fast_sig_known(sig)) return 0;  // (the per-wave fragment budget: only the instantiated lists fit the register file by construction)
+  p.sig = (int32_t)sig;
+  // ---- LDS tensors: overlapping channel ranges of one pixel row (same tensor, pixel stride and image stride) are ONE buffer
+  struct Buf { int ext, cs, fw, lr, lds, pitch; int64_t img, lo, hi; uint64_t valid, pre; bool read; };
+  struct Ref { int ext, cs, C; int64_t addr, img; };
+  Buf buf[16];
+  int nbuf = 0;
+  auto touch = [&](const Ref& r) -> bool {
+    if (nbuf >= 16) return false;
+    Buf n;
+    memset(&n, 0, sizeof(n));
+    n.ext = r.ext; n.cs = r.cs; n.img = r.img; n.lo = r.addr; n.hi = r.addr + 2 * (int64_t)r.C; n.fw = 99; n.lr = -1; n.lds = -1;
+    buf[nbuf++] = n;
+    for (bool again = true; again;) {  // merge until no two buffers of one tensor overlap
+      again = false;
+      for (int a = 0; a < nbuf && !again; ++a)
+        for (int c = a + 1; c < nbuf && !again; ++c) {
+          Buf &u = buf[a], &o = buf[c];
+          if (u.ext != o.ext || u.cs != o.cs || u.img != o.img || u.lo >= o.hi || o.lo >= u.hi) continue;
+          u.lo = u.lo < o.lo ? u.lo : o.lo;
+          u.hi = u.hi > o.hi ? u.hi : o.hi;
+          buf[c] = buf[--nbuf];
+          again = true;
+        }
+    }
+    return true;
+  };
+  auto src_ref = [&](const ey_block_stage& s, int j) { Ref r = {s.src_ext[j], s.src_cs[j], s.src_C[j], s.src[j], s.src_img[j]}; return r; };
+  auto res_ref = [&](const ey_block_stage& s) { Ref r = {s.res_ext, s.res_cs, s.Cout, s.res, s.res_img}; return r; };
+  auto y_ref = [&](const ey_block_stage& s) { Ref r = {s.y_ext, s.y_cs, s.Cout, s.y, s.y_img}; return r; };
+  for (int i = 0; i < nstages; ++i) {
+    const ey_block_stage& s = cs[i];
+    for (int j = 0; j < s.nsrc; ++j) if (!touch(src_ref(s, j))) return 0;
+    if (s.has_res && !touch(res_ref(s))) return 0;
+    if (!touch(y_ref(s))) return 0;
+  }
+  auto find = [&](const Ref& r) -> int {
+    for (int q = 0; q < nbuf; ++q)
+      if (buf[q].ext == r.ext && buf[q].cs == r.cs && buf[q].img == r.img && r.addr >= buf[q].lo && r.addr + 2 * (int64_t)r.C <= buf[q].hi) return q;
+    return -1;
+  };
+  auto mask = [&](const Buf& u, const Ref& r) -> uint64_t {  // the 8-channel units of r inside u
+    const int u0 = (int)((r.addr - u.lo) / 16), n = r.C / 8;
+    return (n >= 64 ? ~0ull : ((1ull << n) - 1)) << u0;
+  };
+  for (int q = 0; q < nbuf; ++q)
+    if ((buf[q].hi - buf[q].lo) > 2 * (int64_t)buf[q].cs || (buf[q].hi - buf[q].lo) > 64 * 16 || (buf[q].lo % 16)) return 0;  // one pixel row, <= 512 channels
+  // ---- walk the stages: what is read before the chain wrote it comes from global memory (preload); lifetimes for the LDS placement
+  for (int i = 0; i < nstages; ++i) {
+    const ey_block_stage& s = cs[i];
+    const Ref yr = y_ref(s);
+    const int yb = find(yr);
+    if (yb < 0) return 0;
+    const uint64_t ym = mask(buf[yb], yr);
+    auto rd = [&](const Ref& r, bool is_res) -> bool {
+      const int q = find(r);
+      if (q < 0) return false;
+      Buf& u = buf[q];
+      const uint64_t m = mask(u, r);
+      if (q == yb && (m & ym) && !(is_res && m == ym)) return false;  // in-place over a source: other waves still read it (a residual of the same range is the lane's own)
+      const uint64_t need = m & ~u.valid;
+      if (need) { u.pre |= need; u.valid |= need; u.fw = -1; }
+      u.read = true;
+      if (u.lr < i) u.lr = i;
+      return true;
+    };
+    for (int j = 0; j < s.nsrc; ++j) if (!rd(src_ref(s, j), false)) return 0;
+    if (s.has_res && !rd(res_ref(s), true)) return 0;
+    Buf& u = buf[yb];
+    u.valid |= ym;
+    if (u.fw > i) u.fw = i;
+    if (u.lr < i) u.lr = i;
+  }
+  // ---- placement: largest first, first fit among the buffers whose lifetimes overlap (a buffer last read in stage s may be
+  // overwritten from the epilogue of stage s + 1 on: a barrier lies between)
+  int order[16], nord = 0;
+  for (int q = 0; q < nbuf; ++q) {
+    Buf& u = buf[q];  // (an output nobody in the chain reads included: its epilogue goes through LDS on the way to global memory)
+    u.pitch = fast_pitch((int)((u.hi - u.lo) / 2));
+    order[nord++] = q;
+  }
+  for (int a = 0; a < nord; ++a)
+    for (int c = a + 1; c < nord; ++c)
+      if (buf[order[c]].pitch > buf[order[a]].pitch) { const int t = order[a]; order[a] = order[c]; order[c] = t; }
+  long top = 0;
+  for (int a = 0; a < nord; ++a) {
+    Buf& u = buf[order[a]];
+    const long size = (long)FAST_PX * u.pitch;
+    long best = -1;
+    for (int c = -1; c < a; ++c) {  // candidate offsets: 0 and the end of every placed buffer
+      const long off = c < 0 ? 0 : buf[order[c]].lds + (long)FAST_PX * buf[order[c]].pitch;
+      bool ok = true;
+      for (int d = 0; d < a && ok; ++d) {
+        const Buf& o = buf[order[d]];
+        const bool live = !(o.lr < u.fw || u.lr < o.fw);
+        if (live && off < o.lds + (long)FAST_PX * o.pitch && o.lds < off + size) ok = false;
+      }
+      if (ok && (best < 0 || off < best)) best = off;
+    }
+    u.lds = (int)best;
+    if (best + size > top) top = best + size;
+  }
+  // ---- preload jobs: runs of units read before written
+  for (int q = 0; q < nbuf; ++q) {
+    const Buf& u = buf[q];
+    for (int b0 = 0; b0 < 64;) {
+      if (!((u.pre >> b0) & 1)) { ++b0; continue; }
+      int b1 = b0;
+      while (b1 < 64 && ((u.pre >> b1) & 1)) ++b1;
+      if (p.njobs >= FAST_MAX_JOBS || u.lds < 0) return 0;
+      FJob jb;
+      memset(&jb, 0, sizeof(jb));
+      jb.addr = u.lo + 16 * (int64_t)b0; jb.img = u.img; jb.ext = u.ext; jb.cs = u.cs;
+      jb.cv = b1 - b0; jb.C = 8 * jb.cv; jb.inv = ((1 << 20) + jb.cv - 1) / jb.cv; jb.nv = FAST_PX * jb.cv;
+      jb.lds = u.lds + 8 * b0; jb.pitch = u.pitch;
+      jb.bytes = (int32_t)((((long)p.M - 1) * jb.cs + jb.C) * 2);
+      if (jb.cv < 2) return 0;
+      for (int v0 = 0; v0 < jb.nv; v0 += 512) {
+        if (p.nslot >= FAST_MAX_SLOTS) return 0;
+        jb.v0 = v0;
+        p.slot[p.nslot++] = jb;
+      }
+      ++p.njobs;
+      b0 = b1;
+    }
+  }
+  // ---- stages
+  p.bias_base = (int32_t)((top + 7) / 8 * 8);
+  int nbias = 0;
+  for (int i = 0; i < nstages; ++i) {
+    const ey_block_stage& s = cs[i];
+    FStage& t = p.st[i];
+    t.w = reinterpret_cast<const f16*>(s.w); t.bias = s.bias;
+    t.y = s.y; t.y_img = s.y_img; t.y_ext = s.y_ext; t.y_cs = s.y_cs;
+    t.y_glob = s.y_ext >= 0;
+    const Ref yr = y_ref(s);
+    const Buf& yb = buf[find(yr)];
+    t.y_lds = -1; t.y_pitch = 0;
+    if (yb.lds < 0) return 0;
+    t.y_lds = yb.lds + (int)((yr.addr - yb.lo) / 2); t.y_pitch = yb.pitch;
+    t.res_lds = -1; t.res_pitch = 0;
+    if (s.has_res) {
+      const Ref rr = res_ref(s);
+      const Buf& rb = buf[find(rr)];
+      if (rb.lds < 0) return 0;
+      t.res_lds = rb.lds + (int)((rr.addr - rb.lo) / 2); t.res_pitch = rb.pitch;
+    }
+    for (int j = 0; j < 2; ++j) { t.src_lds[j] = 0; t.src_pitch[j] = 0; }
+    for (int j = 0; j < s.nsrc; ++j) {
+      const Ref sr = src_ref(s, j);
+      const Buf& sb = buf[find(sr)];
+      if (sb.lds < 0) return 0;
+      t.src_lds[j] = sb.lds + (int)((sr.addr - sb.lo) / 2); t.src_pitch[j] = sb.pitch;
+    }
+    t.nks0 = s.src_C[0] / 32;
+    t.bias_lds = -1;
+    if (s.bias) { t.bias_lds = nbias; t.bias_bytes = 4 * s.Cout; nbias += s.Cout; }
+    t.kpad = s.kpad; t.nt = s.nt_pack; t.nrb = s.Cout / 16; t.Cout = s.Cout; t.act = s.act; t.out_scale = s.out_scale;
+  }
+  const long bytes = (long)p.bias_base * 2 + (long)nbias * 4;
+  if (bytes > FAST_LDS_MAX) return 0;
+  p.lds_bytes = (int32_t)bytes;
+  memcpy(plan_host, &p, sizeof(p));
+  return 1;
+}
+
+template <class... S>
+static int chain_launch(const FPlan& p, int B, hipStream_t st) {
+  const size_t lds = (size_t)p.lds_bytes;
+  if (!ey_lds_reserve<block_chain_kernel<S...>>(lds)) return ey_set_error(EY_ELAUNCH, "block_run_chain: cannot reserve %zu B of LDS", lds);
+  hipLaunchKernelGGL((block_chain_kernel<S...>), dim3((unsigned)((p.M + FAST_PX - 1) / FAST_PX), (unsigned)B), dim3(512), lds, st, p);
+  return EY_OK;
+}
+
+// ey_block_run_tiles with a plan: plan_host = what ey_block_fast_plan filled for this program, or NULL.  With a plan and the tunable
+// chain_fast != 0 the program runs on block_chain_kernel, otherwise on block_tile_kernel; ey_block_last_variant tells which.
+extern "C" int ey_block_run_chain(const void* program_dev, int nstages, int B, int H, int W, int lds_bytes, const void* plan_host,
+                                  const void* const* ext_ptrs_host, int next, ey_stream_t stream) {
+  if (!plan_host || tune().chain_fast == 0) return ey_block_run_tiles(program_dev, nstages, B, H, W, lds_bytes, ext_ptrs_host, next, stream);
+  FPlan p;
+  memcpy(&p, plan_host, sizeof(p));
+  EY_CHECK(B > 0 && B <= 65535 && H > 0 && W > 0 && p.nstages == nstages && p.M == H * W && p.lds_bytes > 0 && p.lds_bytes <= FAST_LDS_MAX &&
+               p.njobs >= 0 && p.njobs <= FAST_MAX_JOBS && p.nslot >= 0 && p.nslot <= FAST_MAX_SLOTS,
+           "block_run_chain: the plan does not belong to this program (%d stages, %dx%d)", nstages, H, W);
+  EY_CHECK(next >= 0 && next <= BLK_MAX_EXT && (next == 0 || ext_ptrs_host), "block_run_chain: %d external tensors (0..%d)", next, BLK_MAX_EXT);
+  BlkExt ext;
+  for (int i = 0; i < BLK_MAX_EXT; ++i) {
+    ext.p[i] = i < next ? (char*)const_cast<void*>(ext_ptrs_host[i]) : nullptr;
+    EY_CHECK(i >= next || (ext.p[i] && ey_aligned(ext.p[i], 16)), "block_run_chain: external tensor %d null / not 16-byte aligned", i);
+  }
+  // the kernel takes absolute addresses: (index, byte offset) references are bound to this call's external tensors here
+  for (int u = 0; u < FAST_MAX_SLOTS; ++u) {
+    EY_CHECK(p.slot[u].ext < next, "block_run_chain: the plan names external tensor %d of %d", p.slot[u].ext, next);
+    if (p.slot[u].ext >= 0) p.slot[u].addr += (int64_t)(uintptr_t)ext.p[p.slot[u].ext];
+  }
+  for (int i = 0; i < FAST_MAX_STAGES; ++i) {
+    EY_CHECK(p.st[i].y_ext < next, "block_run_chain: the plan names external tensor %d of %d", p.st[i].y_ext, next);
+    if (p.st[i].y_glob && p.st[i].y_ext >= 0) p.st[i].y += (int64_t)(uintptr_t)ext.p[p.st[i].y_ext];
+  }
+  int rc = EY_EINVAL;
+  bool found = false;
+#define EY_X(...) if (!found && (uint32_t)p.sig == fast_sig<__VA_ARGS__>()) { found = true; rc = chain_launch<__VA_ARGS__>(p, B, (hipStream_t)stream); }
+  FAST_CHAINS(EY_X)
+#undef EY_X
+  EY_CHECK(found, "block_run_chain: no kernel for chain signature %#x", (unsigned)p.sig);
+  if (rc != EY_OK) return rc;
+  EY_LAUNCH_CHECK("ey_block_run_chain");
+  g_blk_last_variant = EY_BLK_RAN_CHAIN;
   return EY_OK;
 }
 // developer tool: same launch; workgroup 0 also writes wall_clock64() (100 MHz) at the start and after every stage into tstamps_dev[nstages + 1]

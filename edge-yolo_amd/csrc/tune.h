@@ -64,6 +64,7 @@ struct EyTune {
   long nms_mask_k = 1536;       // ... all-pairs bit matrix over the first this-many of them (multiple of 512); later candidates are tested against the kept boxes on the fly
   long head_fuse = 2;           // predict-mode Detect head: the towers' closing 1x1 convs inside the decode kernel (head_tail_decode_kernel): 0 = separate launches, 1 = box tail, 2 = box tail and class chain (read by nn/modules/head.py; same bits)
   long head_lean = 1;           // head decode, candidates without pred (f16): best class from the largest logit, 2 sigmoids per anchor (0 = score every class; same bits)
+  long chain_fast = 1;          // tiled block programs: the register-weight executor (block_chain_kernel) where ey_block_fast_plan made a plan (0 = always block_tile_kernel; same bits)
   long nms_fast_k = 2048;       // predict-mode NMS: the three-kernel fast path over the best K candidates per image (<= 2048; 0 = general kernel only)
 };
 extern EyTune g_ey_tune;

@@ -149,8 +149,9 @@ class BlockRecorder:
 
     # -- finish: external tensors -> (index, byte offset); compile; upload
     def finish(self, ins, outs, tag="", tiled=False):
-        """tiled=True: the chain must be pointwise (1x1 convs on one map): it then runs as one workgroup per 16-pixel tile over the whole
-        chip (ey_block_run_tiles) instead of one workgroup per image."""
+        """tiled=True: the chain must be pointwise (1x1 convs on one map): it then runs as one workgroup per pixel tile over the whole
+        chip (ey_block_run_chain: 64-pixel tiles with register-resident weights where ey_block_fast_plan takes the program, else
+        block_tile_kernel's 32-pixel tiles) instead of one workgroup per image."""
         if not self.stages:
             raise BlockUnsupported("empty chain")
         ext = []  # (storage ptr, nbytes, "in" | "out")
@@ -194,6 +195,9 @@ class BlockRecorder:
             raise BlockUnsupported("not a pointwise chain")
         prog = BlockProgram(host.to(dev), n, ins, outs, ext, [t for t in self.keep if t is not None], self.flops, self.wbytes, tag)
         prog.tiled, prog.HW, prog.tile_lds = bool(tiled), (cs[0].Ho, cs[0].Wo), int(cs[0].tile_lds_bytes)
+        if tiled:  # the register-weight executor's plan (host memory, position-independent), or None: not eligible
+            plan = ctypes.create_string_buffer(L.lib().ey_block_fast_plan_bytes())
+            prog.fast_plan = plan if L.lib().ey_block_fast_plan(cs, n, plan, len(plan)) else None
         prog.desc = [f"{d}  tile {cs[i].mt}x{cs[i].nti}{' lds' if cs[i].lds else ''}" if cs[i].op == L.BLK_CONV else d for i, d in enumerate(self.desc)]
         return prog
 
@@ -216,7 +220,7 @@ class BlockProgram:
         self.alg_bytes = sum(t.numel() * t.element_size() for t in list(ins) + list(outs)) + wbytes
         self.first_outs = list(outs)  # the tensors allocated while recording serve the first run
         self.timing = None
-        self.tiled, self.HW, self.tile_lds = False, (0, 0), 0
+        self.tiled, self.HW, self.tile_lds, self.fast_plan = False, (0, 0), 0, None
 
     def matches(self, ins):
         return len(ins) == len(self.in_sig) and all(_sig(t) == s for t, s in zip(ins, self.in_sig))
@@ -251,11 +255,18 @@ class BlockProgram:
             return outs
         if self.tiled:
             with _ops._tr(f"block_tile_kernel<{self.tag}>", self.alg_bytes, self.flops, note=f"{self.n} stages"):
-                L.check(L.lib().ey_block_run_tiles(self.prog.data_ptr(), self.n, self.B, self.HW[0], self.HW[1], self.tile_lds, arr, len(ptrs), L.stream()), "ey_block_run_tiles")
+                L.check(L.lib().ey_block_run_chain(self.prog.data_ptr(), self.n, self.B, self.HW[0], self.HW[1], self.tile_lds, self.fast_plan, arr, len(ptrs),
+                                                   L.stream()), "ey_block_run_chain")
             return outs
         with _ops._tr(f"block_kernel<{self.tag}>", self.alg_bytes, self.flops, note=f"{self.n} stages"):
             L.check(L.lib().ey_block_run(self.prog.data_ptr(), self.n, self.B, arr, len(ptrs), L.stream()), "ey_block_run")
         return outs
+
+
+def last_executor():
+    """Which executor the last block-program launch of this thread took: "image" (block_kernel), "tile" (block_tile_kernel) or "fast"
+    (block_chain_kernel, register-resident weights); None before the first launch."""
+    return {L.BLK_RAN_IMAGE: "image", L.BLK_RAN_TILE: "tile", L.BLK_RAN_CHAIN: "fast"}.get(L.lib().ey_block_last_variant())
 
 
 class BlockCache:

@@ -27,11 +27,14 @@ def _slot(buf, i, c):
 
 class _Chains(nn.Module):
     """Mixin: pointwise chains of a block -- runs of 1x1 convs whose pixels do not interact -- as ONE launch each (nn/_block.py tiled
-    programs: recorded from the ordinary module code below, one 256-thread workgroup per 16-pixel tile walks the stages).  The caches
+    programs: recorded from the ordinary module code below; one 512-thread workgroup per 64-pixel tile with register-resident weights
+    where ey_block_fast_plan takes the chain, else one 256-thread workgroup per 32-pixel tile walks the stages).  The caches
     hold packed weights, so they are dropped whenever parameters move or reload.  `pw_chains = False` keeps one launch per conv."""
 
-    # True, False, or a tuple of chain names.  Measured on MI355X at batch 32 (C2PSA at 256 channels, 20x20): the four-conv tail as one
-    # launch 43 us vs 55 us for four launches; the two-conv head 43 us vs 36 us (its 16 MB of outputs bound it, not launches)
+    # True, False, or a tuple of chain names.  Measured on MI355X inside the benchmarked step (batch 32, C2PSA at 256 channels, 20x20,
+    # kernel trace; profiles/chain_fast_*): the four-conv tail as one launch 22.9 us on the register-weight executor (44.5 us on
+    # block_tile_kernel).  The two-conv head as one launch takes 23.9 us against 10.8 + 15.2 us for its two conv_pwn launches: the
+    # step is not faster for it in the pipelined mode (see profiles/chain_fast_bench_parent_vs_branch.txt), so it stays off
     pw_chains = ("proj_ffn_cv2",)
 
     def _chain(self, name):

@@ -633,6 +633,24 @@ int ey_block_run(const void* program_dev, int nstages, int B, const void* const*
 int ey_block_tileable(const ey_block_stage* compiled_host, int nstages);
 int ey_block_run_tiles(const void* program_dev, int nstages, int B, int H, int W, int lds_bytes /* compiled stage 0's tile_lds_bytes */,
                        const void* const* ext_ptrs_host, int next, ey_stream_t stream);
+/* Register-weight executor for the same programs (block_chain_kernel): one 512-thread workgroup per 64 consecutive pixels of an image
+ * (grid = ceil(H*W/64) x B); in every stage a wave keeps the weight fragments of ITS 16-row output blocks in registers (requested at
+ * kernel start / while the stage before multiplies), every global source, residual and bias goes to LDS once before the first
+ * barrier, one LDS-only barrier per stage.  Same arithmetic, byte-equal results.
+ * ey_block_fast_plan: pure host function of a COMPILED program; returns 1 and fills plan_host (ey_block_fast_plan_bytes() bytes, host
+ * memory, position-independent: keep it beside the program) when the program is eligible, 0 otherwise.  Eligible = tileable, at most
+ * 4 stages, no addz, source channels multiples of 32, Cout a multiple of its packed block tile (16 * nt_pack) and <= 512, the list of
+ * (k-steps, row blocks per wave) per stage is one the kernel is instantiated for (the per-wave fragment budget; C2PSA's head and tail
+ * at c = 64 / 128), no stage writes in place over one of its own sources, at most 4096 16-byte vectors of global inputs per tile,
+ * and the LDS plan (dead tensors aliased) fits 96 KiB.
+ * ey_block_run_chain = ey_block_run_tiles plus the plan (NULL = none): with a plan and the tunable chain_fast != 0 it launches the
+ * register-weight executor, otherwise block_tile_kernel.  ey_block_last_variant: the executor the last ey_block_run* call on this thread took. */
+enum { EY_BLK_RAN_IMAGE = 1, EY_BLK_RAN_TILE = 2, EY_BLK_RAN_CHAIN = 3 };
+size_t ey_block_fast_plan_bytes(void);
+int ey_block_fast_plan(const ey_block_stage* compiled_host, int nstages, void* plan_host, size_t plan_bytes);
+int ey_block_run_chain(const void* program_dev, int nstages, int B, int H, int W, int lds_bytes, const void* plan_host,
+                       const void* const* ext_ptrs_host, int next, ey_stream_t stream);
+int ey_block_last_variant(void);
 /* Developer tool: the same launch; workgroup 0 also stores wall_clock64() (100 MHz ticks) at the start and after every stage into
  * tstamps_dev[nstages + 1] (tools/block_stage_times.py prints the per-stage split). */
 int ey_block_run_timed(const void* program_dev, int nstages, int B, const void* const* ext_ptrs_host, int next, long long* tstamps_dev, ey_stream_t stream);
