@@ -91,6 +91,10 @@ SIGNATURES = {
     "ey_stem_conv_ks": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_stem_conv_ks_last_variant": (_i, []),
     "ey_maxpool2d": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_maxpool3x3s2": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "ey_resnet_stem": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ey_resnet_stem_last_variant": (_i, []),
+    "ey_resnet_tail": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_dwconv": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_dsconv": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ey_dsconv_toeplitz_bytes": (_sz, [_i, _i]),

@@ -1,22 +1,14 @@
-// Operators of the classic families (YOLOv3, YOLOv5, YOLOv6): the image stems that are not 3x3 stride 2 -- Conv(3, c, 6, 2, 2) of YOLOv5 and
-// Conv(3, c, 3, 1, 1) of YOLOv3 -- read from the planar NCHW image and written NHWC, and the 2x2 max-pool of YOLOv3-tiny with explicit ZERO
+// Operators of the classic families (YOLOv3, YOLOv5, YOLOv6): the image stems that are not 3x3 stride 2 -- Conv(3, c, 6, 2, 2) of YOLOv5,
+// Conv(3, c, 3, 1, 1) of YOLOv3 and Conv(3, 64, 7, 2, 3) of the ResNet stem (resnet.hip) -- read from the planar NCHW image and written NHWC, and the 2x2 max-pool of YOLOv3-tiny with explicit ZERO
 // padding (nn.ZeroPad2d in front of nn.MaxPool2d).
 #include "common.h"
 #include "tune.h"
+#include "stem_ks.inc.h"
 
-// ============================================================================ stems: NCHW image -> NHWC, (k, s, p) = (6, 2, 2) and (3, 1, 1)
+// ============================================================================ stems: NCHW image -> NHWC, (k, s, p) = (6, 2, 2), (3, 1, 1), (7, 2, 3)
 // Same two forms as the 3x3 stride-2 stem of ops_misc.hip.  The 6x6 window is NOT centred: output pixel o reads the input columns
 // 2o - 2 ... 2o + 3 (pad 2 in front, taps 0 ... 5).
-#define SK_TR 8
-#define SK_TC 64
-template <int K, int S, int P>
-struct SkGeo {
-  static constexpr int HR = S * (SK_TR - 1) + K;                    // staged input rows of a tile: 2 TR + 4 at (6, 2, 2)
-  static constexpr int NVC = (8 - P + S * (SK_TC - 1) + K + 7) / 8;  // staged 8-column vectors of a row; the first starts at S ox0 - 8
-  static constexpr int LW = NVC * 8 + 8;                              // LDS row stride (elements)
-  static constexpr int KK = 3 * K * K;                                // GEMM K: 108 / 27
-  static constexpr int KC = (KK + 31) / 32;                           // 16x16x32 MFMAs per 16 pixels x 16 channels: 4 / 1
-};
+// (geometry and the per-pixel device functions: stem_ks.inc.h, shared with the single-launch ResNet stem of resnet.hip)
 
 // MFMA form (f16 image -> f16 NHWC, Cin = 3, W % 8 == 0).  A workgroup stages the 3 x HR x (8 NVC) input patch of an 8 x 64 output tile into LDS
 // with range-checked 16-byte loads of the planar image (out of range = the zero padding), then every lane gathers its taps
@@ -26,99 +18,34 @@ template <int NT, int K, int S, int P>
 __global__ __launch_bounds__(256) void stem_ks_mfma_kernel(int B, int H, int W, int Ho, int Wo, int act, const f16* __restrict__ x, unsigned xbytes,
                                                            const float* __restrict__ w, const float* __restrict__ bias, f16* __restrict__ y, int yCs) {
   using G = SkGeo<K, S, P>;
-  constexpr int HR = G::HR, NVC = G::NVC, LW = G::LW, KK = G::KK, KC = G::KC, NV = 3 * HR * NVC;
+  constexpr int HR = G::HR, LW = G::LW, KC = G::KC;
   __shared__ __attribute__((aligned(16))) f16 s_in[3 * HR * LW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
   const int tilesX = (Wo + SK_TC - 1) / SK_TC, tilesY = (Ho + SK_TR - 1) / SK_TR;
   const int b = blockIdx.x / (tilesX * tilesY), trem = blockIdx.x - b * (tilesX * tilesY);
   const int oy0 = (trem / tilesX) * SK_TR, ox0 = (trem % tilesX) * SK_TC;
-  const int iy0 = S * oy0 - P, ixa = S * ox0 - 8;  // first staged input row / (8-aligned) column
-  const __amdgpu_buffer_rsrc_t rs = ey_rsrc(x, xbytes);
-#pragma unroll
-  for (int u = 0; u < (NV + 255) / 256; ++u) {
-    const int v = tid + u * 256;
-    if (v < NV) {
-      const int c = v / (HR * NVC), rem = v - c * (HR * NVC), row = rem / NVC, vc = rem - row * NVC;
-      const int iy = iy0 + row, ix = ixa + 8 * vc;
-      const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;  // W % 8 == 0: a vector is entirely inside or entirely outside
-      Vec8<f16> t;
-      BufLoad8<f16>::load(t, rs, ok ? (unsigned)(((((long)b * 3 + c) * H + iy) * W + ix) * 2) : EY_OOB);
-      t.store(s_in + (c * HR + row) * LW + 8 * vc);
-    }
-  }
-  // A fragments (weights, fp32 OIHW -> f16) and this lane's tap offsets: k = 32 kc + 8 g + t = c K K + ky K + kx
+  sk_stage<K, S, P>(s_in, ey_rsrc(x, xbytes), b, H, W, oy0, ox0, tid);
   Vec8<f16> af[NT][KC];
   int off[KC][8];
-#pragma unroll
-  for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int k = 32 * kc + 8 * g + t, c = k / (K * K), ky = (k - K * K * c) / K, kx = k - K * K * c - K * ky;
-      off[kc][t] = k < KK ? (c * HR + ky) * LW + kx : -1;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) af[nt][kc].v[t] = k < KK ? (f16)w[(nt * 16 + r) * KK + k] : (f16)0.f;
-    }
   float bs[NT][4];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bs[nt][j] = bias ? bias[nt * 16 + 4 * g + j] : 0.f;
+  sk_frags<NT, K, S, P>(w, bias, r, g, af, off, bs);
   __syncthreads();
   // wave w: output rows 2w, 2w+1 of the tile, 4 column blocks of 16 pixels each
 #pragma unroll 1
   for (int blk = 0; blk < 8; ++blk) {
     const int rr = 2 * wave + (blk >> 2), j = (blk & 3) * 16 + r;
-    const f16* bp = s_in + (S * rr) * LW + S * j + (8 - P);
     f32x4 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4)0.f;
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc) {
-      Vec8<f16> bq;
-      if constexpr (K % 2 == 0 && S % 2 == 0 && P % 2 == 0) {
-        // an even window at an even stride: the taps (kx, kx + 1) of an even kx are neighbours in k and in LDS, and every offset is even --
-        // four 4-byte reads instead of eight 2-byte reads and their packing
-        ey_u32x4 u;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) u[t] = off[kc][2 * t] >= 0 ? *reinterpret_cast<const unsigned*>(bp + off[kc][2 * t]) : 0u;
-        bq.v = __builtin_bit_cast(f16x8, u);
-      } else {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) bq.v[t] = off[kc][t] >= 0 ? bp[off[kc][t]] : (f16)0.f;
-      }
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt][kc].v, bq.v, acc[nt], 0, 0, 0);
-    }
+    sk_px16<NT, K, S, P>(s_in + (S * rr) * LW + S * j + (8 - P), off, af, acc);
     const int oy = oy0 + rr, ox = ox0 + j;
     if (oy < Ho && ox < Wo) {
       f16* yp = y + (((long)b * Ho + oy) * Wo + ox) * yCs + 4 * g;
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        float v4[4] = {acc[nt][0] + bs[nt][0], acc[nt][1] + bs[nt][1], acc[nt][2] + bs[nt][2], acc[nt][3] + bs[nt][3]};
-        ey_act_n(v4, act);
-        const f16x4 o = {(f16)v4[0], (f16)v4[1], (f16)v4[2], (f16)v4[3]};
-        *reinterpret_cast<f16x4*>(yp + nt * 16) = o;
-      }
+      for (int nt = 0; nt < NT; ++nt) *reinterpret_cast<f16x4*>(yp + nt * 16) = sk_out(acc[nt], bs[nt], act);
     }
   }
 }
 
-// VALU form (fp32, Cin 1..4, any width): the exact-f32 parity mode.  One thread = one output pixel x 16 output channels; the K x K window of
-// one input channel at a time comes by range-checked buffer loads (the zero padding and the right / bottom edges need no branches), the
-// weights are wave-uniform.
-template <typename TI> struct SkLoad;
-template <> struct SkLoad<f16> {
-  static __device__ __forceinline__ float at(__amdgpu_buffer_rsrc_t r, long e, bool ok) {
-    const unsigned short s = __builtin_amdgcn_raw_buffer_load_b16(r, ok ? (unsigned)(e * 2) : EY_OOB, 0, 0);
-    return (float)__builtin_bit_cast(f16, s);
-  }
-};
-template <> struct SkLoad<float> {
-  static __device__ __forceinline__ float at(__amdgpu_buffer_rsrc_t r, long e, bool ok) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, ok ? (unsigned)(e * 4) : EY_OOB, 0, 0));
-  }
-};
-
+// VALU form (fp32, Cin 1..4, any width): the exact-f32 parity mode.  One thread = one output pixel x 16 output channels (sk_valu_px).
 template <typename TI, typename TO, int K, int S, int P>
 __global__ __launch_bounds__(256) void stem_ks_kernel(int B, int Cin, int H, int W, int Ho, int Wo, int act, const TI* __restrict__ x, unsigned xbytes,
                                                       const float* __restrict__ w, const float* __restrict__ bias, TO* __restrict__ y, int yCs) {
@@ -129,33 +56,8 @@ __global__ __launch_bounds__(256) void stem_ks_kernel(int B, int Cin, int H, int
   const int ox = (int)(t % Wo);
   const long tt = t / Wo;
   const int oy = (int)(tt % Ho), b = (int)(tt / Ho);
-  const __amdgpu_buffer_rsrc_t rs = ey_rsrc(x, xbytes);
   float acc[16];
-#pragma unroll
-  for (int o = 0; o < 16; ++o) acc[o] = bias ? bias[co0 + o] : 0.f;
-  for (int c = 0; c < Cin; ++c) {
-    float in[K][K];
-#pragma unroll
-    for (int ky = 0; ky < K; ++ky) {
-      const int iy = oy * S - P + ky;
-      const bool rowok = iy >= 0 && iy < H;
-      const long rowbase = (((long)b * Cin + c) * H + iy) * W;
-#pragma unroll
-      for (int kx = 0; kx < K; ++kx) {
-        const int ix = ox * S - P + kx;
-        in[ky][kx] = SkLoad<TI>::at(rs, rowbase + ix, rowok && ix >= 0 && ix < W);
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < 16; ++o) {
-      const float* wo = w + ((long)(co0 + o) * Cin + c) * (K * K);
-#pragma unroll
-      for (int ky = 0; ky < K; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < K; ++kx) acc[o] = __builtin_fmaf(in[ky][kx], wo[ky * K + kx], acc[o]);
-    }
-  }
-  ey_act_n(acc, act);
+  sk_valu_px<TI, K, S, P>(ey_rsrc(x, xbytes), b, Cin, H, W, oy, ox, co0, w, bias, act, acc);
   TO* yp = y + t * yCs + co0;
   Vec8<TO> v;
 #pragma unroll
@@ -217,8 +119,9 @@ static int stem_ks_typed(int x_dtype, int y_dtype, int B, int Cin, int H, int W,
 extern "C" int ey_stem_conv_ks(int x_dtype, int y_dtype, int B, int Cin, int H, int W, int Cout, int k, int stride, int pad, int act, const void* x,
                                const float* w, const float* bias, void* y, int y_cstride, ey_stream_t stream) {
   EY_CHECK(x && w && y, "stem_ks: null pointer");
-  const bool k6 = k == 6 && stride == 2 && pad == 2, k3 = k == 3 && stride == 1 && pad == 1;
-  if (!k6 && !k3) return ey_set_error(EY_EUNSUPPORTED, "stem_ks: (k, s, p) = (%d, %d, %d); (6, 2, 2) and (3, 1, 1) are built, (3, 2, 1) is ey_stem_conv", k, stride, pad);
+  const bool k6 = k == 6 && stride == 2 && pad == 2, k3 = k == 3 && stride == 1 && pad == 1, k7 = k == 7 && stride == 2 && pad == 3;
+  if (!k6 && !k3 && !k7)
+    return ey_set_error(EY_EUNSUPPORTED, "stem_ks: (k, s, p) = (%d, %d, %d); (6, 2, 2), (3, 1, 1) and (7, 2, 3) are built, (3, 2, 1) is ey_stem_conv", k, stride, pad);
   EY_CHECK((x_dtype == EY_F16 || x_dtype == EY_F32) && (y_dtype == EY_F16 || y_dtype == EY_F32), "stem_ks: bad dtype");
   EY_CHECK(Cin >= 1 && Cin <= 4 && Cout % 16 == 0 && Cout > 0, "stem_ks: Cin=%d (1..4) Cout=%d (multiple of 16)", Cin, Cout);
   EY_CHECK(B > 0 && H > 0 && W > 0 && H + 2 * pad >= k && W + 2 * pad >= k, "stem_ks: bad extent");
@@ -226,6 +129,7 @@ extern "C" int ey_stem_conv_ks(int x_dtype, int y_dtype, int B, int Cin, int H, 
   EY_CHECK(y_cstride >= Cout && (y_cstride * es) % 16 == 0 && ey_aligned(y, 16), "stem_ks: output view not 16-byte aligned");
   EY_CHECK(ey_aligned(x, x_dtype == EY_F16 ? 2 : 4), "stem_ks: image not aligned to its element size");
   hipStream_t st = (hipStream_t)stream;
+  if (k7) return stem_ks_typed<7, 2, 3>(x_dtype, y_dtype, B, Cin, H, W, Cout, act, x, w, bias, y, y_cstride, st);
   return k6 ? stem_ks_typed<6, 2, 2>(x_dtype, y_dtype, B, Cin, H, W, Cout, act, x, w, bias, y, y_cstride, st)
             : stem_ks_typed<3, 1, 1>(x_dtype, y_dtype, B, Cin, H, W, Cout, act, x, w, bias, y, y_cstride, st);
 }

@@ -17,7 +17,8 @@
 #define CP_THREADS 256
 #define CP_NT 128       // output channels per workgroup of the MFMA kernel (32 per wave)
 #define CP_LDS (64 * 1024)
-#define CP_MAXC1 2016   // 16 pixel rows of (C1 + 16) f16 / 4 rows of C1 fp32 stay inside 64 KiB
+#define CP_MAXC1 4096   // f16: up to 2016 the 16 pixel rows of (C1 + 16) f16 stay inside 64 KiB, wider tiles (2048 of the ResNets) take up to 129 KiB
+                        // of the CU's 160 KiB as dynamic LDS; fp32: tp = (64 KiB / (4 C1)) & ~3 pixel rows, exactly 4 at C1 = 4096
 #define CL_THREADS 1024
 #define CL_ROWS 4      // class rows a wave has in flight
 #define CL_MAXNC 8192
@@ -185,7 +186,11 @@ extern "C" int ey_classify_pool(int dtype, int B, int HW, int C1, int Cout, int 
     int tp = 64;
     while (tp > 16 && (size_t)tp * (kp + 16) * 2 > CP_LDS) tp >>= 1;
     while (tp > 16 && tp / 2 >= HW) tp >>= 1;
-    const size_t lds = (size_t)tp * (kp + 16) * 2;
+    const size_t lds = (size_t)tp * (kp + 16) * 2;  // C1 <= 2016: at most 64 KiB, the launch every earlier width has always had
+    // wider tiles: the kernel's dynamic LDS limit is raised to the widest supported tile (16 rows of 4096 + 16 halves).  The attribute belongs to
+    // the function on the CURRENT device, so it is set on every such launch (a host-side call, legal during stream capture), not once per process
+    if (lds > CP_LDS && hipFuncSetAttribute((const void*)classify_pool_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * (CP_MAXC1 + 16) * 2) != hipSuccess)
+      return ey_set_error(EY_EUNSUPPORTED, "classify_pool: %zu bytes of LDS for C1=%d refused by the runtime", lds, C1);
     hipLaunchKernelGGL(classify_pool_mfma_kernel, dim3(ey_cdiv(Cout, CP_NT), B), dim3(CP_THREADS), lds, st, (const f16*)x, HW, C1, x_cstride, (const f16*)w, bias, Cout,
                        act, out, tp, kp, vec);
   } else {

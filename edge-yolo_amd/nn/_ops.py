@@ -346,12 +346,12 @@ def stem_conv(mod, x, folded_fn, act, out_dtype, out=None):
     return out
 
 
-STEM_KS = {(6, 2, 2): "stem6", (3, 1, 1): "stem3s1"}  # (k, s, p) of ey_stem_conv_ks -> trace label stem
+STEM_KS = {(6, 2, 2): "stem6", (3, 1, 1): "stem3s1", (7, 2, 3): "stem7"}  # (k, s, p) of ey_stem_conv_ks -> trace label stem
 
 
 def stem_conv_ks(mod, x, folded_fn, k, s, p, act, out_dtype, out=None):
-    """The image stems that are not 3x3 stride 2, straight from the NCHW-contiguous image (ey_stem_conv_ks): (k, s, p) = (6, 2, 2) of YOLOv5
-    and (3, 1, 1) of YOLOv3.  out= may be a channel slot of a wider NHWC buffer."""
+    """The image stems that are not 3x3 stride 2, straight from the NCHW-contiguous image (ey_stem_conv_ks): (k, s, p) = (6, 2, 2) of YOLOv5,
+    (3, 1, 1) of YOLOv3 and (7, 2, 3) of the ResNet stem.  out= may be a channel slot of a wider NHWC buffer."""
     L.require_device(x, "stem_conv_ks")
     _no_block("stem conv")
     B, cin, H, W = x.shape
@@ -401,6 +401,87 @@ def maxpool2d(x, k, s, pad=(0, 0, 0, 0), out=None):
     with _tr("maxpool_kernel" if k > 1 else "zeropad_kernel", _nb(x, out), float(k * k * out.numel()), note=f"C{c} k{k}s{s} pad{(pl, pr, pt, pb)} {H}x{W}"):
         L.check(L.lib().ey_maxpool2d(L.dtype_code(x.dtype), B, H, W, c, k, s, pl, pr, pt, pb, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out),
                                      L.stream()), "ey_maxpool2d")
+    return out
+
+
+def maxpool3x3s2(x, out=None):
+    """nn.MaxPool2d(3, 2, 1) of the ResNet stem (ey_maxpool3x3s2): torch's own padding, the cells outside the map are left out of the maximum.
+    Reached from ResNetLayer only; maxpool2d (explicit zero padding that takes part) keeps refusing a 3x3 window.  x and out= may be channel
+    slots of wider NHWC buffers."""
+    x = L.as_nhwc(as_tensor(x))
+    L.require_device(x, "maxpool3x3s2")
+    _no_block("max pool")
+    B, c, H, W = x.shape
+    if c % 8:
+        raise NotImplementedError(f"maxpool3x3s2: C={c} must be a multiple of 8")
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    _slot_view(x, "maxpool3x3s2: x", x.shape, x.dtype)
+    out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device) if out is None else _slot_view(out, "maxpool3x3s2: out=", (B, c, Ho, Wo), x.dtype)
+    with _tr("maxpool3x3s2_kernel", _nb(x, out), float(9 * out.numel()), note=f"C{c} {H}x{W}"):
+        L.check(L.lib().ey_maxpool3x3s2(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()), "ey_maxpool3x3s2")
+    return out
+
+
+def resnet_stem(mod, x, folded_fn, act, out=None):
+    """Layer 0 of a ResNet as ONE launch (ey_resnet_stem): Conv 7x7 / 2 / 3 + activation from the NCHW-contiguous image and MaxPool 3x3 / 2 / 1; the
+    half-resolution map stays in LDS.  Bit-identical to stem_conv_ks(7, 2, 3) + maxpool3x3s2.  Returns None where the kernel does not take the
+    shape (other than 64 output channels, more than 4 input channels): the caller then makes the two launches."""
+    L.require_device(x, "resnet_stem")
+    _no_block("stem conv")
+    B, cin, H, W = x.shape
+
+    def build():
+        w, b = folded_fn()
+        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
+
+    w, bias = mod._packed(("stem", x.device), build)  # (the slot and the layout stem_conv_ks uses for this conv)
+    cout = w.shape[0]
+    if cout != 64 or cin > 4 or tuple(w.shape[2:]) != (7, 7) or x.dtype not in (torch.float16, torch.float32):
+        return None
+    Hp, Wp = ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1
+    out = L.empty_nhwc(B, cout, Hp, Wp, x.dtype, x.device) if out is None else _slot_view(out, "resnet_stem: out=", (B, cout, Hp, Wp), x.dtype)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    rec = _tr("resnet_stem_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * cin * 49, note=f"{cin}->{cout} {H}x{W}")
+    with rec:
+        L.check(L.lib().ey_resnet_stem(L.dtype_code(x.dtype), L.dtype_code(x.dtype), B, cin, H, W, cout, act, x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                       L.cstride(out), L.stream()), "ey_resnet_stem")
+        if rec is not _NT and L.lib().ey_resnet_stem_last_variant() == 1:
+            rec.kernel = "resnet_stem_mfma_kernel"
+    return out
+
+
+def resnet_tail(mod, t, x, folded_fn, stride, identity, out=None, tag=""):
+    """The closing 1x1 of a ResNet bottleneck block as ONE launch (ey_resnet_tail, f16): relu(W [t ; x at pixel stride s] + b) for a projection
+    block -- folded_fn() gives ([W3 | Ws] concatenated along K as (4 C2, C2 + C1, 1, 1), b3 + bs) --, relu(W3 t + b3 + x) for an identity block
+    (x is the residual, added in fp32 before the ReLU).  Returns None where the kernel does not take the shape (fp32, widths outside its list,
+    misaligned views): the caller then takes the composed form."""
+    t, x = L.as_nhwc(as_tensor(t)), L.as_nhwc(as_tensor(x))
+    L.require_device(t, "resnet_tail")
+    _no_block("resnet_tail")
+    B, C2, Ho, Wo = t.shape
+    _, cx, H, W = x.shape
+    C1 = 0 if identity else cx
+    if (t.dtype != torch.float16 or x.dtype != torch.float16 or C2 not in (64, 128, 256, 512) or C1 % 32 or C1 > 2048 or stride not in (1, 2) or (identity and (stride != 1 or cx != 4 * C2))
+            or x.shape[0] != B or ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo)):
+        return None
+    for v in (t, x):
+        if (L.cstride(v) * 2) % 16 or v.data_ptr() % 16:
+            return None
+
+    def build():
+        w, b = folded_fn()
+        return w.reshape(w.shape[0], -1).to(device=t.device, dtype=torch.float16).contiguous(), b.to(device=t.device, dtype=torch.float32).contiguous()
+
+    w, bias = mod._packed(_dev_key(t, "rtail" + tag), build)
+    if tuple(w.shape) != (4 * C2, C2 + C1):
+        raise ValueError(f"resnet_tail: weight {tuple(w.shape)} does not match (4 C2, C2 + C1) = {(4 * C2, C2 + C1)}")
+    out = L.empty_nhwc(B, 4 * C2, Ho, Wo, t.dtype, t.device) if out is None else _slot_view(out, "resnet_tail: out=", (B, 4 * C2, Ho, Wo), t.dtype)
+    M = B * Ho * Wo
+    nbytes = 2 * (M * (C2 + C1 + 4 * C2 * (2 if identity else 1)) + w.numel())
+    with _tr("resnet_tail_kernel", nbytes, 2.0 * M * 4 * C2 * (C2 + C1), note=f"{C2}+{C1}->{4 * C2} s{stride} {Ho}x{Wo}{' +res' if identity else ''}"):
+        L.check(L.lib().ey_resnet_tail(L.dtype_code(t.dtype), B, H, W, stride, C1, C2, t.data_ptr(), L.cstride(t), None if identity else x.data_ptr(), 0 if identity else L.cstride(x),
+                                       w.data_ptr(), bias.data_ptr(), x.data_ptr() if identity else None, L.cstride(x) if identity else 0, out.data_ptr(), L.cstride(out),
+                                       L.stream()), "ey_resnet_tail")
     return out
 
 

@@ -5,7 +5,7 @@ from .block import (DFL, Proto, SPPF, C2f, C2fAttn, MaxSigmoidAttnBlock, BNContr
                     Mlp, CMlp, LocalAgg, GlobalSparseAttn, SelfAttn, LGLBlock, DSC3K2_LGL,
                     AdaHGComputation, C3AH, FuseModule, HyperACE, DownsampleConv, FullPAD_Tunnel,
                     RepBottleneck, RepCSP, RepNCSPELAN4, ELAN1, SPPELAN, AConv, ADown, CBLinear, CBFuse,
-                    SCDown, RepVGGDW, CIB, C2fCIB, PSA, C2, GhostBottleneck, C3Ghost, SPP)
+                    SCDown, RepVGGDW, CIB, C2fCIB, PSA, C2, GhostBottleneck, C3Ghost, SPP, ResNetBlock, ResNetLayer)
 from .conv import Conv, DWConv, DSConv, RepConv, GhostConv, Concat, Upsample, autopad
 from .classic import ConvTranspose2d, MaxPool2d, ZeroPad2d
 from .dysample import DySample
@@ -18,4 +18,4 @@ __all__ = ("Conv", "DWConv", "DSConv", "Concat", "Upsample", "autopad", "DFL", "
            "C2fAttn", "MaxSigmoidAttnBlock", "BNContrastiveHead", "WorldDetect",
            "RepConv", "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "SPPELAN", "AConv", "ADown", "CBLinear", "CBFuse",
            "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA", "v10Detect", "C2", "GhostConv", "GhostBottleneck", "C3Ghost",
-           "SPP", "MaxPool2d", "ZeroPad2d", "ConvTranspose2d")
+           "SPP", "MaxPool2d", "ZeroPad2d", "ConvTranspose2d", "ResNetBlock", "ResNetLayer")

@@ -18,7 +18,7 @@ __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNC
            "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
            "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA",
-           "C2", "GhostBottleneck", "C3Ghost", "SPP")
+           "C2", "GhostBottleneck", "C3Ghost", "SPP", "ResNetBlock", "ResNetLayer")
 
 
 def _slot(buf, i, c):
@@ -1621,3 +1621,94 @@ class C3Ghost(C3):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
+
+
+class ResNetBlock(_Packed):
+    """Bottleneck block of the ResNets (reference block.py:505-519): relu(cv3(cv2(cv1(x))) + shortcut(x)), cv1 1x1 and cv2 3x3 (stride s) with the
+    default activation, cv3 1x1 to e c2 channels and the shortcut -- a 1x1 stride-s Conv where the shape changes, else the identity -- without
+    one.  The sum comes BEFORE the ReLU, so it is not the `res=` of ey_conv2d (added behind the activation).  The closing launch is
+      * fused (f16): ONE ey_resnet_tail launch.  A projection block reads t = cv2(cv1(x)) and x at pixel stride s against [W3 | Ws]
+        concatenated along K with the bias b3 + bs -- the shortcut conv's output never exists --, an identity block adds the block input in
+        fp32 before the ReLU; one rounding either way;
+      * composed (fp32 always, and every shape the kernel refuses): the shortcut conv where the block has one, then cv3 on ey_conv2d with
+        ReLU and the shortcut (or the block input) as its pre-activation term `addz` at the output's own size, where the bilinear index
+        arithmetic of that term gives the weights exactly 1 and 0.
+    `tail_fused` = True / False forces a form where the kernel takes the shape; "auto" (the default) follows the measurement on MI355X at
+    batch 32, f16, 224 x 224 (profiles/resnet_bench.txt): `fused_shapes` lists the (c1 or 0, c2) pairs at which the fused
+    kernel was faster than the composed form by more than the spread; every other shape takes the composed form.  The list is keyed on the
+    channel widths alone and comes from that one operating point: it is not re-derived for other batch or map sizes."""
+
+    tail_fused = "auto"
+    # (c1, c2) of projection blocks / (0, c2) of identity blocks.  Fused against composed, us: (64, 64) at 56 x 56 53.7 / 89.5 -- taken; (256, 128)
+    # stride 2 64.4 / 64.4, (512, 256) 69.4 / 47.5, (1024, 512) 68.1 / 52.2, identity 64: 58.1 / 54.3, 128: 40.2 / 34.2, 256: 33.8 / 23.9, 512: 29.6 / 18.0
+    fused_shapes = frozenset({(64, 64)})
+
+    def __init__(self, c1, c2, s=1, e=4):
+        super().__init__()
+        c3 = e * c2
+        self.cv1 = Conv(c1, c2, k=1, s=1, act=True)
+        self.cv2 = Conv(c2, c2, k=3, s=s, p=1, act=True)
+        self.cv3 = Conv(c2, c3, k=1, act=False)
+        self.shortcut = nn.Sequential(Conv(c1, c3, k=1, s=s, act=False)) if s != 1 or c1 != c3 else nn.Identity()
+
+    def _tail_folded(self):
+        w3, b3 = self.cv3.folded()
+        if not isinstance(self.shortcut, nn.Sequential):
+            return w3, b3
+        ws, bs = self.shortcut[0].folded()
+        return torch.cat([w3, ws], 1), b3 + bs
+
+    def tail(self, t, x, out=None):
+        """relu(cv3(t) + shortcut(x)) for t = cv2(cv1(x))."""
+        proj = isinstance(self.shortcut, nn.Sequential)
+        fused = self.tail_fused
+        if fused == "auto":
+            fused = ((self.shortcut[0].conv.in_channels if proj else 0), t.shape[1]) in self.fused_shapes
+        if fused and torch.is_tensor(x) and x.dtype == torch.float16 and self.cv3.conv.out_channels == 4 * t.shape[1]:
+            # (the cache slot names the fused state: fuse() rewrites the parameters of cv3 and the shortcut, whose own caches it drops)
+            y = ops.resnet_tail(self, t, x, self._tail_folded, self.shortcut[0].conv.stride[0] if proj else 1, not proj, out=out, tag=str(int(hasattr(self.cv3, "bn"))))
+            if y is not None:
+                return y
+        z = self.shortcut[0](x) if proj else ops.as_tensor(x)
+        return ops.conv2d(self.cv3, [t], self.cv3.folded, 1, 1, 0, L.ACT_RELU, out=out, addz=z)
+
+    def forward(self, x, out=None):
+        return self.tail(self.cv2(self.cv1(x)), x, out=out)
+
+
+class ResNetLayer(nn.Module):
+    """One stage of a ResNet (reference block.py:522-541), args (c1, c2, s, is_first, n, e).  `is_first`: the stem, Conv(c1, c2, 7, 2, 3) from the
+    planar image and nn.MaxPool2d(3, 2, 1) (the torch module is a parameter-free place holder that keeps the reference's `layer.0` /
+    `layer.1` numbering and is never called).  Two forms with the same bits: ONE ey_resnet_stem launch (the half-resolution map stays in LDS),
+    or ey_stem_conv_ks + ey_maxpool3x3s2.  `stem_fused` = True / False forces a form where the kernel takes the shape; "auto" (the default)
+    follows the measurement on MI355X at batch 32, f16 (profiles/resnet_bench.txt).  Otherwise n ResNetBlocks, the
+    first with stride s."""
+
+    stem_fused = "auto"
+    # what "auto" takes.  Batch 32, f16: one ey_resnet_stem launch 101.4 us at 224 x 224 and 815.2 us at 640 x 640 against 60.1 and 428.5 us for the two
+    # launches (one workgroup per CU beside its 83 KiB LDS tile, a quarter of the conv tile recomputed or unused): not faster, so the pair is taken
+    stem_fused_auto = False
+
+    def __init__(self, c1, c2, s=1, is_first=False, n=1, e=4):
+        super().__init__()
+        self.is_first = is_first
+        if self.is_first:
+            self.layer = nn.Sequential(Conv(c1, c2, k=7, s=2, p=3, act=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        else:
+            blocks = [ResNetBlock(c1, c2, s, e=e)]
+            blocks.extend([ResNetBlock(e * c2, c2, 1, e=e) for _ in range(n - 1)])
+            self.layer = nn.Sequential(*blocks)
+
+    def forward(self, x, out=None):
+        ops._no_block("ResNetLayer")
+        if self.is_first:
+            conv = self.layer[0]
+            fused = self.stem_fused_auto if self.stem_fused == "auto" else self.stem_fused
+            if fused and torch.is_tensor(x) and x.dim() == 4 and x.is_contiguous() and not L.is_nhwc_view(x) and conv.conv.groups == 1:
+                y = ops.resnet_stem(conv, x, conv.folded, _act_code(conv.act), out=out)
+                if y is not None:
+                    return y
+            return ops.maxpool3x3s2(conv(x), out=out)
+        for i, b in enumerate(self.layer):
+            x = b(x, out=out if i == len(self.layer) - 1 else None)
+        return x

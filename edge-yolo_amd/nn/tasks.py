@@ -15,7 +15,7 @@ import yaml
 from . import _ops as ops
 from .modules import (A2C2f, AConv, ADown, CBFuse, CBLinear, ELAN1, RepConv, RepNCSPELAN4, SPPELAN, C2PSA, C2PSA_LinearAttention, C2f, C2fAttn, C3, C3k2, Classify, Concat, Conv, DSC3K2, DSC3K2_LGL, DSC3K2_Wavelet, DSConv, DWConv, Detect, DownsampleConv,
                       DySample, E2EDetect, FullPAD_Tunnel, GF2Detect, GFLHeadv2_uniH, HyperACE, OBB, Pose, SPPF, Segment, Upsample, WorldDetect, SCDown, PSA, C2fCIB, RepVGGDW, v10Detect, C2, GhostConv, GhostBottleneck, C3Ghost,
-                      Bottleneck, SPP, MaxPool2d, ZeroPad2d, ConvTranspose2d)
+                      Bottleneck, SPP, MaxPool2d, ZeroPad2d, ConvTranspose2d, ResNetLayer)
 from .modules import *  # noqa: F401,F403  (registry: YAML names resolve through globals(), as in the reference)
 from .modules.conv import _Packed
 from .. import _lib as L
@@ -176,6 +176,8 @@ def _parse_model(d, ch, verbose=False):
             if scale in "lx":
                 args.append(False)
                 c2 = c1
+        elif m is ResNetLayer:  # reference tasks.py:1086-1087: the row names its own channels [c1, c2, s, is_first, n]; no width or depth scaling
+            c2 = args[1] if args[3] else args[1] * 4
         elif m is FullPAD_Tunnel:
             c2 = ch[f[0]]
         elif m is DySample:  # reference tasks.py:1127-1130
@@ -226,6 +228,8 @@ def _layer_down(m, down):
         src *= m.cv1.conv.stride[0]
     elif isinstance(m, (DownsampleConv, ADown, AConv)):
         src *= 2
+    elif isinstance(m, ResNetLayer):  # the stem: conv / 2 and max-pool / 2; a stage: its first block's stride
+        src *= 4 if m.is_first else m.layer[0].cv2.conv.stride[0]
     elif isinstance(m, MaxPool2d):  # (ZeroPad2d: x 1, like every row not listed here)
         src *= m.stride if isinstance(m.stride, int) else m.stride[0]
     elif isinstance(m, (Upsample, ConvTranspose2d)):

@@ -133,8 +133,8 @@ int ey_conv2d_direct(const ey_conv_direct_desc* d, ey_stream_t stream);
  * x: [B,Cin,H,W] contiguous, x_dtype EY_F16|EY_F32; w: fp32 [Cout][Cin][3][3] device; Cin<=4, Cout%16==0. */
 int ey_stem_conv(int x_dtype, int y_dtype, int B, int Cin, int H, int W, int Cout, int act, const void* x_nchw,
                  const float* w_oihw, const float* bias, void* y, int y_cstride, ey_stream_t stream);
-/* The same contract for the other image stems: (k, stride, pad) = (6, 2, 2) (YOLOv5's Conv(3, c, 6, 2, 2)) and (3, 1, 1) (YOLOv3's
- * Conv(3, c, 3, 1)); w: fp32 [Cout][Cin][k][k] device.  Ho = (H + 2 pad - k) / stride + 1: the 6x6 window of output o covers the input
+/* The same contract for the other image stems: (k, stride, pad) = (6, 2, 2) (YOLOv5's Conv(3, c, 6, 2, 2)), (3, 1, 1) (YOLOv3's
+ * Conv(3, c, 3, 1)) and (7, 2, 3) (the ResNet stem, K = 147 zero-filled to 160 on the MFMA); w: fp32 [Cout][Cin][k][k] device.  Ho = (H + 2 pad - k) / stride + 1: the 6x6 window of output o covers the input
  * columns 2o - 2 ... 2o + 3.  f16 -> f16 with Cin = 3, W % 8 == 0, a 16-byte aligned image and Cout <= 80 runs on the MFMA (weights rounded to
  * f16); everything else on the exact fp32 VALU form.  EY_EUNSUPPORTED (before anything is launched) for every other (k, stride, pad).
  * ey_stem_conv_ks_last_variant: 1 when the last launch took the MFMA form, 0 for the VALU form (developer tools, tests). */
@@ -149,6 +149,30 @@ int ey_stem_conv_ks_last_variant(void);
  * inputs.  EY_EUNSUPPORTED for every other (k, stride). */
 int ey_maxpool2d(int dtype, int B, int H, int W, int C, int k, int stride, int pad_l, int pad_r, int pad_t, int pad_b, const void* x, int x_cstride,
                  void* y, int y_cstride, ey_stream_t stream);
+
+/* ---- nn.MaxPool2d(3, 2, 1) of the ResNet stem (csrc/resnet.hip): torch's own padding, i.e. the cells outside the map are LEFT OUT of the
+ * maximum (ey_maxpool2d's zero ring takes part in it).  Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  x [B,H,W,*] and y [B,Ho,Wo,*] are 16-byte
+ * aligned channel windows of NHWC buffers of `dtype` (EY_F16 | EY_F32), C a multiple of 8: EY_EUNSUPPORTED before any launch otherwise.  The
+ * window is walked row by row and a cell replaces the running maximum only when it is greater, as torch's CPU kernel does: bit-identical to
+ * F.max_pool2d(x, 3, 2, 1). */
+int ey_maxpool3x3s2(int dtype, int B, int H, int W, int C, const void* x, int x_cstride, void* y, int y_cstride, ey_stream_t stream);
+/* Layer 0 of a ResNet as ONE launch (csrc/resnet.hip): Conv 7x7 / 2 / 3 + bias + activation from the planar NCHW image into an LDS tile of the
+ * half-resolution 64-channel map, nn.MaxPool2d(3, 2, 1) from that tile; only the quarter-resolution map y [B,Hp,Wp,*] is written,
+ * Hp = ((H - 1) / 2) / 2 + 1.  The convolution runs on the device functions of ey_stem_conv_ks: bit-identical to ey_stem_conv_ks(7, 2, 3)
+ * followed by ey_maxpool3x3s2, in the MFMA form (f16, Cin = 3, W % 8 == 0, 16-byte aligned image) and the VALU form (fp32, or f16 otherwise).
+ * x_dtype == y_dtype, Cin 1..4, Cout = 64, y a 16-byte aligned channel slot; w fp32 [64][Cin][7][7], bias fp32: EY_EUNSUPPORTED before any
+ * launch otherwise.  Up to 128 KiB of dynamic LDS.  ey_resnet_stem_last_variant: 1 = MFMA form, 0 = VALU form (developer tools, tests). */
+int ey_resnet_stem(int x_dtype, int y_dtype, int B, int Cin, int H, int W, int Cout, int act, const void* x_nchw, const float* w_oihw, const float* bias, void* y,
+                   int y_cstride, ey_stream_t stream);
+int ey_resnet_stem_last_variant(void);
+/* The closing 1x1 of a ResNet bottleneck block (csrc/resnet.hip), f16 on the MFMA: y = relu(W [t ; x|s] + b + res), the residual added in fp32
+ * BEFORE the activation, one f16 rounding.  t: [B,Ho,Wo,*] with C2 channels (C2 = 64 | 128 | 256 | 512), y: [B,Ho,Wo,*] with 4 C2 channels,
+ * Ho = (H - 1) / stride + 1.  Identity block: C1 = 0, x NULL, stride 1, w DEVICE f16 [4 C2][C2] row-major, res [B,Ho,Wo,*] = the block input.
+ * Projection block: x [B,H,W,*] with C1 channels (a multiple of 32 up to 2048) is read at pixel (stride oy, stride ox), stride 1 | 2, w is
+ * [W3 | Ws] concatenated along K ([4 C2][C2 + C1]), bias = b3 + bs (fp32, 16-byte aligned), res NULL: the shortcut conv's output never exists.
+ * Sources 16-byte, y and res 8-byte aligned channel slots.  EY_EUNSUPPORTED before any launch for fp32 and every other shape. */
+int ey_resnet_tail(int dtype, int B, int H, int W, int stride, int C1, int C2, const void* t, int t_cstride, const void* x, int x_cstride, const void* w,
+                   const float* bias, const void* res, int res_cstride, void* y, int y_cstride, ey_stream_t stream);
 
 /* ---- two chained 1x1 convs as one launch (f16, 64 or 128 channels, small maps): `second` must read exactly what `first` writes
  * (second->src[0] == first->y, same cstride, one source each; `first` may carry bias / addz / activation / out_scale / residual, `second`
@@ -730,7 +754,8 @@ int ey_kpt_iou(int B, int K, int ndim, const float* pred, const int* pred_off, c
  *   aligned is read with scalar loads); w: DEVICE [Cout][C1] in `dtype`, 16-byte aligned (the BN-folded 1x1 weight, row-major); bias: DEVICE
  *   fp32 [Cout]; out: DEVICE fp32 [B][Cout].  The (B, Cout, H, W) map is never written.  f16: MFMA with fp32 accumulation, Cout a multiple of
  *   16; fp32: a k-ordered fmaf chain per output, any Cout.  Any HW >= 1 (pixel tiles accumulate the per-channel sums of the activated values
- *   in fp32; the mean is that sum followed by one IEEE division), C1 a multiple of 8 up to 2016: EY_EUNSUPPORTED before any launch otherwise.
+ *   in fp32; the mean is that sum followed by one IEEE division), C1 a multiple of 8 up to 4096 (f16 above 2016: a pixel tile of more than 64 KiB
+ *   of dynamic LDS; up to 2016 the launch is what it always was): EY_EUNSUPPORTED before any launch otherwise.
  * ey_classify_linear_softmax: Classify.linear + softmax(1) (head.py:472-475) + the top-min(nc, 5) classes in ONE launch, all outputs of fixed
  *   size (graph-capturable, no atomics, the same bytes run to run).  pooled: DEVICE fp32 [B][K]; w: DEVICE [nc][K] in `dtype`, 16-byte aligned;
  *   bias fp32 [nc].  logits / probs: fp32 [B][nc] (accumulation and everything behind it in fp32; softmax subtracts the row maximum);
