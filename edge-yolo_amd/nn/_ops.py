@@ -40,6 +40,57 @@ def _dev_key(x, tag=""):
     return (tag, x.dtype, x.device)
 
 
+def _act_code(act):
+    from .modules.conv import _act_code as code  # (modules.conv imports this module: resolved at call time)
+    return code(act)
+
+
+def _p(t):
+    """Pointer of an optional tensor: None (NULL) when it is absent."""
+    return None if t is None else t.data_ptr()
+
+
+def _pcs(t):
+    """(pointer, pixel stride) of an optional NHWC view: (None, 0) when it is absent."""
+    return (None, 0) if t is None else (t.data_ptr(), L.cstride(t))
+
+
+def _aligned16(t, channels=True, width=16):
+    """True when the NHWC view `t` starts on a `width`-byte boundary and its pixel stride is a multiple of `width` bytes (what the kernels' vector
+    accesses need); channels: and its channel count is a multiple of 8."""
+    return not ((channels and t.shape[1] % 8) or (L.cstride(t) * t.element_size()) % width or t.data_ptr() % width)
+
+
+def _nhwc_view(t, what, shape, dtype, slot=False):
+    """`t` must be an NHWC view of exactly `shape` and `dtype`; slot: whose channel window (a multiple of 8 channels) starts on a 16-byte boundary
+    with a 16-byte pixel stride."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not L.is_nhwc_view(t):
+        raise ValueError(f"{what} must be an NHWC view of shape {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
+    if slot and not _aligned16(t):
+        raise ValueError(f"{what}: {t.shape[1]} channels at pixel stride {L.cstride(t)}: channel counts, slot offsets and strides must be multiples of 8 elements")
+    return t
+
+
+def _out(what, out, shape, dtype, device, slot=False):
+    """The output of the op `what` (names the argument too, "conv2d: out="): a new NHWC tensor when `out` is None, else `out` after _nhwc_view's
+    check -- the kernels trust the pointer and the pixel stride they are given, a wrong view would be written past its end."""
+    return L.empty_nhwc(*shape, dtype, device) if out is None else _nhwc_view(out, what, shape, dtype, slot)
+
+
+def _try_launch(rec, what, fn, *args, kernel=None):
+    """Call the fused-op entry fn(*args) under the trace record `rec`.  False when it answers EY_EUNSUPPORTED, which the C side returns before
+    anything is launched (`rec` is dropped by its __exit__): the caller then composes the op from its parts.  kernel: called after a launch
+    under trace() for the name of the kernel that ran."""
+    try:
+        with rec:
+            L.check(fn(*args), what)
+            if kernel is not None and rec is not _NT:
+                rec.kernel = kernel()
+    except NotImplementedError:
+        return False
+    return True
+
+
 class VirtualCat:
     """Channel concat of NHWC tensors that is never written: `parts` = [(tensor, up)], `up`=1 meaning "read through a
     nearest x2 upsample".  Produced by Upsample / Concat when the graph knows the consumer is a 1x1 conv (layers
@@ -80,14 +131,65 @@ def pack_conv_weight(w_oihw, dtype, device):
     return buf.to(device)
 
 
+def _conv_pack(mod, x0, cin, k, tag="", folded_fn=None, w_sets=1):
+    """(packed MFMA weights, fp32 bias or None, Cout, elements per weight set) of a conv reading `cin` channels of x0's dtype / device, cached on
+    `mod` in the slot "igemm" + tag.  folded_fn() -> fp32 (w, b), mod.folded by default; with w_sets > 1 a list of them (group g of a grouped
+    conv uses set min(g, w_sets - 1)): packed back to back, biases stacked."""
+    def build():
+        ws, bs = zip(*([(folded_fn or mod.folded)()] if w_sets == 1 else (folded_fn or mod.folded)()))
+        for w in ws:
+            if w.shape[1] != cin or w.shape[2] != k or w.shape[0] != ws[0].shape[0]:
+                raise ValueError(f"conv: weight {tuple(w.shape)} does not match Cin={cin} k={k}")
+        packs = [pack_conv_weight(w, x0.dtype, x0.device) for w in ws]
+        bias = None if bs[0] is None else torch.cat([b.to(x0.device).float() for b in bs]).contiguous()
+        return torch.cat(packs), bias, ws[0].shape[0], packs[0].numel() // x0.element_size()
+
+    return mod._packed(_dev_key(x0, "igemm" + tag), build)
+
+
+def _stem_pack(mod, x, folded_fn):
+    """fp32 OIHW weights and bias of an image stem on x's device, in the one cache slot every stem kernel reads."""
+    def build():
+        w, b = folded_fn()
+        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
+
+    return mod._packed(("stem", x.device), build)
+
+
+def _dw_pack(mod, x, folded_fn, c, k, tag):
+    """Depthwise weights [k][k][C] in x's dtype and the fp32 bias (const float* in every depthwise entry point) or None, cached on `mod` in
+    the slot `tag`.  folded_fn() -> (w (C,1,k,k), b or None)."""
+    def build():
+        w, b = folded_fn()
+        wk = w.view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)
+        return wk, (None if b is None else b.to(x.device).float().contiguous())
+
+    return mod._packed(_dev_key(x, tag), build)
+
+
 def igemm_ok(srcs, k, s, p):
     if k not in (1, 3) or s not in (1, 2) or p != k // 2:
         return False
-    for t in srcs:
-        es = t.element_size()
-        if t.shape[1] % 8 or (L.cstride(t) * es) % 16 or t.data_ptr() % 16:
+    for t in srcs:  # (a plain loop: this runs once per conv launch of an eager forward)
+        if not _aligned16(t):
             return False
     return True
+
+
+_CONV_VARIANTS = (  # (lowest ey_conv_last_variant code of the range, kernel name): h, t, u = the code's hundreds, tens and units, ht = h and t together
+    (13000, "conv_igemm_kernel<{tn},{ht},{u}>"), (12000, "conv_ws_kernel<{tn},{h},{t},{u}>"), (11000, "conv3_halo_kernel<{tn},{ht},{u}>"),
+    (10000, "conv_small_kernel<{tn},{ht},{u}>"), (9000, "conv3p_kernel<{ht}>"), (8000, "conv3s_kernel<{h},{t},{u}>"), (7000, "conv3r_kernel<{ht},{u}>"),
+    (6000, "conv3_tile_kernel<{tn},{ht},{u}>"), (5000, "conv_pwr_kernel<{tn},{ht},{u}>"), (4000, "conv_pw_kernel<{tn},{ht}>"),
+    (3000, "conv_pwn_kernel<{tn},{ht},{u}>"))
+
+
+def _conv_variant(lv, tn):
+    """Kernel instantiation behind the code ey_conv_last_variant() reports after an ey_conv2d launch; tn: "f16" or "f32"."""
+    for floor, name in _CONV_VARIANTS:
+        if lv >= floor:
+            return name.format(tn=tn, ht=lv % 1000 // 10, h=lv % 1000 // 100, t=lv % 100 // 10, u=lv % 10)
+    # every launch path of ey_conv2d reports its instantiation
+    raise AssertionError(f"ey_conv2d launched without reporting its kernel (variant {lv})")
 
 
 def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=None, addz=None, out_scale=1.0,
@@ -120,26 +222,10 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
             raise NotImplementedError("this conv shape needs the generic direct kernel, which takes a single plain source")
         return conv2d_direct(mod, srcs[0], folded_fn, k, s, p, 1, act, out=out, res=res, tag=tag)
     dtype, dev = x0.dtype, x0.device
-
-    def build():
-        if w_sets == 1:
-            w, b = folded_fn()
-            ws, bs = [w], [b]
-        else:  # several weight sets (group g uses set min(g, w_sets-1)): packed back to back, biases stacked
-            ws, bs = zip(*folded_fn())
-        for w in ws:
-            if w.shape[1] != cin or w.shape[2] != k or w.shape[0] != ws[0].shape[0]:
-                raise ValueError(f"conv2d: weight {tuple(w.shape)} does not match Cin={cin} k={k}")
-        packs = [pack_conv_weight(w, dtype, dev) for w in ws]
-        bias = None if bs[0] is None else torch.cat([b.to(dev).float() for b in bs]).contiguous()
-        return torch.cat(packs), bias, ws[0].shape[0], packs[0].numel() // x0.element_size()
-
-    wp, bias, cout, wset_elems = mod._packed(_dev_key(x0, "igemm" + tag), build)
+    wp, bias, cout, wset_elems = _conv_pack(mod, x0, cin, k, tag, folded_fn, w_sets)
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    if out is None:
-        out = L.empty_nhwc(B, cout * (ngroup if y_gstride == 0 and ngroup > 1 else 1), Ho, Wo, dtype, dev)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != dtype:
-        raise ValueError(f"conv2d: out= must be an NHWC view of shape {(B, cout, Ho, Wo)} {dtype}, got {tuple(out.shape)} {out.dtype}")
+    # a grouped conv is given the group-0 slice of its output (Cout channels), or allocates every group's channels when the groups share a pixel
+    out = _out("conv2d: out=", out, (B, cout * (ngroup if out is None and y_gstride == 0 and ngroup > 1 else 1), Ho, Wo), dtype, dev)
     d = L.ConvDesc()
     d.dtype = L.dtype_code(dtype)
     d.B, d.H, d.W, d.Ho, d.Wo, d.Cout = B, H, W, Ho, Wo, cout
@@ -150,7 +236,7 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
         d.src_cstride[i] = L.cstride(t)
         d.src_up[i] = up[i]
     d.w = wp.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
+    d.bias = _p(bias)
     d.y, d.y_cstride = out.data_ptr(), L.cstride(out)
     if res is not None:
         res = L.as_nhwc(res)
@@ -173,37 +259,12 @@ def conv2d(mod, srcs, folded_fn, k, s, p, act, out=None, res=None, tag="", up=No
     if TRACE is not None:
         M = B * Ho * Wo
         es = x0.element_size()
-        tn = "f16" if es == 2 else "f32"
         nbytes = ngroup * (_nb(*srcs) + M * cout * es * (2 if res is not None else 1) + _nb(addz)) + cout * cin * k * k * es
         rec = _tr("conv", nbytes, 2.0 * ngroup * M * cout * cin * k * k,
                   note=f"{cin}->{cout} k{k}s{s} {H}x{W} g{ngroup}{' +res' if res is not None else ''}{' +addz' if addz is not None else ''}{' 2src' if len(srcs) > 1 else ''}")
         with rec:
             L.check(L.lib().ey_conv2d(ctypes.byref(d), L.stream()), "ey_conv2d")
-            lv = L.lib().ey_conv_last_variant()
-            if lv >= 13000:
-                rec.kernel = f"conv_igemm_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 12000:
-                rec.kernel = f"conv_ws_kernel<{tn},{lv % 1000 // 100},{lv % 100 // 10},{lv % 10}>"
-            elif lv >= 11000:
-                rec.kernel = f"conv3_halo_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 10000:
-                rec.kernel = f"conv_small_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 9000:
-                rec.kernel = f"conv3p_kernel<{lv % 1000 // 10}>"
-            elif lv >= 8000:
-                rec.kernel = f"conv3s_kernel<{lv % 1000 // 100},{lv % 100 // 10},{lv % 10}>"
-            elif lv >= 7000:
-                rec.kernel = f"conv3r_kernel<{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 6000:
-                rec.kernel = f"conv3_tile_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 5000:
-                rec.kernel = f"conv_pwr_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            elif lv >= 4000:
-                rec.kernel = f"conv_pw_kernel<{tn},{lv % 1000 // 10}>"
-            elif lv >= 3000:
-                rec.kernel = f"conv_pwn_kernel<{tn},{lv % 1000 // 10},{lv % 10}>"
-            else:  # every launch path of ey_conv2d reports its instantiation (ey_conv_last_variant)
-                raise AssertionError(f"ey_conv2d launched without reporting its kernel (variant {lv})")
+            rec.kernel = _conv_variant(L.lib().ey_conv_last_variant(), "f16" if es == 2 else "f32")
         return out
     L.check(L.lib().ey_conv2d(ctypes.byref(d), L.stream()), "ey_conv2d")
     return out
@@ -236,14 +297,7 @@ def pw_chain_packed(mod, x, fold1, fold2):
 
 def packed_conv1x1(mod, x, folded_fn):
     """(packed weight, bias, cout, elements) of a plain 1x1 conv reading `x`, in the cache slot ops.conv2d uses for it."""
-    def build():
-        w, b = folded_fn()
-        if w.shape[1] != x.shape[1] or w.shape[2] != 1:
-            raise ValueError(f"conv 1x1: weight {tuple(w.shape)} does not match Cin={x.shape[1]}")
-        pk = pack_conv_weight(w, x.dtype, x.device)
-        return pk, (None if b is None else b.to(x.device).float().contiguous()), w.shape[0], pk.numel() // x.element_size()
-
-    return mod._packed(_dev_key(x, "igemm"), build)
+    return _conv_pack(mod, x, x.shape[1], 1, folded_fn=folded_fn)
 
 
 def conv_pw_chain(mod, x, fold1, act1, fold2, act2, out):
@@ -254,20 +308,18 @@ def conv_pw_chain(mod, x, fold1, act1, fold2, act2, out):
         return None  # (block programs run the two convs as two stages)
     x = L.as_nhwc(x)
     B, cin, H, W = x.shape
-    if x.dtype != torch.float16 or cin % 8 or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16:
+    if x.dtype != torch.float16 or not _aligned16(x):
         return None
 
     packed = pw_chain_packed(mod, x, fold1, fold2)
     if packed is False:
         return None
     w1p, b1, w2p, b2, cmid, cout = packed
-    if not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, H, W) or out.dtype != x.dtype:
-        raise ValueError("conv_pw_chain: out= must be an NHWC view of the output shape")
+    out = _out("conv_pw_chain: out=", out, (B, cout, H, W), x.dtype, x.device)
     M = B * H * W
     with _tr("conv_pw2_kernel", _nb(x, out) + (cmid * cin + cout * cmid) * 2, 2.0 * M * (cmid * cin + cout * cmid), note=f"{cin}->{cmid}->{cout} {H}x{W}"):
-        L.check(L.lib().ey_conv_pw_chain(L.dtype_code(x.dtype), B, H, W, cin, cmid, cout, x.data_ptr(), L.cstride(x), w1p.data_ptr(),
-                                         b1.data_ptr() if b1 is not None else None, act1, w2p.data_ptr(), b2.data_ptr() if b2 is not None else None, act2,
-                                         out.data_ptr(), L.cstride(out), L.stream()), "ey_conv_pw_chain")
+        L.check(L.lib().ey_conv_pw_chain(L.dtype_code(x.dtype), B, H, W, cin, cmid, cout, x.data_ptr(), L.cstride(x), w1p.data_ptr(), _p(b1), act1, w2p.data_ptr(),
+                                         _p(b2), act2, out.data_ptr(), L.cstride(out), L.stream()), "ey_conv_pw_chain")
     return out
 
 
@@ -285,13 +337,10 @@ def conv_pw_pair(a, b):
             if b2 is not None:
                 d2, y2, keep2 = b2
                 B, cmid, H, W = y1.shape
-                try:
-                    with _tr(f"conv_pwc_kernel<f16,{cmid // 16}>", _nb(x, y1, y2, a.get("res"), a.get("addz")), 2.0 * B * H * W * cmid * (x.shape[1] + y2.shape[1]),
-                             note=f"{x.shape[1]}->{cmid}->{y2.shape[1]} k1 {H}x{W}"):
-                        L.check(L.lib().ey_conv_pw_pair(ctypes.byref(d1), ctypes.byref(d2), L.stream()), "ey_conv_pw_pair")
+                rec = _tr(f"conv_pwc_kernel<f16,{cmid // 16}>", _nb(x, y1, y2, a.get("res"), a.get("addz")), 2.0 * B * H * W * cmid * (x.shape[1] + y2.shape[1]),
+                          note=f"{x.shape[1]}->{cmid}->{y2.shape[1]} k1 {H}x{W}")
+                if _try_launch(rec, "ey_conv_pw_pair", L.lib().ey_conv_pw_pair, ctypes.byref(d1), ctypes.byref(d2), L.stream()):
                     return y1, y2
-                except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
-                    pass
     return conv2d(**first), None
 
 
@@ -310,15 +359,14 @@ def conv2d_direct(mod, x, folded_fn, k, s, p, g, act, out=None, res=None, tag=""
     w, bias = mod._packed(_dev_key(x, "direct" + tag), build)
     cout = w.shape[0]
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    if out is None:
-        out = L.empty_nhwc(B, cout, Ho, Wo, x.dtype, x.device)
+    out = _out("conv2d_direct: out=", out, (B, cout, Ho, Wo), x.dtype, x.device)
     d = L.ConvDirectDesc()
     d.dtype = L.dtype_code(x.dtype)
     d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = B, H, W, cin, Ho, Wo, cout
     d.k, d.stride, d.pad, d.groups, d.act = k, s, p, g, act
     d.x, d.x_cstride = x.data_ptr(), L.cstride(x)
     d.w_oihw = w.data_ptr()
-    d.bias = bias.data_ptr() if bias is not None else None
+    d.bias = _p(bias)
     d.y, d.y_cstride = out.data_ptr(), L.cstride(out)
     with _tr("conv_direct_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * (cin // g) * k * k):
         L.check(L.lib().ey_conv2d_direct(ctypes.byref(d), L.stream()), "ey_conv2d_direct")
@@ -330,16 +378,10 @@ def stem_conv(mod, x, folded_fn, act, out_dtype, out=None):
     L.require_device(x, "stem_conv")
     _no_block("stem conv")
     B, cin, H, W = x.shape
-
-    def build():
-        w, b = folded_fn()
-        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
-
-    w, bias = mod._packed(("stem", x.device), build)
+    w, bias = _stem_pack(mod, x, folded_fn)
     cout = w.shape[0]
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if out is None:
-        out = L.empty_nhwc(B, cout, Ho, Wo, out_dtype, x.device)
+    out = _out("stem_conv: out=", out, (B, cout, Ho, Wo), out_dtype, x.device)
     with _tr("stem_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * cin * 9):
         L.check(L.lib().ey_stem_conv(L.dtype_code(x.dtype), L.dtype_code(out_dtype), B, cin, H, W, cout, act, x.data_ptr(), w.data_ptr(),
                                      bias.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_stem_conv")
@@ -355,20 +397,12 @@ def stem_conv_ks(mod, x, folded_fn, k, s, p, act, out_dtype, out=None):
     L.require_device(x, "stem_conv_ks")
     _no_block("stem conv")
     B, cin, H, W = x.shape
-
-    def build():
-        w, b = folded_fn()
-        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
-
-    w, bias = mod._packed(("stem", x.device), build)
+    w, bias = _stem_pack(mod, x, folded_fn)
     cout = w.shape[0]
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     if Ho < 1 or Wo < 1:
         raise ValueError(f"stem_conv_ks: a {H}x{W} image has no {k}x{k} window at padding {p}")
-    if out is None:
-        out = L.empty_nhwc(B, cout, Ho, Wo, out_dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != out_dtype:
-        raise ValueError(f"stem_conv_ks: out= must be an NHWC view of shape {(B, cout, Ho, Wo)} {out_dtype}")
+    out = _out("stem_conv_ks: out=", out, (B, cout, Ho, Wo), out_dtype, x.device)
     stem = STEM_KS.get((k, s, p), f"stem_k{k}s{s}p{p}")
     rec = _tr(stem + "_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * cin * k * k, note=f"{cin}->{cout} k{k}s{s} {H}x{W}")
     with rec:
@@ -396,8 +430,8 @@ def maxpool2d(x, k, s, pad=(0, 0, 0, 0), out=None):
     Ho, Wo = (H + pt + pb - k) // s + 1, (W + pl + pr - k) // s + 1
     if Ho < 1 or Wo < 1:
         raise ValueError(f"maxpool2d: a {H}x{W} map padded by {tuple(pad)} has no {k}x{k} window")
-    _slot_view(x, "maxpool2d: x", x.shape, x.dtype)
-    out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device) if out is None else _slot_view(out, "maxpool2d: out=", (B, c, Ho, Wo), x.dtype)
+    _nhwc_view(x, "maxpool2d: x", x.shape, x.dtype, slot=True)
+    out = _out("maxpool2d: out=", out, (B, c, Ho, Wo), x.dtype, x.device, slot=True)
     with _tr("maxpool_kernel" if k > 1 else "zeropad_kernel", _nb(x, out), float(k * k * out.numel()), note=f"C{c} k{k}s{s} pad{(pl, pr, pt, pb)} {H}x{W}"):
         L.check(L.lib().ey_maxpool2d(L.dtype_code(x.dtype), B, H, W, c, k, s, pl, pr, pt, pb, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out),
                                      L.stream()), "ey_maxpool2d")
@@ -415,8 +449,8 @@ def maxpool3x3s2(x, out=None):
     if c % 8:
         raise NotImplementedError(f"maxpool3x3s2: C={c} must be a multiple of 8")
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    _slot_view(x, "maxpool3x3s2: x", x.shape, x.dtype)
-    out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device) if out is None else _slot_view(out, "maxpool3x3s2: out=", (B, c, Ho, Wo), x.dtype)
+    _nhwc_view(x, "maxpool3x3s2: x", x.shape, x.dtype, slot=True)
+    out = _out("maxpool3x3s2: out=", out, (B, c, Ho, Wo), x.dtype, x.device, slot=True)
     with _tr("maxpool3x3s2_kernel", _nb(x, out), float(9 * out.numel()), note=f"C{c} {H}x{W}"):
         L.check(L.lib().ey_maxpool3x3s2(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()), "ey_maxpool3x3s2")
     return out
@@ -429,17 +463,12 @@ def resnet_stem(mod, x, folded_fn, act, out=None):
     L.require_device(x, "resnet_stem")
     _no_block("stem conv")
     B, cin, H, W = x.shape
-
-    def build():
-        w, b = folded_fn()
-        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
-
-    w, bias = mod._packed(("stem", x.device), build)  # (the slot and the layout stem_conv_ks uses for this conv)
+    w, bias = _stem_pack(mod, x, folded_fn)
     cout = w.shape[0]
     if cout != 64 or cin > 4 or tuple(w.shape[2:]) != (7, 7) or x.dtype not in (torch.float16, torch.float32):
         return None
     Hp, Wp = ((H - 1) // 2) // 2 + 1, ((W - 1) // 2) // 2 + 1
-    out = L.empty_nhwc(B, cout, Hp, Wp, x.dtype, x.device) if out is None else _slot_view(out, "resnet_stem: out=", (B, cout, Hp, Wp), x.dtype)
+    out = _out("resnet_stem: out=", out, (B, cout, Hp, Wp), x.dtype, x.device, slot=True)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     rec = _tr("resnet_stem_kernel", _nb(x, out), 2.0 * B * Ho * Wo * cout * cin * 49, note=f"{cin}->{cout} {H}x{W}")
     with rec:
@@ -464,9 +493,8 @@ def resnet_tail(mod, t, x, folded_fn, stride, identity, out=None, tag=""):
     if (t.dtype != torch.float16 or x.dtype != torch.float16 or C2 not in (64, 128, 256, 512) or C1 % 32 or C1 > 2048 or stride not in (1, 2) or (identity and (stride != 1 or cx != 4 * C2))
             or x.shape[0] != B or ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo)):
         return None
-    for v in (t, x):
-        if (L.cstride(v) * 2) % 16 or v.data_ptr() % 16:
-            return None
+    if not (_aligned16(t, channels=False) and _aligned16(x, channels=False)):
+        return None
 
     def build():
         w, b = folded_fn()
@@ -475,26 +503,13 @@ def resnet_tail(mod, t, x, folded_fn, stride, identity, out=None, tag=""):
     w, bias = mod._packed(_dev_key(t, "rtail" + tag), build)
     if tuple(w.shape) != (4 * C2, C2 + C1):
         raise ValueError(f"resnet_tail: weight {tuple(w.shape)} does not match (4 C2, C2 + C1) = {(4 * C2, C2 + C1)}")
-    out = L.empty_nhwc(B, 4 * C2, Ho, Wo, t.dtype, t.device) if out is None else _slot_view(out, "resnet_tail: out=", (B, 4 * C2, Ho, Wo), t.dtype)
+    out = _out("resnet_tail: out=", out, (B, 4 * C2, Ho, Wo), t.dtype, t.device, slot=True)
     M = B * Ho * Wo
     nbytes = 2 * (M * (C2 + C1 + 4 * C2 * (2 if identity else 1)) + w.numel())
     with _tr("resnet_tail_kernel", nbytes, 2.0 * M * 4 * C2 * (C2 + C1), note=f"{C2}+{C1}->{4 * C2} s{stride} {Ho}x{Wo}{' +res' if identity else ''}"):
-        L.check(L.lib().ey_resnet_tail(L.dtype_code(t.dtype), B, H, W, stride, C1, C2, t.data_ptr(), L.cstride(t), None if identity else x.data_ptr(), 0 if identity else L.cstride(x),
-                                       w.data_ptr(), bias.data_ptr(), x.data_ptr() if identity else None, L.cstride(x) if identity else 0, out.data_ptr(), L.cstride(out),
-                                       L.stream()), "ey_resnet_tail")
+        L.check(L.lib().ey_resnet_tail(L.dtype_code(t.dtype), B, H, W, stride, C1, C2, t.data_ptr(), L.cstride(t), *_pcs(None if identity else x), w.data_ptr(), bias.data_ptr(),
+                                       *_pcs(x if identity else None), out.data_ptr(), L.cstride(out), L.stream()), "ey_resnet_tail")
     return out
-
-
-def _conv_pack(mod, x0, cin, k, tag=""):
-    """Packed MFMA weights + fp32 bias of a plain Conv module, under the cache key (and with the tuple layout) ops.conv2d uses."""
-    def build():
-        w, b = mod.folded()
-        if w.shape[1] != cin or w.shape[2] != k:
-            raise ValueError(f"conv weight {tuple(w.shape)} does not match Cin={cin} k={k}")
-        pk = pack_conv_weight(w, x0.dtype, x0.device)
-        return pk, (None if b is None else b.to(x0.device).float().contiguous()), w.shape[0], pk.numel() // x0.element_size()
-
-    return mod._packed(_dev_key(x0, "igemm" + tag), build)
 
 
 def pw_conv3s2(cv2, conv3, srcs, out=None):
@@ -510,27 +525,21 @@ def pw_conv3s2(cv2, conv3, srcs, out=None):
     srcs = [L.as_nhwc(t) for t in srcs]
     B, _, H, W = srcs[0].shape
     c1, c3 = cv2.conv, conv3.conv
-    from .modules.conv import _act_code
     if (tuple(srcs[1].shape[0:1] + srcs[1].shape[2:]) != (B, H, W) or c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.groups != 1 or c1.out_channels != 64
             or c3.kernel_size != (3, 3) or c3.stride != (2, 2) or c3.padding != (1, 1) or c3.dilation != (1, 1) or c3.groups != 1 or c3.in_channels != 64
             or c3.out_channels != 64 or c1.in_channels != srcs[0].shape[1] + srcs[1].shape[1] or any(t.shape[1] > 32 or t.shape[1] % 8 for t in srcs)
             or _act_code(cv2.act) != L.ACT_SILU or _act_code(conv3.act) != L.ACT_SILU
-            or any((L.cstride(t) * 2) % 16 or t.data_ptr() % 16 for t in srcs)):
+            or not all(_aligned16(t, channels=False) for t in srcs)):
         return None
     w1, b1 = _conv_pack(cv2, x0, c1.in_channels, 1)[:2]
     w2, b2 = _conv_pack(conv3, x0, 64, 3)[:2]
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if out is None:
-        out = L.empty_nhwc(B, 64, Ho, Wo, x0.dtype, x0.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, 64, Ho, Wo) or out.dtype != x0.dtype:
-        raise ValueError("pw_conv3s2: out= must be an NHWC view of the output shape")
+    out = _out("pw_conv3s2: out=", out, (B, 64, Ho, Wo), x0.dtype, x0.device)
     c0n, c1n = srcs[0].shape[1], srcs[1].shape[1]
-    try:
-        with _tr("pw3_kernel", _nb(srcs[0], srcs[1], out), 2.0 * B * (H * W * 64 * (c0n + c1n) + Ho * Wo * 64 * 576), note=f"{c0n}+{c1n}->64 k1 -> 64 k3s2 {H}x{W}"):
-            L.check(L.lib().ey_conv_pw_conv3s2(L.dtype_code(x0.dtype), B, H, W, srcs[0].data_ptr(), c0n, L.cstride(srcs[0]), srcs[1].data_ptr(), c1n, L.cstride(srcs[1]), 64,
-                                               w1.data_ptr(), b1.data_ptr(), L.ACT_SILU, 64, w2.data_ptr(), b2.data_ptr(), L.ACT_SILU, out.data_ptr(), L.cstride(out),
-                                               L.stream()), "ey_conv_pw_conv3s2")
-    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+    rec = _tr("pw3_kernel", _nb(srcs[0], srcs[1], out), 2.0 * B * (H * W * 64 * (c0n + c1n) + Ho * Wo * 64 * 576), note=f"{c0n}+{c1n}->64 k1 -> 64 k3s2 {H}x{W}")
+    if not _try_launch(rec, "ey_conv_pw_conv3s2", L.lib().ey_conv_pw_conv3s2, L.dtype_code(x0.dtype), B, H, W, srcs[0].data_ptr(), c0n, L.cstride(srcs[0]),
+                       srcs[1].data_ptr(), c1n, L.cstride(srcs[1]), 64, w1.data_ptr(), b1.data_ptr(), L.ACT_SILU, 64, w2.data_ptr(), b2.data_ptr(), L.ACT_SILU,
+                       out.data_ptr(), L.cstride(out), L.stream()):
         return None
     return out
 
@@ -544,7 +553,6 @@ def scdown(cv1, cv2, x, out=None):
     L.require_device(x, "scdown")
     if x.dtype != torch.float16:
         return None
-    from .modules.conv import _act_code
     x = L.as_nhwc(x)
     B, c1n, H, W = x.shape
     c1, c2 = cv1.conv, cv2.conv
@@ -552,29 +560,18 @@ def scdown(cv1, cv2, x, out=None):
     cout = c2.out_channels
     if (c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.groups != 1 or c1.in_channels != c1n or c1.out_channels != cout or c2.kernel_size != (k, k)
             or k != 3 or c2.stride != (2, 2) or c2.padding != (k // 2, k // 2) or c2.dilation != (1, 1) or not c2.groups == c2.in_channels == cout
-            or c1n % 8 or cout % 64 or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16):
+            or cout % 64 or not _aligned16(x)):
         return None
     act1, act2 = _act_code(cv1.act), _act_code(cv2.act)
     w1, b1 = _conv_pack(cv1, x, c1n, 1)[:2]
-
-    def build():  # (the cache slot and layout ops.dwconv_s2 uses for cv2)
-        w, b = cv2.folded()
-        wk = w.view(cout, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)
-        return wk, (b.to(x.device).float().contiguous() if b is not None else None)
-
-    w2, b2 = cv2._packed(_dev_key(x, "dw2"), build)
+    w2, b2 = _dw_pack(cv2, x, cv2.folded, cout, k, "dw2")  # (the slot ops.dwconv_s2 uses for cv2)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if out is None:
-        out = L.empty_nhwc(B, cout, Ho, Wo, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, Ho, Wo) or out.dtype != x.dtype:
-        raise ValueError(f"scdown: out= must be an NHWC view of shape {(B, cout, Ho, Wo)} {x.dtype}")
-    if (L.cstride(out) * 2) % 16 or out.data_ptr() % 16:
+    out = _out("scdown: out=", out, (B, cout, Ho, Wo), x.dtype, x.device)
+    if not _aligned16(out, channels=False):
         return None
-    try:
-        with _tr("scdown_kernel", _nb(x, out) + (cout * c1n + 9 * cout) * 2, 2.0 * B * (H * W * cout * c1n + Ho * Wo * cout * k * k), note=f"{c1n}->{cout} k1 -> dw k{k}s2 {H}x{W}"):
-            L.check(L.lib().ey_scdown(L.dtype_code(x.dtype), B, H, W, c1n, cout, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), b1.data_ptr() if b1 is not None else None, act1,
-                                      w2.data_ptr(), b2.data_ptr() if b2 is not None else None, act2, out.data_ptr(), L.cstride(out), L.stream()), "ey_scdown")
-    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+    rec = _tr("scdown_kernel", _nb(x, out) + (cout * c1n + 9 * cout) * 2, 2.0 * B * (H * W * cout * c1n + Ho * Wo * cout * k * k), note=f"{c1n}->{cout} k1 -> dw k{k}s2 {H}x{W}")
+    if not _try_launch(rec, "ey_scdown", L.lib().ey_scdown, L.dtype_code(x.dtype), B, H, W, c1n, cout, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), _p(b1), act1,
+                       w2.data_ptr(), _p(b2), act2, out.data_ptr(), L.cstride(out), L.stream()):
         return None
     return out
 
@@ -590,7 +587,6 @@ def ghost_conv(cv1, cv2, x, out=None, res=None):
     L.require_device(x, "ghost_conv")
     if x.dtype != torch.float16:
         return None
-    from .modules.conv import _act_code
     x = L.as_nhwc(x)
     B, c1n, H, W = x.shape
     c1, c2 = cv1.conv, cv2.conv
@@ -599,38 +595,24 @@ def ghost_conv(cv1, cv2, x, out=None, res=None):
     act = _act_code(cv1.act)
     if (c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.groups != 1 or c1.in_channels != c1n or c2.kernel_size != (k, k) or k != 5
             or c2.stride != (1, 1) or c2.padding != (k // 2, k // 2) or c2.dilation != (1, 1) or not c2.groups == c2.in_channels == c2.out_channels == ch
-            or c1n % 8 or ch % 4 or act != _act_code(cv2.act) or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16):
+            or ch % 4 or act != _act_code(cv2.act) or not _aligned16(x)):
         return None
-    va = 8 if ch % 8 else 16
-    if out is not None:
-        if not L.is_nhwc_view(out) or tuple(out.shape) != (B, 2 * ch, H, W) or out.dtype != x.dtype:
-            raise ValueError(f"ghost_conv: out= must be an NHWC view of shape {(B, 2 * ch, H, W)} {x.dtype}")
-        if (L.cstride(out) * 2) % va or out.data_ptr() % va:
-            return None
+    va = 8 if ch % 8 else 16  # (a hidden width of 8 n + 4 channels puts the second half of the output on 8-byte boundaries)
+    out = _out("ghost_conv: out=", out, (B, 2 * ch, H, W), x.dtype, x.device)
+    if not _aligned16(out, channels=False, width=va):
+        return None
     if res is not None:
         res = L.as_nhwc(res)
         if tuple(res.shape) != (B, 2 * ch, H, W) or res.dtype != x.dtype:
             raise ValueError("ghost_conv: residual shape/dtype mismatch")
-        if (L.cstride(res) * 2) % va or res.data_ptr() % va:
+        if not _aligned16(res, channels=False, width=va):
             return None
     w1, b1 = _conv_pack(cv1, x, c1n, 1)[:2]
-
-    def build():  # (the cache slot and layout ops.dwconv uses for cv2)
-        w, b = cv2.folded()
-        wk = w.view(ch, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)
-        return wk, (b.to(x.device).contiguous() if b is not None else None)
-
-    w2, b2 = cv2._packed(_dev_key(x, "dw"), build)
-    fresh = out is None
-    if fresh:
-        out = L.empty_nhwc(B, 2 * ch, H, W, x.dtype, x.device)
-    try:
-        with _tr("ghost_conv_kernel", _nb(x, out, res) + (ch * c1n + k * k * ch) * 2, 2.0 * B * H * W * ch * (c1n + k * k),
-                 note=f"{c1n}->{ch} k1 -> dw k{k} {H}x{W}{' +res' if res is not None else ''}"):
-            L.check(L.lib().ey_ghost_conv(L.dtype_code(x.dtype), B, H, W, c1n, ch, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), b1.data_ptr() if b1 is not None else None,
-                                          w2.data_ptr(), b2.data_ptr() if b2 is not None else None, act, res.data_ptr() if res is not None else None,
-                                          L.cstride(res) if res is not None else 0, out.data_ptr(), L.cstride(out), L.stream()), "ey_ghost_conv")
-    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+    w2, b2 = _dw_pack(cv2, x, cv2.folded, ch, k, "dw")  # (the slot ops.dwconv uses for cv2)
+    rec = _tr("ghost_conv_kernel", _nb(x, out, res) + (ch * c1n + k * k * ch) * 2, 2.0 * B * H * W * ch * (c1n + k * k),
+              note=f"{c1n}->{ch} k1 -> dw k{k} {H}x{W}{' +res' if res is not None else ''}")
+    if not _try_launch(rec, "ey_ghost_conv", L.lib().ey_ghost_conv, L.dtype_code(x.dtype), B, H, W, c1n, ch, k, x.data_ptr(), L.cstride(x), w1.data_ptr(), _p(b1),
+                       w2.data_ptr(), _p(b2), act, *_pcs(res), out.data_ptr(), L.cstride(out), L.stream()):
         return None
     return out
 
@@ -647,25 +629,14 @@ def stem_pair(m0, m1, x, out=None):
     if (cin != 3 or c0.in_channels != 3 or c0.out_channels != 16 or c1.in_channels != 16 or c1.out_channels != 32 or W % 8 or x.data_ptr() % 16
             or any(c.kernel_size != (3, 3) or c.stride != (2, 2) or c.padding != (1, 1) or c.dilation != (1, 1) or c.groups != 1 for c in (c0, c1))):
         return None
-
-    def build0():
-        w, b = m0.folded()
-        return w.to(x.device).contiguous(), b.to(x.device).contiguous()
-
-    w0, b0 = m0._packed(("stem", x.device), build0)
+    w0, b0 = _stem_pack(m0, x, m0.folded)
     w1, b1 = _conv_pack(m1, x, 16, 3)[:2]
     Hs, Ws = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Ho, Wo = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
-    if out is None:
-        out = L.empty_nhwc(B, 32, Ho, Wo, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, 32, Ho, Wo) or out.dtype != x.dtype:
-        raise ValueError("stem_pair: out= must be an NHWC view of the output shape")
-    from .modules.conv import _act_code
-    try:
-        with _tr("stem_pair_kernel", _nb(x, out), 2.0 * B * (Hs * Ws * 16 * 27 + Ho * Wo * 32 * 144), note=f"3->16->32 {H}x{W}"):
-            L.check(L.lib().ey_stem_pair(B, H, W, x.data_ptr(), w0.data_ptr(), b0.data_ptr(), _act_code(m0.act), 32, w1.data_ptr(), b1.data_ptr(), _act_code(m1.act),
-                                         out.data_ptr(), L.cstride(out), L.stream()), "ey_stem_pair")
-    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+    out = _out("stem_pair: out=", out, (B, 32, Ho, Wo), x.dtype, x.device)
+    rec = _tr("stem_pair_kernel", _nb(x, out), 2.0 * B * (Hs * Ws * 16 * 27 + Ho * Wo * 32 * 144), note=f"3->16->32 {H}x{W}")
+    if not _try_launch(rec, "ey_stem_pair", L.lib().ey_stem_pair, B, H, W, x.data_ptr(), w0.data_ptr(), b0.data_ptr(), _act_code(m0.act), 32, w1.data_ptr(), b1.data_ptr(),
+                       _act_code(m1.act), out.data_ptr(), L.cstride(out), L.stream()):
         return None
     return out
 
@@ -674,24 +645,16 @@ def dwconv(mod, x, folded_fn, k, act, out=None, tag=""):
     L.require_device(x, "dwconv")
     x = L.as_nhwc(x)
     B, c, H, W = x.shape
-    es = x.element_size()
-    if c % 8 or (L.cstride(x) * es) % 16 or x.data_ptr() % 16:
+    if not _aligned16(x):
         return conv2d_direct(mod, x, folded_fn, k, 1, k // 2, c, act, out=out, tag=tag)
-
-    def build():
-        w, b = folded_fn()  # (C,1,k,k)
-        wk = w.view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)  # [k][k][C]
-        return wk, (b.to(x.device).contiguous() if b is not None else None)
-
-    wk, bias = mod._packed(_dev_key(x, "dw" + tag), build)
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, x.dtype, x.device)
+    wk, bias = _dw_pack(mod, x, folded_fn, c, k, "dw" + tag)
+    out = _out("dwconv: out=", out, (B, c, H, W), x.dtype, x.device)
     if RECORD is not None:
         RECORD.dw(x, wk, bias, k, act, out)
         return out
     with _tr(f"dwconv_kernel<{k}>", _nb(x, out), 2.0 * x.numel() * k * k, note=f"C{c} {H}x{W}"):
-        L.check(L.lib().ey_dwconv(L.dtype_code(x.dtype), B, H, W, c, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(),
-                                  bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out), L.stream()), "ey_dwconv")
+        L.check(L.lib().ey_dwconv(L.dtype_code(x.dtype), B, H, W, c, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(), _p(bias), out.data_ptr(), L.cstride(out),
+                                  L.stream()), "ey_dwconv")
     return out
 
 
@@ -703,7 +666,8 @@ def _dsconv_pack(mod, x, dw_fn, pw_fn, k):
     def build():
         wd, bd = dw_fn()
         wp, bp = pw_fn()
-        wkf = wd.detach().float().view(c, k, k).permute(1, 2, 0).contiguous().cpu()  # [k][k][C] fp32 host
+        # not _dw_pack: the Toeplitz pack below needs the fp32 [k][k][C] weights on the host, and the pack shares one slot with the pointwise half
+        wkf = wd.detach().float().view(c, k, k).permute(1, 2, 0).contiguous().cpu()
         wk = wkf.to(device=x.device, dtype=x.dtype)
         tz = None
         if x.dtype == torch.float16 and c in (16, 32) and wp.shape[0] <= 32:  # Toeplitz-MFMA depthwise stage (ey_dsconv_tz)
@@ -730,13 +694,10 @@ def dsb_pair(cv1, cv2, x, add, out=None):
     k1, k2 = cv1.dw.kernel_size[0], cv2.dw.kernel_size[0]
     if (c not in (32, 64) or k1 != 3 or k2 not in (5, 7) or cv1.pw.out_channels != c or cv2.pw.out_channels != c or cv2.dw.in_channels != c
             or any(m.dw.stride != (1, 1) or m.dw.dilation != (1, 1) or m.dw.padding != (m.dw.kernel_size[0] // 2,) * 2 or m.dw.bias is not None for m in (cv1, cv2))
-            or (L.cstride(x) * 2) % 16 or x.data_ptr() % 16):
+            or not _aligned16(x, channels=False)):
         return None
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H, W):
-        raise ValueError("dsb_pair: out= must be an NHWC view of the output shape")
-    if (L.cstride(out) * 2) % 16 or out.data_ptr() % 16:
+    out = _out("dsb_pair: out=", out, (B, c, H, W), x.dtype, x.device)
+    if not _aligned16(out, channels=False):
         return None
     base = x.untyped_storage().data_ptr()
     if out.untyped_storage().data_ptr() == base:
@@ -747,12 +708,9 @@ def dsb_pair(cv1, cv2, x, add, out=None):
             return None
     wk1, _, wp1, b1, _, _ = _dsconv_pack(cv1, x, cv1._dw_folded, cv1._pw_folded, k1)
     wk2, _, wp2, b2, _, _ = _dsconv_pack(cv2, x, cv2._dw_folded, cv2._pw_folded, k2)
-    try:
-        with _tr(f"dsb_pair_kernel<{k1},{k2}>", _nb(x, out), 2.0 * B * H * W * c * (k1 * k1 + k2 * k2 + 2 * c), note=f"C{c} {H}x{W}{' +res' if add else ''}"):
-            L.check(L.lib().ey_dsb_pair(L.dtype_code(x.dtype), B, H, W, c, k1, k2, L.ACT_SILU, x.data_ptr(), L.cstride(x), wk1.data_ptr(), wp1.data_ptr(),
-                                        b1.data_ptr() if b1 is not None else None, wk2.data_ptr(), wp2.data_ptr(), b2.data_ptr() if b2 is not None else None,
-                                        1 if add else 0, out.data_ptr(), L.cstride(out), L.stream()), "ey_dsb_pair")
-    except NotImplementedError:  # EY_EUNSUPPORTED: returned before anything is launched
+    rec = _tr(f"dsb_pair_kernel<{k1},{k2}>", _nb(x, out), 2.0 * B * H * W * c * (k1 * k1 + k2 * k2 + 2 * c), note=f"C{c} {H}x{W}{' +res' if add else ''}")
+    if not _try_launch(rec, "ey_dsb_pair", L.lib().ey_dsb_pair, L.dtype_code(x.dtype), B, H, W, c, k1, k2, L.ACT_SILU, x.data_ptr(), L.cstride(x), wk1.data_ptr(), wp1.data_ptr(),
+                       _p(b1), wk2.data_ptr(), wp2.data_ptr(), _p(b2), 1 if add else 0, out.data_ptr(), L.cstride(out), L.stream()):
         return None
     return out
 
@@ -764,14 +722,11 @@ def dsconv(mod, x, dw_fn, pw_fn, k, act, out=None, res=None, dw_act=0):
     x = L.as_nhwc(x)
     B, c, H, W = x.shape
     es = x.element_size()
-    if c % 8 or c > 256 or (L.cstride(x) * es) % 16 or x.data_ptr() % 16:
+    if c > 256 or not _aligned16(x):
         return None
 
     wk, dwb, wp, bias, cout, tz = _dsconv_pack(mod, x, dw_fn, pw_fn, k)
-    if out is None:
-        out = L.empty_nhwc(B, cout, H, W, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, H, W):
-        raise ValueError("dsconv: out= must be an NHWC view of the output shape")
+    out = _out("dsconv: out=", out, (B, cout, H, W), x.dtype, x.device)
     if res is not None:
         res = L.as_nhwc(res)
     if RECORD is not None:  # two stages: depthwise (rounded to the storage type like the reference's intermediate tensor) -> pointwise 1x1
@@ -784,20 +739,18 @@ def dsconv(mod, x, dw_fn, pw_fn, k, act, out=None, res=None, dw_act=0):
         d.y_cstride, d.out_scale, d.ngroup = L.cstride(out), 1.0, 1
         RECORD.conv(d, [t], [0], out, res, None, wp, bias, 2.0 * B * H * W * c * cout, cout * c * es)
         return out
-    try:
-      rec = _tr(f"dsconv_kernel<{k}>", _nb(x, out, res), 2.0 * B * H * W * c * (k * k + cout), note=f"C{c}->{cout} {H}x{W}{' +res' if res is not None else ''}")
-      with rec:
-        tail = (dwb.data_ptr() if dwb is not None else None, dw_act, wp.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out),
-                res.data_ptr() if res is not None else None, L.cstride(res) if res is not None else 0, L.stream())
-        if tz is not None:
-            L.check(L.lib().ey_dsconv_tz(L.dtype_code(x.dtype), B, H, W, c, cout, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(), tz.data_ptr(), *tail), "ey_dsconv_tz")
-        else:
-            L.check(L.lib().ey_dsconv(L.dtype_code(x.dtype), B, H, W, c, cout, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(), *tail), "ey_dsconv")
-        if TRACE is not None:
-            rec.kernel = {2: f"dsconv_strip_kernel<{k}>", 3: f"dsconv_tz_kernel<{k}>"}.get(L.lib().ey_dsconv_last_variant(), rec.kernel)
-    except NotImplementedError:  # EY_EUNSUPPORTED is returned before anything is launched (tile does not fit LDS): two-kernel form
-        return None
-    return out
+    rec = _tr(f"dsconv_kernel<{k}>", _nb(x, out, res), 2.0 * B * H * W * c * (k * k + cout), note=f"C{c}->{cout} {H}x{W}{' +res' if res is not None else ''}")
+    head = (L.dtype_code(x.dtype), B, H, W, c, cout, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr())
+    tail = (_p(dwb), dw_act, wp.data_ptr(), _p(bias), out.data_ptr(), L.cstride(out), *_pcs(res), L.stream())
+
+    def ran():
+        return {2: f"dsconv_strip_kernel<{k}>", 3: f"dsconv_tz_kernel<{k}>"}.get(L.lib().ey_dsconv_last_variant(), rec.kernel)
+
+    if tz is not None:
+        ok = _try_launch(rec, "ey_dsconv_tz", L.lib().ey_dsconv_tz, *head, tz.data_ptr(), *tail, kernel=ran)
+    else:
+        ok = _try_launch(rec, "ey_dsconv", L.lib().ey_dsconv, *head, *tail, kernel=ran)
+    return out if ok else None  # (unsupported: the tile does not fit LDS -> the two-kernel form)
 
 
 def dwt_haar(x, out=None):
@@ -805,10 +758,9 @@ def dwt_haar(x, out=None):
     L.require_device(x, "dwt_haar")
     x = L.as_nhwc(x)
     B, c, H, W = x.shape
-    if out is None:
-        out = L.empty_nhwc(B, 4 * c, H // 2, W // 2, x.dtype, x.device)
+    out = _out("dwt_haar: out=", out, (B, 4 * c, H // 2, W // 2), x.dtype, x.device)
     if RECORD is not None:
-        if c % 8 or (L.cstride(x) * x.element_size()) % 16 or x.data_ptr() % 16:
+        if not _aligned16(x):
             _no_block("dwt alignment")
         RECORD.dwt(x, out)
         return out
@@ -826,8 +778,7 @@ def dwt(x, taps, k, out=None):
     if k // 2 - 1 >= H or k // 2 - 1 >= W:
         raise ValueError(f"dwt: a {k}-tap filter bank reflect-pads by {k // 2 - 1}, which needs a map larger than {H}x{W}")
     _no_block("dwt with a general filter bank")
-    if out is None:
-        out = L.empty_nhwc(B, 4 * c, H // 2, W // 2, x.dtype, x.device)
+    out = _out("dwt: out=", out, (B, 4 * c, H // 2, W // 2), x.dtype, x.device)
     with _tr(f"dwt_general_kernel<k{k}>", _nb(x, out), 8.0 * k * k * c * B * (H // 2) * (W // 2)):
         L.check(L.lib().ey_dwt(L.dtype_code(x.dtype), B, H, W, c, k, taps.data_ptr(), x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out),
                                L.stream()), "ey_dwt")
@@ -845,14 +796,15 @@ def wavelet_z(mod, b, sets_fn, z_fn, dwt=None, dw_fn=None):
     B, c, H, W = b.shape
     k = 2 if dwt is None or dwt.haar else dwt.k
     if (RECORD is not None or b.dtype != torch.float16 or c not in (16, 32, 64, 128) or k not in (2, 4, 6, 8) or H < 2 or W < 2 or k // 2 - 1 >= min(H, W)
-            or (L.cstride(b) * 2) % 16 or b.data_ptr() % 16):
+            or not _aligned16(b, channels=False)):
         return None
 
     def build():
         (wl, bl), (wh, bh) = sets_fn()
         wz, _ = z_fn()
         packs = [pack_conv_weight(w, b.dtype, b.device) for w in (wl, wh)]
-        wdw = dw_fn().float().view(c, 3, 3).permute(1, 2, 0).contiguous().to(b.device, b.dtype) if dw_fn is not None else None  # [3][3][c]
+        # f_h's depthwise weights [3][3][c]: one member of this op's own pack, not a _dw_pack slot (no bias, no module of their own)
+        wdw = dw_fn().float().view(c, 3, 3).permute(1, 2, 0).contiguous().to(b.device, b.dtype) if dw_fn is not None else None
         return (torch.cat(packs), packs[0].numel() // 2, torch.cat([bl.to(b.device).float(), bh.to(b.device).float()]).contiguous(),
                 pack_conv_weight(wz, b.dtype, b.device), wdw)
 
@@ -868,9 +820,8 @@ def wavelet_z(mod, b, sets_fn, z_fn, dwt=None, dw_fn=None):
     taps = dwt.taps(b) if k > 2 else None
     label = f"wavelet_z_kernel<k{k}{',ds' if wdw is not None else ''}>"
     with _tr(label, _nb(b, z) + ((c // 2) * 10 * c + 2 * c * c) * 2, flops, note=f"C{c} {H}x{W}"):
-        L.check(L.lib().ey_wavelet_z2(L.dtype_code(b.dtype), B, H, W, c, k, taps.data_ptr() if taps is not None else None, int(wdw is not None),
-                                      wdw.data_ptr() if wdw is not None else None, b.data_ptr(), L.cstride(b), wsub.data_ptr(), wset, bias.data_ptr(),
-                                      wz.data_ptr(), z.data_ptr(), L.cstride(z), L.stream()), "ey_wavelet_z2")
+        L.check(L.lib().ey_wavelet_z2(L.dtype_code(b.dtype), B, H, W, c, k, _p(taps), int(wdw is not None), _p(wdw), b.data_ptr(), L.cstride(b), wsub.data_ptr(), wset,
+                                      bias.data_ptr(), wz.data_ptr(), z.data_ptr(), L.cstride(z), L.stream()), "ey_wavelet_z2")
     return z
 
 
@@ -934,8 +885,7 @@ def linear_attention(qkv, heads, out=None):
     qkv = L.as_nhwc(qkv)
     B, c3, H, W = qkv.shape
     c = c3 // 3
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, qkv.dtype, qkv.device)
+    out = _out("linear_attention: out=", out, (B, c, H, W), qkv.dtype, qkv.device)
     if RECORD is not None:
         RECORD.linattn(qkv, heads, out)
         return out
@@ -950,8 +900,7 @@ def softmax_attention(qkv, heads, kd, hd, scale, out=None):
     _no_block("softmax attention")
     qkv = L.as_nhwc(qkv)
     B, _, H, W = qkv.shape
-    if out is None:
-        out = L.empty_nhwc(B, heads * hd, H, W, qkv.dtype, qkv.device)
+    out = _out("softmax_attention: out=", out, (B, heads * hd, H, W), qkv.dtype, qkv.device)
     with _tr("softattn_kernel", _nb(qkv, out), 2.0 * B * heads * (H * W) ** 2 * (kd + hd)):
         L.check(L.lib().ey_softmax_attention(L.dtype_code(qkv.dtype), B, H * W, heads, kd, hd, float(scale), qkv.data_ptr(), L.cstride(qkv),
                                              out.data_ptr(), L.cstride(out), L.stream()), "ey_softmax_attention")
@@ -969,7 +918,7 @@ def _group_attention(name, q, k, v, heads, area, scale, out):
         raise ValueError(f"{name}: {H}x{W} = {N} tokens do not split into {area} equal areas")
     if c % heads or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, heads {heads}")
-    out = _out_like(q, out, name)
+    out = _out(name + ": out=", out, q.shape, q.dtype, q.device)
     hd = c // heads
     note = f"{H}x{W} area{area} h{heads}" if area else f"{H}x{W} h{heads} hd{hd}"
     views = (float(scale), q.data_ptr(), L.cstride(q), k.data_ptr(), L.cstride(k), v.data_ptr(), L.cstride(v), out.data_ptr(), L.cstride(out), L.stream())
@@ -999,8 +948,7 @@ def scale_add_channels(x, gamma, t, out=None):
     B, c, H, W = t.shape
     if tuple(x.shape) != (B, c, H, W) or gamma.numel() != c or gamma.dtype != torch.float32:
         raise ValueError(f"scale_add_channels: x {tuple(x.shape)}, t {tuple(t.shape)}, gamma {tuple(gamma.shape)} {gamma.dtype}")
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, t.dtype, t.device)
+    out = _out("scale_add_channels: out=", out, (B, c, H, W), t.dtype, t.device)
     with _tr("scale_add_kernel", _nb(x, t, out)):
         L.check(L.lib().ey_scale_add_channels(L.dtype_code(t.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), gamma.data_ptr(), t.data_ptr(),
                                               L.cstride(t), out.data_ptr(), L.cstride(out), L.stream()), "ey_scale_add_channels")
@@ -1015,24 +963,11 @@ def avgpool2(x, out=None):
     B, c, H, W = x.shape
     if H < 2 or W < 2:
         raise ValueError(f"avgpool2: a {H}x{W} map has no 2x2 window")
-    if out is None:
-        out = L.empty_nhwc(B, c, H // 2, W // 2, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H // 2, W // 2) or out.dtype != x.dtype:
-        raise ValueError(f"avgpool2: out= must be an NHWC view of shape {(B, c, H // 2, W // 2)} {x.dtype}")
+    out = _out("avgpool2: out=", out, (B, c, H // 2, W // 2), x.dtype, x.device)
     with _tr("avgpool2_kernel", _nb(x, out), 4.0 * out.numel(), note=f"C{c} {H}x{W}"):
         L.check(L.lib().ey_avgpool2(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()),
                 "ey_avgpool2")
     return out
-
-
-def _slot_view(t, what, shape, dtype):
-    """`t` must be an NHWC view of `shape` and `dtype` whose channel window starts on a 16-byte boundary with a 16-byte pixel stride."""
-    if not L.is_nhwc_view(t) or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-        raise ValueError(f"{what} must be an NHWC view of shape {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}")
-    es = t.element_size()
-    if t.shape[1] % 8 or (L.cstride(t) * es) % 16 or t.data_ptr() % 16:
-        raise ValueError(f"{what}: {t.shape[1]} channels at pixel stride {L.cstride(t)}: channel counts, slot offsets and strides must be multiples of 8 elements")
-    return t
 
 
 def adown_pool(x, c_avg=None, a=None, m=None):
@@ -1048,17 +983,16 @@ def adown_pool(x, c_avg=None, a=None, m=None):
     L.require_device(x, "adown_pool")
     _no_block("adown pool")
     x = L.as_nhwc(as_tensor(x))
-    _slot_view(x, "adown_pool: x", x.shape, x.dtype)
-    a = L.empty_nhwc(B, c_avg, H - 1, W - 1, x.dtype, x.device) if a is None else _slot_view(a, "adown_pool: a=", (B, c_avg, H - 1, W - 1), x.dtype)
+    _nhwc_view(x, "adown_pool: x", x.shape, x.dtype, slot=True)
+    a = _out("adown_pool: a=", a, (B, c_avg, H - 1, W - 1), x.dtype, x.device, slot=True)
     if c_avg == c:
         if m is not None:
             raise ValueError("adown_pool: m= given but c_avg == C leaves no channels to max-pool")
     else:
-        m = (L.empty_nhwc(B, c - c_avg, H // 2, W // 2, x.dtype, x.device) if m is None
-             else _slot_view(m, "adown_pool: m=", (B, c - c_avg, H // 2, W // 2), x.dtype))
+        m = _out("adown_pool: m=", m, (B, c - c_avg, H // 2, W // 2), x.dtype, x.device, slot=True)
     with _tr("adown_kernel", _nb(x, a, m), 4.0 * a.numel() + (13.0 * m.numel() if m is not None else 0.0), note=f"C{c} split{c_avg} {H}x{W}"):
-        L.check(L.lib().ey_adown_pool(L.dtype_code(x.dtype), B, H, W, c, c_avg, x.data_ptr(), L.cstride(x), a.data_ptr(), L.cstride(a),
-                                      m.data_ptr() if m is not None else None, L.cstride(m) if m is not None else 0, L.stream()), "ey_adown_pool")
+        L.check(L.lib().ey_adown_pool(L.dtype_code(x.dtype), B, H, W, c, c_avg, x.data_ptr(), L.cstride(x), a.data_ptr(), L.cstride(a), *_pcs(m), L.stream()),
+                "ey_adown_pool")
     return a, m
 
 
@@ -1078,8 +1012,8 @@ def cbfuse(xs, out=None):
     for i, t in enumerate(xs):
         if t.shape[0] != B or t.shape[1] != c or t.dtype != dt:
             raise ValueError(f"cbfuse: source {i} is {tuple(t.shape)} {t.dtype}, the target {tuple(xs[-1].shape)} {dt}")
-        _slot_view(t, f"cbfuse: source {i}", t.shape, dt)
-    out = L.empty_nhwc(B, c, H, W, dt, xs[-1].device) if out is None else _slot_view(out, "cbfuse: out=", (B, c, H, W), dt)
+        _nhwc_view(t, f"cbfuse: source {i}", t.shape, dt, slot=True)
+    out = _out("cbfuse: out=", out, (B, c, H, W), dt, xs[-1].device, slot=True)
     srcs = (L.CBFuseSrc * len(xs))()
     for s, t in zip(srcs, xs):
         s.ptr, s.cstride, s.Hi, s.Wi = t.data_ptr(), L.cstride(t), t.shape[2], t.shape[3]
@@ -1106,14 +1040,11 @@ def dysample(mod, x, out=None):
                 mod.init_pos.detach().to(dev, torch.float32).flatten().contiguous())
 
     w, b, s, pos = mod._packed(_dev_key(x, "dysample"), build)
-    if out is None:
-        out = L.empty_nhwc(B, c, 2 * H, 2 * W, dtype, dev)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, 2 * H, 2 * W) or out.dtype != dtype:
-        raise ValueError(f"dysample: out= must be an NHWC view of shape {(B, c, 2 * H, 2 * W)} {dtype}")
+    out = _out("dysample: out=", out, (B, c, 2 * H, 2 * W), dtype, dev)
     flops = 2.0 * B * H * W * c * w.shape[0] * (2 if s is not None else 1) + 7.0 * out.numel()
     with _tr("dysample_kernel", _nb(x, out), flops, note=f"C{c} G{mod.groups} {H}x{W}"):
         L.check(L.lib().ey_dysample(L.dtype_code(dtype), B, H, W, c, mod.scale, mod.groups, x.data_ptr(), L.cstride(x), w.data_ptr(), b.data_ptr(),
-                                    None if s is None else s.data_ptr(), pos.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_dysample")
+                                    _p(s), pos.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_dysample")
     return out
 
 
@@ -1130,14 +1061,11 @@ def max_sigmoid_attn(e, p, guide, bias, scale, nh, out=None):
         raise ValueError(f"max_sigmoid_attn: p is {tuple(p.shape)} {p.dtype}, e is {(B, c, H, W)} {dtype}")
     if guide.dim() != 3 or guide.shape[2] != c or guide.shape[0] not in (1, B) or guide.dtype != dtype or not guide.is_contiguous() or guide.device != dev:
         raise ValueError(f"max_sigmoid_attn: guide must be a contiguous (1 or {B}, n, {c}) {dtype} tensor on {dev}, got {tuple(guide.shape)} {guide.dtype}")
-    if out is None:
-        out = L.empty_nhwc(B, c, H, W, dtype, dev)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H, W) or out.dtype != dtype:
-        raise ValueError(f"max_sigmoid_attn: out= must be an NHWC view of shape {(B, c, H, W)} {dtype}")
+    out = _out("max_sigmoid_attn: out=", out, (B, c, H, W), dtype, dev)
     n = guide.shape[1]
     with _tr("max_sigmoid_attn_kernel", _nb(e, p, out, guide), 2.0 * B * H * W * c * n, note=f"C{c} n{n} {H}x{W}"):
         L.check(L.lib().ey_max_sigmoid_attn(L.dtype_code(dtype), B, H * W, nh, c // nh if nh else 0, c, n, guide.shape[0], e.data_ptr(), L.cstride(e), p.data_ptr(),
-                                            L.cstride(p), guide.data_ptr(), bias.data_ptr(), None if scale is None else scale.data_ptr(), out.data_ptr(),
+                                            L.cstride(p), guide.data_ptr(), bias.data_ptr(), _p(scale), out.data_ptr(),
                                             L.cstride(out), L.stream()), "ey_max_sigmoid_attn")
     return out
 
@@ -1166,10 +1094,7 @@ def deconv2x2(mod, x, deconv, out=None):
         return buf.to(dev), b.to(dev).contiguous()
 
     wp, bias = mod._packed(_dev_key(x, "deconv2x2"), build)
-    if out is None:
-        out = L.empty_nhwc(B, cout, 2 * H, 2 * W, dtype, dev)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, cout, 2 * H, 2 * W) or out.dtype != dtype:
-        raise ValueError(f"deconv2x2: out= must be an NHWC view of shape {(B, cout, 2 * H, 2 * W)} {dtype}")
+    out = _out("deconv2x2: out=", out, (B, cout, 2 * H, 2 * W), dtype, dev)
     with _tr("deconv2x2_kernel", _nb(x, out) + wp.numel(), 8.0 * B * H * W * cin * cout, note=f"C{cin}->{cout} {H}x{W}"):
         L.check(L.lib().ey_deconv2x2(L.dtype_code(dtype), B, H, W, cin, cout, x.data_ptr(), L.cstride(x), wp.data_ptr(), bias.data_ptr(), out.data_ptr(),
                                      L.cstride(out), L.stream()), "ey_deconv2x2")
@@ -1249,7 +1174,7 @@ def mask_iou(pred, pred_off, gt, gt_off, index=False, out_off=None, iou=None, in
     with _tr("mask_iou_kernels", pred_off[-1] * H * W + gt.numel() * gt.element_size() + 8 * end, 2.0 * sum(sizes) * words,
              note=f"B{B} N{pred_off[-1]} M{gt_off[-1]} {H}x{W}", kernels=3):
         L.check(L.lib().ey_mask_iou(L.MASK_GT_INDEX if index else L.MASK_GT_STACK, B, H, W, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off),
-                                    LA(*out_off), iou.data_ptr(), None if inter is None else inter.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                    LA(*out_off), iou.data_ptr(), _p(inter), workspace.data_ptr(), workspace.numel(),
                                     L.stream()), "ey_mask_iou")
     return iou, out_off, inter
 
@@ -1260,19 +1185,12 @@ def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
     L.require_device(x, "dwconv_s2")
     _no_block("stride-2 depthwise conv")
     B, c, H, W = x.shape
-
-    def build():
-        w, b = folded_fn()  # (C,1,k,k)
-        wk = w.view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)  # [k][k][C]
-        return wk, (b.to(x.device).float().contiguous() if b is not None else None)
-
-    wk, bias = mod._packed(_dev_key(x, tag), build)
+    wk, bias = _dw_pack(mod, x, folded_fn, c, k, tag)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if out is None:
-        out = L.empty_nhwc(B, c, Ho, Wo, x.dtype, x.device)
+    out = _out("dwconv_s2: out=", out, (B, c, Ho, Wo), x.dtype, x.device)
     with _tr(f"dwconv_s2_kernel<{k}>", _nb(x, out), 2.0 * B * Ho * Wo * c * k * k, note=f"C{c} {H}x{W}"):
-        L.check(L.lib().ey_dwconv_s2(L.dtype_code(x.dtype), B, H, W, c, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(),
-                                     bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out), L.stream()), "ey_dwconv_s2")
+        L.check(L.lib().ey_dwconv_s2(L.dtype_code(x.dtype), B, H, W, c, k, act, x.data_ptr(), L.cstride(x), wk.data_ptr(), _p(bias), out.data_ptr(), L.cstride(out),
+                                     L.stream()), "ey_dwconv_s2")
     return out
 
 
@@ -1310,10 +1228,7 @@ def hypergraph_conv(mod, x, out=None):
     w = mod._packed(_dev_key(x, "hypergraph"), build)
     nbytes = L.lib().ey_hypergraph_workspace_bytes(B, N, D, E)
     ws = mod._packed(("hg_ws", B, N, D, x.device), lambda: torch.empty(nbytes, dtype=torch.uint8, device=x.device))
-    if out is None:
-        out = L.empty_nhwc(B, D, H, W, x.dtype, x.device)
-    elif not L.is_nhwc_view(out) or tuple(out.shape) != (B, D, H, W) or out.dtype != x.dtype:
-        raise ValueError(f"hypergraph_conv: out= must be an NHWC view of shape {(B, D, H, W)} {x.dtype}")
+    out = _out("hypergraph_conv: out=", out, (B, D, H, W), x.dtype, x.device)
     flops = 2.0 * B * N * D * (E * 3 + D) + 2.0 * B * E * D * (D * 2 + (2 if g.context == "both" else 1) * D)
     with _tr("hypergraph_kernels", _nb(x, x, x, out) + 8.0 * B * N * E, flops, note=f"{H}x{W} D{D} E{E}", kernels=HG_LAUNCHES):
         L.check(L.lib().ey_hypergraph_conv(L.dtype_code(x.dtype), B, N, D, E, g.num_heads, HG_CONTEXT[g.context], x.data_ptr(), L.cstride(x), out.data_ptr(),
@@ -1322,16 +1237,6 @@ def hypergraph_conv(mod, x, out=None):
 
 
 # ----------------------------------------------------------------------------------------------- LGL block (YOLOv13 DSC3K2_LGL)
-def _out_like(x, out, what, hw=None):
-    B, c, H, W = x.shape
-    H, W = hw or (H, W)
-    if out is None:
-        return L.empty_nhwc(B, c, H, W, x.dtype, x.device)
-    if not L.is_nhwc_view(out) or tuple(out.shape) != (B, c, H, W) or out.dtype != x.dtype:
-        raise ValueError(f"{what}: out= must be an NHWC view of shape {(B, c, H, W)} {x.dtype}, got {tuple(out.shape)} {out.dtype}")
-    return out
-
-
 def flash_attention(q, k, v, heads, scale, out=None):
     """Softmax attention over all H*W tokens of each image (ey_flash_attention): q, k, v (B,C,H,W) NHWC views, C = heads*head_dim."""
     return _group_attention("flash_attention", q, k, v, heads, None, scale, out)
@@ -1344,16 +1249,11 @@ def dwconv_gate(mod, x, conv, mode, out=None, tag=""):
     _no_block("gated depthwise conv")
     B, c, H, W = x.shape
     k = conv.kernel_size[0]
-
-    def build():
-        wk = conv.weight.detach().float().view(c, k, k).permute(1, 2, 0).contiguous().to(device=x.device, dtype=x.dtype)  # [k][k][C]
-        return wk, (conv.bias.detach().float().to(x.device).contiguous() if conv.bias is not None else None)
-
-    wk, bias = mod._packed(_dev_key(x, "dwg" + tag), build)
-    out = _out_like(x, out, "dwconv_gate")
+    wk, bias = _dw_pack(mod, x, lambda: (conv.weight.detach().float(), None if conv.bias is None else conv.bias.detach()), c, k, "dwg" + tag)
+    out = _out("dwconv_gate: out=", out, x.shape, x.dtype, x.device)
     with _tr(f"lgl_dw_kernel<{k}>", _nb(x, out), 2.0 * x.numel() * k * k, note=f"C{c} {H}x{W} mode{mode}"):
-        L.check(L.lib().ey_dwconv_gate(L.dtype_code(x.dtype), B, H, W, c, k, mode, x.data_ptr(), L.cstride(x), wk.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None, out.data_ptr(), L.cstride(out), L.stream()), "ey_dwconv_gate")
+        L.check(L.lib().ey_dwconv_gate(L.dtype_code(x.dtype), B, H, W, c, k, mode, x.data_ptr(), L.cstride(x), wk.data_ptr(), _p(bias), out.data_ptr(), L.cstride(out),
+                                       L.stream()), "ey_dwconv_gate")
     return out
 
 
@@ -1365,7 +1265,7 @@ def sigmoid_gate(x, g, out=None):
     B, c, H, W = x.shape
     if g.shape != x.shape or g.dtype != x.dtype:
         raise ValueError(f"sigmoid_gate: x {tuple(x.shape)} {x.dtype}, g {tuple(g.shape)} {g.dtype}")
-    out = _out_like(x, out, "sigmoid_gate")
+    out = _out("sigmoid_gate: out=", out, x.shape, x.dtype, x.device)
     with _tr("lgl_gate_kernel", _nb(x, g, out), 4.0 * x.numel()):
         L.check(L.lib().ey_sigmoid_gate(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), g.data_ptr(), L.cstride(g), out.data_ptr(),
                                         L.cstride(out), L.stream()), "ey_sigmoid_gate")
@@ -1378,7 +1278,7 @@ def gelu(x, out=None):
     L.require_device(x, "gelu")
     _no_block("GELU")
     B, c, H, W = x.shape
-    out = _out_like(x, out, "gelu")
+    out = _out("gelu: out=", out, x.shape, x.dtype, x.device)
     with _tr("lgl_gelu_kernel", _nb(x, out), 8.0 * x.numel()):
         L.check(L.lib().ey_gelu(L.dtype_code(x.dtype), B, H, W, c, x.data_ptr(), L.cstride(x), out.data_ptr(), L.cstride(out), L.stream()), "ey_gelu")
     return out
@@ -1399,7 +1299,7 @@ def cmlp(mod, x, fc1, fc2, bn=None, gate=False, out=None):
 
     def build():
         f = lambda t: t.detach().float().to(x.device).contiguous()  # noqa: E731
-        w1 = fc1.weight.detach().float().view(c, r, 9).permute(1, 2, 0)  # [r][9][C]
+        w1 = fc1.weight.detach().float().view(c, r, 9).permute(1, 2, 0)  # [r][9][C]: grouped-conv taps per expansion channel, fp32 with their own bias layout -- not a _dw_pack
         w2 = fc2.weight.detach().float().view(c, r, 9).permute(1, 2, 0)
         b1 = fc1.bias.detach().float().view(c, r).t() if fc1.bias is not None else torch.zeros(r, c)
         b2 = fc2.bias.detach().float() if fc2.bias is not None else torch.zeros(c)
@@ -1409,11 +1309,10 @@ def cmlp(mod, x, fc1, fc2, bn=None, gate=False, out=None):
         return f(s), f(bn.bias.detach().float() - bn.running_mean.detach().float() * s), f(w1), f(b1), f(w2), f(b2)
 
     sc, sh, w1, b1, w2, b2 = mod._packed(_dev_key(x, "cmlp"), build)
-    out = _out_like(x, out, "cmlp")
+    out = _out("cmlp: out=", out, x.shape, x.dtype, x.device)
     with _tr("lgl_cmlp_kernel", _nb(x, out), 2.0 * x.numel() * r * 9 * 10, note=f"C{c} r{r} {H}x{W}"):
-        L.check(L.lib().ey_cmlp(L.dtype_code(x.dtype), B, H, W, c, r, int(bool(gate)), x.data_ptr(), L.cstride(x), sc.data_ptr() if sc is not None else None,
-                                sh.data_ptr() if sh is not None else None, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(),
-                                L.cstride(out), L.stream()), "ey_cmlp")
+        L.check(L.lib().ey_cmlp(L.dtype_code(x.dtype), B, H, W, c, r, int(bool(gate)), x.data_ptr(), L.cstride(x), _p(sc), _p(sh), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                b2.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_cmlp")
     return out
 
 
@@ -1438,7 +1337,7 @@ def layernorm_channels(mod, x, ln, pool=False, out=None, tag=""):
     _no_block("LayerNorm")
     B, c, H, W = x.shape
     g, b = _ln_params(mod, x, ln, tag)
-    out = _out_like(x, out, "layernorm_channels", ((H + 1) // 2, (W + 1) // 2) if pool else None)
+    out = _out("layernorm_channels: out=", out, (B, c, (H + 1) // 2, (W + 1) // 2) if pool else x.shape, x.dtype, x.device)
     with _tr("lgl_layernorm_kernel", _nb(x, out), 8.0 * x.numel(), note=f"C{c} {H}x{W}{' +pool' if pool else ''}"):
         L.check(L.lib().ey_layernorm_channels(L.dtype_code(x.dtype), B, H, W, c, float(ln.eps), int(bool(pool)), x.data_ptr(), L.cstride(x), g.data_ptr(),
                                               b.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_layernorm_channels")
@@ -1455,8 +1354,9 @@ def unpool2_layernorm(mod, t, deconv, ln, H, W, out=None, tag="up"):
             or deconv.bias is not None or deconv.padding != (0, 0) or deconv.output_padding != (0, 0)):
         raise NotImplementedError("unpool2_layernorm: the kernel takes a depthwise ConvTranspose2d(C, C, 2, 2, groups=C, bias=False)")
     g, b = _ln_params(mod, t, ln, tag)
-    w = mod._packed(_dev_key(t, "unpool" + tag), lambda: deconv.weight.detach().float().view(c, 2, 2).permute(1, 2, 0).contiguous().to(t.device))  # [a][b][C]
-    out = _out_like(t, out, "unpool2_layernorm", (H, W))
+    # the transposed conv's 2x2 taps [a][b][C], kept in fp32 and without a bias: not a _dw_pack
+    w = mod._packed(_dev_key(t, "unpool" + tag), lambda: deconv.weight.detach().float().view(c, 2, 2).permute(1, 2, 0).contiguous().to(t.device))
+    out = _out("unpool2_layernorm: out=", out, (B, c, H, W), t.dtype, t.device)
     with _tr("lgl_unpool_ln_kernel", _nb(t, out), 10.0 * out.numel(), note=f"C{c} {Hs}x{Ws}->{H}x{W}"):
         L.check(L.lib().ey_unpool2_layernorm(L.dtype_code(t.dtype), B, Hs, Ws, H, W, c, float(ln.eps), t.data_ptr(), L.cstride(t), w.data_ptr(), g.data_ptr(),
                                              b.data_ptr(), out.data_ptr(), L.cstride(out), L.stream()), "ey_unpool2_layernorm")
@@ -1500,6 +1400,31 @@ def nms_candidates(cand, iou_thres, max_det, max_nms, max_wh, agnostic):
     return boxes, count, index
 
 
+def _ia(values):
+    values = list(values)
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _pa(tensors):
+    """void* array of the tensors' pointers (NULL for None)."""
+    ptrs = [_p(t) for t in tensors]
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _level_arrays(levels, nmaps, stride_i, off_i):
+    """The ctypes arrays a per-level launch takes.  levels: one tuple per pyramid level that starts with `nmaps` NHWC views and holds the level's
+    stride at index `stride_i` and its anchor offset at `off_i` -> (Hs, Ws, strides, offsets) with the sizes of map 0, [pointers of map j],
+    [pixel strides of map j]."""
+    strides = (ctypes.c_float * len(levels))(*[float(lv[stride_i]) for lv in levels])
+    grid = _ia(lv[0].shape[2] for lv in levels), _ia(lv[0].shape[3] for lv in levels), strides, _ia(int(lv[off_i]) for lv in levels)
+    return grid, [_pa(lv[j] for lv in levels) for j in range(nmaps)], [_ia(L.cstride(lv[j]) for lv in levels) for j in range(nmaps)]
+
+
+def _quality_arrays(levels):
+    """Four pointer arrays of the levels' DGQP weights lv[3] = (w1, b1, w2, b2) or None."""
+    return [_pa(None if lv[3] is None else lv[3][j] for lv in levels) for j in range(4)]
+
+
 def head_decode_levels(levels, pred, nms=None, xyxy=False):
     """levels: list (<= 4) of (box, cls, stride, q-or-None, a_off) -> every level of the fused DGQP + DFL + decode in ONE launch.
     nms = (conf_thres, class_mask uint8 tensor or None, classes): also build the NMS candidates in the same pass (pred may then be None);
@@ -1510,13 +1435,8 @@ def head_decode_levels(levels, pred, nms=None, xyxy=False):
     B, nc = box0.shape[0], cls0.shape[1]
     q0 = levels[0][3]
     hid = q0[0].shape[0] if q0 is not None else 0
-    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
-    Hs, Ws = IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels])
-    st = FA(*[float(lv[2]) for lv in levels])
-    boxp, clsp = PA(*[lv[0].data_ptr() for lv in levels]), PA(*[lv[1].data_ptr() for lv in levels])
-    boxcs, clscs = IA(*[L.cstride(lv[0]) for lv in levels]), IA(*[L.cstride(lv[1]) for lv in levels])
-    offs = IA(*[int(lv[4]) for lv in levels])
-    qa = [PA(*[(lv[3][j].data_ptr() if lv[3] is not None else None) for lv in levels]) for j in range(4)]
+    (Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs) = _level_arrays(levels, 2, 2, 4)
+    qa = _quality_arrays(levels)
     nbytes = sum(_nb(lv[0], lv[1]) + B * lv[0].shape[2] * lv[0].shape[3] * (4 + nc) * 4 for lv in levels)
     flops = sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * (hid * 21 + 200) for lv in levels)
     if nms is not None:
@@ -1527,8 +1447,7 @@ def head_decode_levels(levels, pred, nms=None, xyxy=False):
         in_bytes = sum(_nb(lv[0], lv[1]) for lv in levels)
         with _tr("head_decode_kernel", in_bytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0), flops, note=f"{n} levels + NMS keys"):
             L.check(L.lib().ey_head_decode_levels_nms(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
-                                                      pred.data_ptr() if pred is not None else None, A, offs, float(conf), mask.data_ptr() if mask is not None else None,
-                                                      buf.data_ptr(), nb, L.stream()), "ey_head_decode_levels_nms")
+                                                      _p(pred), A, offs, float(conf), _p(mask), buf.data_ptr(), nb, L.stream()), "ey_head_decode_levels_nms")
         return Candidates(buf, B, nc, A, conf, classes, pred)
     with _tr("head_decode_kernel", nbytes, flops, note=f"{n} levels"):
         fn = L.lib().ey_head_decode_levels_xyxy if xyxy else L.lib().ey_head_decode_levels
@@ -1551,16 +1470,11 @@ def head_tail_decode_levels(levels, tails, pred, nms):
     fuse_cls = tails[0][2] is not None
     q0 = levels[0][3]
     hid = q0[0].shape[0] if q0 is not None else 0
-    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
-    Hs, Ws = IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels])
-    st = FA(*[float(lv[2]) for lv in levels])
-    boxp, clsp = PA(*[lv[0].data_ptr() for lv in levels]), PA(*[lv[1].data_ptr() for lv in levels])
-    boxcs, clscs = IA(*[L.cstride(lv[0]) for lv in levels]), IA(*[L.cstride(lv[1]) for lv in levels])
-    clscin = IA(*[lv[1].shape[1] for lv in levels])
-    offs = IA(*[int(lv[4]) for lv in levels])
-    qa = [PA(*[(lv[3][j].data_ptr() if lv[3] is not None else None) for lv in levels]) for j in range(4)]
-    bw, bb = PA(*[t[0].data_ptr() for t in tails]), PA(*[(t[1].data_ptr() if t[1] is not None else None) for t in tails])
-    ch = [PA(*[(t[2][j].data_ptr() if fuse_cls and t[2][j] is not None else None) for t in tails]) for j in range(4)]
+    (Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs) = _level_arrays(levels, 2, 2, 4)
+    qa = _quality_arrays(levels)
+    clscin = _ia(lv[1].shape[1] for lv in levels)
+    bw, bb = _pa(t[0] for t in tails), _pa(t[1] for t in tails)
+    ch = [_pa(t[2][j] if fuse_cls else None for t in tails) for j in range(4)]
     A = sum(lv[0].shape[2] * lv[0].shape[3] for lv in levels)
     nb = L.lib().ey_nms_candidates_bytes(B, A)
     buf = torch.empty(nb, dtype=torch.uint8, device=box0.device)
@@ -1568,13 +1482,9 @@ def head_tail_decode_levels(levels, tails, pred, nms):
     wbytes = sum(64 * cin * 2 + ((80 * lv[1].shape[1] + nc * 80) * 2 if fuse_cls else 0) for lv in levels)
     flops = sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * (hid * 21 + 200 + 64 * cin + ((80 * lv[1].shape[1] + nc * 80) if fuse_cls else 0)) for lv in levels)
     nbytes = sum(_nb(lv[0], lv[1]) for lv in levels) + wbytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0)
-    try:
-        with _tr("head_tail_decode_kernel", nbytes, flops, note=f"{n} levels, box tail{' + class chain' if fuse_cls else ''} + NMS keys"):
-            L.check(L.lib().ey_head_tail_decode_levels_nms(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, cin, 64, bw, bb, clsp, clscs, int(fuse_cls), clscin, 80,
-                                                           ch[0], ch[1], ch[2], ch[3], nc, qa[0], qa[1], qa[2], qa[3], hid, pred.data_ptr() if pred is not None else None,
-                                                           A, offs, float(conf), mask.data_ptr() if mask is not None else None, buf.data_ptr(), nb, L.stream()),
-                    "ey_head_tail_decode_levels_nms")
-    except NotImplementedError:  # EY_EUNSUPPORTED: nothing was launched (and nothing traced)
+    rec = _tr("head_tail_decode_kernel", nbytes, flops, note=f"{n} levels, box tail{' + class chain' if fuse_cls else ''} + NMS keys")
+    if not _try_launch(rec, "ey_head_tail_decode_levels_nms", L.lib().ey_head_tail_decode_levels_nms, L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, cin, 64, bw, bb,
+                       clsp, clscs, int(fuse_cls), clscin, 80, *ch, nc, *qa, hid, _p(pred), A, offs, float(conf), _p(mask), buf.data_ptr(), nb, L.stream()):
         return None
     return Candidates(buf, B, nc, A, conf, classes, pred)
 
@@ -1638,7 +1548,7 @@ def e2e_topk(pred, k, want_index=False):
     nb = L.lib().ey_e2e_topk_workspace_bytes(B, nc, A)
     ws = torch.empty(nb, dtype=torch.uint8, device=pred.device)
     with _tr("e2e_topk(score+select)", pred.numel() * 4 + out.numel() * 4):
-        L.check(L.lib().ey_e2e_topk(B, nc, A, pred.data_ptr(), k, out.data_ptr(), index.data_ptr() if want_index else None, ws.data_ptr(), nb, L.stream()), "ey_e2e_topk")
+        L.check(L.lib().ey_e2e_topk(B, nc, A, pred.data_ptr(), k, out.data_ptr(), _p(index), ws.data_ptr(), nb, L.stream()), "ey_e2e_topk")
     return (out, index) if want_index else out
 
 
@@ -1658,7 +1568,7 @@ def nms(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, class_m
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with _tr("nms(score+sort_greedy)", _nb(pred, boxes)):
         L.check(L.lib().ey_nms(B, no - 4, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh), int(bool(agnostic)), int(bool(multi_label)),
-                               class_mask.data_ptr() if class_mask is not None else None, boxes.data_ptr(), count.data_ptr(), index.data_ptr(),
+                               _p(class_mask), boxes.data_ptr(), count.data_ptr(), index.data_ptr(),
                                ws.data_ptr(), nbytes, L.stream()), "ey_nms")
     return (boxes, count, index, ws) if return_workspace else (boxes, count, index)
 
@@ -1673,12 +1583,7 @@ def obb_decode_levels(levels, pred):
     B, nc = box0.shape[0], cls0.shape[1]
     if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[0] != B or pred.shape[1] != 4 + nc + 1:
         raise ValueError(f"obb_decode: pred must be a contiguous float32 (B, 4+nc+1, A) tensor, got {tuple(pred.shape)} {pred.dtype}")
-    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
-    Hs, Ws = IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels])
-    st = FA(*[float(lv[3]) for lv in levels])
-    ptr = [PA(*[lv[j].data_ptr() for lv in levels]) for j in range(3)]
-    cs = [IA(*[L.cstride(lv[j]) for lv in levels]) for j in range(3)]
-    offs = IA(*[int(lv[4]) for lv in levels])
+    (Hs, Ws, st, offs), ptr, cs = _level_arrays(levels, 3, 3, 4)
     nbytes = sum(_nb(lv[0], lv[1], lv[2]) for lv in levels) + _nb(pred)
     with _tr("obb_decode_kernel", nbytes, sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * 220 for lv in levels), note=f"{n} levels"):
         L.check(L.lib().ey_obb_decode_levels(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, ptr[0], cs[0], ptr[1], cs[1], ptr[2], cs[2], nc, pred.data_ptr(), pred.shape[2],
@@ -1713,7 +1618,7 @@ def nms_rotated(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic,
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with _tr("nms_rotated(init+score+rank+pair+resolve)", _nb(pred, rows), kernels=5):
         L.check(L.lib().ey_nms_rotated(B, no - 5, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh), int(bool(agnostic)),
-                                       class_mask.data_ptr() if class_mask is not None else None, rows.data_ptr(), count.data_ptr(), index.data_ptr(),
+                                       _p(class_mask), rows.data_ptr(), count.data_ptr(), index.data_ptr(),
                                        ws.data_ptr(), nbytes, L.stream()), "ey_nms_rotated")
     return rows, count, index
 
@@ -1728,9 +1633,8 @@ def _kpt_levels(levels, kpt_shape, what):
     for lv in levels:
         if lv[0].dim() != 4 or lv[0].shape[1] != nkpt * ndim or lv[0].dtype != m0.dtype or lv[0].shape[0] != m0.shape[0]:
             raise ValueError(f"{what}: every level must be a (B, {nkpt * ndim}, H, W) map of one dtype, got {tuple(lv[0].shape)} {lv[0].dtype}")
-    IA, FA, PA = ctypes.c_int * n, ctypes.c_float * n, ctypes.c_void_p * n
-    return (L.dtype_code(m0.dtype), m0.shape[0], n, IA(*[lv[0].shape[2] for lv in levels]), IA(*[lv[0].shape[3] for lv in levels]), FA(*[float(lv[1]) for lv in levels]),
-            PA(*[lv[0].data_ptr() for lv in levels]), IA(*[L.cstride(lv[0]) for lv in levels]), nkpt, ndim), IA(*[int(lv[2]) for lv in levels])
+    (Hs, Ws, st, offs), ptr, cs = _level_arrays(levels, 1, 1, 2)
+    return (L.dtype_code(m0.dtype), m0.shape[0], n, Hs, Ws, st, ptr[0], cs[0], nkpt, ndim), offs
 
 
 def kpts_decode_levels(levels, kpt_shape, out):

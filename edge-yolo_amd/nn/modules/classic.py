@@ -6,6 +6,7 @@ import torch
 import torch.nn as nn
 
 from .. import _ops as ops
+from .conv import _Packed
 
 __all__ = ("MaxPool2d", "ZeroPad2d", "ConvTranspose2d", "ZeroPadded")
 
@@ -59,7 +60,7 @@ class MaxPool2d(nn.MaxPool2d):
         return ops.maxpool2d(x, 2, s, out=out)
 
 
-class ConvTranspose2d(nn.ConvTranspose2d):
+class ConvTranspose2d(nn.ConvTranspose2d, _Packed):  # (torch's class first: its name is the layer type a model reports)
     """nn.ConvTranspose2d(c1, c2, 2, 2, 0) of the YOLOv6 neck on ey_deconv2x2 (one GEMM launch with a scatter epilogue; channels multiples of 8
     up to 384).  The packed weight is cached per (dtype, device) and dropped whenever the parameters move or reload."""
 
@@ -68,19 +69,6 @@ class ConvTranspose2d(nn.ConvTranspose2d):
         if (self.kernel_size != (2, 2) or self.stride != (2, 2) or self.padding != (0, 0) or self.output_padding != (0, 0) or self.groups != 1
                 or self.dilation != (1, 1)):
             raise NotImplementedError(f"ConvTranspose2d({self.extra_repr()}): the kernel is built for a dense kernel 2, stride 2, padding 0")
-        self._cache = {}
-        self.register_load_state_dict_post_hook(lambda m, _keys: m._cache.clear())
-
-    def _apply(self, fn, *a, **k):
-        self._cache = {}
-        return super()._apply(fn, *a, **k)
-
-    def _packed(self, key, build):
-        v = self._cache.get(key)
-        if v is None:
-            with torch.no_grad():
-                v = self._cache[key] = build()
-        return v
 
     def forward(self, x, out=None):
         return ops.deconv2x2(self, x, self, out=out)

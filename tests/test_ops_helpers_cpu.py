@@ -1,0 +1,111 @@
+"""The helpers every wrapper of nn/_ops.py goes through, on CPU tensors (no launch is made): the output check `_out`, the alignment predicate
+`_aligned16`, the optional-pointer helpers and the table behind ey_conv_last_variant."""
+import pytest
+import torch
+
+import edge_yolo_amd  # noqa: F401
+from edge_yolo_amd import _lib as L
+from edge_yolo_amd.nn import _ops
+
+CPU = torch.device("cpu")
+
+
+def _nhwc(B, C, H, W, dtype=torch.float16):
+    return L.empty_nhwc(B, C, H, W, dtype, CPU)
+
+
+def test_out_allocates_an_nhwc_tensor():
+    y = _ops._out("op: out=", None, (2, 8, 3, 5), torch.float16, CPU)
+    assert tuple(y.shape) == (2, 8, 3, 5) and y.dtype == torch.float16 and L.is_nhwc_view(y) and L.cstride(y) == 8
+
+
+def test_out_hands_back_a_matching_view_and_slot():
+    y = _nhwc(1, 8, 4, 4)
+    assert _ops._out("op: out=", y, (1, 8, 4, 4), torch.float16, CPU) is y
+    wide = _nhwc(1, 24, 4, 4)
+    slot = wide[:, 8:16]
+    assert _ops._out("op: out=", slot, (1, 8, 4, 4), torch.float16, CPU, slot=True) is slot
+
+
+@pytest.mark.parametrize("bad, why", [
+    (lambda: _nhwc(1, 8, 4, 5), "spatial shape"),
+    (lambda: _nhwc(1, 16, 4, 4), "channels"),
+    (lambda: _nhwc(1, 8, 4, 4, torch.float32), "dtype"),
+    (lambda: torch.empty((1, 8, 4, 4), dtype=torch.float16), "NCHW-contiguous"),
+    (lambda: torch.empty((8, 4, 4), dtype=torch.float16), "3 dimensions"),
+])
+def test_out_error_names_wanted_and_given(bad, why):
+    t = bad()
+    with pytest.raises(ValueError) as e:
+        _ops._out("some_op: out=", t, (1, 8, 4, 4), torch.float16, CPU)
+    msg = str(e.value)
+    assert "some_op: out=" in msg and "NHWC view" in msg, why
+    assert str((1, 8, 4, 4)) in msg and str(tuple(t.shape)) in msg, why  # both shapes
+    assert "torch.float16" in msg and str(t.dtype) in msg and msg.count("torch.float") == 2, why  # both dtypes
+
+
+def test_out_slot_requires_sixteen_byte_windows_of_eight_channels():
+    wide = _nhwc(1, 24, 4, 4)
+    with pytest.raises(ValueError, match="multiples of 8"):  # window starting at element 4: 8 bytes into a pixel
+        _ops._out("op: out=", wide[:, 4:12], (1, 8, 4, 4), torch.float16, CPU, slot=True)
+    with pytest.raises(ValueError, match="multiples of 8"):  # 4 channels
+        _ops._out("op: out=", wide[:, 8:12], (1, 4, 4, 4), torch.float16, CPU, slot=True)
+    with pytest.raises(ValueError, match="multiples of 8"):  # pixel stride of 12 elements = 24 bytes
+        _ops._out("op: out=", _nhwc(1, 12, 4, 4)[:, :8], (1, 8, 4, 4), torch.float16, CPU, slot=True)
+    assert _ops._out("op: out=", wide[:, 4:12], (1, 8, 4, 4), torch.float16, CPU) is not None  # a plain output may sit anywhere
+
+
+def test_aligned16_on_offsets_and_strides():
+    wide = _nhwc(2, 24, 3, 3)
+    assert wide.data_ptr() % 16 == 0
+    assert _ops._aligned16(wide) and _ops._aligned16(wide[:, 8:16]) and _ops._aligned16(wide[:, 16:])
+    assert not _ops._aligned16(wide[:, 4:12])  # offset of 4 f16 elements = 8 bytes
+    assert not _ops._aligned16(wide[:, 1:9]) and not _ops._aligned16(wide[:, 3:11])  # odd offsets
+    assert not _ops._aligned16(wide[:, :12]) and _ops._aligned16(wide[:, :12], channels=False)  # 12 channels: only the count fails
+    odd = _nhwc(1, 20, 3, 3)  # pixel stride 20 elements = 40 bytes
+    assert not _ops._aligned16(odd[:, :8]) and not _ops._aligned16(odd[:, :8], channels=False)
+    assert _ops._aligned16(odd[:, :8], channels=False, width=8) and _ops._aligned16(wide[:, 4:12], channels=False, width=8)
+    assert not _ops._aligned16(wide[:, 2:10], channels=False, width=8)  # 4 bytes in
+    f32 = _nhwc(1, 12, 3, 3, torch.float32)  # 48-byte pixels: element size counts
+    assert _ops._aligned16(f32[:, 4:12]) and not _ops._aligned16(f32[:, 2:10])
+    seven = _nhwc(1, 7, 3, 3)  # odd stride
+    assert not _ops._aligned16(seven, channels=False) and not _ops._aligned16(seven, channels=False, width=8)
+
+
+def test_optional_pointers():
+    t = _nhwc(1, 16, 2, 2)[:, 8:]
+    assert _ops._p(None) is None and _ops._p(t) == t.data_ptr()
+    assert _ops._pcs(None) == (None, 0) and _ops._pcs(t) == (t.data_ptr(), 16)
+
+
+# one code of each range of ey_conv_last_variant -> the kernel name tests/test_gpu_conv_exact.py expects for it (case id behind each row)
+VARIANTS = [
+    (13081, "f16", "conv_igemm_kernel<f16,8,1>"),  # igemm_mt1
+    (13082, "f32", "conv_igemm_kernel<f32,8,2>"),  # igemm_mt2
+    (12511, "f16", "conv_ws_kernel<f16,5,1,1>"),  # ws_k1_mt1
+    (12223, "f32", "conv_ws_kernel<f32,2,2,3>"),  # ws_k3_mt2_s2
+    (11051, "f16", "conv3_halo_kernel<f16,5,1>"),  # halo_s1
+    (10048, "f16", "conv_small_kernel<f16,4,8>"),  # small_nt4
+    (9040, "f16", "conv3p_kernel<4>"),  # c3p_64
+    (8441, "f16", "conv3s_kernel<4,4,1>"),  # c3s_s1_mt4
+    (8122, "f16", "conv3s_kernel<1,2,2>"),  # c3s_s2_nt1
+    (7022, "f16", "conv3r_kernel<2,2>"),  # c3r_s2
+    (6041, "f32", "conv3_tile_kernel<f32,4,1>"),  # tile_s1_nt4
+    (5083, "f16", "conv_pwr_kernel<f16,8,3>"),  # pwr_nt8_two
+    (4050, "f16", "conv_pw_kernel<f16,5>"),  # pw_nt5 (reference variant)
+    (3162, "f16", "conv_pwn_kernel<f16,16,2>"),  # pwn_ks16_ntw2
+    (3000, "f32", "conv_pwn_kernel<f32,0,0>"),  # the lowest code of the lowest range still has a name
+]
+
+
+@pytest.mark.parametrize("code, tn, name", VARIANTS)
+def test_conv_variant_table(code, tn, name):
+    assert _ops._conv_variant(code, tn) == name
+
+
+def test_conv_variant_table_is_sorted_and_refuses_lower_codes():
+    floors = [f for f, _ in _ops._CONV_VARIANTS]
+    assert floors == sorted(floors, reverse=True) and len(set(floors)) == len(floors)
+    for code in (2999, 0, -1):
+        with pytest.raises(AssertionError, match="without reporting its kernel"):
+            _ops._conv_variant(code, "f16")

@@ -29,7 +29,7 @@ for n in (1, 50):
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     print(f"{n} steps: host enqueue {1e3 * (t1 - t0) / n:.3f} ms/step, total {1e3 * (t2 - t0) / n:.3f} ms/step", flush=True)
-g = pipe.sets[0]["g1"]
+g = pipe.sets[0]["graphs"][0]  # the first stage's graph
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(20):
