@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI: take logical-NCHW torch tensors (NHWC memory), hand plain pointers /
 strides to libedgeyolo_hip.so on the current HIP stream.  No arithmetic happens in Python or in torch here."""
+import collections
 import ctypes
 
 import torch
@@ -1420,38 +1421,48 @@ def _level_arrays(levels, nmaps, stride_i, off_i):
     return grid, [_pa(lv[j] for lv in levels) for j in range(nmaps)], [_ia(L.cstride(lv[j]) for lv in levels) for j in range(nmaps)]
 
 
+# One pyramid level of the head decode: box / class maps (NHWC views), the level's stride, its DGQP weights (w1, b1, w2, b2) or None, and the
+# index of its first anchor.  A plain 5-tuple in this order is accepted wherever a Level is.
+Level = collections.namedtuple("Level", "box cls stride q a_off")
+
+
 def _quality_arrays(levels):
-    """Four pointer arrays of the levels' DGQP weights lv[3] = (w1, b1, w2, b2) or None."""
-    return [_pa(None if lv[3] is None else lv[3][j] for lv in levels) for j in range(4)]
+    """Four pointer arrays of the levels' DGQP weights q = (w1, b1, w2, b2) or None."""
+    return [_pa(None if lv.q is None else lv.q[j] for lv in levels) for j in range(4)]
+
+
+def _decode_prologue(levels, what, cand):
+    """What head_decode_levels and head_tail_decode_levels set up alike -> (levels as Level, B, hid, level arrays, quality arrays, A,
+    bytes of the candidate buffer, the buffer); the last two are 0 / None unless `cand`."""
+    levels = [Level(*lv) for lv in levels]
+    box0, q0 = levels[0].box, levels[0].q
+    L.require_device(box0, what)
+    B = box0.shape[0]
+    hid = q0[0].shape[0] if q0 is not None else 0
+    arrays = _level_arrays([(lv.box, lv.cls, lv.stride, lv.a_off) for lv in levels], 2, 2, 3)
+    A = sum(lv.box.shape[2] * lv.box.shape[3] for lv in levels)
+    nb = L.lib().ey_nms_candidates_bytes(B, A) if cand else 0
+    buf = torch.empty(nb, dtype=torch.uint8, device=box0.device) if cand else None
+    return levels, B, hid, arrays, _quality_arrays(levels), A, nb, buf
 
 
 def head_decode_levels(levels, pred, nms=None, xyxy=False):
     """levels: list (<= 4) of (box, cls, stride, q-or-None, a_off) -> every level of the fused DGQP + DFL + decode in ONE launch.
     nms = (conf_thres, class_mask uint8 tensor or None, classes): also build the NMS candidates in the same pass (pred may then be None);
     returns a Candidates object.  xyxy: rows 0-3 = x1,y1,x2,y2 (end2end heads, reference head.py:163-165)."""
-    n = len(levels)
-    box0, cls0 = levels[0][0], levels[0][1]
-    L.require_device(box0, "head_decode")
-    B, nc = box0.shape[0], cls0.shape[1]
-    q0 = levels[0][3]
-    hid = q0[0].shape[0] if q0 is not None else 0
-    (Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs) = _level_arrays(levels, 2, 2, 4)
-    qa = _quality_arrays(levels)
-    nbytes = sum(_nb(lv[0], lv[1]) + B * lv[0].shape[2] * lv[0].shape[3] * (4 + nc) * 4 for lv in levels)
-    flops = sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * (hid * 21 + 200) for lv in levels)
+    levels, B, hid, ((Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs)), qa, A, nb, buf = _decode_prologue(levels, "head_decode", nms is not None)
+    n, dt, nc = len(levels), L.dtype_code(levels[0].box.dtype), levels[0].cls.shape[1]
+    in_bytes = sum(_nb(lv.box, lv.cls) for lv in levels)
+    flops = sum(2.0 * B * lv.box.shape[2] * lv.box.shape[3] * (hid * 21 + 200) for lv in levels)
     if nms is not None:
         conf, mask, classes = nms
-        A = sum(lv[0].shape[2] * lv[0].shape[3] for lv in levels)
-        nb = L.lib().ey_nms_candidates_bytes(B, A)
-        buf = torch.empty(nb, dtype=torch.uint8, device=box0.device)
-        in_bytes = sum(_nb(lv[0], lv[1]) for lv in levels)
         with _tr("head_decode_kernel", in_bytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0), flops, note=f"{n} levels + NMS keys"):
-            L.check(L.lib().ey_head_decode_levels_nms(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
+            L.check(L.lib().ey_head_decode_levels_nms(dt, B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
                                                       _p(pred), A, offs, float(conf), _p(mask), buf.data_ptr(), nb, L.stream()), "ey_head_decode_levels_nms")
         return Candidates(buf, B, nc, A, conf, classes, pred)
-    with _tr("head_decode_kernel", nbytes, flops, note=f"{n} levels"):
+    with _tr("head_decode_kernel", in_bytes + B * A * (4 + nc) * 4, flops, note=f"{n} levels"):
         fn = L.lib().ey_head_decode_levels_xyxy if xyxy else L.lib().ey_head_decode_levels
-        L.check(fn(L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
+        L.check(fn(dt, B, n, Hs, Ws, st, boxp, boxcs, clsp, clscs, nc, qa[0], qa[1], qa[2], qa[3], hid,
                    pred.data_ptr(), pred.shape[2], offs, L.stream()), "ey_head_decode_levels")
 
 
@@ -1461,27 +1472,18 @@ def head_tail_decode_levels(levels, tails, pred, nms):
     (w1p, b1, w2p, b2) -- cls_in is then the class-tower feature in front of the chain -- or None on every level (cls_in = the
     class logits).  nc: tails' class count = `nms[3]`.  Returns a Candidates object, or None when the shapes are outside the fused
     kernel (nothing launched: the caller runs the convs and head_decode_levels)."""
-    n = len(levels)
-    box0 = levels[0][0]
-    L.require_device(box0, "head_tail_decode")
     _no_block("head decode")
+    levels, B, hid, ((Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs)), qa, A, nb, buf = _decode_prologue(levels, "head_tail_decode", True)
     conf, mask, classes, nc = nms
-    B = box0.shape[0]
+    n, box0 = len(levels), levels[0].box
     fuse_cls = tails[0][2] is not None
-    q0 = levels[0][3]
-    hid = q0[0].shape[0] if q0 is not None else 0
-    (Hs, Ws, st, offs), (boxp, clsp), (boxcs, clscs) = _level_arrays(levels, 2, 2, 4)
-    qa = _quality_arrays(levels)
-    clscin = _ia(lv[1].shape[1] for lv in levels)
+    clscin = _ia(lv.cls.shape[1] for lv in levels)
     bw, bb = _pa(t[0] for t in tails), _pa(t[1] for t in tails)
     ch = [_pa(t[2][j] if fuse_cls else None for t in tails) for j in range(4)]
-    A = sum(lv[0].shape[2] * lv[0].shape[3] for lv in levels)
-    nb = L.lib().ey_nms_candidates_bytes(B, A)
-    buf = torch.empty(nb, dtype=torch.uint8, device=box0.device)
     cin = box0.shape[1]
-    wbytes = sum(64 * cin * 2 + ((80 * lv[1].shape[1] + nc * 80) * 2 if fuse_cls else 0) for lv in levels)
-    flops = sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * (hid * 21 + 200 + 64 * cin + ((80 * lv[1].shape[1] + nc * 80) if fuse_cls else 0)) for lv in levels)
-    nbytes = sum(_nb(lv[0], lv[1]) for lv in levels) + wbytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0)
+    wbytes = sum(64 * cin * 2 + ((80 * lv.cls.shape[1] + nc * 80) * 2 if fuse_cls else 0) for lv in levels)
+    flops = sum(2.0 * B * lv.box.shape[2] * lv.box.shape[3] * (hid * 21 + 200 + 64 * cin + ((80 * lv.cls.shape[1] + nc * 80) if fuse_cls else 0)) for lv in levels)
+    nbytes = sum(_nb(lv.box, lv.cls) for lv in levels) + wbytes + nb + (B * A * (4 + nc) * 4 if pred is not None else 0)
     rec = _tr("head_tail_decode_kernel", nbytes, flops, note=f"{n} levels, box tail{' + class chain' if fuse_cls else ''} + NMS keys")
     if not _try_launch(rec, "ey_head_tail_decode_levels_nms", L.lib().ey_head_tail_decode_levels_nms, L.dtype_code(box0.dtype), B, n, Hs, Ws, st, boxp, boxcs, cin, 64, bw, bb,
                        clsp, clscs, int(fuse_cls), clscin, 80, *ch, nc, *qa, hid, _p(pred), A, offs, float(conf), _p(mask), buf.data_ptr(), nb, L.stream()):

@@ -2,9 +2,14 @@
 `GFLHeadv2_uniH` (:827-908).  Same constructor signatures / attribute names / state_dict keys.  The towers are MFMA convs and
 depthwise kernels; everything after them (DGQP statistics + quality FCs, DFL softmax-expectation, anchor decode,
 score modulation) is ONE fused kernel per pyramid level writing the (B, 4+nc, A) fp32 prediction tensor.
+
+Host structure: module-level builders make the towers the heads share; `Detect._run_towers` is the one fork / join over HIP streams
+(`_stream_map` places the towers); `_padded` allocates a level's map, `Detect._levels` makes the `_ops.Level` list the decode kernels
+take; the towers' branch ("" or "one2one_") is an argument of whatever reads weights, and caches are keyed by what an entry is.
 """
 import copy
 import math
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -13,6 +18,7 @@ from .block import DFL, Proto
 from .conv import Conv, DWConv, _Packed, _act_code, fold_bn
 from .. import _ops as ops
 from ... import _lib as L
+from ...utils.ops import _class_mask
 
 __all__ = ("Detect", "Segment", "OBB", "Pose", "Classify", "GF2Detect", "E2EDetect", "GFLHeadv2_uniH", "WorldDetect", "v10Detect")
 
@@ -24,9 +30,45 @@ class _Plain(_Packed):
         super().__init__()
         self.__dict__["_ref"] = conv  # not registered: the nn.Conv2d stays where the reference keeps it
 
-    def run(self, x, out):
+    def folded(self):
         c = self._ref
-        return ops.conv2d(self, [x], lambda: fold_bn(c.weight, c.bias, None), 1, 1, 0, L.ACT_NONE, out=out)
+        return fold_bn(c.weight, c.bias, None)
+
+    def run(self, x, out):
+        return ops.conv2d(self, [x], self.folded, 1, 1, 0, L.ACT_NONE, out=out)
+
+
+def _plain_towers(ch, c, cout):
+    """One Conv 3x3 -> Conv 3x3 -> nn.Conv2d 1x1 tower per level: the box tower (head.py:60-62), the legacy class tower (:64) and every cv4."""
+    return nn.ModuleList(nn.Sequential(Conv(x, c, 3), Conv(c, c, 3), nn.Conv2d(c, cout, 1)) for x in ch)
+
+
+def _light_towers(ch, c3, nc):
+    """The light class tower per level (head.py:66-74): DWConv -> Conv 1x1 -> DWConv -> Conv 1x1 -> nn.Conv2d 1x1."""
+    return nn.ModuleList(
+        nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), nn.Conv2d(c3, nc, 1))
+        for x in ch)
+
+
+def _reg_conf(ch, reg_topk, add_mean, reg_channels):
+    """The DGQP quality head per level (head.py:211-219)."""
+    in_stat = 4 * (reg_topk + (1 if add_mean else 0))
+    return nn.ModuleList(
+        nn.Sequential(nn.Conv2d(in_stat, reg_channels, 1, bias=True), nn.ReLU(inplace=True), nn.Conv2d(reg_channels, 1, 1, bias=True), nn.Sigmoid())
+        for _ in ch)
+
+
+def _light_closing(c):
+    """Does the class tower `c` close as the light tower does: Sequential(DWConv, Conv 1x1 + SiLU), then a dense nn.Conv2d 1x1?"""
+    last, ct = c[-2], c[-1]
+    return (isinstance(last, nn.Sequential) and len(last) == 2 and isinstance(last[0], DWConv) and isinstance(last[1], Conv)
+            and last[1].conv.kernel_size == (1, 1) and last[1].conv.groups == 1 and isinstance(last[1].act, nn.SiLU)
+            and isinstance(ct, nn.Conv2d) and ct.kernel_size == (1, 1) and ct.groups == 1)
+
+
+def _padded(t, c):
+    """An NHWC map of `c` channels over the pixels of `t` whose pixel stride is rounded up to 8 channels (kept 16-byte aligned for any c)."""
+    return L.empty_nhwc(t.shape[0], (c + 7) // 8 * 8, t.shape[2], t.shape[3], t.dtype, t.device)[:, :c]
 
 
 class Detect(nn.Module):
@@ -63,15 +105,8 @@ class Detect(nn.Module):
         self.no = nc + self.reg_max * 4
         self.stride = torch.zeros(self.nl)
         c2, c3 = max((16, ch[0] // 4, self.reg_max * 4)), max(ch[0], min(self.nc, 100))
-        self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * self.reg_max, 1)) for x in ch)
-        self.cv3 = (
-            nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, self.nc, 1)) for x in ch)
-            if self.legacy
-            else nn.ModuleList(
-                nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)),
-                              nn.Conv2d(c3, self.nc, 1))
-                for x in ch)
-        )
+        self.cv2 = _plain_towers(ch, c2, 4 * self.reg_max)
+        self.cv3 = _plain_towers(ch, c3, self.nc) if self.legacy else _light_towers(ch, c3, self.nc)
         self.dfl = DFL(self.reg_max) if self.reg_max > 1 else nn.Identity()
         if self.end2end:  # head.py:76-78
             self.one2one_cv2 = copy.deepcopy(self.cv2)
@@ -87,51 +122,62 @@ class Detect(nn.Module):
         if hasattr(self, "_qcache"):
             self._qcache = {}
 
-    # ---- towers
-    def _tail(self, conv):
-        t = self._tails.get(id(conv))
-        if t is None:
-            t = self._tails[id(conv)] = _Plain(conv)
-        return t
-
     def _apply(self, fn, *a, **k):
         self._reset_caches()
         return super()._apply(fn, *a, **k)
 
-    # branch of the towers the inference decodes: "" (cv2 / cv3 / reg_conf) or "one2one_" (their end2end copies, head.py:76-78,220-221)
-    _branch = ""
+    def _refuse(self, head=None):
+        """The refusals that open a forward: training mode, and (`head` = the class's name) end2end where that head has no such path."""
+        if self.training:
+            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
+        if head and self.end2end:
+            raise NotImplementedError(f"{head}: end2end heads are not built")
 
-    def _box_tower(self, i, x, raw):
+    # ---- towers.  `branch` = which towers' weights run: "" (cv2 / cv3 / reg_conf) or "one2one_" (their end2end copies, head.py:76-78,220-221)
+    def _tail(self, tower, i, branch=""):
+        """The packed closing nn.Conv2d of level i's `tower` ("cv2" / "cv3" / "cv4")."""
+        key = (branch, tower, i)
+        t = self._tails.get(key)
+        if t is None:
+            t = self._tails[key] = _Plain(getattr(self, branch + tower)[i][-1])
+        return t
+
+    def _box_tower(self, i, x, raw, branch=""):
         """box logits -> raw[:, :64]."""
-        b = getattr(self, self._branch + "cv2")[i]
-        self._tail(b[2]).run(b[1](b[0](x)), raw[:, :4 * self.reg_max])
+        b = getattr(self, branch + "cv2")[i]
+        self._tail("cv2", i, branch).run(b[1](b[0](x)), raw[:, :4 * self.reg_max])
 
-    def _cls_tower(self, i, x, raw, out=None):
-        """class logits -> raw[:, 64:] (or `out`)."""
-        c = getattr(self, self._branch + "cv3")[i]
-        t = x
-        if out is None:
-            out = raw[:, 4 * self.reg_max:]
-        last = c[-2]
-        # non-legacy tower (head.py:68-70): ... -> DWConv -> Conv(c3,c3,1)+SiLU -> nn.Conv2d(c3,nc,1): the last two 1x1 convs run as ONE
-        # register-only kernel when the shape fits (ey_conv_pw_chain), the intermediate (B,c3,H,W) tensor never exists
-        if (self.chain and isinstance(last, nn.Sequential) and len(last) == 2 and isinstance(last[0], DWConv) and isinstance(last[1], Conv)
-                and last[1].conv.kernel_size == (1, 1) and isinstance(last[1].act, nn.SiLU) and x.dtype == torch.float16):
-            for j in range(len(c) - 2):
-                t = c[j](t)
-            t = last[0](t)
-            tail = c[-1]
-            if ops.conv_pw_chain(self._tail(tail), t, last[1].folded, L.ACT_SILU, lambda: fold_bn(tail.weight, tail.bias, None), L.ACT_NONE, out) is not None:
+    def _chained(self, i, x, branch=""):
+        """non-legacy tower (head.py:68-70): ... -> DWConv -> Conv(c3,c3,1)+SiLU -> nn.Conv2d(c3,nc,1): the last two 1x1 convs run as ONE
+        register-only kernel when the shape fits (ey_conv_pw_chain), the intermediate (B,c3,H,W) tensor never exists."""
+        return self.chain and x.dtype == torch.float16 and _light_closing(getattr(self, branch + "cv3")[i])
+
+    def _cls_stem(self, i, x, chained, branch="", out=None):
+        """The class tower of level i up to its closing (`_cls_close`): chained, up to and including the last DWConv (into `out` when
+        given); else everything but the nn.Conv2d."""
+        c = getattr(self, branch + "cv3")[i]
+        for j in range(len(c) - (2 if chained else 1)):
+            x = c[j](x)  # (ops.dsconv fuses DWConv+Conv into one kernel; measured slower than the two kernels at these widths)
+        return c[-2][0](x, out=out) if chained else x
+
+    def _cls_close(self, i, t, out, chained, branch=""):
+        """The closing of level i's class tower: `_cls_stem`'s feature -> class logits in `out`."""
+        tail = self._tail("cv3", i, branch)
+        if chained:
+            pw = getattr(self, branch + "cv3")[i][-2][1]
+            if ops.conv_pw_chain(tail, t, pw.folded, L.ACT_SILU, tail.folded, L.ACT_NONE, out) is not None:
                 return
-            self._tail(tail).run(last[1](t), out)
-            return
-        for j in range(len(c) - 1):
-            t = c[j](t)  # (self._dw_pw fuses DWConv+Conv into one kernel; measured slower than the two kernels at these widths)
-        self._tail(c[-1]).run(t, out)
+            t = pw(t)
+        tail.run(t, out)
 
-    def _towers(self, i, x, raw):
-        self._box_tower(i, x, raw)
-        self._cls_tower(i, x, raw)
+    def _cls_tower(self, i, x, raw, out=None, branch=""):
+        """class logits -> raw[:, 64:] (or `out`)."""
+        chained = self._chained(i, x, branch)
+        self._cls_close(i, self._cls_stem(i, x, chained, branch), raw[:, 4 * self.reg_max:] if out is None else out, chained, branch)
+
+    def _towers(self, i, x, raw, branch=""):
+        self._box_tower(i, x, raw, branch)
+        self._cls_tower(i, x, raw, branch=branch)
 
     def _towers_block(self, i, x, raw):
         """Both towers of level i as one block program; False when the level is not block-executable (per-layer kernels then)."""
@@ -148,22 +194,64 @@ class Detect(nn.Module):
 
         return cache.run(chain, [x], [raw]) is not None
 
-    @staticmethod
-    def _dw_pw(blk, t):
-        """Sequential(DWConv 3x3 (+BN+SiLU), Conv 1x1 (+BN+SiLU)) of the non-legacy cls tower (reference head.py:68-69) as
-        ONE fused depthwise->pointwise kernel; anything else runs module by module."""
-        if isinstance(blk, nn.Sequential) and len(blk) == 2 and isinstance(blk[0], DWConv) and isinstance(blk[1], Conv):
-            dw, pw = blk[0].conv, blk[1].conv
-            k = dw.kernel_size[0]
-            if (dw.groups == dw.in_channels == dw.out_channels and dw.stride == (1, 1) and k in (3, 5, 7) and dw.padding == (k // 2, k // 2)
-                    and pw.kernel_size == (1, 1) and pw.groups == 1 and isinstance(blk[0].act, nn.SiLU) and isinstance(blk[1].act, nn.SiLU)):
-                y = ops.dsconv(blk[1], t, blk[0].folded, blk[1].folded, k, L.ACT_SILU, dw_act=L.ACT_SILU)
-                if y is not None:
-                    return y
-        return blk(t)
+    def _level_towers(self, i, x, raw):
+        """Both towers of level i on one stream: small levels go through one block program."""
+        if not self._towers_block(i, x, raw):
+            self._towers(i, x, raw)
 
-    def _quality_params(self, i, device):
+    def _stream_map(self, n):
+        """Stream index (0 = the caller's stream) of each of the 2n towers, in the order of `tower_streams`."""
+        ts = self.tower_streams
+        # default: the first (largest) level on the caller's stream, all smaller levels one after the other on ONE side stream
+        return list(ts) if ts and len(ts) == 2 * n else [0, 0] + [1] * (2 * n - 2)
+
+    def _run_towers(self, tasks, smap, dev):
+        """tasks: [(tower number = 2 * level + (0 box | 1 class), callable)] in launch order; each runs on the stream `smap` gives its tower.
+        The towers of the pyramid levels are independent: the small levels run on a second HIP stream (fork / join around them),
+        which a captured hipGraph records as a parallel branch -- the 20x20 and 40x40 towers (a few hundred workgroups per kernel)
+        then run beside the 80x80 ones instead of after them (2.18 -> 2.08 ms/step).  More branches are slower (3 level streams
+        2.38 ms, 6 tower streams 2.40 ms: the persistent kernels fight for the CUs).  `head_streams = False` keeps one stream.
+        The caller allocates every buffer a side stream WRITES before this call, that is before the fork: a block handed out later on
+        the caller's stream could be one that kernels still queued there are using (the caching allocator orders reuse per stream only)."""
+        if not (self.head_streams and dev.type == "cuda" and len(smap) > 2):
+            for _, run in tasks:
+                run()
+            return
+        if getattr(self, "_side", None) is None or self._side_dev != dev or len(self._side) != max(smap):
+            self._side, self._side_dev = [torch.cuda.Stream(device=dev) for _ in range(max(smap))], dev
+        cur = torch.cuda.current_stream(dev)
+        for side in self._side:
+            side.wait_stream(cur)
+        for k, run in tasks:
+            if smap[k] > 0:
+                with torch.cuda.stream(self._side[smap[k] - 1]):
+                    run()
+            else:
+                run()
+        for side in self._side:
+            cur.wait_stream(side)
+
+    # ---- levels
+    def _quality_params(self, i, device, branch=""):
         return None
+
+    def _walk(self, maps):
+        """[(stride, first anchor)] of the per-level maps, in order."""
+        if getattr(self, "_stride_f", None) is None:
+            self._stride_f = [float(s) for s in self.stride]  # host copy once (no D2H inside a captured graph)
+        walk, a_off = [], 0
+        for i, m in enumerate(maps):
+            walk.append((self._stride_f[i], a_off))
+            a_off += m.shape[2] * m.shape[3]
+        return walk
+
+    def _split(self, raw):
+        return raw[:, :4 * self.reg_max], raw[:, 4 * self.reg_max:]
+
+    def _levels(self, maps, branch=""):
+        """Per-level (box map, class map) pairs -> the decode kernels' level list."""
+        walk = self._walk([box for box, _ in maps])
+        return [ops.Level(box, cls, st, self._quality_params(i, box.device, branch), off) for i, ((box, cls), (st, off)) in enumerate(zip(maps, walk))]
 
     def forward(self, x, nms=None, towers_only=False):
         """towers_only (subclasses that decode themselves, OBB): stop behind the towers and return (levels, raw maps) as `defer_decode` does.
@@ -174,69 +262,30 @@ class Detect(nn.Module):
         tower, class chain c3 -> 80 -> nc with nc % 8 == 0, 64 < nc <= 80) the closing 1x1 convs of both towers run inside the decode
         kernel (tunable head_fuse): their logits are then never written, and the second return value holds None per level -- pass
         nms["keep_raw"]=True to keep the separate launches and get the raw maps."""
-        if self.training:
-            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
+        self._refuse()
         if self.reg_max != 16:
             raise NotImplementedError("the decode kernel is built for reg_max=16")
         xs = [L.as_nhwc(t) for t in x]
         if self.end2end:
             return self._forward_end2end(x, xs)
-        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
+        B, dev = xs[0].shape[0], xs[0].device
         A = sum(t.shape[2] * t.shape[3] for t in xs)
         want_pred = not towers_only and (nms is None or nms.get("keep_pred") or not (len(xs) <= 4 and self.nc > 1))
         pred = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev) if want_pred else None
-        a_off = 0
-        if getattr(self, "_stride_f", None) is None:
-            self._stride_f = [float(s) for s in self.stride]  # host copy once (no D2H inside a captured graph)
-        levels = []
-        # The towers of the pyramid levels are independent: the small levels run on a second HIP stream (fork / join around them),
-        # which a captured hipGraph records as a parallel branch -- the 20x20 and 40x40 towers (a few hundred workgroups per kernel)
-        # then run beside the 80x80 ones instead of after them (2.18 -> 2.08 ms/step).  More branches are slower (3 level streams
-        # 2.38 ms, 6 tower streams 2.40 ms: the persistent kernels fight for the CUs).  `head_streams = False` keeps one stream.
-        fork = self.head_streams and dev.type == "cuda" and len(xs) > 1
-        cur = torch.cuda.current_stream(dev) if fork else None
-        # default: the first (largest) level on the caller's stream, all smaller levels one after the other on ONE side stream
-        smap = list(self.tower_streams) if (self.tower_streams and len(self.tower_streams) == 2 * len(xs)) else [0, 0] + [1] * (2 * len(xs) - 2)
-        if fork and (getattr(self, "_side", None) is None or self._side_dev != dev or len(self._side) != max(smap)):
-            self._side, self._side_dev = [torch.cuda.Stream(device=dev) for _ in range(max(smap))], dev
+        smap = self._stream_map(len(xs))
         fuse = self._head_fuse(xs, nms)
         if fuse:
-            return self._forward_fused(xs, nms, fuse, pred, fork, cur, smap)
-        # every buffer a side stream WRITES is allocated before the fork: a block handed out later on the caller's stream could be one
-        # that kernels still queued there are using (the caching allocator orders reuse per stream only)
-        raws = [L.empty_nhwc(B, (self.no + 7) // 8 * 8, t.shape[2], t.shape[3], dt, dev)[:, :self.no] for t in xs]  # pixel stride kept 16-byte aligned for any nc
-        if fork:
-            for side in self._side:
-                side.wait_stream(cur)
-        task = 0
-        for i, t in enumerate(xs):
-            H, W = t.shape[2:]
-            raw = raws[i]
-            if smap[task] == smap[task + 1]:  # both towers on one stream: small levels go through one block program
-                if fork and smap[task] > 0:
-                    with torch.cuda.stream(self._side[smap[task] - 1]):
-                        done = self._towers_block(i, t, raw)
-                else:
-                    done = self._towers_block(i, t, raw)
-                if done:
-                    task += 2
-                    levels.append((raw[:, :4 * self.reg_max], raw[:, 4 * self.reg_max:], self._stride_f[i], self._quality_params(i, dev), a_off))
-                    a_off += H * W
-                    x[i] = raw
-                    continue
-            for tower in (self._box_tower, self._cls_tower):
-                if fork and smap[task] > 0:
-                    with torch.cuda.stream(self._side[smap[task] - 1]):
-                        tower(i, t, raw)
-                else:
-                    tower(i, t, raw)
-                task += 1
-            levels.append((raw[:, :4 * self.reg_max], raw[:, 4 * self.reg_max:], self._stride_f[i], self._quality_params(i, dev), a_off))
-            a_off += H * W
+            return self._forward_fused(xs, nms, fuse, pred, smap)
+        raws = [_padded(t, self.no) for t in xs]
+        tasks = []
+        for i, (t, raw) in enumerate(zip(xs, raws)):
+            if smap[2 * i] == smap[2 * i + 1]:
+                tasks.append((2 * i, partial(self._level_towers, i, t, raw)))
+            else:
+                tasks += [(2 * i, partial(self._box_tower, i, t, raw)), (2 * i + 1, partial(self._cls_tower, i, t, raw))]
             x[i] = raw
-        if fork:
-            for side in self._side:
-                cur.wait_stream(side)
+        self._run_towers(tasks, smap, dev)
+        levels = self._levels([self._split(raw) for raw in raws])
         if towers_only or getattr(self, "defer_decode", False):
             # two-stage pipelines (engine/predictor.py::PipelinedRunner) put the decode into the post-processing stage, next to the
             # NMS: the next batch's backbone then starts as soon as the towers are done instead of behind the decode launch
@@ -249,17 +298,10 @@ class Detect(nn.Module):
         return pred if self.export else (pred, x)
 
     def _class_mask(self, classes, dev):
-        if classes is None:
-            return None
-        key = (tuple(classes), dev)
-        if getattr(self, "_mask_key", None) != key:  # tiny host->device upload, once per filter (not inside a captured graph)
-            m = torch.zeros(self.nc, dtype=torch.uint8)
-            m[torch.as_tensor(list(classes), dtype=torch.long)] = 1
-            self._mask, self._mask_key = m.to(dev), key
-        return self._mask
+        return _class_mask(classes, self.nc, dev)
 
     # ---- predict mode: the towers' closing 1x1 convs inside the decode kernel (ey_head_tail_decode_levels_nms)
-    def _head_fuse(self, xs, nms):
+    def _head_fuse(self, xs, nms, branch=""):
         """0 = the towers write their logits and the decode reads them; 1 = the box tail (nn.Conv2d(64, 64, 1)) runs inside the decode
         kernel; 2 = so does the class chain (Conv(c3, 80, 1) + SiLU -> nn.Conv2d(80, nc, 1)).  The tunable head_fuse (csrc/tune.h) picks the
         level; the structure and shape gate below mirrors the kernel's."""
@@ -270,26 +312,23 @@ class Detect(nn.Module):
         if fuse not in (1, 2):
             return 0
         for i in range(len(xs)):
-            b, c = getattr(self, self._branch + "cv2")[i], getattr(self, self._branch + "cv3")[i]
+            b, c = getattr(self, branch + "cv2")[i], getattr(self, branch + "cv3")[i]
             if not (len(b) == 3 and isinstance(b[1], Conv) and isinstance(b[2], nn.Conv2d) and b[2].kernel_size == (1, 1) and b[2].groups == 1
                     and b[2].in_channels == 64 and b[2].out_channels == 64 and b[2].bias is not None):
                 return 0
-            last, ct = c[-2], c[-1]
-            if not (isinstance(last, nn.Sequential) and len(last) == 2 and isinstance(last[0], DWConv) and isinstance(last[1], Conv)
-                    and last[1].conv.kernel_size == (1, 1) and last[1].conv.groups == 1 and isinstance(last[1].act, nn.SiLU)
-                    and last[1].conv.out_channels == 80 and 72 <= last[1].conv.in_channels <= 96 and last[1].conv.in_channels % 8 == 0
-                    and isinstance(ct, nn.Conv2d) and ct.kernel_size == (1, 1) and ct.groups == 1 and ct.in_channels == 80 and ct.out_channels == self.nc
-                    and ct.bias is not None):
+            if not _light_closing(c):
+                return 0
+            mid, ct = c[-2][1].conv, c[-1]
+            if not (mid.out_channels == 80 and 72 <= mid.in_channels <= 96 and mid.in_channels % 8 == 0 and ct.in_channels == 80
+                    and ct.out_channels == self.nc and ct.bias is not None):
                 return 0
         return fuse
 
-    def _forward_fused(self, xs, nms, fuse, pred, fork, cur, smap):
+    def _forward_fused(self, xs, nms, fuse, pred, smap, branch=""):
         """forward(nms=...) with head_fuse = 1 / 2: the towers stop one conv (box) / two convs (class) early, their features go to the decode
         kernel with the packed weights of what was skipped.  Returns (Candidates, [None] * levels): the raw maps are not produced."""
         B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
-        n = len(xs)
-        cv2, cv3 = getattr(self, self._branch + "cv2"), getattr(self, self._branch + "cv3")
-        # (allocated before the fork, like the raw maps of the unfused path and for the same reason)
+        cv2, cv3 = getattr(self, branch + "cv2"), getattr(self, branch + "cv3")
         bfeat = [L.empty_nhwc(B, 64, t.shape[2], t.shape[3], dt, dev) for t in xs]
         cbuf = [L.empty_nhwc(B, cv3[i][-2][1].conv.in_channels if fuse == 2 else self.nc, t.shape[2], t.shape[3], dt, dev) for i, t in enumerate(xs)]
 
@@ -298,38 +337,21 @@ class Detect(nn.Module):
 
         def cls_tower(i, t):
             if fuse == 1:
-                return self._cls_tower(i, t, None, out=cbuf[i])
-            c = cv3[i]
-            for j in range(len(c) - 2):
-                t = c[j](t)
-            c[-2][0](t, out=cbuf[i])
+                self._cls_tower(i, t, None, cbuf[i], branch)
+            else:
+                self._cls_stem(i, t, True, branch, cbuf[i])
 
-        if fork:
-            for side in self._side:
-                side.wait_stream(cur)
-        task = 0
-        for i, t in enumerate(xs):
-            for tower in (box_tower, cls_tower):
-                if fork and smap[task] > 0:
-                    with torch.cuda.stream(self._side[smap[task] - 1]):
-                        tower(i, t)
-                else:
-                    tower(i, t)
-                task += 1
-        if fork:
-            for side in self._side:
-                cur.wait_stream(side)
-        levels, tails, a_off = [], [], 0
-        for i, t in enumerate(xs):
-            bt, ct = cv2[i][2], cv3[i][-1]
-            wp, bias, _, _ = ops.packed_conv1x1(self._tail(bt), bfeat[i], lambda bt=bt: fold_bn(bt.weight, bt.bias, None))
+        self._run_towers([(2 * i + k, partial(tower, i, t)) for i, t in enumerate(xs) for k, tower in enumerate((box_tower, cls_tower))], smap, dev)
+        levels, tails = self._levels(list(zip(bfeat, cbuf)), branch), []
+        for i, lv in enumerate(levels):
+            bt = self._tail("cv2", i, branch)
+            wp, bias, _, _ = ops.packed_conv1x1(bt, lv.box, bt.folded)
             chain = None
             if fuse == 2:
-                chain = ops.pw_chain_packed(self._tail(ct), cbuf[i], cv3[i][-2][1].folded, lambda ct=ct: fold_bn(ct.weight, ct.bias, None))
+                ct = self._tail("cv3", i, branch)
+                chain = ops.pw_chain_packed(ct, lv.cls, cv3[i][-2][1].folded, ct.folded)
                 chain = chain[:4] if chain else (None,) * 4  # (a pair outside the chained kernel: the separate launches below)
-            levels.append((bfeat[i], cbuf[i], self._stride_f[i], self._quality_params(i, dev), a_off))
             tails.append((wp, bias, chain))
-            a_off += t.shape[2] * t.shape[3]
         classes = nms.get("classes")
         mask = self._class_mask(classes, dev)
         keep = pred if nms.get("keep_pred") else None
@@ -338,38 +360,27 @@ class Detect(nn.Module):
             cand = ops.head_tail_decode_levels(levels, tails, keep, (nms["conf"], mask, classes, self.nc))
         if cand is None:  # outside the fused kernel after all (a misaligned view): the skipped convs as launches of their own, then today's decode
             plain = []
-            for i, (bf, cb, st, q, off) in enumerate(levels):
-                raw = L.empty_nhwc(B, (self.no + 7) // 8 * 8, bf.shape[2], bf.shape[3], dt, dev)[:, :self.no]
-                self._tail(cv2[i][2]).run(bf, raw[:, :4 * self.reg_max])
-                out = raw[:, 4 * self.reg_max:]
+            for i, lv in enumerate(levels):
+                box, cls = self._split(_padded(lv.box, self.no))
+                self._tail("cv2", i, branch).run(lv.box, box)
                 if fuse == 1:
-                    out = cb
+                    cls = lv.cls
                 else:
-                    ct, mid = cv3[i][-1], cv3[i][-2][1]
-                    if ops.conv_pw_chain(self._tail(ct), cb, mid.folded, L.ACT_SILU, lambda ct=ct: fold_bn(ct.weight, ct.bias, None), L.ACT_NONE, out) is None:
-                        self._tail(ct).run(mid(cb), out)
-                plain.append((raw[:, :4 * self.reg_max], out, st, q, off))
+                    self._cls_close(i, lv.cls, cls, True, branch)
+                plain.append(lv._replace(box=box, cls=cls))
             cand = ops.head_decode_levels(plain, keep, nms=(nms["conf"], mask, classes))
-        return cand, [None] * n
+        return cand, [None] * len(xs)
 
     # ---- end2end (NMS-free) inference, reference head.py:93-115 (Detect) / :273-298 (GF2Detect)
     one2many_in_inference = False  # the reference also runs the one2many towers in eval mode and returns their maps next to the result,
     #                                where nothing reads them; True reproduces that ("one2many" is None otherwise)
 
-    def _branch_maps(self, xs, branch):
-        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
-        self.__dict__["_branch"] = branch
-        try:
-            raws, levels, a_off = [], [], 0
-            for i, t in enumerate(xs):
-                raw = L.empty_nhwc(B, (self.no + 7) // 8 * 8, t.shape[2], t.shape[3], dt, dev)[:, :self.no]
-                self._towers(i, t, raw)
-                levels.append((raw[:, :4 * self.reg_max], raw[:, 4 * self.reg_max:], self._stride_f[i], self._quality_params(i, dev), a_off))
-                a_off += t.shape[2] * t.shape[3]
-                raws.append(raw)
-        finally:
-            self.__dict__.pop("_branch", None)
-        return raws, levels, a_off
+    def _tower_maps(self, xs, branch):
+        """Both towers of every level of one branch, on the caller's stream -> (raw maps, levels)."""
+        raws = [_padded(t, self.no) for t in xs]
+        for i, t in enumerate(xs):
+            self._towers(i, t, raws[i], branch)
+        return raws, self._levels([self._split(raw) for raw in raws], branch)
 
     def _forward_end2end(self, x, xs):
         """-> (y (B, min(max_det, A), 6) fp32 rows [x1,y1,x2,y2,score,class], {"one2many": maps or None, "one2one": maps}): the one2one
@@ -377,13 +388,12 @@ class Detect(nn.Module):
         as the top-k selection kernel -- no NMS follows (utils/ops.py:224-228 only filters these rows)."""
         if len(xs) > 4:
             raise NotImplementedError("end2end heads: at most 4 pyramid levels")
-        if getattr(self, "_stride_f", None) is None:
-            self._stride_f = [float(s) for s in self.stride]
-        raws, levels, A = self._branch_maps(xs, "one2one_")
+        raws, levels = self._tower_maps(xs, "one2one_")
+        A = sum(t.shape[2] * t.shape[3] for t in xs)
         pred = torch.empty((xs[0].shape[0], 4 + self.nc, A), dtype=torch.float32, device=xs[0].device)
         ops.head_decode_levels(levels, pred, xyxy=True)
         y = ops.e2e_topk(pred, min(self.max_det, A))
-        many = self._branch_maps(xs, "")[0] if self.one2many_in_inference else None
+        many = self._tower_maps(xs, "")[0] if self.one2many_in_inference else None
         return y if self.export else (y, {"one2many": many, "one2one": raws})
 
     def _decode(self, levels, pred):
@@ -403,15 +413,25 @@ class Detect(nn.Module):
         return self._decode(levels, pred)
 
     def bias_init(self):
-        """reference head.py:150-161 (needs self.stride)."""
-        for a, b, s in zip(self.cv2, self.cv3, self.stride):
-            a[-1].bias.data[:] = 1.0
-            b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / float(s)) ** 2)
-        if self.end2end:  # reference :158-161
-            for a, b, s in zip(self.one2one_cv2, self.one2one_cv3, self.stride):
+        """reference head.py:150-161 (needs self.stride); end2end heads also their one2one towers (:158-161)."""
+        for br in ("", "one2one_") if self.end2end else ("",):
+            for a, b, s in zip(getattr(self, br + "cv2"), getattr(self, br + "cv3"), self.stride):
                 a[-1].bias.data[:] = 1.0
                 b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / float(s)) ** 2)
         self._reset_caches()
+
+    # ---- one more tower per level (`cv4` of Segment / OBB / Pose)
+    def _cv4_tower(self, i, t, out):
+        c = self.cv4[i]
+        self._tail("cv4", i).run(c[1](c[0](t)), out)
+
+    def _cv4_maps(self, xs, c, tower=None):
+        """-> one map per level [(B,c,H_l,W_l) NHWC, pixel stride padded to a multiple of 8 channels] that `tower` (default: cv4[i] as it
+        stands) has written, all on the caller's stream."""
+        maps = [_padded(t, c) for t in xs]
+        for i, t in enumerate(xs):
+            (tower or self._cv4_tower)(i, t, maps[i])
+        return maps
 
 
 class Segment(Detect):
@@ -425,27 +445,17 @@ class Segment(Detect):
         self.nm = nm
         self.npr = npr
         self.proto = Proto(ch[0], self.npr, self.nm)
-        c4 = max(ch[0] // 4, self.nm)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+        self.cv4 = _plain_towers(ch, max(ch[0] // 4, self.nm), self.nm)
 
     def mask_maps(self, xs):
         """-> (per-level coefficient maps [(B,nm,H_l,W_l) NHWC], p (B,nm,mh,mw) NHWC), all on the caller's stream."""
-        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
-        cpad = (self.nm + 7) // 8 * 8  # pixel stride kept 16-byte aligned for any nm
-        mcs = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.nm] for t in xs]
         p = self.proto(xs[0])
-        for i, t in enumerate(xs):
-            c = self.cv4[i]
-            self._tail(c[2]).run(c[1](c[0](t)), mcs[i])
-        return mcs, p
+        return self._cv4_maps(xs, self.nm), p
 
     def forward(self, x, nms=None):
         """nms=None: the reference's eval-mode return (head.py:360-369): (cat([y, mc], 1) (B,4+nc+nm,A) fp32, (raw maps, mc (B,nm,A), p)).
         nms=dict(...) (predict pipelines, see Detect.forward): (Candidates, (raw maps, [coefficient map per level], p))."""
-        if self.training:
-            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
-        if self.end2end:
-            raise NotImplementedError("Segment: end2end heads are not built")
+        self._refuse("Segment")
         xs = [L.as_nhwc(t) for t in x]
         mcs, p = self.mask_maps(xs)
         got = Detect.forward(self, list(xs), nms=nms)
@@ -477,14 +487,14 @@ class WorldDetect(Detect):
             raise NotImplementedError("WorldDetect(with_bn=False): ContrastiveHead (per-pixel L2 normalisation, yolov8-world.yaml) is not built; "
                                       "the worldv2 YAML uses with_bn=True")
         from .block import BNContrastiveHead
-        c3 = max(ch[0], min(self.nc, 100))
         self.embed = embed
-        self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, embed, 1)) for x in ch)
+        self.cv3 = _plain_towers(ch, max(ch[0], min(self.nc, 100)), embed)
         self.cv4 = nn.ModuleList(BNContrastiveHead(embed) for _ in ch)
         self.__dict__["_txt"] = None
 
     def set_text(self, txt):
-        """txt: (1, n, embed) text embeddings (the model's original text, not one an ImagePoolingAttn refined); sets nc / no and drops the folds."""
+        """txt: (1, n, embed) text embeddings (the model's original text, not one an ImagePoolingAttn refined); sets nc / no and drops the folds
+        (the class-filter masks are keyed by nc)."""
         if txt.dim() != 3 or txt.shape[0] != 1 or txt.shape[2] != self.embed:
             raise ValueError(f"WorldDetect: text must be (1, n, {self.embed}), got {tuple(txt.shape)}")
         n = int(txt.shape[1])
@@ -494,7 +504,6 @@ class WorldDetect(Detect):
         self.nc = n
         self.no = n + self.reg_max * 4
         self._reset_caches()
-        self.__dict__["_mask_key"] = None
 
     def folded_tail(self, i):
         """fp32 (weight (n, c3, 1, 1), bias (n,)) of level i's class tail folded over the current vocabulary (float64 arithmetic)."""
@@ -520,12 +529,10 @@ class WorldDetect(Detect):
             t = self._tails[("fold", i)] = _Packed()
         return t
 
-    def _cls_tower(self, i, x, raw, out=None):
+    def _cls_tower(self, i, x, raw, out=None, branch=""):
         """class logits of the current vocabulary -> raw[:, 64:] (or `out`): two 3x3 convs, then the folded tail as a 1x1 conv."""
         c = self.cv3[i]
-        if out is None:
-            out = raw[:, 4 * self.reg_max:]
-        ops.conv2d(self._fold(i), [c[1](c[0](x))], lambda: self.folded_tail(i), 1, 1, 0, L.ACT_NONE, out=out)
+        ops.conv2d(self._fold(i), [c[1](c[0](x))], lambda: self.folded_tail(i), 1, 1, 0, L.ACT_NONE, out=self._split(raw)[1] if out is None else out)
 
     def forward(self, x, nms=None, towers_only=False):
         if self.__dict__.get("_txt") is None:
@@ -549,26 +556,16 @@ class OBB(Detect):
     def __init__(self, nc=80, ne=1, ch=()):
         super().__init__(nc, ch)
         self.ne = ne
-        c4 = max(ch[0] // 4, self.ne)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.ne, 1)) for x in ch)
+        self.cv4 = _plain_towers(ch, max(ch[0] // 4, self.ne), self.ne)
 
     def angle_maps(self, xs):
         """-> per-level angle logit maps [(B,ne,H_l,W_l) NHWC, pixel stride padded to 8 channels], on the caller's stream."""
-        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
-        cpad = (self.ne + 7) // 8 * 8  # pixel stride kept 16-byte aligned
-        maps = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.ne] for t in xs]
-        for i, t in enumerate(xs):
-            c = self.cv4[i]
-            self._tail(c[2]).run(c[1](c[0](t)), maps[i])
-        return maps
+        return self._cv4_maps(xs, self.ne)
 
     def forward(self, x, nms=None):
         """The reference's eval-mode return (head.py:383-395): (cat([y, angle], 1) (B,4+nc+1,A) fp32, (raw maps, angle (B,1,A))) with
         angle = (sigmoid(logit) - 0.25) * pi; rows 0-3 of y are the rotated box (cx, cy, w, h) in input pixels."""
-        if self.training:
-            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
-        if self.end2end:
-            raise NotImplementedError("OBB: end2end heads are not built")
+        self._refuse("OBB")
         if self.ne != 1:
             raise NotImplementedError(f"OBB: ne={self.ne} (the decode kernel is built for one angle channel)")
         if nms is not None:
@@ -578,7 +575,7 @@ class OBB(Detect):
         levels, raw = Detect.forward(self, list(xs), towers_only=True)
         B, A = xs[0].shape[0], sum(t.shape[2] * t.shape[3] for t in xs)
         pred = torch.empty((B, 4 + self.nc + 1, A), dtype=torch.float32, device=xs[0].device)
-        ops.obb_decode_levels([(box, cls, angs[i], st, off) for i, (box, cls, st, _, off) in enumerate(levels)], pred)
+        ops.obb_decode_levels([(lv.box, lv.cls, ang, lv.stride, lv.a_off) for lv, ang in zip(levels, angs)], pred)
         return pred if self.export else (pred, (raw, pred[:, 4 + self.nc:]))
 
 
@@ -592,48 +589,38 @@ class Pose(Detect):
         super().__init__(nc, ch)
         self.kpt_shape = kpt_shape  # number of keypoints, number of dims (2 for x,y or 3 for x,y,visible)
         self.nk = kpt_shape[0] * kpt_shape[1]
-        c4 = max(ch[0] // 4, self.nk)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+        self.cv4 = _plain_towers(ch, max(ch[0] // 4, self.nk), self.nk)
 
     def kpt_maps(self, xs):
         """-> per-level keypoint logit maps [(B,nk,H_l,W_l) NHWC, pixel stride padded to a multiple of 8 channels], on the caller's stream."""
-        B, dev, dt = xs[0].shape[0], xs[0].device, xs[0].dtype
-        cpad = (self.nk + 7) // 8 * 8  # pixel stride kept 16-byte aligned for any nk
-        maps = [L.empty_nhwc(B, cpad, t.shape[2], t.shape[3], dt, dev)[:, :self.nk] for t in xs]
-        for i, t in enumerate(xs):
-            self._kpt_tower(self.cv4[i], t, maps[i])
-        return maps
+        return self._cv4_maps(xs, self.nk, self._kpt_tower)
 
-    def _kpt_tower(self, c, t, out):
+    def _kpt_tower(self, i, t, out):
         """Conv(x, c4, 3) -> Conv(c4, c4, 3) -> nn.Conv2d(c4, nk, 1) with c4 = max(x // 4, nk).  The MFMA conv reads sources whose channel
         count is a multiple of 8; c4 = 51 is not, and the second and third conv would take the generic direct kernel (measured 8.8 ms
         instead of 0.06 ms for the 80x80 level at batch 32).  So the tower runs on c4 rounded up to a multiple of 8: the weights are
         packed with zero rows / zero input columns for the extra channels, which therefore hold SiLU(0) = 0 and add 0 to every sum."""
+        c = self.cv4[i]
         c4 = c[0].conv.out_channels
         pad = -c4 % 8
         plain = all(isinstance(m, Conv) and m.conv.kernel_size == (3, 3) and m.conv.stride == (1, 1) and m.conv.padding == (1, 1) and m.conv.groups == 1
                     and m.conv.dilation == (1, 1) for m in (c[0], c[1]))
         if not pad or not plain or c[2].kernel_size != (1, 1) or c[2].groups != 1:
-            return self._tail(c[2]).run(c[1](c[0](t)), out)
+            return self._cv4_tower(i, t, out)
         F = nn.functional
 
         def padded(fn, po, pi):  # (w (O,I,k,k), b (O,)) -> po zero output channels, pi zero input channels appended
             w, b = fn()
             return F.pad(w, (0, 0, 0, 0, 0, pi, 0, po)), F.pad(b, (0, po))
 
+        tail = self._tail("cv4", i)
         h = ops.conv2d(c[0], [t], lambda: padded(c[0].folded, pad, 0), 3, 1, 1, _act_code(c[0].act), tag="kpad")
         h = ops.conv2d(c[1], [h], lambda: padded(c[1].folded, pad, pad), 3, 1, 1, _act_code(c[1].act), tag="kpad")
-        return ops.conv2d(self._tail(c[2]), [h], lambda: padded(lambda: fold_bn(c[2].weight, c[2].bias, None), 0, pad), 1, 1, 0, L.ACT_NONE, out=out, tag="kpad")
+        return ops.conv2d(tail, [h], lambda: padded(tail.folded, 0, pad), 1, 1, 0, L.ACT_NONE, out=out, tag="kpad")
 
     def kpt_levels(self, maps):
         """the keypoint maps as the level list of _ops.kpts_decode_levels / kpts_decode_rows: [(map, stride, first anchor)]."""
-        if getattr(self, "_stride_f", None) is None:
-            self._stride_f = [float(s) for s in self.stride]
-        levels, a_off = [], 0
-        for i, m in enumerate(maps):
-            levels.append((m, self._stride_f[i], a_off))
-            a_off += m.shape[2] * m.shape[3]
-        return levels
+        return [(m, st, off) for m, (st, off) in zip(maps, self._walk(maps))]
 
     decode_kpts = True  # instance attribute (or forward keyword): False leaves the (B,nk,A) decode out of the nms=None return, see forward
 
@@ -643,10 +630,7 @@ class Pose(Detect):
         attribute of that name): (y (B,4+nc,A), (raw maps, [keypoint map per level])) -- the (B,nk,A) decode is left out,
         ey_kpts_decode_rows serves the kept rows.
         nms=dict(...) (predict pipelines, see Detect.forward): (Candidates, (raw maps, [keypoint map per level]))."""
-        if self.training:
-            raise RuntimeError("edge-yolo_amd implements the inference forward only: call model.eval()")
-        if self.end2end:
-            raise NotImplementedError("Pose: end2end heads are not built")
+        self._refuse("Pose")
         if self.kpt_shape[1] not in (2, 3) or self.nk > 256 or len(x) > 4:
             raise NotImplementedError(f"Pose: kpt_shape={tuple(self.kpt_shape)} on {len(x)} levels (the keypoint kernels are built for ndim 2 or 3, nk <= 256, <= 4 levels)")
         if getattr(self, "defer_decode", False):
@@ -681,24 +665,21 @@ class GF2Detect(Detect):
         self.add_mean = True
         self.reg_channels = 64
         self.apply_quality_in_inference = True
-        in_stat = 4 * (self.reg_topk + (1 if self.add_mean else 0))
-        self.reg_conf = nn.ModuleList(
-            nn.Sequential(nn.Conv2d(in_stat, self.reg_channels, 1, bias=True), nn.ReLU(inplace=True), nn.Conv2d(self.reg_channels, 1, 1, bias=True),
-                          nn.Sigmoid()) for _ in ch)
+        self.reg_conf = _reg_conf(ch, self.reg_topk, self.add_mean, self.reg_channels)
         if self.end2end:  # head.py:220-221
             self.one2one_reg_conf = copy.deepcopy(self.reg_conf)
         self._qcache = {}
 
-    def _quality_params(self, i, device):
+    def _quality_params(self, i, device, branch=""):
         if not self.apply_quality_in_inference:
             return None
         if self.reg_topk != 4 or not self.add_mean:
             raise NotImplementedError("the decode kernel is built for reg_topk=4, add_mean=True (the reference defaults)")
-        q = self._qcache.get((self._branch, i, device))
+        q = self._qcache.get((branch, i, device))
         if q is None:
-            m = getattr(self, self._branch + "reg_conf")[i]
+            m = getattr(self, branch + "reg_conf")[i]
             f = lambda t: t.detach().float().to(device).contiguous()  # noqa: E731
-            q = self._qcache[(self._branch, i, device)] = (f(m[0].weight).view(m[0].out_channels, -1), f(m[0].bias), f(m[2].weight).view(-1), f(m[2].bias))
+            q = self._qcache[(branch, i, device)] = (f(m[0].weight).view(m[0].out_channels, -1), f(m[0].bias), f(m[2].weight).view(-1), f(m[2].bias))
         return q
 
 
@@ -711,10 +692,7 @@ class E2EDetect(GF2Detect):
 
     def __init__(self, nc=80, ch=()):
         super().__init__(nc, ch)
-        c3 = max(ch[0], min(self.nc, 100))
-        self.cv3 = nn.ModuleList(
-            nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), nn.Conv2d(c3, self.nc, 1))
-            for x in ch)
+        self.cv3 = _light_towers(ch, max(ch[0], min(self.nc, 100)), self.nc)
         self.one2one_cv3 = copy.deepcopy(self.cv3)
 
 
@@ -728,10 +706,7 @@ class v10Detect(Detect):
 
     def __init__(self, nc=80, ch=()):
         super().__init__(nc, ch)
-        c3 = max(ch[0], min(self.nc, 100))
-        self.cv3 = nn.ModuleList(
-            nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), nn.Conv2d(c3, self.nc, 1))
-            for x in ch)
+        self.cv3 = _light_towers(ch, max(ch[0], min(self.nc, 100)), self.nc)
         self.one2one_cv3 = copy.deepcopy(self.cv3)
 
 
@@ -748,10 +723,7 @@ class GFLHeadv2_uniH(GF2Detect):
         self.reg_topk = reg_topk
         self.add_mean = add_mean
         self.reg_channels = reg_channels
-        in_stat = 4 * (self.reg_topk + (1 if self.add_mean else 0))
-        self.reg_conf = nn.ModuleList(
-            nn.Sequential(nn.Conv2d(in_stat, self.reg_channels, 1, bias=True), nn.ReLU(inplace=True), nn.Conv2d(self.reg_channels, 1, 1, bias=True),
-                          nn.Sigmoid()) for _ in ch)
+        self.reg_conf = _reg_conf(ch, self.reg_topk, self.add_mean, self.reg_channels)
 
 
 class Classify(_Packed):

@@ -121,7 +121,8 @@ _CLASS_MASKS = {}
 
 def _class_mask(classes, nc, device):
     """uint8 [nc] class-filter mask on `device`, uploaded once per (classes, nc, device): the first, eager, call of a predictor builds it, so
-    nothing is copied from the host inside a captured graph (as `_CLASS_TENSORS` above and Detect._class_mask)."""
+    nothing is copied from the host inside a captured graph (as `_CLASS_TENSORS` above).  The heads' fused decode takes its mask from here
+    too (Detect._class_mask); a WorldDetect vocabulary change moves `nc` and with it the key."""
     if classes is None:
         return None
     key = (tuple(classes), int(nc), device)

@@ -493,3 +493,45 @@ def test_predict_option_changes_rebuild_cleanly(E):
         for i in range(2):
             assert torch.equal(a[i].boxes.data.cpu(), ref[i]) and torch.equal(b[i].boxes.data.cpu(), ref[i]) and torch.equal(c[i].boxes.data.cpu(), ref[i])
             assert len(d[i]) <= len(ref[i])
+
+
+def test_tower_streams_fork_join_bit_identical_eager_and_graph():
+    """Detect's tower scheduler on two levels (8x8 and 4x4, batch 2, f16): one stream, the default fork (level 1 on a side stream) and
+    tower_streams=(0, 1, 2, 0) (two side streams, both levels split across streams) give the same bits, eagerly and as a captured graph
+    replayed twice (the second replay on another input).  The stream options never change results; a missing wait would."""
+    from edge_yolo_amd.engine.predictor import GraphRunner
+    from edge_yolo_amd.nn.modules.head import Detect
+    class Light(Detect):
+        legacy = False  # (parse_model assigns `legacy` on the class: pinned, whatever model an earlier test built)
+
+    torch.manual_seed(0)
+    h = Light(nc=8, ch=(16, 32))
+    h.stride = torch.tensor([8.0, 16.0])
+    h = h.to("cuda").half().eval()
+    n0, n1 = 2 * 16 * 8 * 8, 2 * 32 * 4 * 4
+    flats = [torch.randn(n0 + n1, device="cuda").half() for _ in range(2)]
+
+    def fn(v):
+        pred, raws = h([v[:n0].view(2, 16, 8, 8), v[n0:].view(2, 32, 4, 4)])
+        return (pred, *raws)
+
+    def snap(out):
+        torch.cuda.synchronize()
+        return [t.clone() for t in out]
+
+    want = None
+    for streams, towers, sides in ((False, None, None), (True, None, 1), (True, (0, 1, 2, 0), 2)):
+        h.head_streams, h.tower_streams = streams, towers
+        eager = [snap(fn(v)) for v in flats]
+        if want is None:
+            want = eager
+            assert [tuple(t.shape) for t in want[0]] == [(2, 12, 80), (2, 72, 8, 8), (2, 72, 4, 4)]
+            assert all(bool(torch.isfinite(t).all()) for w in want for t in w) and not torch.equal(want[0][0], want[1][0])
+        else:
+            assert len(h._side) == sides
+        run = GraphRunner(fn)
+        replayed = [snap(run(v)) for v in flats]  # capture + first replay, then a second replay of the same graph
+        assert len(run.graphs) == 1
+        for got in (eager, replayed):
+            for a, b in zip(got, want):
+                assert len(a) == len(b) and all(torch.equal(s, t) for s, t in zip(a, b)), (streams, towers)
