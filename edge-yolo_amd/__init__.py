@@ -9,4 +9,5 @@ The directory is called `edge-yolo_amd`; import it as `edge_yolo_amd` (see `edge
 """
 __version__ = "0.1.0"
 
-from .engine.model import YOLO, YOLOWorld  # noqa: E402,F401
+from .engine.model import YOLO, FastSAM, YOLOWorld  # noqa: E402,F401
+from .utils.ops import adjust_bboxes_to_image_border  # noqa: E402,F401

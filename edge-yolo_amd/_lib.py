@@ -16,6 +16,7 @@ ATTN_AREA_F32, ATTN_AREA_F16, ATTN_AREA_MFMA = 401, 402, 403  # ey_attention_las
 ATTN_FLASH_MFMA, ATTN_FLASH_F32, ATTN_FLASH_F16 = 500, 501, 502  # ... of ey_flash_attention (MFMA: + head_dim)
 DWG_PLAIN, DWG_GATE, DWG_RESIDUAL = 0, 1, 2  # ey_dwconv_gate epilogues
 MASK_GT_STACK, MASK_GT_INDEX = 0, 1  # ey_mask_iou ground-truth forms
+MASK_U8 = 2  # EY_MASK_U8: ey_scale_masks' uint8 input
 MSA_MAX_TEXTS = 4096  # EY_MSA_MAX_TEXTS: the most texts ey_max_sigmoid_attn takes
 
 
@@ -140,6 +141,9 @@ SIGNATURES = {
     "ey_deconv2x2": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ey_mask_iou_workspace_bytes": (_sz, [_i, _i, C.c_long, C.c_long]),
     "ey_mask_iou": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_mask_prompt_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ey_mask_prompt": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_scale_masks": (_i, [_i, C.c_long, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ey_head_decode_last_variant": (_i, []),
     "ey_head_decode": (_i, [_i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ey_head_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

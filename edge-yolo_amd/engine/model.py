@@ -4,8 +4,8 @@ from pathlib import Path
 
 import torch
 
-from .predictor import ClassificationPredictor, DetectionPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
-from .validator import ClassificationValidator, DetectionValidator, PoseValidator, SegmentationValidator
+from .predictor import ClassificationPredictor, DetectionPredictor, FastSAMPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
+from .validator import ClassificationValidator, DetectionValidator, FastSAMValidator, PoseValidator, SegmentationValidator
 from ..nn.tasks import ClassificationModel, DetectionModel, OBBModel, PoseModel, SegmentationModel, WorldModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
@@ -143,8 +143,8 @@ class Model(torch.nn.Module):
                                "(BASELINE configs[0], the CPU plumbing case, is the reference's own CPU predictor.)")
         return device
 
-    def predict(self, source=None, stream=False, predictor=None, **kwargs):
-        """kwargs (reference cfg/default.yaml:51-65 names): imgsz, half, conf, iou, max_det, agnostic_nms, classes, device, augment.
+    def predict(self, source=None, stream=False, predictor=None, prompts=None, **kwargs):
+        """prompts (reference engine/model.py:554-555): handed to the predictor's `set_prompts` where it has one (FastSAM).  kwargs (reference cfg/default.yaml:51-65 names): imgsz, half, conf, iou, max_det, agnostic_nms, classes, device, augment.
         predictor (reference engine/model.py:505,552: `(predictor or self._smart_load("predictor"))(overrides=...)`): a predictor CLASS to use
         instead of the task's default; it is constructed with DetectionPredictor's signature (see there) and called with the source."""
         if source is None:
@@ -177,6 +177,8 @@ class Model(torch.nn.Module):
         # letterbox target for ndarray sources (reference cfg default 640); classify: the crop size of ClassifyTransform, default 224 (the
         # reference's 640 only holds until a checkpoint's train args override it: every released -cls checkpoint says 224)
         self.predictor.imgsz = kwargs.get("imgsz", 224 if self.task == "classify" else 640)
+        if prompts and hasattr(self.predictor, "set_prompts"):
+            self.predictor.set_prompts(prompts)
         results = self.predictor(source)
         return iter(results) if stream else results
 
@@ -389,3 +391,45 @@ class YOLOWorld(Model):
     def predict_batches(self, batches, stages=4, **kwargs):
         raise NotImplementedError("predict_batches: the pipelined stages are built and verified for fixed-vocabulary detect models only; a YOLOWorld model, "
                                   "whose neck and head depend on the vocabulary set at run time, runs through predict()")
+
+
+_FASTSAM_TASK_MAP = {"segment": {"model": SegmentationModel, "predictor": FastSAMPredictor, "validator": FastSAMValidator}}
+_FASTSAM_YAMLS = {"FastSAM-s": "yolov8s-seg.yaml", "FastSAM-x": "yolov8x-seg.yaml"}
+
+
+class FastSAM(Model):
+    """FastSAM (reference models/fastsam/model.py:11-55): a single-class yolov8{s,x}-seg whose predictor returns only the instances that box
+    and point prompts select.  `model`: a tensor-only checkpoint (see YOLO.save), or -- unlike the reference, which ships weights and refuses
+    YAMLs (:28) while this build downloads nothing -- a YAML: "FastSAM-s.yaml" / "FastSAM-x.yaml" are yolov8s-seg.yaml / yolov8x-seg.yaml
+    with nc = 1, and any other segment YAML is built with nc = 1 too.  The class is named "object"."""
+
+    def __init__(self, model="FastSAM-x.yaml", verbose=False):
+        name = str(model).strip() if not isinstance(model, dict) else None
+        if name == "FastSAM.pt":
+            name = "FastSAM-x.pt"
+        if name is not None and Path(name).suffix in {".yaml", ".yml"}:
+            cfg = dict(yaml_model_load(_FASTSAM_YAMLS.get(Path(name).stem, name)))
+            cfg["yaml_file"] = name
+            model = cfg
+        elif name is not None:
+            model = name
+        super().__init__(model=model, task="segment", verbose=verbose, nc=1 if isinstance(model, dict) else None)
+        if len(self.model.names) == 1:
+            self.model.names = {0: "object"}
+
+    @property
+    def task_map(self):
+        return _FASTSAM_TASK_MAP
+
+    def predict(self, source=None, stream=False, bboxes=None, points=None, labels=None, texts=None, **kwargs):
+        """predict() of the segment task plus prompts in ORIGINAL-image pixels, shared by all images of the call (reference :34-50): bboxes
+        (P,4) x1,y1,x2,y2 -- each keeps the mask of the highest IoU with it --, points (Q,2) x,y with labels (Q,) (1 = keep the masks
+        under the point, 0 = drop them; default 1).  Without prompts every instance is returned.  texts raises NotImplementedError: the
+        CLIP encoder is not part of the build (as YOLOWorld.set_classes takes embeddings)."""
+        FastSAMPredictor.check_prompts(bboxes, points, labels, texts)
+        return super().predict(source, stream=stream, prompts=dict(bboxes=bboxes, points=points, labels=labels, texts=texts), **kwargs)
+
+    __call__ = predict
+
+    def predict_batches(self, batches, stages=4, **kwargs):
+        raise NotImplementedError("predict_batches: pipelined throughput is built for the detect task only, not 'segment' (use predict())")

@@ -299,6 +299,10 @@ class DetectionPredictor:
         """device-step outputs -> list of Results (subclasses with more outputs than boxes override this)."""
         return self.postprocess(out[0], out[1], im, source)
 
+    def _boxes_in_image(self, boxes, count, shape):
+        """Hook for subclasses: the clipped (B, max_det, 6+) rows of a batch whose originals all have the network input's `shape`, before they are
+        cut into Results (FastSAMPredictor sticks them to the border here).  Nothing for the other tasks."""
+
     def postprocess(self, boxes, count, img, source):
         """reference detect/predict.py:23-41: per image rows -> scale_boxes to the original shape -> Results."""
         n = count.tolist()
@@ -310,6 +314,7 @@ class DetectionPredictor:
         same = self._orig is None or all(tuple(o.shape[:2]) == tuple(img.shape[2:]) for o in self._orig)
         if same:
             ops.clip_boxes(boxes, img.shape[2:])
+            self._boxes_in_image(boxes, count, tuple(img.shape[2:]))
         for i in range(len(n)):
             det = boxes[i, : n[i]]
             orig = self._orig[i] if self._orig is not None else None
@@ -360,6 +365,7 @@ class SegmentationPredictor(DetectionPredictor):
             keep = torch.arange(max_det, device=index.device)[None, :] < count[:, None]
             rows = torch.stack([torch.arange(B, dtype=torch.int32, device=index.device)[:, None].expand(B, max_det)[keep], index[keep]], 1).contiguous()
             masks = _ops.process_mask(proto, coefs, rows, boxes[keep][:, :4].contiguous(), s)  # boxes in network-input pixels, before scale_boxes
+        self._masks, self._mask_counts = masks, n  # the batch's masks as ONE uint8 tensor, image after image (FastSAMPredictor scores them in one launch)
         results = super().postprocess(boxes, count, img, source)
         off = 0
         for i, r in enumerate(results):
@@ -368,6 +374,104 @@ class SegmentationPredictor(DetectionPredictor):
                 r.masks = Masks(masks[off:off + n[i]], r.orig_shape)
             off += n[i]
         return results
+
+
+class FastSAMPredictor(SegmentationPredictor):
+    """reference models/fastsam/predict.py:13-159.  SegmentationPredictor's device step and mask assembly; `postprocess` then sticks boxes
+    near the image border to it, replaces boxes that cover more than 0.9 of the image by the full image, and selects the instances the
+    prompts ask for: boxes and points in ORIGINAL-image pixels, shared by all images of the batch.  The reference resizes every mask to
+    the original image (scale_masks) and sums slices of that tensor per prompt; here ONE ey_mask_prompt call scores the network-resolution
+    masks of the whole batch (the resize is folded into per-axis weights) and nothing of the original resolution is allocated.  Text
+    prompts need the CLIP encoder, which is not part of the build."""
+
+    def __init__(self, model, device, *args, **kwargs):
+        super().__init__(model, device, *args, **kwargs)
+        self.prompts = {}
+
+    def set_prompts(self, prompts):
+        """Prompts of the NEXT call (reference :157-159): a dict with any of bboxes, points, labels, texts; postprocess consumes them."""
+        self.prompts = dict(prompts or {})
+
+    @staticmethod
+    def check_prompts(bboxes=None, points=None, labels=None, texts=None, shapes=()):
+        """Host-side form of the prompts -> (boxes int32 (P,4) or None, points int32 (Q,2) or None, labels int32 (Q,) or None), converted as
+        the reference does (torch.as_tensor(..., dtype=int32): fractions are cut off; a single box / point gains a leading axis; labels
+        default to 1).  Raises what ey_mask_prompt refuses, before anything runs: the reference slices with Python's rules for boxes with
+        x2 <= x1, y2 <= y1 or negative coordinates (predict.py:80) and raises an IndexError for points outside the image (:101)."""
+        if texts is not None:
+            raise NotImplementedError("FastSAM: text prompts need the CLIP text and image encoders, which are not part of this build; use bboxes= / points=")
+        if bboxes is None and points is None:
+            if labels is not None:
+                raise ValueError("FastSAM: labels= without points=")
+            return None, None, None
+        b = q = lab = None
+        if bboxes is not None:
+            b = np.asarray(bboxes).astype(np.int32)
+            b = b[None] if b.ndim == 1 else b
+            if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] == 0:
+                raise ValueError(f"FastSAM: bboxes must be (P,4) rows x1,y1,x2,y2 with P >= 1, got shape {tuple(b.shape)}")
+            bad = (b[:, :2] < 0).any(1) | (b[:, 2] <= b[:, 0]) | (b[:, 3] <= b[:, 1])
+            if bad.any():
+                raise ValueError(f"FastSAM: box prompt {b[bad][0].tolist()} needs 0 <= x1 < x2 and 0 <= y1 < y2 (original-image pixels)")
+        if points is not None:
+            q = np.asarray(points).astype(np.int32)
+            q = q[None] if q.ndim == 1 else q
+            if q.ndim != 2 or q.shape[1] != 2 or q.shape[0] == 0:
+                raise ValueError(f"FastSAM: points must be (Q,2) rows x,y with Q >= 1, got shape {tuple(q.shape)}")
+            lab = np.ones(len(q), np.int32) if labels is None else np.asarray(labels).astype(np.int32).reshape(-1)
+            if len(lab) != len(q):
+                raise ValueError(f"FastSAM: expected as many labels as points, got {len(lab)} and {len(q)}")
+            for h, w in shapes:
+                out = (q[:, 0] < 0) | (q[:, 1] < 0) | (q[:, 0] >= w) | (q[:, 1] >= h)
+                if out.any():
+                    raise ValueError(f"FastSAM: point prompt {q[out][0].tolist()} lies outside the {h}x{w} image")
+        elif labels is not None:
+            raise ValueError("FastSAM: labels= without points=")
+        return b, q, lab
+
+    @staticmethod
+    def stick_to_border(xyxy, shape, threshold=20, valid=None):
+        """reference :36-44, in place on xyxy (n,4) -- or (B,n,4) with valid (B,n), the rows that exist --: adjust_bboxes_to_image_border, then
+        every box whose IoU with the full image exceeds 0.9 becomes the full image.  box_iou(full, boxes) is utils/metrics.py:54-77 in fp32;
+        the intersection with the full image is the clamped box.  The reference flattens the (row, column) pairs that torch.nonzero returns
+        for the (1, n) IoU matrix (:42), so its index list holds a 0 for every match: box 0 becomes the full image too whenever any box
+        qualifies.  Kept, so that rows equal the reference's.  No host sync."""
+        h, w = shape
+        ops.adjust_bboxes_to_image_border(xyxy, shape, threshold)
+        inter = (xyxy[..., 2].clamp(max=w) - xyxy[..., 0].clamp(min=0)).clamp_(0) * (xyxy[..., 3].clamp(max=h) - xyxy[..., 1].clamp(min=0)).clamp_(0)
+        iou = inter / (float(w) * float(h) + (xyxy[..., 2] - xyxy[..., 0]) * (xyxy[..., 3] - xyxy[..., 1]) - inter + 1e-7)
+        sel = iou > 0.9
+        if valid is not None:
+            sel &= valid
+        sel[..., 0] |= sel.any(-1)
+        xyxy.copy_(torch.where(sel[..., None], torch.tensor([0, 0, w, h], dtype=xyxy.dtype, device=xyxy.device), xyxy))
+        return xyxy
+
+    def _boxes_in_image(self, boxes, count, shape):
+        """original == network input for the whole batch: the border step over all images at once (a handful of launches, not per image)."""
+        valid = torch.arange(boxes.shape[1], device=boxes.device)[None, :] < count[:, None]
+        self.stick_to_border(boxes[..., :4], shape, valid=valid)
+        self._stuck = True
+
+    def postprocess(self, boxes, count, img, source, index=None, proto=None, coefs=None):
+        from ..nn import _ops
+        prompts, self.prompts = self.prompts, {}
+        self.check_prompts(texts=prompts.get("texts"))  # (before the device work below)
+        self._stuck = False
+        results = super().postprocess(boxes, count, img, source, index=index, proto=proto, coefs=coefs)
+        if not self._stuck:  # originals of other shapes: image by image, after scale_boxes
+            for r in results:
+                if len(r):
+                    self.stick_to_border(r.boxes.xyxy, r.orig_shape)  # in place: xyxy is a view of the result's rows
+        n = self._mask_counts
+        b, q, lab = self.check_prompts(prompts.get("bboxes"), prompts.get("points"), prompts.get("labels"), None, [r.orig_shape for r in results])
+        if (b is None and q is None) or not sum(n):
+            return results
+        off = [0]
+        for k in n:
+            off.append(off[-1] + k)
+        keep = _ops.mask_prompt(self._masks, off, [r.orig_shape for r in results], b, q, lab)["keep"].view(torch.bool)
+        return [r[keep[off[i]:off[i + 1]]] if n[i] else r for i, r in enumerate(results)]
 
 
 class OBBPredictor(DetectionPredictor):

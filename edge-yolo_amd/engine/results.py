@@ -44,6 +44,10 @@ class Boxes:
     def numpy(self):
         return Boxes(self.data.cpu().numpy(), self.orig_shape)
 
+    def __getitem__(self, idx):
+        """rows `idx` (int, slice, index or bool tensor) as a new container (reference BaseTensor.__getitem__, engine/results.py:167-184)."""
+        return self.__class__(self.data[idx], self.orig_shape)
+
     def __len__(self):
         return len(self.data)
 
@@ -77,6 +81,10 @@ class Masks:
 
     def numpy(self):
         return Masks(self.data.cpu().numpy(), self.orig_shape)
+
+    def __getitem__(self, idx):
+        """rows `idx` (int, slice, index or bool tensor) as a new container (reference BaseTensor.__getitem__, engine/results.py:167-184)."""
+        return self.__class__(self.data[idx], self.orig_shape)
 
     def __len__(self):
         return len(self.data)
@@ -133,6 +141,10 @@ class OBB:
     def numpy(self):
         return self if isinstance(self.data, np.ndarray) else OBB(self.data.cpu().numpy(), self.orig_shape)
 
+    def __getitem__(self, idx):
+        """rows `idx` (int, slice, index or bool tensor) as a new container (reference BaseTensor.__getitem__, engine/results.py:167-184)."""
+        return self.__class__(self.data[idx], self.orig_shape)
+
     def __len__(self):
         return len(self.data)
 
@@ -175,6 +187,10 @@ class Keypoints:
 
     def numpy(self):
         return self if isinstance(self.data, np.ndarray) else Keypoints(self.data.cpu().numpy(), self.orig_shape)
+
+    def __getitem__(self, idx):
+        """rows `idx` (int, slice, index or bool tensor) as a new container (reference BaseTensor.__getitem__, engine/results.py:167-184)."""
+        return self.__class__(self.data[idx], self.orig_shape)
 
     def __len__(self):
         return len(self.data)
@@ -223,6 +239,10 @@ class Probs:
     def numpy(self):
         return self if isinstance(self.data, np.ndarray) else self._like(lambda t: t.cpu().numpy())
 
+    def __getitem__(self, idx):
+        """entries `idx` of the probability vector as a new Probs (reference BaseTensor.__getitem__; the head's own top-5 does not carry over)."""
+        return Probs(self.data[idx], self.orig_shape)
+
     def __len__(self):
         return len(self.data)
 
@@ -239,6 +259,17 @@ class Results:
         self.names = names
         self.path = path
         self.speed = speed or {"preprocess": None, "inference": None, "postprocess": None}
+
+    def __getitem__(self, idx):
+        """The detections `idx` -- an int, a slice, an index tensor or a bool tensor, on the data's device -- of every attribute present
+        (boxes, masks, probs, keypoints, obb) as a new Results (reference engine/results.py:273-288 via _apply)."""
+        r = Results(self.orig_img, path=self.path, names=self.names, speed=self.speed)
+        r.orig_shape = self.orig_shape
+        for k in ("boxes", "masks", "probs", "keypoints", "obb"):
+            v = getattr(self, k)
+            if v is not None:
+                setattr(r, k, v[idx])
+        return r
 
     def __len__(self):
         if self.boxes is not None:

@@ -622,3 +622,8 @@ class ClassificationValidator:
                 top = self.postprocess(None)
             self.update_metrics(top, batch)
         return self.get_stats()
+
+
+class FastSAMValidator(SegmentationValidator):
+    """SegmentationValidator under its FastSAM name (reference models/fastsam/val.py:7-40: the same validator with the task fixed to
+    "segment" and the plots, which are not built here at all, switched off)."""

@@ -1180,6 +1180,99 @@ def mask_iou(pred, pred_off, gt, gt_off, index=False, out_off=None, iou=None, in
     return iou, out_off, inter
 
 
+def mask_geometry(mask_hw, shape, padding=True):
+    """The crop and target of scale_masks (reference utils/ops.py:726-733, the same Python float arithmetic) as the record ey_mask_prompt
+    and ey_scale_masks take: (top, bottom, left, right, H0, W0).  padding=False: the crop starts at the top-left corner and the whole
+    padding comes off the bottom and the right (the reference halves `pad` only with padding=True and subtracts it either way)."""
+    mh, mw = int(mask_hw[0]), int(mask_hw[1])
+    h0, w0 = int(shape[0]), int(shape[1])
+    gain = min(mh / h0, mw / w0)
+    pad = [mw - w0 * gain, mh - h0 * gain]
+    if padding:
+        pad[0] /= 2
+        pad[1] /= 2
+    top, left = (int(pad[1]), int(pad[0])) if padding else (0, 0)
+    return (top, int(mh - pad[1]), left, int(mw - pad[0]), h0, w0)
+
+
+def mask_prompt(masks, mask_off, shapes, bboxes=None, points=None, labels=None, out=None, workspace=None):
+    """FastSAM prompt selection of a batch (ey_mask_prompt): masks uint8 (N,mh,mw) 0/1 grouped by image through the host list mask_off
+    (B+1 entries); shapes: the B original (H0, W0); bboxes: P host rows x1,y1,x2,y2 and points: Q host rows x,y with `labels`, int, in
+    original-image pixels, shared by all images.  -> dict(full (N,), inter / iou (P,N), best int32 (B,P), hit uint8 (Q,N), keep uint8 (N,)).
+    out=: a dict of buffers to write instead (full, keep, and inter / iou / best / hit as the prompts need them; inter, iou and hit may be
+    wider than N: their row stride is taken from `inter`, else `hit`)."""
+    L.require_device(masks, "mask_prompt")
+    _no_block("mask_prompt")
+    mask_off = [int(v) for v in mask_off]
+    B = len(mask_off) - 1
+    if B < 0 or mask_off[0] != 0 or len(shapes) != B:
+        raise ValueError("mask_prompt: mask_off must have B+1 entries starting at 0 and shapes B entries")
+    N = mask_off[-1]
+    if masks.dim() != 3 or masks.dtype != torch.uint8 or not masks.is_contiguous() or masks.shape[0] < N:
+        raise ValueError(f"mask_prompt: masks must be a contiguous uint8 (N,mh,mw) tensor with N >= {N}, got {masks.dtype} {tuple(masks.shape)}")
+    mh, mw = int(masks.shape[1]), int(masks.shape[2])
+    boxes = [[int(v) for v in r] for r in ([] if bboxes is None else bboxes)]
+    pts = [[int(v) for v in r] for r in ([] if points is None else points)]
+    labs = [1] * len(pts) if labels is None else [int(v) for v in labels]
+    if any(len(r) != 4 for r in boxes) or any(len(r) != 2 for r in pts) or len(labs) != len(pts):
+        raise ValueError(f"mask_prompt: boxes must be (P,4), points (Q,2) and labels (Q,); got {len(pts)} points and {len(labs)} labels")
+    P, Q = len(boxes), len(pts)
+    dev = masks.device
+    want = {"full": ((N,), torch.float32), "keep": ((N,), torch.uint8)}
+    if P:
+        want.update(inter=((P, N), torch.float32), iou=((P, N), torch.float32), best=((B, P), torch.int32))
+    if Q:
+        want["hit"] = ((Q, N), torch.uint8)
+    if out is None:
+        out = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in want.items()}
+    ld = N
+    for k in ("inter", "hit"):
+        if k in want:
+            ld = int(out[k].shape[1]) if out[k].dim() == 2 else -1
+            break
+    for k, (s, dt) in want.items():
+        t = out.get(k)
+        s = (s[0], ld) if k in ("inter", "iou", "hit") else s
+        if t is None or t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != s or ld < N:
+            raise ValueError(f"mask_prompt: out['{k}'] must be a contiguous {dt} tensor of shape {s} on {dev}")
+    nbytes = L.lib().ey_mask_prompt_workspace_bytes(B, mh, mw, min(P, 32))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes or workspace.device != dev:
+        raise ValueError(f"mask_prompt: workspace must be a contiguous uint8 buffer of at least {nbytes} bytes on {dev}")
+    geo = [v for s in shapes for v in mask_geometry((mh, mw), s)]
+    IA = lambda vals: (ctypes.c_int * max(len(vals), 1))(*vals)  # noqa: E731
+    with _tr("mask_prompt_kernels", N * mh * mw + 4 * N * (2 * P + 1) + N * (Q + 1), 2.0 * N * mh * mw * (P + 1), note=f"B{B} N{N} P{P} Q{Q} {mh}x{mw}", kernels=3):
+        L.check(L.lib().ey_mask_prompt(B, mh, mw, masks.data_ptr(), IA(mask_off), IA(geo), P, IA([v for r in boxes for v in r]), Q, IA([v for r in pts for v in r]),
+                                       IA(labs), max(ld, 0), out["full"].data_ptr(), _p(out.get("inter") if P else None), _p(out.get("iou") if P else None),
+                                       _p(out.get("best") if P else None), _p(out.get("hit") if Q else None), out["keep"].data_ptr(), workspace.data_ptr(),
+                                       workspace.numel(), L.stream()), "ey_mask_prompt")
+    return out
+
+
+def scale_masks(masks, shape, padding=True, out=None):
+    """ey_scale_masks: (N,C,H,W) uint8 / f16 / fp32 -> (N,C,*shape), fp32 for uint8 input, else the input's dtype (reference utils/ops.py:716-737)."""
+    L.require_device(masks, "scale_masks")
+    _no_block("scale_masks")
+    if masks.dim() != 4 or masks.dtype not in (torch.uint8, torch.float16, torch.float32, torch.bool):
+        raise ValueError(f"scale_masks: masks must be an (N,C,H,W) uint8, bool, float16 or float32 tensor, got {masks.dtype} {tuple(masks.shape)}")
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    masks = masks.contiguous()
+    n, c, h, w = (int(v) for v in masks.shape)
+    h0, w0 = int(shape[0]), int(shape[1])
+    top, bottom, left, right = mask_geometry((h, w), shape, padding)[:4]
+    odt = torch.float32 if masks.dtype == torch.uint8 else masks.dtype
+    if out is None:
+        out = torch.empty((n, c, h0, w0), dtype=odt, device=masks.device)
+    elif out.dtype != odt or not out.is_contiguous() or tuple(out.shape) != (n, c, h0, w0) or out.device != masks.device:
+        raise ValueError(f"scale_masks: out= must be a contiguous {odt} tensor of shape {(n, c, h0, w0)} on {masks.device}")
+    code = L.MASK_U8 if masks.dtype == torch.uint8 else L.dtype_code(masks.dtype)
+    with _tr("scale_masks_kernel", _nb(masks, out), 7.0 * out.numel(), note=f"{n * c} x {h}x{w}->{h0}x{w0}"):
+        L.check(L.lib().ey_scale_masks(code, n * c, h, w, top, bottom, left, right, h0, w0, masks.data_ptr(), out.data_ptr(), L.stream()), "ey_scale_masks")
+    return out
+
+
 def dwconv_s2(mod, x, folded_fn, k, act, out=None, tag="dw2"):
     """Depthwise kxk, stride 2, pad k//2 (ey_dwconv_s2): the depthwise half of DSConv(c, c, k, 2)."""
     x = L.as_nhwc(as_tensor(x))

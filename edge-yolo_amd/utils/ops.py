@@ -279,6 +279,26 @@ def process_mask(protos, masks_in, bboxes, shape, upsample=False):
         return _ops.process_mask(proto, [coef], rows, boxes.contiguous(), s)
 
 
+def scale_masks(masks, shape, padding=True):
+    """Reference signature (:716-737): masks (N,C,H,W) -> (N,C,*shape): the letterbox padding is cropped away (padding=True), then
+    F.interpolate(mode="bilinear", align_corners=False), on ey_scale_masks.  uint8 / bool masks give fp32, float16 / float32 keep their
+    dtype.  For callers that want masks at the original resolution; the FastSAM prompt path never calls it (see ey_mask_prompt)."""
+    from ..nn import _ops
+    with torch.cuda.device(masks.device):
+        return _ops.scale_masks(masks, shape, padding=padding)
+
+
+def adjust_bboxes_to_image_border(boxes, image_shape, threshold=20):
+    """Reference models/fastsam/utils.py:4-24: boxes (..., 4) xyxy within `threshold` pixels of the image border stick to it; writes `boxes`
+    in place and returns it.  Masked fills instead of the reference's boolean-index assignments: the same values without a host sync."""
+    h, w = image_shape
+    boxes[..., 0].masked_fill_(boxes[..., 0] < threshold, 0)
+    boxes[..., 1].masked_fill_(boxes[..., 1] < threshold, 0)
+    boxes[..., 2].masked_fill_(boxes[..., 2] > w - threshold, w)
+    boxes[..., 3].masked_fill_(boxes[..., 3] > h - threshold, h)
+    return boxes
+
+
 _CORNER_SIGNS = ((1.0, 1.0), (1.0, -1.0), (-1.0, -1.0), (-1.0, 1.0))  # (along w, along h) of the four corners, in the reference's order
 
 

@@ -467,6 +467,49 @@ size_t ey_mask_iou_workspace_bytes(int H, int W, long n_pred, long n_gt);
 int ey_mask_iou(int gt_mode, int B, int H, int W, const uint8_t* pred, const int* pred_off, const void* gt, const int* gt_off, const long* out_off,
                 float* iou, int* inter, void* workspace, size_t workspace_bytes, ey_stream_t stream);
 
+/* ---- FastSAM prompt selection (ultralytics/models/fastsam/predict.py:61-103 FastSAMPredictor.prompt; the resize of utils/ops.py:716-737
+ * scale_masks is folded in and never materialised).  For every image b of a batch, with M the N_b network-resolution masks of the image,
+ * R(M) = F.interpolate(M[crop], (H0, W0), mode="bilinear", align_corners=False) and the prompts shared by all images (predict.py:75,86):
+ *   full[n]     = sum of R(M_n)
+ *   inter[p][n] = sum of R(M_n) over rows y1 <= y < min(y2, H0) and columns x1 <= x < min(x2, W0)                          (predict.py:80)
+ *   iou[p][n]   = fl(inter / fl(fl(bbox_area_p + full) - inter)),  bbox_area_p = (y2 - y1)(x2 - x1) of the prompt as given     (predict.py:79-84)
+ *   best[b][p]  = argmax_n iou[p][n] over the image's masks as an index INSIDE the image, ties to the lower index; -1 when N_b == 0
+ *   hit[q][n]   = R(M_n)[y_q][x_q] != 0: a set pixel among the (up to) 2 x 2 sources of the point whose two weights are both not 0
+ *   keep[n]     = (n is some box's best) | pk[n];  pk starts all 0 -- all 1 when Q > 0 and the labels sum to 0 -- and every point, in order,
+ *                 writes (label != 0) into the masks it hits (predict.py:94-101).  Q == 0: pk = 0.
+ * None of R(M) is stored: bilinear resizing is linear and separable, so a sum over a box is sum_ij M[i][j] Wy[i] Wx[j] with the per-axis weights
+ * summed over the box's rows / columns; one pass over the mask bytes scores every box.  Per-axis source index and weights are torch's CPU
+ * operator's, in fp32: in == out copies; otherwise r = max(fmaf((float)in / out, y + 0.5f, -0.5f), 0), i0 = min((int)r, in - 1),
+ * l1 = clamp(r - i0, 0, 1), i1 = i0 + (i0 < in - 1), l0 = 1 - l1.  All sums are fp32 in a fixed order (csrc/fastsam.hip): a weight adds its
+ * terms by ascending target coordinate; a thread adds Wx over the set bytes of a row inside one 16-byte word, then Wy times that row sum to its
+ * accumulator, words ascending with a stride of 256; 64 lanes meet in an xor tree, 4 waves in order.  With original == mask size every weight
+ * is 1 and the areas are exact integers.
+ * masks: DEVICE uint8 [mask_off[B]][mh][mw], 0 = clear, anything else = set (what ey_process_mask writes); image b owns rows mask_off[b] ..
+ * mask_off[b+1] - 1.  Every byte is read once.  HOST arrays: mask_off (B + 1 entries, [0] == 0, non-decreasing); geo [B][6] = top, bottom, left,
+ * right, H0, W0: the crop rows top .. bottom - 1 and columns left .. right - 1 of scale_masks(padding=True) (gain = min(mh / H0, mw / W0),
+ * pad = (m - orig * gain) / 2, top = int(pad_h), bottom = int(mh - pad_h), ...) and the target size; boxes [P][4] = x1, y1, x2, y2;
+ * points [Q][2] = x, y; labels [Q].  P and Q may each be 0, not both.
+ * Outputs (DEVICE): full fp32 [N], inter / iou fp32 [P][ld], hit uint8 [Q][ld], keep uint8 [N], best int32 [B][P], with N = mask_off[B] and
+ * ld >= N the row stride; nothing else is written.  inter / iou / best may be NULL when P == 0, hit when Q == 0.  workspace: DEVICE, 16-byte
+ * aligned, ey_mask_prompt_workspace_bytes(B, mh, mw, P) bytes (the weight tables).  Three launches (weights, scores, selection), no atomics: the
+ * same bits run to run; graph-capturable.
+ * EY_EINVAL: null pointers, a box with x2 <= x1 or y2 <= y1, negative coordinates, a point outside [0, W0) x [0, H0) of any image, a bad crop.
+ *   This deviates from the reference, which for such prompts slices with Python's rules (predict.py:80: a negative coordinate counts from the
+ *   far edge, an empty slice sums to 0) or raises an IndexError (predict.py:101); here they are refused.
+ * EY_EUNSUPPORTED (before any launch): B > 64, P > 32, Q > 32, mh * mw > 2^24, a coordinate or target size above 32767 (the reference's
+ *   int32 box area, predict.py:79), or weight tables (mh + mw) * slots(P) * 4 bytes above 156 KiB of LDS, slots = 2, 5, 17, 33 for P <= 1, 4, 16, 32. */
+size_t ey_mask_prompt_workspace_bytes(int B, int mh, int mw, int P);
+int ey_mask_prompt(int B, int mh, int mw, const uint8_t* masks, const int* mask_off, const int* geo, int P, const int* boxes, int Q, const int* points,
+                   const int* labels, long ld, float* full, float* inter, float* iou, int* best, uint8_t* hit, uint8_t* keep, void* workspace,
+                   size_t workspace_bytes, ey_stream_t stream);
+
+/* ---- scale_masks (utils/ops.py:716-737): y[pl] = F.interpolate(x[pl][top:bottom, left:right], (H0, W0), mode="bilinear", align_corners=False)
+ * for `planes` contiguous H x W planes, with the per-axis index and weights of ey_mask_prompt and
+ *   y = fl(fl(l0y * fl(fl(l0x * a) + fl(l1x * b))) + fl(l1y * fl(fl(l0x * c) + fl(l1x * d))))        fp32, one rounding per operation.
+ * in_dtype EY_MASK_U8 -> fp32 output; EY_F32 -> fp32; EY_F16 -> f16 (the fp32 value rounded once).  x, y: DEVICE, contiguous. */
+enum { EY_MASK_U8 = 2 };
+int ey_scale_masks(int in_dtype, long planes, int H, int W, int top, int bottom, int left, int right, int H0, int W0, const void* x, void* y, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
