@@ -143,6 +143,22 @@ class Model(torch.nn.Module):
                                "(BASELINE configs[0], the CPU plumbing case, is the reference's own CPU predictor.)")
         return device
 
+    def _ready(self, device, half):
+        """The model on `device`, fused, in the run's dtype, in eval mode -- in AutoBackend's order (reference nn/autobackend.py:144-155):
+        to(device) -> fuse() -> half()/float()."""
+        m = self.model.to(device)
+        m.fuse()
+        m = m.half() if half else m.float()
+        return m.eval()
+
+    @staticmethod
+    def _options(caller, defaults, kwargs, ignored):
+        """defaults overridden by the caller's kwargs; names outside `defaults` and `ignored` (accepted for the reference's sake, unused) raise."""
+        unknown = set(kwargs) - set(defaults) - set(ignored)
+        if unknown:
+            raise TypeError(f"{caller}() got unsupported arguments {sorted(unknown)}")
+        return {**defaults, **{k: v for k, v in kwargs.items() if k in defaults}}
+
     def predict(self, source=None, stream=False, predictor=None, prompts=None, **kwargs):
         """prompts (reference engine/model.py:554-555): handed to the predictor's `set_prompts` where it has one (FastSAM).  kwargs (reference cfg/default.yaml:51-65 names): imgsz, half, conf, iou, max_det, agnostic_nms, classes, device, augment.
         predictor (reference engine/model.py:505,552: `(predictor or self._smart_load("predictor"))(overrides=...)`): a predictor CLASS to use
@@ -151,32 +167,24 @@ class Model(torch.nn.Module):
             raise ValueError("predict() needs a source: a BCHW float tensor in [0,1] or HWC uint8 BGR ndarray(s)")
         if predictor is not None and not callable(predictor):
             raise TypeError(f"predict(predictor=...): expected a predictor class (constructed like DetectionPredictor), got {type(predictor).__name__}")
-        args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None, "graph": True, "augment": False}
-        if self.task == "segment" and "retina_masks" in kwargs:  # (cfg/default.yaml `retina_masks`; masks come at the network-input resolution)
-            if kwargs.pop("retina_masks"):
-                raise NotImplementedError("retina_masks=True (masks at the original image resolution, ops.process_mask_native) is not built")
-        unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "save", "mode"}
-        if unknown:
-            raise TypeError(f"predict() got unsupported arguments {sorted(unknown)}")
-        args.update({k: v for k, v in kwargs.items() if k in args})
-        device = self._select_device(args["device"] if args["device"] is not None else (source.device if isinstance(source, torch.Tensor) and source.is_cuda else None))
         pcls = predictor or self._task_entry()["predictor"]
+        for name, why in getattr(pcls, "refused_options", {}).items():  # the task's keywords that may only be switched off
+            if kwargs.pop(name, False):
+                raise NotImplementedError(why)
+        args = self._options("predict", {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None,
+                                         "graph": True, "augment": False}, kwargs, {"imgsz", "verbose", "batch", "save", "mode"})
+        device = self._select_device(args["device"] if args["device"] is not None else (source.device if isinstance(source, torch.Tensor) and source.is_cuda else None))
         key = tuple((k, str(v)) for k, v in sorted(args.items())) + (("dev", str(device)), ("predictor", pcls))
         if self.predictor is None or self._pred_key != key:
             if self.predictor is not None:  # options changed: release the old predictor's graphs before anything new is captured
                 self.predictor.close()
                 self.predictor = None
-            # AutoBackend order (reference nn/autobackend.py:144-155): to(device) -> fuse() -> half()/float()
-            m = self.model.to(device)
-            m.fuse()
-            m = m.half() if args["half"] else m.float()
-            m.eval()
+            m = self._ready(device, args["half"])
             self.predictor = pcls(m, device, half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
                                   agnostic_nms=args["agnostic_nms"], classes=args["classes"], graph=args["graph"], augment=args["augment"])
             self._pred_key = key
-        # letterbox target for ndarray sources (reference cfg default 640); classify: the crop size of ClassifyTransform, default 224 (the
-        # reference's 640 only holds until a checkpoint's train args override it: every released -cls checkpoint says 224)
-        self.predictor.imgsz = kwargs.get("imgsz", 224 if self.task == "classify" else 640)
+        # the size ndarray sources are brought to: this call's, or the default the predictor's class states
+        self.predictor.imgsz = kwargs.get("imgsz", getattr(pcls, "imgsz", DetectionPredictor.imgsz))
         if prompts and hasattr(self.predictor, "set_prompts"):
             self.predictor.set_prompts(prompts)
         results = self.predictor(source)
@@ -185,34 +193,24 @@ class Model(torch.nn.Module):
     __call__ = predict
 
     def val(self, dataloader=None, validator=None, **kwargs):
-        """Validate on an iterable of batches in the reference's collate format (engine/validator.py::DetectionValidator.__call__; the
-        segment task adds "masks", see SegmentationValidator; the pose task "keypoints", see PoseValidator) and return the results dict (reference engine/model.py:599-655 returns
-        validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml names): conf (default 0.001), iou,
-        max_det, half, single_cls, agnostic_nms, device, and for the segment task overlap_mask (True: one index map per image) plus
-        save_json / save_txt / plots, which are not built and raise when set.  validator: a validator CLASS to use instead of the task's."""
+        """Validate on an iterable of batches in the reference's collate format (engine/validator.py::DetectionValidator; the segment task
+        adds "masks", see SegmentationValidator; the pose task "keypoints", see PoseValidator) and return the results dict (reference
+        engine/model.py:599-655 returns validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml
+        names): conf (default 0.001), iou, max_det, half, single_cls, agnostic_nms, device, and what the validator class adds in its
+        `val_options` (segment: overlap_mask -- True: one index map per image --; save_json / save_txt / plots, which are not built and raise
+        when set).  validator: a validator CLASS to use instead of the task's."""
         if validator is None and "validator" not in self._task_entry():
             raise NotImplementedError(f"val(): validation of the '{self.task}' task is not built (obb: rotated mAP and multi-label rotated NMS)")
         if dataloader is None:
-            raise ValueError("val() needs an iterable of batch dicts (see DetectionValidator.__call__); datasets are not part of this build")
-        args = {"conf": 0.001, "iou": 0.7, "max_det": 300, "half": False, "single_cls": False, "agnostic_nms": False, "device": None}
-        if self.task == "segment":
-            args.update({"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False})
-        if self.task == "pose":
-            args.update({"save_json": False, "save_txt": False, "plots": False})
-        if self.task == "classify":
-            args.update({"plots": False})
-        unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "batch", "mode"}
-        if unknown:
-            raise TypeError(f"val() got unsupported arguments {sorted(unknown)}")
-        args.update({k: v for k, v in kwargs.items() if k in args})
+            raise ValueError("val() needs an iterable of batch dicts (see DetectionValidator); datasets are not part of this build")
+        vcls = validator or self._task_entry()["validator"]
+        args = self._options("val", {"conf": 0.001, "iou": 0.7, "max_det": 300, "half": False, "single_cls": False, "agnostic_nms": False, "device": None,
+                                     **getattr(vcls, "val_options", {})}, kwargs, {"imgsz", "verbose", "batch", "mode"})
         device = self._select_device(args.pop("device"))
         if self.predictor is not None:  # the model's dtype may change below: a captured predict graph must not outlive it
             self.predictor.close()
             self.predictor = None
-        m = self.model.to(device)
-        m.fuse()
-        m = (m.half() if args["half"] else m.float()).eval()
-        v = (validator or self._task_entry()["validator"])(m, device=device, **args)
+        v = vcls(self._ready(device, args["half"]), device=device, **args)
         self.metrics = v(dataloader)
         self.validator = v
         return self.metrics
@@ -236,11 +234,8 @@ class Model(torch.nn.Module):
         if isinstance(self.model.model[0], torch.nn.Identity):
             raise NotImplementedError("predict_batches: layer 0 of this model is nn.Identity, not a conv (yolov9e): a later layer reads the input image itself "
                                       "and the CBLinear layers hand tuples on, which the pipeline stages' static buffers do not carry; use predict()")
-        args = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None}
-        unknown = set(kwargs) - set(args) - {"imgsz", "verbose", "cuts"}
-        if unknown:
-            raise TypeError(f"predict_batches() got unsupported arguments {sorted(unknown)}")
-        args.update({k: v for k, v in kwargs.items() if k in args})
+        args = self._options("predict_batches", {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "agnostic_nms": False, "classes": None, "device": None},
+                             kwargs, {"imgsz", "verbose", "cuts"})
         pipe, post, pending, nset, dev_ctx = None, None, [], 0, None
         u8, lb, stage_u8, origs, upload = False, None, None, None, None
         try:
@@ -252,9 +247,7 @@ class Model(torch.nn.Module):
                     device = self._select_device(args["device"] if args["device"] is not None else (x.device if x.is_cuda else None))
                     dev_ctx = torch.cuda.device(device)
                     dev_ctx.__enter__()
-                    m = self.model.to(device)
-                    m.fuse()
-                    m = (m.half() if args["half"] else m.float()).eval()
+                    m = self._ready(device, args["half"])
                     post = DetectionPredictor(m, device, half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
                                               agnostic_nms=args["agnostic_nms"], classes=args["classes"], graph=False)
                     n = len(m.model)
@@ -273,7 +266,7 @@ class Model(torch.nn.Module):
                     if u8:
                         from ..data.augment import LetterBox
                         stride = int(max(m.stride)) if hasattr(m, "stride") else 32
-                        lb = LetterBox(kwargs.get("imgsz", 640), auto=True, stride=stride)  # as predict() letterboxes a list of same-shape images
+                        lb = LetterBox(kwargs.get("imgsz", DetectionPredictor.imgsz), auto=True, stride=stride)  # as predict() letterboxes a list of same-shape images
                         example = lb.batch_tensor(x.contiguous().to(device), dt)
                         u8_shape = tuple(x.shape)
                     else:

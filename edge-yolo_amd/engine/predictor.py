@@ -215,6 +215,13 @@ class PipelinedRunner:
 
 
 class DetectionPredictor:
+    # What the facade reads from a predictor class (an injected class without these gets the values here):
+    imgsz = 640  # letterbox target of ndarray sources (reference cfg default); predict(imgsz=) sets it on the instance
+    refused_options = {}  # predict() keyword -> the NotImplementedError text it raises when the keyword is set
+    # augment=True: None = test-time augmentation is built (DetectionModel._predict_augment); ("warn", model class name) = that model has none,
+    # the reference warns and runs single-scale (tasks.py:374-376); ("raise", task name) = refused
+    augment_policy = None
+
     def __init__(self, model, device, half=False, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, classes=None, graph=True, validate_input=None, keep_pred=False,
                  augment=False):
         """This signature is the contract for classes injected through `YOLO.predict(predictor=...)` (reference engine/model.py:505,552):
@@ -225,8 +232,16 @@ class DetectionPredictor:
         whose max exceeds 1 is divided by 255 with a warning).  None (default) = reference behaviour for HOST tensors (the check runs on
         the host, no device sync) and NO check for DEVICE tensors (it would cost a device reduction + a host sync per call -- a
         deliberate divergence: a 0..255 device tensor is fed to the network as is); True = check device tensors too; False = never.
-        augment: scale / flip test-time augmentation (DetectionModel._predict_augment; cfg/default.yaml `augment`)."""
-        self.model, self.device, self.half, self.validate_input, self.keep_pred, self.augment = model, device, half, validate_input, keep_pred, bool(augment)
+        augment: scale / flip test-time augmentation (DetectionModel._predict_augment; cfg/default.yaml `augment`), as far as the class's
+        `augment_policy` has it."""
+        if augment and self.augment_policy is not None:
+            action, who = self.augment_policy
+            if action == "raise":
+                raise NotImplementedError(f"{type(self).__name__}: augment=True (test-time augmentation) is not built for the {who} task")
+            import warnings
+            warnings.warn(f"{who} does not support 'augment=True', reverting to single-scale prediction.")
+            augment = False
+        self.model,self.device, self.half, self.validate_input, self.keep_pred, self.augment = model, device, half, validate_input, keep_pred, bool(augment)
         self.conf, self.iou, self.max_det, self.agnostic_nms, self.classes = conf, iou, max_det, agnostic_nms, classes
         self._lock = threading.Lock()
         self.runner = GraphRunner(self._device_step) if graph else self._device_step
@@ -253,20 +268,26 @@ class DetectionPredictor:
         """Tensor sources: BCHW float in [0,1] (reference LoadTensor, data/loaders.py:516-586).  ndarray / list sources:
         HWC uint8 BGR images, letterboxed to a common stride-32 shape on the host (reference predictor.py:116-161)."""
         if not isinstance(im, torch.Tensor):
-            return self._letterbox_batch(im, getattr(self, "imgsz", 640))
-        if im.dim() == 3:
-            im = im[None]
-        if im.dim() != 4 or im.shape[2] % 32 or im.shape[3] % 32:
-            raise ValueError(f"input tensor should be BCHW with H,W multiples of 32, got {tuple(im.shape)}")
-        if not im.is_floating_point():
-            raise TypeError("tensor sources must be floating point images in [0,1] (uint8 HWC BGR images go in as numpy arrays)")
+            return self._letterbox_batch(im, self.imgsz)
+        shape = (1, *im.shape) if im.dim() == 3 else tuple(im.shape)  # (a CHW tensor is a batch of one)
+        if len(shape) != 4 or shape[2] % 32 or shape[3] % 32:
+            raise ValueError(f"input tensor should be BCHW with H,W multiples of 32, got {shape}")
         check = (not im.is_cuda) if self.validate_input is None else bool(self.validate_input)
-        if check and im.numel():
+        if check and im.numel() and im.is_floating_point():  # (an integer tensor is refused below, whatever its values)
             mx = float(im.max())
             if mx > 1.0 + float(torch.finfo(im.dtype).eps):  # reference LoadTensor._single_check (data/loaders.py:560-566): warn and rescale
                 import warnings
                 warnings.warn(f"torch.Tensor inputs should be normalized 0.0-1.0 but max value is {mx}. Dividing input by 255.")
                 im = im.float() / 255.0
+        return self._tensor_source(im, "(uint8 HWC BGR images go in as numpy arrays)")
+
+    def _tensor_source(self, im, integer_sources):
+        """The tail of every task's tensor source, behind the task's own checks of a CHW / BCHW tensor: leading axis, floating-point check
+        (`integer_sources`: where the task's integer images go instead, for the error text), device, dtype, contiguous."""
+        if im.dim() == 3:
+            im = im[None]
+        if not im.is_floating_point():
+            raise TypeError(f"tensor sources must be floating point images in [0,1] {integer_sources}")
         im = im.to(self.device, non_blocking=True)
         return (im.half() if self.half else im.float()).contiguous()
 
@@ -303,29 +324,46 @@ class DetectionPredictor:
         """Hook for subclasses: the clipped (B, max_det, 6+) rows of a batch whose originals all have the network input's `shape`, before they are
         cut into Results (FastSAMPredictor sticks them to the border here).  Nothing for the other tasks."""
 
-    def postprocess(self, boxes, count, img, source):
-        """reference detect/predict.py:23-41: per image rows -> scale_boxes to the original shape -> Results."""
-        n = count.tolist()
-        boxes = boxes.clone()
-        results = []
-        names = self.model.names
-        # original image == network input (tensor sources; images that already have the network's shape: scale_boxes is gain 1, pad 0):
-        # one clip over the whole batch (4 launches, not 4 per image)
-        same = self._orig is None or all(tuple(o.shape[:2]) == tuple(img.shape[2:]) for o in self._orig)
+    def _assemble(self, count, img, one_image, whole_batch=None):
+        """The one path from a batch's device-step outputs to its list of Results, for every task.
+        count: (B,) rows kept per image, read back here (the one host sync of the batch); None for a task without rows (n_i is None then).
+        whole_batch(shape): the task's arithmetic over the whole batch at once, called when there is one and every original has the network
+        input's `shape` (tensor sources; images that already have it: scaling is gain 1, pad 0), so it is a handful of launches, not that per image.
+        one_image(i, n_i, shape) -> the keyword arguments of image i's Results; `shape` is the (h, w) its rows still have to be scaled to,
+        None once whole_batch has done it."""
+        n = count.tolist() if count is not None else [None] * img.shape[0]
+        inp = tuple(img.shape[2:])
+        same = whole_batch is not None and (self._orig is None or all(tuple(o.shape[:2]) == inp for o in self._orig))
         if same:
-            ops.clip_boxes(boxes, img.shape[2:])
-            self._boxes_in_image(boxes, count, tuple(img.shape[2:]))
+            whole_batch(inp)
+        results = []
         for i in range(len(n)):
-            det = boxes[i, : n[i]]
             orig = self._orig[i] if self._orig is not None else None
-            if not same:
-                det[:, :4] = ops.scale_boxes(img.shape[2:], det[:, :4], orig.shape)
-            r = Results(orig, path=f"image{i}.jpg", names=names, boxes=det)
-            if orig is None:
-                r.orig_shape = tuple(img.shape[2:])
-                r.boxes.orig_shape = r.orig_shape
+            shape = inp if orig is None else tuple(orig.shape[:2])
+            r = Results(orig, path=f"image{i}.jpg", names=self.model.names, **one_image(i, n[i], None if same else shape))
+            if orig is None:  # tensor sources: the frame of the result and of every field it carries is the network input
+                r.orig_shape = inp
+                for field in (r.boxes, r.masks, r.keypoints, r.obb, r.probs):
+                    if field is not None:
+                        field.orig_shape = inp
             results.append(r)
         return results
+
+    def postprocess(self, boxes, count, img, source):
+        """reference detect/predict.py:23-41: per image rows -> scale_boxes to the original shape -> Results."""
+        boxes = boxes.clone()
+
+        def whole_batch(shape):  # one clip over the whole batch (4 launches, not 4 per image)
+            ops.clip_boxes(boxes, shape)
+            self._boxes_in_image(boxes, count, shape)
+
+        def one_image(i, k, shape):
+            det = boxes[i, :k]
+            if shape is not None:
+                det[:, :4] = ops.scale_boxes(img.shape[2:], det[:, :4], shape)
+            return {"boxes": det}
+
+        return self._assemble(count, img, one_image, whole_batch)
 
 
 class SegmentationPredictor(DetectionPredictor):
@@ -333,12 +371,9 @@ class SegmentationPredictor(DetectionPredictor):
     of the Segment head; `postprocess` assembles the masks of the whole batch with ONE ey_process_mask launch sized by the true number of
     kept boxes (it runs after the count came back, outside the graph).  Masks are at the network-input resolution (retina_masks=False)."""
 
-    def __init__(self, model, device, *args, **kwargs):
-        super().__init__(model, device, *args, **kwargs)
-        if self.augment:  # SegmentationModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
-            import warnings
-            warnings.warn("SegmentationModel does not support 'augment=True', reverting to single-scale prediction.")
-            self.augment = False
+    augment_policy = ("warn", "SegmentationModel")
+    # (cfg/default.yaml `retina_masks`; masks come at the network-input resolution)
+    refused_options = {"retina_masks": "retina_masks=True (masks at the original image resolution, ops.process_mask_native) is not built"}
 
     def _device_step(self, im):
         cand, (_, mcs, p) = self.model(im, head_nms={"conf": self.conf, "classes": self.classes, "keep_pred": self.keep_pred})
@@ -362,7 +397,7 @@ class SegmentationPredictor(DetectionPredictor):
         masks = None
         if total:
             # rows (image, anchor) and boxes of the kept detections, image after image, built on the device from count and index
-            keep = torch.arange(max_det, device=index.device)[None, :] < count[:, None]
+            keep = ops.kept_rows(count, max_det)
             rows = torch.stack([torch.arange(B, dtype=torch.int32, device=index.device)[:, None].expand(B, max_det)[keep], index[keep]], 1).contiguous()
             masks = _ops.process_mask(proto, coefs, rows, boxes[keep][:, :4].contiguous(), s)  # boxes in network-input pixels, before scale_boxes
         self._masks, self._mask_counts = masks, n  # the batch's masks as ONE uint8 tensor, image after image (FastSAMPredictor scores them in one launch)
@@ -449,8 +484,7 @@ class FastSAMPredictor(SegmentationPredictor):
 
     def _boxes_in_image(self, boxes, count, shape):
         """original == network input for the whole batch: the border step over all images at once (a handful of launches, not per image)."""
-        valid = torch.arange(boxes.shape[1], device=boxes.device)[None, :] < count[:, None]
-        self.stick_to_border(boxes[..., :4], shape, valid=valid)
+        self.stick_to_border(boxes[..., :4], shape, valid=ops.kept_rows(count, boxes.shape[1]))
         self._stuck = True
 
     def postprocess(self, boxes, count, img, source, index=None, proto=None, coefs=None):
@@ -479,12 +513,7 @@ class OBBPredictor(DetectionPredictor):
     read-back of the counts the kept rows are regularised (w >= h, angle in [0, pi)) and scaled to the original image as xywh.
     Results carry `obb` rows [cx,cy,w,h,rotation,conf,cls]; `boxes` is None."""
 
-    def __init__(self, model, device, *args, **kwargs):
-        super().__init__(model, device, *args, **kwargs)
-        if self.augment:  # OBBModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
-            import warnings
-            warnings.warn("OBBModel does not support 'augment=True', reverting to single-scale prediction.")
-            self.augment = False
+    augment_policy = ("warn", "OBBModel")
 
     def _device_step(self, im):
         pred = self.model(im)[0]
@@ -492,20 +521,13 @@ class OBBPredictor(DetectionPredictor):
         return rows, count, index, pred
 
     def postprocess(self, rows, count, img, source):
-        n = count.tolist()  # (the one host sync of the batch)
-        results = []
-        for i in range(len(n)):
-            det = rows[i, : n[i]]
-            orig = self._orig[i] if self._orig is not None else None
-            shape = tuple(orig.shape[:2]) if orig is not None else tuple(img.shape[2:])
+        def one_image(i, k, shape):  # (no whole-batch form: the kept rows are regularised and rebuilt image by image, whatever the frame)
+            det = rows[i, :k]
             rboxes = ops.regularize_rboxes(torch.cat([det[:, :4], det[:, -1:]], dim=-1))
             rboxes[:, :4] = ops.scale_boxes(img.shape[2:], rboxes[:, :4], shape, xywh=True)
-            r = Results(orig, path=f"image{i}.jpg", names=self.model.names, obb=torch.cat([rboxes, det[:, 4:6]], dim=-1))
-            if orig is None:
-                r.orig_shape = shape
-                r.obb.orig_shape = shape
-            results.append(r)
-        return results
+            return {"obb": torch.cat([rboxes, det[:, 4:6]], dim=-1)}
+
+        return self._assemble(count, img, one_image)
 
 
 class PosePredictor(DetectionPredictor):
@@ -514,12 +536,7 @@ class PosePredictor(DetectionPredictor):
     a fixed (B, max_det, K, ndim) tensor, nothing is decoded for the anchors NMS dropped.  After the one read-back of the counts the boxes
     are scaled and rounded (pose/predict.py:50; detect does not round) and the keypoints go through scale_coords."""
 
-    def __init__(self, model, device, *args, **kwargs):
-        super().__init__(model, device, *args, **kwargs)
-        if self.augment:  # PoseModel has no TTA: the reference warns and runs single-scale (tasks.py:374-376)
-            import warnings
-            warnings.warn("PoseModel does not support 'augment=True', reverting to single-scale prediction.")
-            self.augment = False
+    augment_policy = ("warn", "PoseModel")
 
     def _device_step(self, im):
         from ..nn import _ops
@@ -533,27 +550,21 @@ class PosePredictor(DetectionPredictor):
         return self.postprocess(out[0], out[1], im, source, kpts=out[4])
 
     def postprocess(self, boxes, count, img, source, kpts=None):
-        n = count.tolist()  # (the one host sync of the batch)
         boxes, kpts = boxes.clone(), kpts.clone()
-        names = self.model.names
-        results = []
-        same = self._orig is None or all(tuple(o.shape[:2]) == tuple(img.shape[2:]) for o in self._orig)
-        if same:  # gain 1, pad 0: one clip (and one rounding of the boxes) over the whole batch
-            ops.clip_boxes(boxes, img.shape[2:])
+
+        def whole_batch(shape):  # one clip (and one rounding of the boxes) over the whole batch
+            ops.clip_boxes(boxes, shape)
             boxes[..., :4] = boxes[..., :4].round()
-            ops.clip_coords(kpts, img.shape[2:])
-        for i in range(len(n)):
-            det, kp = boxes[i, : n[i]], kpts[i, : n[i]]
-            orig = self._orig[i] if self._orig is not None else None
-            if not same:
-                det[:, :4] = ops.scale_boxes(img.shape[2:], det[:, :4], orig.shape).round()
-                kp = ops.scale_coords(img.shape[2:], kp, orig.shape)
-            r = Results(orig, path=f"image{i}.jpg", names=names, boxes=det, keypoints=kp)
-            if orig is None:
-                r.orig_shape = tuple(img.shape[2:])
-                r.boxes.orig_shape = r.keypoints.orig_shape = r.orig_shape
-            results.append(r)
-        return results
+            ops.clip_coords(kpts, shape)
+
+        def one_image(i, k, shape):
+            det, kp = boxes[i, :k], kpts[i, :k]
+            if shape is not None:
+                det[:, :4] = ops.scale_boxes(img.shape[2:], det[:, :4], shape).round()
+                kp = ops.scale_coords(img.shape[2:], kp, shape)
+            return {"boxes": det, "keypoints": kp}
+
+        return self._assemble(count, img, one_image, whole_batch)
 
 
 class ClassificationPredictor(DetectionPredictor):
@@ -563,13 +574,10 @@ class ClassificationPredictor(DetectionPredictor):
     Results carry `probs` only; its top-5 comes from the head's kernel.  conf, iou, max_det, classes and agnostic_nms are accepted and
     ignored, as in the reference; augment=True raises."""
 
-    def __init__(self, model, device, half=False, conf=0.25, iou=0.7, max_det=300, agnostic_nms=False, classes=None, graph=True, validate_input=None, keep_pred=False,
-                 augment=False):
-        if augment:
-            raise NotImplementedError("ClassificationPredictor: augment=True (test-time augmentation) is not built for the classify task")
-        super().__init__(model, device, half=half, conf=conf, iou=iou, max_det=max_det, agnostic_nms=agnostic_nms, classes=classes, graph=graph,
-                         validate_input=validate_input, keep_pred=keep_pred, augment=False)
-        self.imgsz = 224
+    # the crop size of ClassifyTransform (the reference's 640 only holds until a checkpoint's train args override it: every released -cls
+    # checkpoint says 224)
+    imgsz = 224
+    augment_policy = ("raise", "classify")
 
     def _device_step(self, im):
         if im.dtype == torch.uint8:  # a decoded batch: the transform is part of the captured graph
@@ -581,7 +589,7 @@ class ClassificationPredictor(DetectionPredictor):
 
     def preprocess(self, im):
         from ..data.augment import ClassifyTransform
-        size = getattr(self, "imgsz", 224)
+        size = self.imgsz
         if isinstance(im, torch.Tensor) and im.dtype == torch.uint8:
             if im.dim() != 4 or im.shape[3] != 3:
                 raise ValueError(f"uint8 tensor sources must be (B,h,w,3) BGR image stacks, got {tuple(im.shape)}")
@@ -594,14 +602,9 @@ class ClassificationPredictor(DetectionPredictor):
             ims = im if isinstance(im, (list, tuple)) else [im]
             self._orig = [np.asarray(a) for a in ims]
             return ClassifyTransform(size).batch(self._orig, self.device, torch.float16 if self.half else torch.float32)
-        if im.dim() == 3:
-            im = im[None]
-        if im.dim() != 4:
+        if im.dim() not in (3, 4):
             raise ValueError(f"input tensor should be BCHW, got {tuple(im.shape)}")
-        if not im.is_floating_point():
-            raise TypeError("tensor sources must be floating point images in [0,1] or uint8 (B,h,w,3) BGR stacks")
-        im = im.to(self.device, non_blocking=True)
-        return (im.half() if self.half else im.float()).contiguous()
+        return self._tensor_source(im, "or uint8 (B,h,w,3) BGR stacks")
 
     def _results(self, out, im, source):
         return self.postprocess(out[0], im, source, top=(out[2], out[3]))
@@ -611,11 +614,4 @@ class ClassificationPredictor(DetectionPredictor):
         from .results import Probs
         probs = probs.clone()
         top = tuple(t.clone() for t in top) if top is not None else None
-        results = []
-        for i in range(probs.shape[0]):
-            orig = self._orig[i] if self._orig is not None else None
-            r = Results(orig, path=f"image{i}.jpg", names=self.model.names, probs=Probs(probs[i], top=None if top is None else (top[0][i], top[1][i])))
-            if orig is None:
-                r.orig_shape = tuple(img.shape[2:])
-            results.append(r)
-        return results
+        return self._assemble(None, img, lambda i, k, shape: {"probs": Probs(probs[i], top=None if top is None else (top[0][i], top[1][i]))})

@@ -21,14 +21,74 @@ def _np(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
 
 
-class DetectionValidator:
+def refuse_options(owner, what, **options):
+    """The options of a validator that are accepted by name and not built: any that is set raises."""
+    for name, on in options.items():
+        if on:
+            raise NotImplementedError(f"{owner}: {name}=True is not built ({what})")
+
+
+def batch_offsets(n):
+    """per-image counts -> the B+1 offsets of the images' rows in a batch's flat row tensor."""
+    return np.concatenate([[0], np.cumsum(n)])
+
+
+def pair_matrices(launch, n, nl):
+    """The [gt x pred] matrices of a batch from ONE launch: `launch(pred_off, gt_off) -> (flat, out_off)` gets the offset tables of the
+    images' n[i] predictions and nl[i] labels and returns the flat buffer that holds image i's row-major (nl[i], n[i]) matrix at out_off[i].
+    One copy to the host -> list of (nl[i], n[i]) arrays, None where either side is empty."""
+    flat, off = launch(batch_offsets(n), batch_offsets(nl))
+    host = flat.cpu().numpy()  # the one D2H copy of the batch's matrices
+    return [host[off[i]: off[i] + nl[i] * n[i]].reshape(nl[i], n[i]) if n[i] and nl[i] else None for i in range(len(n))]
+
+
+class BaseValidator:
+    """What every task's validator shares: the model behind a facade, the device, the image part of `preprocess`, and the loop."""
+
+    val_options = {}  # val() keywords of the task beyond the common ones, with their defaults (the facade reads this off the class)
+
+    def __init__(self, model, half=False, device=None):
+        """model: a task model on its device (fused / dtype set by the caller), or a YOLO facade."""
+        self.model = getattr(model, "model", model) if not hasattr(model, "forward_layers") else model
+        self.half = half
+        self.device = torch.device(device) if device is not None else next(self.model.parameters()).device
+
+    # ---- reference detect/val.py:52-66, classify/val.py:49-54
+    def preprocess(self, batch):
+        """batch["img"]: (B,3,H,W) uint8 (0..255) or float in [0,1] tensor; the uint8 form is divided by 255 like the reference does."""
+        img = batch["img"].to(self.device, non_blocking=True)
+        scale = 255.0 if img.dtype == torch.uint8 else 1.0
+        img = img.half() if self.half else img.float()
+        batch = dict(batch)
+        batch["img"] = (img / scale if scale != 1.0 else img).contiguous()
+        return batch
+
+    def _forward(self, img):
+        return self.model(img)
+
+    @torch.no_grad()
+    def __call__(self, dataloader):
+        """dataloader: iterable of batch dicts in the task's format (see the class).  Returns the task's results dict."""
+        self.init_metrics()
+        for batch in dataloader:
+            batch = self.preprocess(batch)
+            with torch.cuda.device(self.device):  # kernels go to the CURRENT device's stream
+                preds = self.postprocess(self._forward(batch["img"]))
+                self.update_metrics(preds, batch)
+        return self.get_stats()
+
+
+class DetectionValidator(BaseValidator):
+    """Batches: {"img", "cls" (N,1), "bboxes" (N,4 normalised xywh in the network input frame), "batch_idx" (N,), "ori_shape" [B x (h,w)],
+    "ratio_pad" [B x ((gain,gain),(padw,padh))] or absent} (the reference's dataset collate format, data/dataset.py); the results dict is the
+    reference's DetMetrics.results_dict."""
+
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None):
         """model: a DetectionModel on its device (fused / dtype set by the caller or by __call__), or a YOLO facade.
         conf None -> 0.001 like the reference (engine/validator.py:100-101)."""
-        self.model = getattr(model, "model", model) if not hasattr(model, "forward_layers") else model
+        super().__init__(model, half, device)
         self.conf = 0.001 if conf is None else conf
-        self.iou, self.max_det, self.half, self.single_cls, self.agnostic_nms = iou, max_det, half, single_cls, agnostic_nms
-        self.device = torch.device(device) if device is not None else next(self.model.parameters()).device
+        self.iou, self.max_det, self.single_cls, self.agnostic_nms = iou, max_det, single_cls, agnostic_nms
         self.iouv = metrics.IOUV
         self.niou = len(self.iouv)
         self.nc = len(self.model.names)
@@ -40,16 +100,6 @@ class DetectionValidator:
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
         self.results_dict = dict(zip(KEYS + ["fitness"], [0.0] * 6))
         self.box = None
-
-    # ---- reference val.py:52-66
-    def preprocess(self, batch):
-        """batch["img"]: (B,3,H,W) uint8 (0..255) or float in [0,1] tensor; the uint8 form is divided by 255 like the reference does."""
-        img = batch["img"].to(self.device, non_blocking=True)
-        scale = 255.0 if img.dtype == torch.uint8 else 1.0
-        img = img.half() if self.half else img.float()
-        batch = dict(batch)
-        batch["img"] = (img / scale if scale != 1.0 else img).contiguous()
-        return batch
 
     # ---- reference val.py:92-102
     def postprocess(self, preds):
@@ -81,38 +131,53 @@ class DetectionValidator:
 
     # ---- reference val.py:125-172 (plots / json / txt saving are out of scope)
     def update_metrics(self, preds, batch):
-        for si, pred in enumerate(preds):
+        self._image_stats(preds, batch)
+
+    def _image_stats(self, rows, batch, pbatches=None, **more_tp):
+        """The per-image statistics loop of every task with boxes.  rows: per image the kept (n_i, 6+) rows [xyxy, conf, cls, ...] in
+        network-input pixels.  pbatches: the images' `_prepare_batch` dicts where the task's batch-wide work made them already.
+        more_tp: the task's further true-positive arrays by their `stats` key, each a `f(si, predn, pbatch) -> (n_i, niou) bool` that is
+        called for the images that have both predictions and labels."""
+        for si, pred in enumerate(rows):
             self.seen += 1
-            pred = _np(pred).astype(np.float32).reshape(-1, 6)
+            pred = _np(pred).astype(np.float32)
+            pred = pred.reshape(-1, pred.shape[-1] if pred.ndim == 2 else 6)
             npr = pred.shape[0]
-            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), tp=np.zeros((npr, self.niou), bool))
-            pbatch = self._prepare_batch(si, batch)
-            cls, bbox = pbatch.pop("cls"), pbatch.pop("bbox")
-            nl = len(cls)
+            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), **{k: np.zeros((npr, self.niou), bool) for k in ("tp", *more_tp)})
+            pbatch = self._prepare_batch(si, batch) if pbatches is None else pbatches[si]
+            cls, bbox = pbatch["cls"], pbatch["bbox"]
             stat["target_cls"] = cls
             stat["target_img"] = np.unique(cls)
-            if npr == 0:
-                if nl:
+            if npr == 0:  # an image with no predictions contributes only when it has labels
+                if len(cls):
                     for k in self.stats:
                         self.stats[k].append(stat[k])
                 continue
             if self.single_cls:
                 pred = pred.copy()
                 pred[:, 5] = 0
-            predn = self._prepare_pred(pred, pbatch)
+            predn = DetectionValidator._prepare_pred(self, pred[:, :6], pbatch)  # (the boxes; what rides behind column 6 is the task's)
             stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
-            if nl:
+            if len(cls):
                 stat["tp"] = self._process_batch(predn, bbox, cls)
+                for k, f in more_tp.items():
+                    stat[k] = f(si, predn, pbatch)
             for k in self.stats:
                 self.stats[k].append(stat[k])
 
-    # ---- reference val.py:179-188 + DetMetrics.process / results_dict (metrics.py:850-896)
-    def get_stats(self):
-        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k == "tp" else 0)) for k, v in self.stats.items()}
+    def _gather_stats(self):
+        """The accumulated statistics as one array per key, with the label counts per class / per image set aside; None while no prediction
+        has matched a label at any threshold (the reference tests the box matches only, detect/val.py:186)."""
+        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k.startswith("tp") else 0)) for k, v in self.stats.items()}
         self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc)
         self.nt_per_image = np.bincount(stats["target_img"].astype(int), minlength=self.nc)
         stats.pop("target_img", None)
-        if len(stats["tp"]) and stats["tp"].any():
+        return stats if len(stats["tp"]) and stats["tp"].any() else None
+
+    # ---- reference val.py:179-188 + DetMetrics.process / results_dict (metrics.py:850-896)
+    def get_stats(self):
+        stats = self._gather_stats()
+        if stats is not None:
             r = metrics.ap_per_class(stats["tp"], stats["conf"], stats["pred_cls"], stats["target_cls"])
             ap = r["ap"]
             mean = [float(r["p"].mean()) if len(r["p"]) else 0.0, float(r["r"].mean()) if len(r["r"]) else 0.0,
@@ -121,20 +186,6 @@ class DetectionValidator:
             # fitness: the fork weights only mAP50-95 (Metric.fitness, metrics.py:758-761: w = [0, 0, 0, 0, 1])
             self.results_dict = dict(zip(KEYS + ["fitness"], mean + [mean[4]]))
         return self.results_dict
-
-    @torch.no_grad()
-    def __call__(self, dataloader):
-        """dataloader: iterable of batch dicts {"img", "cls" (N,1), "bboxes" (N,4 normalised xywh in the network input frame),
-        "batch_idx" (N,), "ori_shape" [B x (h,w)], "ratio_pad" [B x ((gain,gain),(padw,padh))] or absent} (the reference's
-        dataset collate format, data/dataset.py).  Returns the results dict (reference DetMetrics.results_dict)."""
-        self.init_metrics()
-        for batch in dataloader:
-            batch = self.preprocess(batch)
-            with torch.cuda.device(self.device):
-                preds = self.model(batch["img"])
-                preds = self.postprocess(preds)
-            self.update_metrics(preds, batch)
-        return self.get_stats()
 
     # ---- convenience kept from round 1: labels as (m,5) [cls, x1,y1,x2,y2] in network-input pixels, no letterbox
     @torch.no_grad()
@@ -158,7 +209,34 @@ class DetectionValidator:
         return dict(mp=r[KEYS[0]], mr=r[KEYS[1]], map50=r[KEYS[2]], map75=r[KEYS[3]], map=r[KEYS[4]])
 
 
-class SegmentationValidator(DetectionValidator):
+class TwoMetricValidator(DetectionValidator):
+    """The tasks that score the boxes and a second quantity of every instance side by side (segment: masks, pose: keypoints): the
+    bookkeeping around a metrics object with `box` and that second Metric.  A task names the three class attributes."""
+
+    metrics_cls = None  # metrics.SegmentMetrics or a subclass
+    second = None  # the second Metric's name on the metrics object; get_stats mirrors it on the validator next to `box`
+    tp_second = None  # its true-positive array's key in `stats` (the keyword of metrics_cls.process)
+
+    def init_metrics(self):
+        super().init_metrics()
+        self.metrics = self.metrics_cls()
+        self.stats = {self.tp_second: [], **self.stats}
+        self.results_dict = dict.fromkeys(self.metrics.keys + ["fitness"], 0.0)
+        setattr(self, self.second, None)
+        self.kept = []
+
+    # ---- reference detect/val.py:179-188 + SegmentMetrics / PoseMetrics .process / results_dict (metrics.py:949-1029)
+    def get_stats(self):
+        stats = self._gather_stats()
+        if stats is not None:
+            self.metrics.process(**stats)
+            self.box = self.metrics.box
+            setattr(self, self.second, getattr(self.metrics, self.second))
+        self.results_dict = self.metrics.results_dict
+        return self.results_dict
+
+
+class SegmentationValidator(TwoMetricValidator):
     """Validation loop for the segment task, mirroring the reference's models/yolo/segment/val.py (`preprocess` :39-43, `postprocess` :71-84,
     `_prepare_batch` :86-91, `_prepare_pred` :93-97, `update_metrics` :99-166, `_process_batch` :173-217) with SegmentMetrics.
 
@@ -176,23 +254,16 @@ class SegmentationValidator(DetectionValidator):
     Host masks (numpy / CPU tensors, `update_metrics(..., pred_masks=[...])` with a validator on the CPU) go through the numpy restatement of
     mask_iou: the route the CPU tests take.  save_json, save_txt, plots and process_mask_native (ops.process_mask_native) are not built."""
 
+    metrics_cls, second, tp_second = metrics.SegmentMetrics, "seg", "tp_m"  # (reference segment/val.py:45-53)
+    val_options = {"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False}
+
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, overlap_mask=True,
                  save_json=False, save_txt=False, plots=False, process_mask_native=False):
-        for name, on in (("save_json", save_json), ("save_txt", save_txt), ("plots", plots), ("process_mask_native", process_mask_native)):
-            if on:
-                raise NotImplementedError(f"SegmentationValidator: {name}=True is not built (COCO json / txt export, plots and ops.process_mask_native)")
+        refuse_options("SegmentationValidator", "COCO json / txt export, plots and ops.process_mask_native",
+                       save_json=save_json, save_txt=save_txt, plots=plots, process_mask_native=process_mask_native)
         self.overlap_mask = bool(overlap_mask)
         self.keep_outputs = False  # True: update_metrics appends (rows (n,6+nm), mask bits (n,mh,mw)) per image to self.kept, on the host
         super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
-
-    # ---- reference segment/val.py:45-53
-    def init_metrics(self):
-        super().init_metrics()
-        self.metrics = metrics.SegmentMetrics()
-        self.stats = dict(tp_m=[], tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
-        self.results_dict = dict(zip(metrics.SEG_KEYS + ["fitness"], [0.0] * 11))
-        self.seg = None
-        self.kept = []
 
     # ---- reference segment/val.py:39-43 (the masks stay integers: uint8 0/1 stacks, int32 index maps)
     def preprocess(self, batch):
@@ -282,7 +353,6 @@ class SegmentationValidator(DetectionValidator):
         from ..nn import _ops
         B = len(n)
         gt = batch["masks"]
-        pred_off, gt_off = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(nl)])
         if not any(a and b for a, b in zip(n, nl)):
             return [None] * B
         index = self.overlap_mask
@@ -296,9 +366,7 @@ class SegmentationValidator(DetectionValidator):
                 gt = torch.cat([(gt[i:i + 1] == torch.arange(1, nl[i] + 1, device=gt.device).view(-1, 1, 1)) for i in range(B)], 0)
                 index = False
             gt = self._resize_gt(gt, pred_masks.shape[1:])
-        iou, off, _ = _ops.mask_iou(pred_masks, pred_off, gt.contiguous(), gt_off, index=index)
-        host = iou.cpu().numpy()  # the one D2H copy of the batch's matrices
-        return [host[off[i]: off[i] + nl[i] * n[i]].reshape(nl[i], n[i]) if n[i] and nl[i] else None for i in range(B)]
+        return pair_matrices(lambda pred_off, gt_off: _ops.mask_iou(pred_masks, pred_off, gt.contiguous(), gt_off, index=index)[:2], n, nl)
 
     # ---- reference segment/val.py:99-166
     def update_metrics(self, preds, batch, pred_masks=None):
@@ -306,74 +374,30 @@ class SegmentationValidator(DetectionValidator):
         mask assembly (proto may then be None): host arrays take the numpy route."""
         rows, proto = preds
         B = len(rows)
-        n = [int(r.shape[0]) for r in rows]
-        bi = _np(batch["batch_idx"]).reshape(-1)
-        nl = [int((bi == si).sum()) for si in range(B)]
         ious = [None] * B
         on_device = pred_masks is None
         if on_device:
+            n = [int(r.shape[0]) for r in rows]
+            bi = _np(batch["batch_idx"]).reshape(-1)
+            nl = [int((bi == si).sum()) for si in range(B)]
             imgsz = tuple(int(v) for v in batch["img"].shape[2:])
             all_masks = self._batch_pred_masks(rows, proto, imgsz)
             ious = self._batch_mask_ious(all_masks, n, batch, nl)
             if self.keep_outputs:
-                host, off = all_masks.cpu().numpy(), np.concatenate([[0], np.cumsum(n)])
+                host, off = all_masks.cpu().numpy(), batch_offsets(n)
                 self.kept += [(_np(rows[i]).copy(), host[off[i]:off[i + 1]]) for i in range(B)]
-        for si, pred in enumerate(rows):
-            self.seen += 1
-            pred = _np(pred).astype(np.float32)
-            pred = pred.reshape(-1, pred.shape[-1] if pred.ndim == 2 else 6)
-            npr = pred.shape[0]
-            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), tp=np.zeros((npr, self.niou), bool), tp_m=np.zeros((npr, self.niou), bool))
-            pbatch = self._prepare_batch(si, batch)
-            cls, bbox = pbatch.pop("cls"), pbatch.pop("bbox")
-            stat["target_cls"] = cls
-            stat["target_img"] = np.unique(cls)
-            if npr == 0:
-                if nl[si]:
-                    for k in self.stats:
-                        self.stats[k].append(stat[k])
-                continue
-            gt_masks = pbatch.pop("masks")
-            if self.single_cls:
-                pred = pred.copy()
-                pred[:, 5] = 0
-            predn = DetectionValidator._prepare_pred(self, pred[:, :6], pbatch)
-            stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
-            if nl[si]:
-                stat["tp"] = self._process_batch(predn, bbox, cls)
-                stat["tp_m"] = self._process_batch(predn, bbox, cls, None if on_device else pred_masks[si], gt_masks, self.overlap_mask, masks=True, iou=ious[si])
-            for k in self.stats:
-                self.stats[k].append(stat[k])
 
-    # ---- reference detect/val.py:179-188 + SegmentMetrics.process / results_dict (metrics.py:949-1029)
-    def get_stats(self):
-        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k in ("tp", "tp_m") else 0)) for k, v in self.stats.items()}
-        self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc)
-        self.nt_per_image = np.bincount(stats["target_img"].astype(int), minlength=self.nc)
-        stats.pop("target_img", None)
-        if len(stats["tp"]) and stats["tp"].any():  # (the reference tests the box matches only, detect/val.py:186)
-            self.metrics.process(**stats)
-            self.box, self.seg = self.metrics.box, self.metrics.seg
-        self.results_dict = self.metrics.results_dict
-        return self.results_dict
+        def tp_m(si, predn, pbatch):
+            return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], None if on_device else pred_masks[si], pbatch["masks"], self.overlap_mask,
+                                       masks=True, iou=ious[si])
 
-    @torch.no_grad()
-    def __call__(self, dataloader):
-        """dataloader: iterable of batch dicts in DetectionValidator's format plus "masks" (see the class docstring).  Returns the results
-        dict (reference SegmentMetrics.results_dict: five box keys, five mask keys, fitness)."""
-        self.init_metrics()
-        for batch in dataloader:
-            batch = self.preprocess(batch)
-            with torch.cuda.device(self.device):
-                preds = self.postprocess(self.model(batch["img"]))
-                self.update_metrics(preds, batch)
-        return self.get_stats()
+        self._image_stats(rows, batch, tp_m=tp_m)
 
     def update(self, images, labels):
         raise NotImplementedError("SegmentationValidator: the (images, labels) convenience of the detect task carries no masks; call it with batches")
 
 
-class PoseValidator(DetectionValidator):
+class PoseValidator(TwoMetricValidator):
     """Validation loop for the pose task, mirroring the reference's models/yolo/pose/val.py (`init_metrics` :77-84, `_prepare_batch` :86-96,
     `_prepare_pred` :98-104, `update_metrics` :106-157, `_process_batch` :159-197) with PoseMetrics.
 
@@ -387,11 +411,12 @@ class PoseValidator(DetectionValidator):
     (`update_metrics((rows, kpts), batch)` with numpy arrays / CPU tensors) go through the numpy restatement of kpt_iou: the route the CPU
     tests take.  save_json, save_txt and plots are not built."""
 
+    metrics_cls, second, tp_second = metrics.PoseMetrics, "pose", "tp_p"
+    val_options = {"save_json": False, "save_txt": False, "plots": False}
+
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, save_json=False, save_txt=False,
                  plots=False):
-        for name, on in (("save_json", save_json), ("save_txt", save_txt), ("plots", plots)):
-            if on:
-                raise NotImplementedError(f"PoseValidator: {name}=True is not built (COCO json / txt export and plots)")
+        refuse_options("PoseValidator", "COCO json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
         self.keep_outputs = False  # True: update_metrics appends (rows (n,6), keypoints (n,K,ndim) in input pixels) per image to self.kept, on the host
         super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
 
@@ -401,11 +426,6 @@ class PoseValidator(DetectionValidator):
         self.kpt_shape = [int(v) for v in self.model.model[-1].kpt_shape]
         nkpt = self.kpt_shape[0]
         self.sigma = metrics.OKS_SIGMA if self.kpt_shape == [17, 3] else np.ones(nkpt) / nkpt
-        self.metrics = metrics.PoseMetrics()
-        self.stats = dict(tp_p=[], tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
-        self.results_dict = dict(zip(metrics.POSE_KEYS + ["fitness"], [0.0] * 11))
-        self.pose = None
-        self.kept = []
 
     # ---- reference pose/val.py:64-75 + the keypoints of the kept rows: (rows (n_i, 6) per image, keypoints (B, max_det, K, ndim) in input pixels)
     def postprocess(self, preds):
@@ -444,9 +464,13 @@ class PoseValidator(DetectionValidator):
         if pred_kpts is None and gt_kpts is None and iou is None:
             return super()._process_batch(detections, gt_bboxes, gt_cls)
         if iou is None:
-            area = (ops.xyxy2xywh(torch.as_tensor(gt_bboxes))[:, 2:].prod(1) * 0.53).numpy()  # 0.53: the COCO keypoint evaluation's box-to-area factor
-            iou = _np(metrics.kpt_iou(gt_kpts, pred_kpts, area, self.sigma))
+            iou = _np(metrics.kpt_iou(gt_kpts, pred_kpts, self._gt_area(gt_bboxes), self.sigma))
         return metrics.match_predictions(detections[:, 5], gt_cls, iou, self.iouv)
+
+    @staticmethod
+    def _gt_area(gt_bboxes):
+        """(m, 4) xyxy ground-truth boxes -> the (m,) object areas OKS normalises by (reference pose/val.py:187)."""
+        return (ops.xyxy2xywh(torch.as_tensor(gt_bboxes))[:, 2:].prod(1) * 0.53).numpy()  # 0.53: the COCO keypoint evaluation's box-to-area factor
 
     def _scale_pred_kpts(self, kpts, pbatches):
         """pose/val.py:98-104 for every image at once, on the tensor's device: (B, max_det, K, ndim) input pixels -> original-image pixels
@@ -474,88 +498,38 @@ class PoseValidator(DetectionValidator):
         from ..nn import _ops
         rows, kpts = preds
         B = len(rows)
-        n = [int(r.shape[0]) for r in rows]
         pbatches = [self._prepare_batch(si, batch) for si in range(B)]
-        nl = [len(pb["cls"]) for pb in pbatches]
         K = self.kpt_shape[0]
-        areas = [(ops.xyxy2xywh(torch.from_numpy(pb["bbox"]))[:, 2:].prod(1) * 0.53).numpy() if nl[i] else np.zeros(0, np.float32) for i, pb in enumerate(pbatches)]
         on_device = torch.is_tensor(kpts) and kpts.is_cuda
         ious = [None] * B
         if on_device:
+            n, nl = [int(r.shape[0]) for r in rows], [len(pb["cls"]) for pb in pbatches]
             scaled = self._scale_pred_kpts(kpts, pbatches)
             if self.keep_outputs:
                 host = kpts.cpu().numpy()
                 self.kept += [(_np(rows[i]).copy(), host[i, :n[i]]) for i in range(B)]
             if any(a and b for a, b in zip(n, nl)):
                 dev = kpts.device
-                keep = torch.arange(kpts.shape[1], device=dev)[None, :] < torch.tensor(n, device=dev)[:, None]
-                pk = scaled[keep].contiguous()  # (sum n, K, ndim), image after image
+                pk = scaled[ops.kept_rows(torch.tensor(n, device=dev), kpts.shape[1])].contiguous()  # (sum n, K, ndim), image after image
                 gk = torch.from_numpy(np.concatenate([pb["kpts"].reshape(-1, K, 3) for pb in pbatches], 0)).to(dev)
-                ar = torch.from_numpy(np.concatenate(areas).astype(np.float32)).to(dev)
+                ar = torch.from_numpy(np.concatenate([self._gt_area(pb["bbox"]) for pb in pbatches]).astype(np.float32)).to(dev)
                 sg = torch.from_numpy(np.asarray(self.sigma, np.float32)).to(dev)
-                pred_off, gt_off = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(nl)])
-                out, off = _ops.kpt_iou(pk, pred_off, gk, gt_off, ar, sg)
-                host = out.cpu().numpy()  # the one D2H copy of the batch's matrices
-                ious = [host[off[i]: off[i] + nl[i] * n[i]].reshape(nl[i], n[i]) if n[i] and nl[i] else None for i in range(B)]
-        for si, pred in enumerate(rows):
-            self.seen += 1
-            pred = _np(pred).astype(np.float32).reshape(-1, 6)
-            npr = pred.shape[0]
-            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), tp=np.zeros((npr, self.niou), bool), tp_p=np.zeros((npr, self.niou), bool))
-            pbatch = pbatches[si]
-            cls, bbox = pbatch["cls"], pbatch["bbox"]
-            stat["target_cls"] = cls
-            stat["target_img"] = np.unique(cls)
-            if npr == 0:
-                if nl[si]:
-                    for k in self.stats:
-                        self.stats[k].append(stat[k])
-                continue
-            if self.single_cls:
-                pred = pred.copy()
-                pred[:, 5] = 0
-            predn = DetectionValidator._prepare_pred(self, pred, pbatch)
-            stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
-            if nl[si]:
-                stat["tp"] = self._process_batch(predn, bbox, cls)
-                if on_device:
-                    stat["tp_p"] = self._process_batch(predn, bbox, cls, iou=ious[si])
-                else:
-                    pk = torch.as_tensor(_np(kpts[si]), dtype=torch.float32)[:npr].reshape(npr, K, -1).clone()
-                    ops.scale_coords(pbatch["imgsz"], pk, pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"])
-                    stat["tp_p"] = self._process_batch(predn, bbox, cls, pk.numpy(), pbatch["kpts"])
-            for k in self.stats:
-                self.stats[k].append(stat[k])
+                ious = pair_matrices(lambda pred_off, gt_off: _ops.kpt_iou(pk, pred_off, gk, gt_off, ar, sg), n, nl)
 
-    # ---- reference detect/val.py:179-188 + PoseMetrics.process / results_dict
-    def get_stats(self):
-        stats = {k: (np.concatenate(v, 0) if v else np.zeros((0, self.niou) if k in ("tp", "tp_p") else 0)) for k, v in self.stats.items()}
-        self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc)
-        self.nt_per_image = np.bincount(stats["target_img"].astype(int), minlength=self.nc)
-        stats.pop("target_img", None)
-        if len(stats["tp"]) and stats["tp"].any():  # (the reference tests the box matches only, detect/val.py:186)
-            self.metrics.process(**stats)
-            self.box, self.pose = self.metrics.box, self.metrics.pose
-        self.results_dict = self.metrics.results_dict
-        return self.results_dict
+        def tp_p(si, predn, pbatch):
+            if on_device:
+                return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], iou=ious[si])
+            pk = torch.as_tensor(_np(kpts[si]), dtype=torch.float32)[:len(predn)].reshape(len(predn), K, -1).clone()
+            ops.scale_coords(pbatch["imgsz"], pk, pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"])
+            return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], pk.numpy(), pbatch["kpts"])
 
-    @torch.no_grad()
-    def __call__(self, dataloader):
-        """dataloader: iterable of batch dicts in DetectionValidator's format plus "keypoints" (see the class docstring).  Returns the results
-        dict (reference PoseMetrics.results_dict: five box keys, five pose keys, fitness)."""
-        self.init_metrics()
-        for batch in dataloader:
-            batch = self.preprocess(batch)
-            with torch.cuda.device(self.device):
-                preds = self.postprocess(self._forward(batch["img"]))
-                self.update_metrics(preds, batch)
-        return self.get_stats()
+        self._image_stats(rows, batch, pbatches, tp_p=tp_p)
 
     def update(self, images, labels):
         raise NotImplementedError("PoseValidator: the (images, labels) convenience of the detect task carries no keypoints; call it with batches")
 
 
-class ClassificationValidator:
+class ClassificationValidator(BaseValidator):
     """Validation loop for the classify task, mirroring the reference's models/yolo/classify/val.py (`init_metrics` :41-47, `preprocess`
     :49-54, `update_metrics` :56-60, `postprocess` :74-76, `get_stats` :78-81) with ClassifyMetrics.
 
@@ -565,12 +539,11 @@ class ClassificationValidator:
     batch)` with a numpy array / CPU tensor of probabilities) are ranked by the same rule on the host: the route the CPU tests take.
     plots=True raises; the confusion matrix is not built."""
 
+    val_options = {"plots": False}
+
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, plots=False):
-        if plots:
-            raise NotImplementedError("ClassificationValidator: plots=True is not built (confusion matrix and sample plots)")
-        self.model = getattr(model, "model", model) if not hasattr(model, "forward_layers") else model
-        self.half = half
-        self.device = torch.device(device) if device is not None else next(self.model.parameters()).device
+        refuse_options("ClassificationValidator", "confusion matrix and sample plots", plots=plots)
+        super().__init__(model, half, device)
         self.metrics = metrics.ClassifyMetrics()
         self.init_metrics()
 
@@ -580,16 +553,8 @@ class ClassificationValidator:
         self.pred, self.targets = [], []
         self.results_dict = dict(zip(self.metrics.keys + ["fitness"], [0.0] * 3))
 
-    def preprocess(self, batch):
-        img = batch["img"].to(self.device, non_blocking=True)
-        scale = 255.0 if img.dtype == torch.uint8 else 1.0
-        img = img.half() if self.half else img.float()
-        batch = dict(batch)
-        batch["img"] = (img / scale if scale != 1.0 else img).contiguous()
-        return batch
-
     def postprocess(self, preds):
-        """-> the (B, min(nc, 5)) int32 top classes of the forward that just ran (device tensor)."""
+        """-> the (B, min(nc, 5)) int32 top classes of the forward that just ran (device tensor); what the forward returned is not used."""
         return self.model.model[-1].top5[0]
 
     @staticmethod
@@ -611,17 +576,6 @@ class ClassificationValidator:
         self.metrics.process(self.targets, self.pred)
         self.results_dict = self.metrics.results_dict
         return self.results_dict
-
-    @torch.no_grad()
-    def __call__(self, dataloader):
-        self.init_metrics()
-        for batch in dataloader:
-            batch = self.preprocess(batch)
-            with torch.cuda.device(self.device):
-                self.model(batch["img"])
-                top = self.postprocess(None)
-            self.update_metrics(top, batch)
-        return self.get_stats()
 
 
 class FastSAMValidator(SegmentationValidator):

@@ -31,6 +31,11 @@ def clip_boxes(boxes, shape):
     return boxes
 
 
+def kept_rows(count, max_det):
+    """(B, max_det) bool, on count's device: which rows of a fixed-size (B, max_det, ...) NMS output exist, given the (B,) kept counts."""
+    return torch.arange(max_det, device=count.device)[None, :] < count[:, None]
+
+
 def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xywh=False):
     """Rescale xyxy boxes from the network input shape to the original image shape (reference :92-127)."""
     if ratio_pad is None:

@@ -5,7 +5,9 @@ import pytest
 import torch
 
 import edge_yolo_amd
+import synthdata as synth
 from edge_yolo_amd.data.augment import LetterBox
+from edge_yolo_amd.utils import ops as uops
 from oracle import letterbox as olb
 
 pytestmark = pytest.mark.gpu
@@ -50,3 +52,29 @@ def test_predict_accepts_ndarray_sources():
     b[:, [0, 2]] = b[:, [0, 2]].clamp(max=320)
     b[:, [1, 3]] = b[:, [1, 3]].clamp(max=240)
     torch.testing.assert_close(a, b, rtol=0, atol=1e-3)
+
+
+def test_predict_images_of_two_shapes_in_one_call():
+    """[120x70, 60x90] at imgsz 96: shapes differ, so the letterbox is the full 96x96 square (auto=False) and every image's rows go through
+    scale_boxes with its own gain and pad.  Graph on and off agree exactly; the results are scale_boxes (which clips) applied to the
+    predictor's own device-step rows."""
+    r = np.random.default_rng(7)
+    ims = [r.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((120, 70), (60, 90))]
+    model = edge_yolo_amd.YOLO("yolo11n-test.yaml")
+    model.model.load_state_dict(synth.synth_state_dict({k: tuple(v.shape) for k, v in model.model.state_dict().items()}))
+    kw = dict(conf=0.25, iou=0.7, imgsz=96, device="cuda:0")  # the conf of tests/test_gpu_model.py's predict tests
+    res = model.predict(ims, **kw)
+    eager = model.predict(ims, graph=False, **kw)
+    p = model.predictor
+    im = p.preprocess(ims)
+    assert tuple(im.shape) == (2, 3, 96, 96)
+    boxes, count, _, _ = p._device_step(im)
+    for i, (a, e) in enumerate(zip(res, eager)):
+        n = int(count[i])
+        print(f"image {i}: kept {n}")
+        assert len(a) == n >= 1 and a.orig_shape == a.boxes.orig_shape == ims[i].shape[:2]
+        assert torch.equal(a.boxes.data, e.boxes.data)
+        det = boxes[i, :n].clone()
+        det[:, :4] = uops.scale_boxes(im.shape[2:], det[:, :4], ims[i].shape)
+        assert torch.equal(a.boxes.data, det)
+        assert bool((det[:, :4] >= 0).all()) and bool((det[:, [0, 2]] <= ims[i].shape[1]).all()) and bool((det[:, [1, 3]] <= ims[i].shape[0]).all())

@@ -135,6 +135,34 @@ def test_predict_end_to_end(golden, half):
     assert torch.equal(aug[0].obb.data, r.data)
 
 
+def test_predict_ndarray_source_of_another_aspect(golden):
+    """uint8 HWC images taller than wide (120x70 at imgsz 96: a 96x64 network input, gain 0.8, padded left and right), so
+    scale_boxes(..., xywh=True) runs with a gain and a pad.  Graph on and off agree exactly; the results are what the reference's
+    post-process makes of the predictor's own device step."""
+    import edge_yolo_amd
+    from edge_yolo_amd.utils import ops as uops
+    model = edge_yolo_amd.YOLO("yolo11n-obb.yaml")
+    model.model.load_state_dict(obb_synth.state_dict(model.model.state_dict()))
+    r = np.random.default_rng(3)
+    ims = [r.integers(0, 256, (120, 70, 3), dtype=np.uint8) for _ in range(2)]
+    kw = dict(conf=float(golden["conf"]), iou=0.7, imgsz=96, device="cuda:0")  # the golden's conf
+    res = model.predict(ims, **kw)
+    eager = model.predict(ims, graph=False, **kw)
+    p = model.predictor
+    im = p.preprocess(ims)
+    assert tuple(im.shape) == (2, 3, 96, 64)
+    rows, count, index, _ = p._device_step(im)
+    for i, (a, e) in enumerate(zip(res, eager)):
+        n = int(count[i])
+        print(f"image {i}: kept {n}")
+        assert a.boxes is None and len(a) == len(a.obb) == n >= 1 and a.orig_shape == a.obb.orig_shape == (120, 70)
+        assert torch.equal(a.obb.data, e.obb.data)
+        det = rows[i, :n]
+        rb = uops.regularize_rboxes(torch.cat([det[:, :4], det[:, -1:]], -1))
+        rb[:, :4] = uops.scale_boxes(im.shape[2:], rb[:, :4], (120, 70), xywh=True)
+        assert torch.equal(a.obb.data, torch.cat([rb, det[:, 4:6]], -1))
+
+
 @pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
 def test_predict_with_class_filter(golden, half):
     """predict(classes=[...]) through the captured graph: the class mask is uploaded by the warm-up calls, never inside the capture; the
