@@ -15,7 +15,7 @@ from ... import _lib as L
 
 __all__ = ("DFL", "Proto", "SPPF", "C2f", "C2fAttn", "MaxSigmoidAttnBlock", "BNContrastiveHead","C3", "C3k", "C3k2", "Bottleneck", "Attention", "PSABlock", "C2PSA", "LinearAttention",
            "PSABlock_LinearAttention", "C2PSA_LinearAttention", "AAttn", "ABlock", "A2C2f", "DSBottleneck", "DSC3k", "DSC3K2_Wavelet",
-           "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "_DSUnit", "_LGLAdapter", "_DSUnitWithLGL", "DSC3K2_LGL",
+           "DSC3K2", "Mlp", "CMlp", "LocalAgg", "GlobalSparseAttn", "SelfAttn", "LGLBlock", "DSC3K2_LGL",
            "AdaHyperedgeGen", "AdaHGConv", "AdaHGComputation", "C3AH", "FuseModule", "HyperACE", "DownsampleConv", "FullPAD_Tunnel",
            "RepBottleneck", "RepCSP", "RepNCSPELAN4", "ELAN1", "AConv", "ADown", "SPPELAN", "CBLinear", "CBFuse", "SCDown", "RepVGGDW", "CIB", "C2fCIB", "PSA",
            "C2", "GhostBottleneck", "C3Ghost", "SPP", "ResNetBlock", "ResNetLayer")
@@ -25,11 +25,70 @@ def _slot(buf, i, c):
     return buf[:, i * c:(i + 1) * c]
 
 
-class _Chains(nn.Module):
+def _stacked(*convs):
+    """1x1 convs over the same input as one launch: their (BN-folded) filters and biases concatenated along Cout."""
+    ws, bs = zip(*(m.folded() for m in convs))
+    return torch.cat(ws, 0), torch.cat(bs, 0)
+
+
+def _stacked_act(*convs):
+    """The one activation code a stacked launch of these convs would apply, or None when they do not share one."""
+    acts = {_act_code(m.act) for m in convs}
+    return acts.pop() if len(acts) == 1 else None
+
+
+def _repeated(conv):
+    """conv(a + p) == conv over the virtual concat [a | p] with the weight repeated along Cin: one launch, no add kernel."""
+    w, b = conv.folded()
+    return torch.cat((w, w), 1), b
+
+
+def _scale_vec(mod, tag, param, x):
+    """Device fp32 (C,) scale vector for ops.scale_add_channels on x: a 0-d, (1,) or (C,) `param` rounded to x's dtype (as the reference's
+    product is) and broadcast over the channels; cached on `mod` (a _Packed)."""
+    C = x.shape[1]
+    return mod._packed((tag, x.dtype, x.device, C), lambda: param.detach().to(x.dtype).float().expand(C).to(x.device).contiguous())
+
+
+def _pool_pyramid(cv_in, cv_out, x, out):
+    """cv_in -> three chained 5x5 max-pools (ONE ey_sppf_pool launch into slots 1-3 of a 4 c buffer) -> cv_out over the 4-way concat."""
+    x = L.as_nhwc(x)
+    B, _, H, W = x.shape
+    c = cv_in.conv.out_channels
+    buf = L.empty_nhwc(B, 4 * c, H, W, x.dtype, x.device)
+    cv_in(x, out=buf[:, :c])
+    ops.sppf_pool(_slot(buf, 0, c), _slot(buf, 1, c), _slot(buf, 2, c), _slot(buf, 3, c))
+    return cv_out(buf, out=out)
+
+
+def _attn_ffn(attn, ffn, x, out=None):
+    """x + attn(x); x + ffn(x): both residual adds ride in conv epilogues."""
+    x = attn(x, res=x)
+    return ffn[1](ffn[0](x), out=out, res=x)
+
+
+def _c2psa(mod, x, out):
+    """cv1 splits into (a, b); the blocks of `mod.m` chain on b, the last writing back into b's half of cv1's buffer; cv2 reads the buffer."""
+    t = mod.cv1(x)
+    b = t[:, mod.c:]
+    for i, m in enumerate(mod.m):
+        b = m(b, out=t[:, mod.c:] if i == len(mod.m) - 1 else None)
+    return mod.cv2(t, out=out)
+
+
+def _ds_pair(cv1, cv2, x, add, out):
+    """[x +] cv2(cv1(x)) of two DSConvs: both and the residual as one band kernel on the small maps, else two launches."""
+    y = ops.dsb_pair(cv1, cv2, x, add, out=out)
+    if y is not None:
+        return y
+    return cv2(cv1(x), out=out, res=x if add else None)
+
+
+class _Chains(_Packed):
     """Mixin: pointwise chains of a block -- runs of 1x1 convs whose pixels do not interact -- as ONE launch each (nn/_block.py tiled
     programs: recorded from the ordinary module code below; one 512-thread workgroup per 64-pixel tile with register-resident weights
     where ey_block_fast_plan takes the chain, else one 256-thread workgroup per 32-pixel tile walks the stages).  The caches
-    hold packed weights, so they are dropped whenever parameters move or reload.  `pw_chains = False` keeps one launch per conv."""
+    hold packed weights, so they live in _Packed's cache and drop with it.  `pw_chains = False` keeps one launch per conv."""
 
     # True, False, or a tuple of chain names.  Measured on MI355X inside the benchmarked step (batch 32, C2PSA at 256 channels, 20x20,
     # kernel trace; profiles/chain_fast_*): the four-conv tail as one launch 22.9 us on the register-weight executor (44.5 us on
@@ -39,23 +98,11 @@ class _Chains(nn.Module):
 
     def _chain(self, name):
         from .._block import BlockCache
-        d = self.__dict__.setdefault("_chain_caches", {})
-        c = d.get(name)
-        if c is None:
-            c = d[name] = BlockCache(f"{type(self).__name__}.{name}", tiled=True)
-        return c
+        return self._packed(("chain", name), lambda: BlockCache(f"{type(self).__name__}.{name}", tiled=True))
 
     def _chains_on(self, x, name=None):
         on = self.pw_chains if isinstance(self.pw_chains, bool) else (name is None or name in self.pw_chains)
         return bool(on) and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float16 and ops.RECORD is None
-
-    def _apply(self, fn, *a, **k):
-        self.__dict__["_chain_caches"] = {}
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.__dict__["_chain_caches"] = {}
-        return super()._load_from_state_dict(*a, **k)
 
 
 class DFL(nn.Module):
@@ -108,16 +155,18 @@ class C2f(nn.Module):
         self.cv2 = Conv((2 + n) * self.c, c2, 1)
         self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
 
-    def forward(self, x, out=None, tail=None):
-        """tail (extension): the stride-2 3x3 Conv module that consumes this block's output and nothing else does -- cv2 and that conv then
-        run as one kernel where the shape allows (ops.pw_conv3s2), and the TAIL's output is returned."""
+    def forward(self, x, out=None):
         B, _, H, W = x.shape  # x may be a VirtualCat (upsample+concat folded into cv1)
         c, n = self.c, len(self.m)
-        buf = L.empty_nhwc(B, (2 + n) * c, H, W, x.dtype, x.device)
+        buf = L.empty_nhwc(B, self.cv2.conv.in_channels, H, W, x.dtype, x.device)  # (2 + n) slots, and those a subclass's cv2 reads beyond them
         self.cv1(x, out=buf[:, :2 * c])
         for i, m in enumerate(self.m):
             m(_slot(buf, 1 + i, c), out=_slot(buf, 2 + i, c))
+        self._extra_slots(buf, c, n)
         return self.cv2(buf, out=out)
+
+    def _extra_slots(self, buf, c, n):
+        """Hook: a subclass fills the slots behind the n blocks' (C2fAttn)."""
 
 
 class C3(_Packed):
@@ -133,15 +182,14 @@ class C3(_Packed):
 
     def _cv12(self):
         """cv1 and cv2 are both 1x1 convs over the same input: stack their (BN-folded) filters -> one launch."""
-        (w1, b1), (w2, b2) = self.cv1.folded(), self.cv2.folded()
-        return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
+        return _stacked(self.cv1, self.cv2)
 
     def _cv12_act(self):
         """The one activation code of the stacked launch: cv1 and cv2 carry the same activation (the model's: SiLU, or the YAML's `activation:`)."""
-        a1, a2 = _act_code(self.cv1.act), _act_code(self.cv2.act)
-        if a1 != a2:
+        act = _stacked_act(self.cv1, self.cv2)
+        if act is None:
             raise NotImplementedError("C3: cv1 and cv2 with different activations cannot share the stacked launch")
-        return a1
+        return act
 
     def forward(self, x, out=None, cv12=None):
         """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (chained into the producer of x)."""
@@ -232,7 +280,7 @@ class MaxSigmoidAttnBlock(_Packed):
         return self._packed(("guide", dtype, device), build)
 
     def forward(self, x, out=None):
-        x = L.as_nhwc(ops.as_tensor(x))
+        x = L.as_nhwc(x)
         g, bias, sc = self.guide(x.dtype, x.device)
         if g.shape[0] not in (1, x.shape[0]):
             raise ValueError(f"MaxSigmoidAttnBlock: text for {g.shape[0]} images, batch of {x.shape[0]}")
@@ -249,15 +297,8 @@ class C2fAttn(C2f):
         self.cv2 = Conv((3 + n) * self.c, c2, 1)
         self.attn = MaxSigmoidAttnBlock(self.c, self.c, gc=gc, ec=ec, nh=nh)
 
-    def forward(self, x, out=None):
-        B, _, H, W = x.shape  # x may be a VirtualCat (upsample+concat folded into cv1)
-        c, n = self.c, len(self.m)
-        buf = L.empty_nhwc(B, (3 + n) * c, H, W, x.dtype, x.device)
-        self.cv1(x, out=buf[:, :2 * c])
-        for i, m in enumerate(self.m):
-            m(_slot(buf, 1 + i, c), out=_slot(buf, 2 + i, c))
+    def _extra_slots(self, buf, c, n):
         self.attn(_slot(buf, 1 + n, c), out=_slot(buf, 2 + n, c))
-        return self.cv2(buf, out=out)
 
 
 class BNContrastiveHead(nn.Module):
@@ -283,15 +324,8 @@ class SPPF(nn.Module):
         self.cv1 = Conv(c1, c_, 1, 1)
         self.cv2 = Conv(c_ * 4, c2, 1, 1)
 
-    def forward(self, x, out=None, cv12=None):
-        """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (chained into the producer of x)."""
-        x = L.as_nhwc(x)
-        B, _, H, W = x.shape
-        c_ = self.cv1.conv.out_channels
-        buf = L.empty_nhwc(B, 4 * c_, H, W, x.dtype, x.device)
-        self.cv1(x, out=buf[:, :c_])
-        ops.sppf_pool(_slot(buf, 0, c_), _slot(buf, 1, c_), _slot(buf, 2, c_), _slot(buf, 3, c_))
-        return self.cv2(buf, out=out)
+    def forward(self, x, out=None):
+        return _pool_pyramid(self.cv1, self.cv2, x, out)
 
 
 class SPP(nn.Module):
@@ -309,13 +343,7 @@ class SPP(nn.Module):
         self.m = nn.ModuleList([nn.MaxPool2d(kernel_size=x, stride=1, padding=x // 2) for x in k])
 
     def forward(self, x, out=None):
-        x = L.as_nhwc(ops.as_tensor(x))
-        B, _, H, W = x.shape
-        c_ = self.cv1.conv.out_channels
-        buf = L.empty_nhwc(B, 4 * c_, H, W, x.dtype, x.device)
-        self.cv1(x, out=buf[:, :c_])
-        ops.sppf_pool(_slot(buf, 0, c_), _slot(buf, 1, c_), _slot(buf, 2, c_), _slot(buf, 3, c_))
-        return self.cv2(buf, out=out)
+        return _pool_pyramid(self.cv1, self.cv2, x, out)
 
 
 # ----------------------------------------------------------------------------------------------- attention
@@ -334,11 +362,6 @@ class Attention(_Packed):
         self.proj = Conv(dim, dim, 1, act=False)
         self.pe = Conv(dim, dim, 3, 1, g=dim, act=False)
 
-    def _proj2(self):
-        # proj(a + p) == conv over the virtual concat [a | p] with the weight repeated: one launch, no add kernel
-        w, b = self.proj.folded()
-        return torch.cat((w, w), 1), b
-
     def forward(self, x, out=None, res=None):
         x = L.as_nhwc(x)
         B, C, H, W = x.shape
@@ -350,7 +373,7 @@ class Attention(_Packed):
         for h in range(nh):  # v.reshape(B, C, H, W): gather the per-head value channels
             ops.copy_slice(qkv[:, h * per + 2 * kd:(h + 1) * per], v[:, h * hd:(h + 1) * hd])
         p = self.pe(v)
-        return ops.conv2d(self, [a, p], self._proj2, 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj2")
+        return ops.conv2d(self, [a, p], lambda: _repeated(self.proj), 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj2")  # proj(a + p)
 
 
 class PSABlock(nn.Module):
@@ -365,8 +388,7 @@ class PSABlock(nn.Module):
         self.ffn = nn.Sequential(Conv(c, hidden, k=1, s=1, act=True), Conv(hidden, c, k=1, s=1, act=False))
 
     def forward(self, x, out=None):
-        x = self.attn(x, res=x)
-        return self.ffn[1](self.ffn[0](x), out=out, res=x)
+        return _attn_ffn(self.attn, self.ffn, x, out)
 
 
 class C2PSA(nn.Module):
@@ -381,11 +403,7 @@ class C2PSA(nn.Module):
         self.m = nn.Sequential(*(PSABlock(self.c, attn_ratio=0.5, num_heads=self.c // 64) for _ in range(n)))
 
     def forward(self, x, out=None):
-        t = self.cv1(x)
-        b = t[:, self.c:]
-        for i, m in enumerate(self.m):
-            b = m(b, out=t[:, self.c:] if i == len(self.m) - 1 else None)
-        return self.cv2(t, out=out)
+        return _c2psa(self, x, out)
 
 
 class LinearAttention(_Packed):
@@ -401,11 +419,17 @@ class LinearAttention(_Packed):
         self.qkv = nn.Conv2d(dim, 3 * dim, kernel_size=1, bias=qkv_bias)
         self.proj = nn.Conv2d(dim, dim, kernel_size=1, bias=proj_bias)
 
+    def _qkv_folded(self):
+        return fold_bn(self.qkv.weight, self.qkv.bias, None)
+
+    def _proj_folded(self):
+        """(w, b) of proj in fp32; without a bias b is None (the launch then adds none), not zeros."""
+        return self.proj.weight.detach().float(), self.proj.bias.detach().float() if self.proj.bias is not None else None
+
     def forward(self, x, out=None, res=None):
-        qkv = ops.conv2d(self, [x], lambda: fold_bn(self.qkv.weight, self.qkv.bias, None), 1, 1, 0, L.ACT_NONE, tag="qkv")
+        qkv = ops.conv2d(self, [x], self._qkv_folded, 1, 1, 0, L.ACT_NONE, tag="qkv")
         y = ops.linear_attention(qkv, self.num_heads)
-        bias_fn = (lambda: (self.proj.weight.detach().float(), self.proj.bias.detach().float() if self.proj.bias is not None else None))
-        return ops.conv2d(self, [y], bias_fn, 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj")
+        return ops.conv2d(self, [y], self._proj_folded, 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj")
 
 
 class PSABlock_LinearAttention(nn.Module):
@@ -418,8 +442,7 @@ class PSABlock_LinearAttention(nn.Module):
         self.ffn = nn.Sequential(Conv(dim, hidden, k=1, s=1, act=True), Conv(hidden, dim, k=1, s=1, act=False))
 
     def forward(self, x, out=None):
-        x = self.attn(x, res=x)
-        return self.ffn[1](self.ffn[0](x), out=out, res=x)
+        return _attn_ffn(self.attn, self.ffn, x, out)
 
 
 class C2PSA_LinearAttention(_Chains):
@@ -441,25 +464,19 @@ class C2PSA_LinearAttention(_Chains):
             y = self._forward_chained(x, out)
             if y is not None:
                 return y
-        t = self.cv1(x)
-        b = t[:, self.c:]
-        for i, m in enumerate(self.m):
-            b = m(b, out=t[:, self.c:] if i == len(self.m) - 1 else None)
-        return self.cv2(t, out=out)
+        return _c2psa(self, x, out)
 
     def _forward_chained(self, x, out):
         blk, c = self.m[0], self.c
         at = blk.attn
-        qkv_w = lambda: fold_bn(at.qkv.weight, at.qkv.bias, None)  # noqa: E731
-        proj_w = lambda: (at.proj.weight.detach().float(), at.proj.bias.detach().float() if at.proj.bias is not None else None)  # noqa: E731
 
         def head(x0):  # cv1 -> qkv of the attention branch
             t = self.cv1(x0)
-            return [t, ops.conv2d(at, [t[:, c:]], qkv_w, 1, 1, 0, L.ACT_NONE, tag="qkv")]
+            return [t, ops.conv2d(at, [t[:, c:]], at._qkv_folded, 1, 1, 0, L.ACT_NONE, tag="qkv")]
 
         def tail(y, t):  # x1 = b + proj(y); x2 = x1 + ffn(x1) (written over b, in place per pixel); cv2([a | x2])
             b = t[:, c:]
-            x1 = ops.conv2d(at, [y], proj_w, 1, 1, 0, L.ACT_NONE, res=b, tag="proj")
+            x1 = ops.conv2d(at, [y], at._proj_folded, 1, 1, 0, L.ACT_NONE, res=b, tag="proj")
             blk.ffn[1](blk.ffn[0](x1), out=b, res=x1)
             return [self.cv2(t, out=out)]
 
@@ -489,28 +506,20 @@ class AAttn(_Packed):
         self.proj = Conv(all_head_dim, dim, 1, act=False)
         self.pe = Conv(all_head_dim, dim, 5, 1, 2, g=dim, act=False)
 
-    def _qkv(self):
-        (w1, b1), (w2, b2) = self.qk.folded(), self.v.folded()
-        return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
-
-    def _proj2(self):
-        w, b = self.proj.folded()
-        return torch.cat((w, w), 1), b
-
     def forward(self, x, out=None, res=None):
         B, _, H, W = x.shape
         if (H * W) % self.area:  # the reference's reshape to (B*area, N/area, C) fails here too
             raise ValueError(f"AAttn: {H}x{W} = {H * W} tokens do not split into {self.area} equal areas")
-        x = L.as_nhwc(ops.as_tensor(x))
+        x = L.as_nhwc(x)
         c = self.num_heads * self.head_dim
-        qkv = ops.conv2d(self, [x], self._qkv, 1, 1, 0, L.ACT_NONE, tag="qkv")  # [q | k | v]
+        qkv = ops.conv2d(self, [x], lambda: _stacked(self.qk, self.v), 1, 1, 0, L.ACT_NONE, tag="qkv")  # [q | k | v]
         v = qkv[:, 2 * c:]
         p = self.pe(v)
         a = ops.area_attention(qkv[:, :c], qkv[:, c:2 * c], v, self.num_heads, self.area, self.head_dim ** -0.5)
-        return ops.conv2d(self, [a, p], self._proj2, 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj2")
+        return ops.conv2d(self, [a, p], lambda: _repeated(self.proj), 1, 1, 0, L.ACT_NONE, out=out, res=res, tag="proj2")
 
 
-class ABlock(nn.Module):
+class ABlock(_Packed):
     """x + AAttn(x); x + mlp(x) (reference block.py:1359-1406)."""
 
     def __init__(self, dim, num_heads, mlp_ratio=1.2, area=1):
@@ -533,11 +542,7 @@ class ABlock(nn.Module):
             return self.mlp[1](h, out=out, res=x)
         # a hidden width off the MFMA conv's 8-channel granularity (the default mlp_ratio 1.2 at 64 channels; the YAMLs use 2.0 / 1.5)
         # takes the direct conv, which has no residual epilogue: the add is the layer-scale kernel with gamma = 1 (exact)
-        d = self.__dict__.setdefault("_ones", {})
-        key = (h.device, x.shape[1])
-        if key not in d:
-            d[key] = torch.ones(x.shape[1], device=h.device)
-        return ops.scale_add_channels(x, d[key], self.mlp[1](h), out=out)
+        return ops.scale_add_channels(x, _scale_vec(self, "ones", torch.ones(()), x), self.mlp[1](h), out=out)
 
 
 class A2C2f(_Packed):
@@ -571,8 +576,7 @@ class A2C2f(_Packed):
         if self.gamma is None:
             return self.cv2(buf, out=out)
         x = ops.as_tensor(x)
-        gamma = self._packed(("gamma", x.dtype, x.device), lambda: self.gamma.detach().to(x.dtype).float().to(x.device).contiguous())
-        return ops.scale_add_channels(x, gamma, self.cv2(buf), out=out)
+        return ops.scale_add_channels(x, _scale_vec(self, "gamma", self.gamma, x), self.cv2(buf), out=out)
 
 
 # ----------------------------------------------------------------------------------------------- DS / wavelet
@@ -587,10 +591,7 @@ class DSBottleneck(nn.Module):
         self.add = shortcut and c1 == c2
 
     def forward(self, x, out=None):
-        y = ops.dsb_pair(self.cv1, self.cv2, x, self.add, out=out)  # both DSConvs + the residual as one band kernel on the small maps
-        if y is not None:
-            return y
-        return self.cv2(self.cv1(x), out=out, res=x if self.add else None)
+        return _ds_pair(self.cv1, self.cv2, x, self.add, out)
 
 
 class DSC3k(C3):
@@ -773,16 +774,14 @@ class DSC3K2_Wavelet(nn.Module):
         c, n = self.c, len(self.m)
         t = self.cv1(x)  # [a | b]
         buf = L.empty_nhwc(B, (1 + n) * c, H, W, x.dtype, x.device)  # [wave(b) | m_0 | ...]
-        pre = None
+        kw = {}
         if n and isinstance(self.m[0], C3):  # the DSC3k behind the enhancer starts with a 1x1 over the enhancer's output: chained into its tail conv
-            _, pre = self.wave(t[:, c:], out=_slot(buf, 0, c), then=dict(mod=self.m[0], folded_fn=self.m[0]._cv12, act=self.m[0]._cv12_act(), tag="cv12"))
+            kw["cv12"] = self.wave(t[:, c:], out=_slot(buf, 0, c), then=dict(mod=self.m[0], folded_fn=self.m[0]._cv12, act=self.m[0]._cv12_act(), tag="cv12"))[1]
         else:
             self.wave(t[:, c:], out=_slot(buf, 0, c))
         for i, m in enumerate(self.m):
-            if i == 0 and pre is not None:
-                m(_slot(buf, i, c), out=_slot(buf, 1 + i, c), cv12=pre)
-            else:
-                m(_slot(buf, i, c), out=_slot(buf, 1 + i, c))
+            m(_slot(buf, i, c), out=_slot(buf, 1 + i, c), **kw)
+            kw = {}
         # cat(a, wave(b), m...) is never built: cv2 reads the two buffers as one virtual concat
         if tail is not None:
             y = ops.pw_conv3s2(self.cv2, tail, [t[:, :c], buf])
@@ -919,7 +918,7 @@ class GlobalSparseAttn(_Packed):
                 raise ValueError(f"input tokens {N} != H*W {H * W}")
             y = self.forward(x.contiguous().view(B, H, W, C).permute(0, 3, 1, 2), norm=norm)
             return y.permute(0, 2, 3, 1).reshape(B, N, C)
-        x = L.as_nhwc(ops.as_tensor(x))
+        x = L.as_nhwc(x)
         B, C, H, W = x.shape
         if C % self.num_heads:
             raise ValueError(f"GlobalSparseAttn: {C} channels do not split into {self.num_heads} heads")
@@ -982,10 +981,7 @@ class _DSUnit(nn.Module):
         self.add = bool(shortcut)
 
     def forward(self, x, out=None):
-        y = ops.dsb_pair(self.ds1, self.ds2, x, self.add, out=out)
-        if y is not None:
-            return y
-        return self.ds2(self.ds1(x), out=out, res=x if self.add else None)
+        return _ds_pair(self.ds1, self.ds2, x, self.add, out)
 
 
 class _LGLAdapter(_Packed):
@@ -1003,10 +999,8 @@ class _LGLAdapter(_Packed):
         self.gamma = nn.Parameter(torch.zeros(1))
 
     def forward(self, x, out=None):
-        x = L.as_nhwc(ops.as_tensor(x))
-        C = x.shape[1]
-        gamma = self._packed(("gamma", x.dtype, x.device, C), lambda: self.gamma.detach().to(x.dtype).float().expand(C).to(x.device).contiguous())
-        return ops.scale_add_channels(x, gamma, self.lgl(x), out=out)
+        x = L.as_nhwc(x)
+        return ops.scale_add_channels(x, _scale_vec(self, "gamma", self.gamma, x), self.lgl(x), out=out)
 
 
 class _DSUnitWithLGL(nn.Module):
@@ -1101,16 +1095,15 @@ class C3AH(_Packed):
         self.m = AdaHGComputation(embed_dim=c_, num_hyperedges=num_hyperedges, num_heads=num_heads, dropout=0.1, context=context)
         self.cv3 = Conv(2 * c_, c2, 1)
 
-    def _cv12(self):
-        (w1, b1), (w2, b2) = self.cv1.folded(), self.cv2.folded()
-        return torch.cat((w1, w2), 0), torch.cat((b1, b2), 0)
+    def _run_cv12(self, x):
+        """The stacked cv1|cv2 output (it takes cv1's activation)."""
+        return ops.conv2d(self, [L.as_nhwc(x)], lambda: _stacked(self.cv1, self.cv2), 1, 1, 0, _stacked_act(self.cv1), tag="cv12")
 
     def forward(self, x, out=None, cv12=None):
         """cv12 (extension): the stacked cv1|cv2 output when the caller has already computed it (HyperACE stacks both branches)."""
-        from .conv import _act_code
         c_ = self.cv1.conv.out_channels
         if cv12 is None:
-            cv12 = ops.conv2d(self, [L.as_nhwc(ops.as_tensor(x))], self._cv12, 1, 1, 0, _act_code(self.cv1.act), tag="cv12")
+            cv12 = self._run_cv12(x)
         h = self.m(cv12[:, :c_])
         return ops.conv2d(self.cv3, [h, cv12[:, c_:]], self.cv3.folded, 1, 1, 0, _act_code(self.cv3.act), out=out)
 
@@ -1129,8 +1122,7 @@ class FuseModule(nn.Module):
             self.conv_out = Conv(3 * c_in, c_in, 1)
 
     def forward(self, x, out=None):
-        from .conv import _act_code
-        x0, x1, x2 = (L.as_nhwc(ops.as_tensor(t)) for t in x)
+        x0, x1, x2 = (L.as_nhwc(t) for t in x)
         B, c1, H, W = x1.shape
         c0 = x0.shape[1]
         if (x0.shape[2] // 2, x0.shape[3] // 2) != (H, W) or (2 * x2.shape[2], 2 * x2.shape[3]) != (H, W):
@@ -1157,29 +1149,21 @@ class HyperACE(_Packed):
         self.branch1 = C3AH(self.c, self.c, e2, num_hyperedges, context)
         self.branch2 = C3AH(self.c, self.c, e2, num_hyperedges, context)
 
-    def _cv1234(self):
-        ws, bs = zip(*(m.folded() for b in (self.branch1, self.branch2) for m in (b.cv1, b.cv2)))
-        return torch.cat(ws, 0), torch.cat(bs, 0)
-
     def forward(self, X, out=None):
-        from .conv import _act_code
         x = self.fuse(X)
         B, _, H, W = x.shape
         c, n = self.c, len(self.m)
         buf = L.empty_nhwc(B, (4 + n) * c, H, W, x.dtype, x.device)  # [y0 | out1 | y2 | m_1 .. m_n | out2]
         self.cv1(x, out=buf[:, :3 * c])
         b1, b2 = self.branch1, self.branch2
-        acts = {_act_code(m.act) for b in (b1, b2) for m in (b.cv1, b.cv2)}
-        if len(acts) == 1:
-            t = ops.conv2d(self, [_slot(buf, 1, c)], self._cv1234, 1, 1, 0, acts.pop(), tag="cv1234")  # [b1.cv1 | b1.cv2 | b2.cv1 | b2.cv2]
+        convs = (b1.cv1, b1.cv2, b2.cv1, b2.cv2)
+        y1, act = _slot(buf, 1, c), _stacked_act(*convs)
+        if act is not None:
+            t = ops.conv2d(self, [y1], lambda: _stacked(*convs), 1, 1, 0, act, tag="cv1234")  # [b1.cv1 | b1.cv2 | b2.cv1 | b2.cv2]
             h = b1.cv1.conv.out_channels
             t1, t2 = t[:, :2 * h], t[:, 2 * h:]
         else:
-            t1 = t2 = None
-        y1 = _slot(buf, 1, c)
-        if t1 is None:
-            t1 = ops.conv2d(b1, [y1], b1._cv12, 1, 1, 0, _act_code(b1.cv1.act), tag="cv12")
-            t2 = ops.conv2d(b2, [y1], b2._cv12, 1, 1, 0, _act_code(b2.cv1.act), tag="cv12")
+            t1, t2 = b1._run_cv12(y1), b2._run_cv12(y1)
         b1(y1, out=_slot(buf, 1, c), cv12=t1)  # y1 is dead once both branches' 1x1 convs have read it
         b2(y1, out=_slot(buf, 3 + n, c), cv12=t2)
         for i, m in enumerate(self.m):
@@ -1213,10 +1197,8 @@ class FullPAD_Tunnel(_Packed):
         self.gate = nn.Parameter(torch.tensor(0.0))
 
     def forward(self, x, out=None):
-        a, t = (L.as_nhwc(ops.as_tensor(v)) for v in x)
-        C = t.shape[1]
-        gamma = self._packed(("gate", t.dtype, t.device, C), lambda: self.gate.detach().to(t.dtype).float().expand(C).to(t.device).contiguous())
-        return ops.scale_add_channels(a, gamma, t, out=out)
+        a, t = (L.as_nhwc(v) for v in x)
+        return ops.scale_add_channels(a, _scale_vec(self, "gate", self.gate, t), t, out=out)
 
 
 # ----------------------------------------------------------------------------------------------- YOLOv9 (GELAN)
@@ -1403,13 +1385,7 @@ class SPPELAN(nn.Module):
         self.cv5 = Conv(4 * c3, c2, 1, 1)
 
     def forward(self, x, out=None):
-        x = L.as_nhwc(x)
-        B, _, H, W = x.shape
-        c = self.c
-        buf = L.empty_nhwc(B, 4 * c, H, W, x.dtype, x.device)
-        self.cv1(x, out=buf[:, :c])
-        ops.sppf_pool(_slot(buf, 0, c), _slot(buf, 1, c), _slot(buf, 2, c), _slot(buf, 3, c))
-        return self.cv5(buf, out=out)
+        return _pool_pyramid(self.cv1, self.cv5, x, out)
 
 
 class CBLinear(_Packed):
@@ -1562,9 +1538,7 @@ class PSA(nn.Module):
 
     def forward(self, x, out=None):
         t = self.cv1(x)
-        b = t[:, self.c:]
-        b = self.attn(b, res=b)
-        self.ffn[1](self.ffn[0](b), out=t[:, self.c:], res=b)
+        _attn_ffn(self.attn, self.ffn, t[:, self.c:], out=t[:, self.c:])
         return self.cv2(t, out=out)
 
 

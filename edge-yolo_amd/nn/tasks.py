@@ -214,6 +214,14 @@ def _parse_model(d, ch, verbose=False):
     return nn.Sequential(*layers), sorted(save)
 
 
+def _inputs(m, x, y):
+    """Layer m's input, gathered from the previous layer's output x and the saved outputs y: m.f = -1 is x, an int one saved output, a list
+    one entry per index (-1 in it is x again)."""
+    if isinstance(m.f, int):
+        return x if m.f == -1 else y[m.f]
+    return [x if j == -1 else y[j] for j in m.f]
+
+
 def _layer_down(m, down):
     """Downsampling factor of layer m's output, given those of the layers before it (`down`)."""
     f = m.f if isinstance(m.f, int) else m.f[1 if isinstance(m, HyperACE) else -1 if isinstance(m, CBFuse) else 0]  # HyperACE works at its middle input's resolution, CBFuse at its last's
@@ -273,12 +281,9 @@ class BaseModel(nn.Module):
         """_predict_once without the last (head) module: returns the head's input list (for callers that pipeline the head apart)."""
         y = []
         for m in self.model[:-1]:
-            if m.f != -1:
-                x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
-            x = m(x)
+            x = m(_inputs(m, x, y))
             y.append(x if m.i in self.save else None)
-        h = self.model[-1]
-        return [x if j == -1 else y[j] for j in h.f] if not isinstance(h.f, int) else (x if h.f == -1 else y[h.f])
+        return _inputs(self.model[-1], x, y)
 
     def forward_layers(self, state, lo, hi, head_nms=None):
         """Layers [lo, hi) of _predict_once (reference tasks.py:152-179) on `state` = (x, saved outputs so far) -> new state: lets a
@@ -303,8 +308,7 @@ class BaseModel(nn.Module):
                     y.extend([None, x if 1 in self.save else None])
                     i = 2
                     continue
-            if m.f != -1:
-                x = y[m.f] if isinstance(m.f, int) else [x if j2 == -1 else y[j2] for j2 in m.f]
+            x = _inputs(m, x, y)
             if (type(m) is DSC3K2_Wavelet and i + 1 < hi and i not in self.save and type(self.model[i + 1]) is Conv and self.model[i + 1].f == -1
                     and self.model[i + 1].conv.stride == (2, 2) and self.model[i + 1].conv.kernel_size == (3, 3)):
                 x = m(x, tail=self.model[i + 1])  # the block's closing 1x1 + the down-sampling conv behind it as one kernel where the shape allows
@@ -364,9 +368,7 @@ class BaseModel(nn.Module):
                 yy[j] = t
             xx = x0
             for m in self.model[lo:hi]:
-                if m.f != -1:
-                    xx = yy[m.f] if isinstance(m.f, int) else [xx if j2 == -1 else yy[j2] for j2 in m.f]
-                xx = m(xx)
+                xx = m(_inputs(m, xx, yy))
                 yy.append(xx if m.i in self.save else None)
             if not torch.is_tensor(xx):
                 from ._block import BlockUnsupported

@@ -124,3 +124,28 @@ def test_in_place_update_never_takes_the_band_kernel():
         y0 = blk(xd)
     assert torch.equal(y, y0)
     check(y, om.dsc3k(sd, "dsc3k", x.half().float(), 2, 3, 5), torch.float16, what="DSC3k")
+
+
+@pytest.mark.parametrize("n", [1, 3])
+def test_odd_chain_ends_in_the_spare_buffer(n):
+    """DSC3k with an odd number of DSBottlenecks (every shipped one has two): the chain alternates slot 0 -> spare -> slot 0 -> spare and ends
+    in the spare buffer, so cv3 reads [spare | cv2(x)] as two sources; `out=` may be a channel slot of a wider buffer."""
+    from edge_yolo_amd import _lib as L
+    from edge_yolo_amd.nn import modules as M
+    blk = M.DSC3k(64, 64, n=n, k1=3, k2=5)
+    sd = load_synth(blk, "dsc3k")
+    blk = to_dev(blk, torch.float16)
+    x = synth.synth_images(3, 20, 20, seed=5, c=64) - 0.5
+    xd = x.to("cuda", torch.float16)
+    y, ker = _traced(lambda: blk(xd))
+    assert ker.count("dsb_pair_kernel<3,5>") == n and sum("dsb_pair" in k for k in ker) == n, ker
+    with tuned(dsb_pair=0):
+        y0 = blk(xd)
+    assert torch.equal(y, y0)
+    check(y, om.dsc3k(sd, "dsc3k", x.half().float(), n, 3, 5), torch.float16, what=f"DSC3k n={n}")
+    buf = L.empty_nhwc(3, 192, 20, 20, torch.float16, "cuda")
+    buf.fill_(-7.0)
+    before = buf.clone()
+    y2 = blk(xd, out=buf[:, 64:128])
+    assert y2.data_ptr() == buf[:, 64:128].data_ptr() and torch.equal(buf[:, 64:128], y)
+    assert torch.equal(buf[:, :64], before[:, :64]) and torch.equal(buf[:, 128:], before[:, 128:])

@@ -181,12 +181,17 @@ def test_sppf_channel_groups(M, dtype, c1, h, w):
 
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("linear", [True, False])
-@pytest.mark.parametrize("h,w", [(4, 4), (20, 20)])
-def test_c2psa(M, dtype, linear, h, w):
-    m = (M.C2PSA_LinearAttention if linear else M.C2PSA)(256, 256, 1)
+@pytest.mark.parametrize("h,w,n", [pytest.param(4, 4, 1, id="4-4"), pytest.param(20, 20, 1, id="20-20"), pytest.param(4, 4, 2, id="4-4-n2")])
+def test_c2psa(M, dtype, linear, h, w, n):
+    """n = 2: only the last block writes back into b's half of cv1's buffer; the first one's output is a map of its own."""
+    m = (M.C2PSA_LinearAttention if linear else M.C2PSA)(256, 256, n)
     sd = load_synth(m, "psa")
     x, xd = _x(2, 256, h, w, dtype)
-    check(to_dev(m, dtype)(xd), om.c2psa(sd, "psa", x, 1, linear), dtype, scale=2)
+    # n = 2 in f16 through two softmax-attention blocks: max |error| 0.1910 against the oracle (|y| up to 64.3) measured at the commit before the
+    # shared bodies, outside the scale=2 gate -> scale = ceil(2 * 0.1910 / 0.03) = 13.  The other n = 2 cases hold scale=2 there (linear f16
+    # 0.0138, fp32 8.8e-5 / 8.8e-6) and keep it.
+    scale = 13 if (n == 2 and not linear and dtype == torch.float16) else 2
+    check(to_dev(m, dtype)(xd), om.c2psa(sd, "psa", x, n, linear), dtype, scale=scale)
 
 
 @pytest.mark.parametrize("dtype", DT)
