@@ -136,6 +136,7 @@ SIGNATURES = {
     "ey_unpool2_layernorm": (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_dysample": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ey_process_mask": (_i, [_i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "ey_process_mask_native": (_i, [_i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ey_deconv2x2_packed_bytes": (_sz, [_i, _i, _i]),
     "ey_deconv2x2_pack_weight": (_i, [_i, _i, _i, _vp, _vp, _sz]),
     "ey_deconv2x2": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp]),

@@ -16,14 +16,15 @@
 //               touch a source row of some point).  Threads meet through a wave
 //               shuffle tree and LDS in a fixed order.  Writes inter[p][n], full[n], hit[q][n].
 //   mp_select   a workgroup owns one image: iou, the per-box argmax (ties to the lower index) and keep.
-// Per-axis source index and weights are torch's CPU operator's (aten/src/ATen/native/UpSample.h compute_source_index_and_lambda with
-// float opmath; the source coordinate is ONE fused multiply-add, which is what the operator's compiled code evaluates -- the two-rounding
-// form differs from it in individual weights):
+// Per-axis source index and weights (mp_source, mask_source.h) are torch's CPU operator's (aten/src/ATen/native/UpSample.h
+// compute_source_index_and_lambda with float opmath; the source coordinate is ONE fused multiply-add, which is what the operator's compiled
+// code evaluates -- the two-rounding form differs from it in individual weights):
 //   in == out:  i0 = i1 = y, l0 = 1, l1 = 0
 //   otherwise:  r = max(fmaf((float)in / out, y + 0.5f, -0.5f), 0);  i0 = min((int)r, in - 1);  l1 = min(max(r - i0, 0), 1);
 //               i1 = i0 + (i0 < in - 1);  l0 = 1 - l1
 // This file is built with -ffp-contract=off: every fused operation below is written out.
 #include "common.h"
+#include "mask_source.h"
 
 #define MP_MAXB 64   // images per call (the tables travel as a kernel argument)
 #define MP_MAXP 32   // box prompts
@@ -41,29 +42,6 @@ struct mp_tab {
 struct __attribute__((packed, aligned(1))) mp_u4 {
   unsigned x, y, z, w;
 };
-
-struct mp_src {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ mp_src mp_source(int y, int in, int out) {
-  mp_src s;
-  if (in == out) {
-    s.i0 = s.i1 = y;
-    s.l0 = 1.f;
-    s.l1 = 0.f;
-    return s;
-  }
-  const float scale = __fdiv_rn((float)in, (float)out);
-  float r = __builtin_fmaf(scale, __fadd_rn((float)y, 0.5f), -0.5f);
-  r = r < 0.f ? 0.f : r;
-  s.i0 = min((int)floorf(r), in - 1);
-  s.l1 = fminf(fmaxf(__fsub_rn(r, (float)s.i0), 0.f), 1.f);
-  s.i1 = s.i0 + (s.i0 < in - 1 ? 1 : 0);
-  s.l0 = __fsub_rn(1.f, s.l1);
-  return s;
-}
 
 // W[b][axis][index * NB + slot]; axis 0 = rows (mh entries), axis 1 = columns (mw entries)
 __global__ __launch_bounds__(256) void mp_weights(mp_tab tab, int mh, int mw, int NB, float* __restrict__ W) {

@@ -368,12 +368,22 @@ class DetectionPredictor:
 
 class SegmentationPredictor(DetectionPredictor):
     """reference models/yolo/segment/predict.py:9-57.  The device step is DetectionPredictor's captured graph plus the Proto and cv4 launches
-    of the Segment head; `postprocess` assembles the masks of the whole batch with ONE ey_process_mask launch sized by the true number of
-    kept boxes (it runs after the count came back, outside the graph).  Masks are at the network-input resolution (retina_masks=False)."""
+    of the Segment head; `postprocess` assembles the masks of the whole batch with ONE launch sized by the true number of kept boxes (it
+    runs after the count came back, outside the graph).  retina_masks=False (default): ey_process_mask, masks at the network-input
+    resolution, cropped by the boxes before scale_boxes.  retina_masks=True (:48-50): the boxes are scaled to each original image first,
+    then ey_process_mask_native resizes every mask to its image's original shape -- the images of a batch may all differ -- and crops it
+    there; tensor sources have original == input shape and still take that path (resize, then crop).  retina_masks is a constructor
+    argument; through the facade it is the predictor class RetinaMasksPredictor (`YOLO.predict(source, predictor=RetinaMasksPredictor)`),
+    the facade's `retina_masks=True` keyword itself still raises."""
 
     augment_policy = ("warn", "SegmentationModel")
-    # (cfg/default.yaml `retina_masks`; masks come at the network-input resolution)
-    refused_options = {"retina_masks": "retina_masks=True (masks at the original image resolution, ops.process_mask_native) is not built"}
+    # (cfg/default.yaml `retina_masks`: the keyword of YOLO.predict stays refused; the built path is named in the text)
+    refused_options = {"retina_masks": "retina_masks=True is not a keyword of predict(): masks at the original image resolution (ops.process_mask_native) come "
+                                       "from predict(source, predictor=RetinaMasksPredictor) or SegmentationPredictor(model, device, retina_masks=True)"}
+
+    def __init__(self, model, device, *args, retina_masks=False, **kwargs):
+        super().__init__(model, device, *args, **kwargs)
+        self.retina_masks = bool(retina_masks)
 
     def _device_step(self, im):
         cand, (_, mcs, p) = self.model(im, head_nms={"conf": self.conf, "classes": self.classes, "keep_pred": self.keep_pred})
@@ -386,29 +396,44 @@ class SegmentationPredictor(DetectionPredictor):
 
     def postprocess(self, boxes, count, img, source, index=None, proto=None, coefs=None):
         from ..nn import _ops
+        from .results import Masks
         n = count.tolist()  # (the one host sync of the batch; everything below is sized by it)
         B, max_det = index.shape
         ih, iw = img.shape[2:]
         mh, mw = proto.shape[2:]
         s = ih // mh
-        if s * mh != ih or s * mw != iw:
+        if not self.retina_masks and (s * mh != ih or s * mw != iw):
             raise NotImplementedError(f"SegmentationPredictor: input {ih}x{iw} over proto {mh}x{mw} is not one integer ratio")
         total = sum(n)
-        masks = None
+        masks, rows = None, None
         if total:
             # rows (image, anchor) and boxes of the kept detections, image after image, built on the device from count and index
             keep = ops.kept_rows(count, max_det)
             rows = torch.stack([torch.arange(B, dtype=torch.int32, device=index.device)[:, None].expand(B, max_det)[keep], index[keep]], 1).contiguous()
-            masks = _ops.process_mask(proto, coefs, rows, boxes[keep][:, :4].contiguous(), s)  # boxes in network-input pixels, before scale_boxes
+            if not self.retina_masks:
+                masks = _ops.process_mask(proto, coefs, rows, boxes[keep][:, :4].contiguous(), s)  # boxes in network-input pixels, before scale_boxes
         self._masks, self._mask_counts = masks, n  # the batch's masks as ONE uint8 tensor, image after image (FastSAMPredictor scores them in one launch)
         results = super().postprocess(boxes, count, img, source)
-        off = 0
+        off = [0]
+        for k in n:
+            off.append(off[-1] + k)
+        if total and self.retina_masks:  # (segment/predict.py:48-50) the boxes are in original-image pixels now: one launch for all originals
+            scaled = torch.cat([r.boxes.xyxy for r in results if len(r.boxes)], 0).float().contiguous()
+            masks = _ops.process_mask_native(proto, coefs, rows, scaled, off, [r.orig_shape for r in results])[1]
         for i, r in enumerate(results):
             if n[i]:
-                from .results import Masks
-                r.masks = Masks(masks[off:off + n[i]], r.orig_shape)
-            off += n[i]
+                r.masks = Masks(masks[i] if self.retina_masks else masks[off[i]:off[i + 1]], r.orig_shape)
         return results
+
+
+class RetinaMasksPredictor(SegmentationPredictor):
+    """SegmentationPredictor with retina_masks=True, as a class the facade can be handed: `YOLO.predict(source, predictor=RetinaMasksPredictor)`
+    returns `masks.data` of shape (n_i, H0_i, W0_i) per image; boxes as without it."""
+
+    refused_options = {}
+
+    def __init__(self, model, device, *args, retina_masks=True, **kwargs):
+        super().__init__(model, device, *args, retina_masks=retina_masks, **kwargs)
 
 
 class FastSAMPredictor(SegmentationPredictor):
@@ -419,7 +444,13 @@ class FastSAMPredictor(SegmentationPredictor):
     masks of the whole batch (the resize is folded into per-axis weights) and nothing of the original resolution is allocated.  Text
     prompts need the CLIP encoder, which is not part of the build."""
 
-    def __init__(self, model, device, *args, **kwargs):
+    # the prompt kernel scores one (mh, mw) stack of the whole batch; masks at the original resolutions are not built for it
+    refused_options = {"retina_masks": "FastSAM: retina_masks=True (masks at the original image resolution) is not built: ey_mask_prompt scores the "
+                                       "network-resolution masks; use retina_masks=False"}
+
+    def __init__(self, model, device, *args, retina_masks=False, **kwargs):
+        if retina_masks:
+            raise NotImplementedError(self.refused_options["retina_masks"])
         super().__init__(model, device, *args, **kwargs)
         self.prompts = {}
 

@@ -53,7 +53,8 @@ class Boxes:
 
 
 class Masks:
-    """(n,h,w) instance masks at the network-input resolution.  `data` is torch.bool -- a view of the uint8 bytes ey_process_mask wrote (the
+    """(n,h,w) instance masks: at the network-input resolution (retina_masks=False, ey_process_mask), or at the image's original resolution
+    (retina_masks=True, ey_process_mask_native: h, w = orig_shape).  `data` is torch.bool -- a view of the uint8 bytes the kernel wrote (the
     reference keeps the same 0 / 1 values as fp32).  Polygon extraction (`xy`, `xyn`) needs cv2.findContours and is not built."""
 
     def __init__(self, masks, orig_shape):

@@ -252,18 +252,26 @@ class SegmentationValidator(TwoMetricValidator):
     resolution (mask_ratio 4) -- that does materialise the (nl, h, w) stack.
 
     Host masks (numpy / CPU tensors, `update_metrics(..., pred_masks=[...])` with a validator on the CPU) go through the numpy restatement of
-    mask_iou: the route the CPU tests take.  save_json, save_txt, plots and process_mask_native (ops.process_mask_native) are not built."""
+    mask_iou: the route the CPU tests take.
+
+    process_mask_native=True (the reference's `self.process = ops.process_mask_native` branch, segment/val.py:52, which it takes for
+    save_json / save_txt): the masks of all images at the network-input resolution in one `ey_process_mask_native` launch (shape = imgsz:
+    resized first, cropped by the boxes in input pixels after); the ground truth is resized to them on the cold path above.  It needs
+    a validator on the device: on the CPU, where only ready masks are scored, it raises.  save_json, save_txt and plots are not built."""
 
     metrics_cls, second, tp_second = metrics.SegmentMetrics, "seg", "tp_m"  # (reference segment/val.py:45-53)
-    val_options = {"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False}
+    val_options = {"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False, "process_mask_native": False}
 
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, overlap_mask=True,
                  save_json=False, save_txt=False, plots=False, process_mask_native=False):
-        refuse_options("SegmentationValidator", "COCO json / txt export, plots and ops.process_mask_native",
-                       save_json=save_json, save_txt=save_txt, plots=plots, process_mask_native=process_mask_native)
+        refuse_options("SegmentationValidator", "COCO json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
+        self.process_mask_native = bool(process_mask_native)
         self.overlap_mask = bool(overlap_mask)
         self.keep_outputs = False  # True: update_metrics appends (rows (n,6+nm), mask bits (n,mh,mw)) per image to self.kept, on the host
         super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+        if self.process_mask_native and self.device.type != "cuda":  # (the host route takes ready masks; the native assembly is the kernel alone)
+            raise NotImplementedError(f"SegmentationValidator: process_mask_native=True is built on ey_process_mask_native and this validator is on '{self.device}': "
+                                      "there is no CPU path; put the model on the device first (YOLO.val does) or pass device=")
 
     # ---- reference segment/val.py:39-43 (the masks stay integers: uint8 0/1 stacks, int32 index maps)
     def preprocess(self, batch):
@@ -307,6 +315,10 @@ class SegmentationValidator(TwoMetricValidator):
         dev = proto.device
         idx = torch.tensor([[i, j] for i in range(B) for j in range(n[i])], dtype=torch.int32).to(dev)
         ih, iw = imgsz
+        if self.process_mask_native:  # (N_total, ih, iw): every image has the network input's shape, so the flat buffer is one stack
+            boxes = torch.cat([r[:, :4].float() for r in rows], 0).contiguous()
+            flat, _ = _ops.process_mask_native(L.as_nhwc(proto), [coef], idx, boxes, batch_offsets(n), [(ih, iw)] * B)
+            return flat.view(sum(n), ih, iw)
         scale = torch.tensor([mw / iw, mh / ih, mw / iw, mh / ih], dtype=torch.float32, device=dev)
         boxes = (torch.cat([r[:, :4].float() for r in rows], 0) * scale).contiguous()
         return _ops.process_mask(L.as_nhwc(proto), [coef], idx, boxes, 1)
@@ -314,7 +326,8 @@ class SegmentationValidator(TwoMetricValidator):
     # ---- reference segment/val.py:93-97 (one image; update_metrics assembles the masks of the whole batch at once instead)
     def _prepare_pred(self, pred, pbatch, proto):
         predn = super()._prepare_pred(pred[:, :6], pbatch)
-        pred_masks = ops.process_mask(proto, pred[:, 6:], pred[:, :4], shape=pbatch["imgsz"])
+        process = ops.process_mask_native if self.process_mask_native else ops.process_mask
+        pred_masks = process(proto, pred[:, 6:], pred[:, :4], shape=pbatch["imgsz"])
         return predn, pred_masks
 
     @staticmethod

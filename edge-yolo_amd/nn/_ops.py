@@ -1195,6 +1195,53 @@ def mask_geometry(mask_hw, shape, padding=True):
     return (top, int(mh - pad[1]), left, int(mw - pad[0]), h0, w0)
 
 
+def process_mask_native(proto, coefs, rows, boxes, mask_off, shapes, out=None):
+    """Mask assembly at the original resolution (ey_process_mask_native): proto, coefs and rows as for process_mask; boxes fp32 (N,4) xyxy
+    in ORIGINAL-image pixels of the row's image (after scale_boxes); mask_off: host list, B+1 entries, image b owns rows mask_off[b] ..
+    mask_off[b+1]-1; shapes: the B original (H0, W0), which may all differ.  -> (flat, views): one flat uint8 buffer and image b's masks as
+    its (n_b, H0_b, W0_b) view, values 0 / 1, one after the other.  out=: a flat contiguous uint8 buffer of at least that many bytes to
+    fill (its first sum n_b H0_b W0_b bytes are written)."""
+    L.require_device(proto, "process_mask_native")
+    _no_block("process_mask_native")
+    if not L.is_nhwc_view(proto) or any(not L.is_nhwc_view(c) for c in coefs):
+        raise ValueError("process_mask_native: proto and the coefficient maps must be NHWC views")
+    B, nm, mh, mw = proto.shape
+    mask_off = [int(v) for v in mask_off]
+    if len(mask_off) != B + 1 or len(shapes) != B or mask_off[0] != 0:
+        raise ValueError(f"process_mask_native: mask_off must have B+1 = {B + 1} entries starting at 0 and shapes B entries")
+    N = mask_off[-1]
+    if rows.dtype != torch.int32 or boxes.dtype != torch.float32 or not rows.is_contiguous() or not boxes.is_contiguous() or rows.shape[0] < N or boxes.shape[0] < N:
+        raise ValueError("process_mask_native: rows must be contiguous int32 (N,2) and boxes contiguous fp32 (N,4)")
+    if any(c.shape[0] != B or c.shape[1] != nm or c.dtype != coefs[0].dtype for c in coefs):
+        raise ValueError(f"process_mask_native: coefficient maps {[tuple(c.shape) for c in coefs]} do not match proto {tuple(proto.shape)}")
+    nl = len(coefs)
+    if any(int(s[0]) < 1 or int(s[1]) < 1 for s in shapes):
+        raise ValueError(f"process_mask_native: original shapes {[tuple(s) for s in shapes]} must be at least 1 x 1")
+    geo = [mask_geometry((mh, mw), s) for s in shapes]
+    counts = [mask_off[b + 1] - mask_off[b] for b in range(B)]
+    out_off, total = [], 0
+    for k, g in zip(counts, geo):
+        out_off.append(total)
+        total += max(k, 0) * max(g[4], 0) * max(g[5], 0)
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=proto.device)
+    elif out.dim() != 1 or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < total or out.device != proto.device:
+        raise ValueError(f"process_mask_native: out= must be a flat contiguous uint8 buffer of at least {total} bytes on {proto.device}")
+    IA, PA, LA = ctypes.c_int * max(nl, 1), ctypes.c_void_p * max(nl, 1), ctypes.c_long * max(B, 1)
+    cp, cs = PA(*[c.data_ptr() for c in coefs]), IA(*[L.cstride(c) for c in coefs])
+    Hs, Ws = IA(*[c.shape[2] for c in coefs]), IA(*[c.shape[3] for c in coefs])
+    with _tr("process_mask_native_kernel", total + N * 24 + _nb(proto), 2.0 * N * mh * mw * nm, note=f"B{B} N{N} {mh}x{mw} -> {sorted(set(map(tuple, shapes)))}"):
+        rc = L.lib().ey_process_mask_native(L.dtype_code(proto.dtype), B, mh, mw, nm, proto.data_ptr(), L.cstride(proto), nl, cp,
+                                            L.dtype_code(coefs[0].dtype) if nl else L.F32, cs, Hs, Ws, N, rows.data_ptr(), boxes.data_ptr(),
+                                            (ctypes.c_int * (B + 1))(*mask_off), (ctypes.c_int * (6 * max(B, 1)))(*[v for g in geo for v in g]), LA(*out_off),
+                                            out.data_ptr(), L.stream())
+        if rc == -1:  # EY_EINVAL: a bad argument of the caller's (an empty crop, offsets that do not group the rows)
+            raise ValueError("ey_process_mask_native: " + L.lib().ey_last_error().decode(errors="replace"))
+        L.check(rc, "ey_process_mask_native")
+    views = [out[o:o + k * g[4] * g[5]].view(k, g[4], g[5]) if k > 0 else out[:0].view(0, max(g[4], 0), max(g[5], 0)) for o, k, g in zip(out_off, counts, geo)]
+    return out, views
+
+
 def mask_prompt(masks, mask_off, shapes, bboxes=None, points=None, labels=None, out=None, workspace=None):
     """FastSAM prompt selection of a batch (ey_mask_prompt): masks uint8 (N,mh,mw) 0/1 grouped by image through the host list mask_off
     (B+1 entries); shapes: the B original (H0, W0); bboxes: P host rows x1,y1,x2,y2 and points: Q host rows x,y with `labels`, int, in

@@ -1,7 +1,7 @@
 """Post-processing of the detection path, mirroring the reference's ultralytics/utils/ops.py:
 `make_divisible` (:130-143), `non_max_suppression` (:167-316), `xywh2xyxy` (:416-433), `scale_boxes` (:92-127),
-`clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693), `nms_rotated` (:146-164), `xywhr2xyxyxyxy` (:556-584),
-`regularize_rboxes` (:775-790).  NMS and mask assembly run in the HIP library (ey_nms, ey_nms_rotated, ey_process_mask); there is no
+`clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693), `process_mask_native` (:696-713), `nms_rotated` (:146-164), `xywhr2xyxyxyxy` (:556-584),
+`regularize_rboxes` (:775-790).  NMS and mask assembly run in the HIP library (ey_nms, ey_nms_rotated, ey_process_mask, ey_process_mask_native); there is no
 torch/torchvision fallback."""
 import math
 
@@ -282,6 +282,26 @@ def process_mask(protos, masks_in, bboxes, shape, upsample=False):
         if n == 0:
             return torch.empty((0, s * mh, s * mw), dtype=torch.uint8, device=protos.device)
         return _ops.process_mask(proto, [coef], rows, boxes.contiguous(), s)
+
+
+def process_mask_native(protos, masks_in, bboxes, shape):
+    """Reference signature (:696-713): protos [nm,mh,mw], masks_in [n,nm], bboxes [n,4] xyxy in `shape` = (h, w) pixels -> [n,h,w]: the
+    product, scale_masks' crop and bilinear resize to `shape` (any ratio), crop_mask on the resized map and the > 0 compare in one
+    ey_process_mask_native launch.  Returns uint8 0 / 1 where the reference returns the same values as fp32.  nm a multiple of 8 up to 64
+    (NotImplementedError otherwise); an empty crop raises ValueError where the reference's F.interpolate raises."""
+    from ..nn import _ops
+    from .. import _lib as L
+    nm, mh, mw = protos.shape
+    h, w = int(shape[0]), int(shape[1])
+    n = int(masks_in.shape[0])
+    if n == 0:
+        return torch.empty((0, h, w), dtype=torch.uint8, device=protos.device)
+    with torch.cuda.device(protos.device):
+        if masks_in.dtype not in (torch.float16, torch.float32):
+            masks_in = masks_in.float()
+        coef = masks_in.contiguous().view(1, n, 1, nm).permute(0, 3, 1, 2)  # one level, one row per "anchor"
+        rows = torch.stack([torch.zeros(n, dtype=torch.int32, device=protos.device), torch.arange(n, dtype=torch.int32, device=protos.device)], 1).contiguous()
+        return _ops.process_mask_native(L.as_nhwc(protos[None]), [coef], rows, bboxes[:, :4].float().contiguous(), [0, n], [(h, w)])[1][0]
 
 
 def scale_masks(masks, shape, padding=True):

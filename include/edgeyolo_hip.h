@@ -434,6 +434,31 @@ int ey_process_mask(int dtype, int B, int mh, int mw, int nm, const void* proto,
                     int coef_dtype, const int* coef_cstride, const int* H, const int* W, int N, const int* rows, const float* boxes, int s,
                     uint8_t* out, ey_stream_t stream);
 
+/* ---- Instance segmentation at the original resolution (utils/ops.py:696-737 process_mask_native + scale_masks + crop_mask, behind
+ * retina_masks=True in models/yolo/segment/predict.py:48-50 and process_mask_native in segment/val.py:52).  For each of N kept detections of a
+ * batch of B images, image b with the record geo[b] = (top, bottom, left, right, H0, W0):
+ *   v[r][c]    = sum_k coef_n[k] * proto[b, r, c, k]                          fp32, k ascending (as ey_process_mask)
+ *   v          = v[top:bottom, left:right]                                    scale_masks' crop of the proto grid
+ *   V[oy][ox]  = bilinear_{align_corners=False}(v -> H0 x W0)                 any ratio, up or down; per-axis index and weights of ey_scale_masks,
+ *                fl(fl(l0y * fl(fl(l0x * a) + fl(l1x * b))) + fl(l1y * fl(fl(l0x * c) + fl(l1x * d))))
+ *   out[oy][ox] = V > 0 and ox >= x1 and ox < x2 and oy >= y1 and oy < y2     crop_mask AFTER the resize, fp32 comparisons, as uint8 0 / 1
+ * proto, coef, coef_dtype, coef_cstride, H, W, rows: as for ey_process_mask.  boxes: DEVICE fp32 [N][4] x1,y1,x2,y2 in ORIGINAL-image pixels
+ * of the row's image (after scale_boxes, clipping included).  HOST arrays: mask_off (B + 1 entries, [0] == 0, non-decreasing, [B] == N): image
+ * b owns rows mask_off[b] .. mask_off[b+1] - 1; geo [B][6] as _ops.mask_geometry / ey_mask_prompt state it (the images may all differ);
+ * out_off [B]: image b's masks are the bytes out[out_off[b] .. out_off[b] + N_b H0 W0) viewed as (N_b, H0, W0), every one of them is written
+ * and nothing else; all output indexing is 64-bit.  A row whose image is not the one that owns it, or whose anchor is out of range, gives
+ * an all-zero mask and reads nothing; so does a box with a NaN corner.  N == 0 launches nothing.
+ * One launch: a workgroup owns (detection, band of output rows), keeps the low-resolution pixels a tile blends in LDS as fp32, and stores 16
+ * result bytes at a time wherever the address is a multiple of 16.  Tiles shrink with the ratio; where the original is smaller than half the crop
+ * (or a tile's sources would not fit the LDS) the four products of a pixel are read from proto directly, so no ratio is refused.  No
+ * atomics, fixed summation order: the same bytes run to run.
+ * EY_EUNSUPPORTED (nothing launched, nothing written): nm not a multiple of 8 up to 64, nlevels outside 1..4, B > 64, a target side of 2^24 or more,
+ * 2^31 or more work items.  EY_EINVAL: null pointers with N > 0, H0 or W0 < 1, an empty or misplaced crop (top >= bottom, left >= right: the
+ * reference's F.interpolate fails there too), offsets that do not group the rows by image. */
+int ey_process_mask_native(int dtype, int B, int mh, int mw, int nm, const void* proto, int proto_cstride, int nlevels, const void* const* coef,
+                           int coef_dtype, const int* coef_cstride, const int* H, const int* W, int N, const int* rows, const float* boxes,
+                           const int* mask_off, const int* geo, const long* out_off, uint8_t* out, ey_stream_t stream);
+
 /* ---- Dense transposed convolution k 2, s 2 with bias: Proto.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True) (nn/modules/block.py:123,129).
  *   y[b, 2i+di, 2j+dj, co] = bias[co] + sum_ci x[b, i, j, ci] * W[ci][co][di][dj]
  * as one GEMM [B H W x Cin] . [Cin x 4 Cout] whose epilogue scatters the four positions.  f16: MFMA with fp32 accumulation; fp32: the exact
