@@ -192,6 +192,41 @@ class Model(torch.nn.Module):
 
     __call__ = predict
 
+    def track(self, source=None, stream=False, persist=False, tracker=None, **kwargs):
+        """predict() followed by ByteTrack (reference engine/model.py `track`, trackers/track.py:53-87): image i of the batch is video stream i,
+        and every call is the next frame of each stream.  All streams advance in ONE ey_bytetrack_update launch, on the rows predict() returns
+        (original-image pixels); the tracks never leave the device.  An image with detections and returned tracks becomes `results[i][idx]`
+        (masks and keypoints follow their rows) with boxes [x1, y1, x2, y2, id, conf, cls]; an image without detections, or without returned
+        tracks, keeps its untracked Results (`boxes.id is None`).
+        persist: keep the tracks from the last call (a new batch size, max_det, device or tracker settings start afresh); without it every call
+        starts new trackers, as the reference does.  tracker: None, a dict or a YAML path with ByteTrack's settings (trackers.load_settings).
+        kwargs: predict()'s, conf defaults to 0.1 (ByteTrack wants the low-score detections); max_tracks (extension): slots per stream, 1024."""
+        from ..trackers import BYTETracker, load_settings
+        if self.task in ("obb", "classify"):
+            raise NotImplementedError(f"track(): the '{self.task}' task is not tracked (built: detect, segment, pose)")
+        settings = load_settings(tracker)
+        max_tracks = int(kwargs.pop("max_tracks", 1024))
+        kwargs.setdefault("conf", 0.1)
+        results = self.predict(source, **kwargs)
+        B, cap, dev = len(results), int(self.predictor.max_det), self.predictor.device
+        key = (B, cap, max_tracks, str(dev), tuple(sorted(settings.items())))
+        if not persist or getattr(self, "_tracker", None) is None or self._tracker_key != key:
+            self._tracker, self._tracker_key = BYTETracker(settings, streams=B, max_det=cap, max_tracks=max_tracks, device=dev), key
+        with torch.cuda.device(dev):
+            rows = torch.zeros((B, cap, 6), dtype=torch.float32, device=dev)
+            n = [min(len(r.boxes), cap) for r in results]
+            for i, r in enumerate(results):
+                if n[i]:
+                    rows[i, :n[i]] = r.boxes.data[:n[i], :6]
+            tracks, _, counts = self._tracker.update(rows, torch.tensor(n, dtype=torch.int32).to(dev))
+            for i, k in enumerate(counts.tolist()):
+                if n[i] == 0 or k == 0:
+                    continue
+                r = results[i][tracks[i, :k, 7].long()]
+                r.boxes = type(r.boxes)(tracks[i, :k, :7].to(results[i].boxes.data.dtype), r.boxes.orig_shape)
+                results[i] = r
+        return iter(results) if stream else results
+
     def val(self, dataloader=None, validator=None, **kwargs):
         """Validate on an iterable of batches in the reference's collate format (engine/validator.py::DetectionValidator; the segment task
         adds "masks", see SegmentationValidator; the pose task "keypoints", see PoseValidator) and return the results dict (reference

@@ -5,14 +5,21 @@ import torch
 
 
 class Boxes:
-    """(n,6) rows [x1,y1,x2,y2,conf,cls] in original-image pixels."""
+    """(n,6) rows [x1,y1,x2,y2,conf,cls], or (n,7) rows [x1,y1,x2,y2,track id,conf,cls] behind Model.track(), in original-image pixels
+    (reference engine/results.py:938-1010)."""
 
     def __init__(self, boxes, orig_shape):
         if boxes.ndim == 1:
             boxes = boxes[None, :]
-        assert boxes.shape[-1] == 6, f"expected 6 values but got {boxes.shape[-1]}"
+        assert boxes.shape[-1] in {6, 7}, f"expected 6 or 7 values but got {boxes.shape[-1]}"  # xyxy, track_id, conf, cls
         self.data = boxes
         self.orig_shape = orig_shape
+        self.is_track = boxes.shape[-1] == 7
+
+    @property
+    def id(self):
+        """track ids (n,), None without tracks."""
+        return self.data[:, -3] if self.is_track else None
 
     @property
     def xyxy(self):

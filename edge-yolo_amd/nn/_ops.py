@@ -1916,3 +1916,91 @@ def classify_transform(images, size, dtype, out=None, swap_rb=True):
         L.check(L.lib().ey_classify_transform(L.dtype_code(dtype), images.data_ptr(), B, h, w, 3 * w, 3 * w * h, out.data_ptr(), S, int(swap_rb), L.stream()),
                 "ey_classify_transform")
     return out
+
+
+def _int_out(what, name, t, rows, cols, dev):
+    """an int32 output of `what` handed in through out=: contiguous, on `dev`, (rows, >= cols)."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"{what}: out= {name} must be a contiguous int32 ({rows}, >= {cols}) tensor on {dev}")
+    return t
+
+
+def linear_assignment(costs, thresh, out=None):
+    """Thresholded linear assignments of a batch in one launch (ey_linear_assignment; what lap.lapjv(cost, extend_cost=True, cost_limit=thresh)
+    computes, reference trackers/utils/matching.py:20-61).  costs: a list of 2-D float32 device tensors (n_b, m_b) with unit column stride,
+    sizes may differ and may be 0; thresh: one float or one per problem.  -> (row_to_col (B, nmax), col_to_row (B, mmax)) int32, -1 =
+    unmatched; entries past a problem's own n_b / m_b are -1 when the tensors are made here and untouched in out= (a pair of contiguous
+    int32 tensors (B, >= nmax), (B, >= mmax))."""
+    costs = list(costs)
+    B = len(costs)
+    if B == 0:
+        raise ValueError("linear_assignment: no problems")
+    dev = costs[0].device
+    L.require_device(costs[0], "linear_assignment")
+    _no_block("linear_assignment")
+    for c in costs:
+        if not torch.is_tensor(c) or c.dim() != 2 or c.dtype != torch.float32 or c.device != dev or (c.numel() > 0 and ((c.shape[1] > 1 and c.stride(1) != 1) or (c.shape[0] > 1 and c.stride(0) < c.shape[1]))):
+            raise ValueError("linear_assignment: every cost matrix must be a 2-D float32 tensor with unit column stride on one device")
+    th = [float(thresh)] * B if not isinstance(thresh, (list, tuple)) else [float(t) for t in thresh]
+    if len(th) != B:
+        raise ValueError(f"linear_assignment: {len(th)} thresholds for {B} problems")
+    nmax, mmax = max(int(c.shape[0]) for c in costs), max(int(c.shape[1]) for c in costs)
+    if out is None:
+        r2c = torch.full((B, max(nmax, 1)), -1, dtype=torch.int32, device=dev)
+        c2r = torch.full((B, max(mmax, 1)), -1, dtype=torch.int32, device=dev)
+    else:
+        r2c, c2r = _int_out("linear_assignment", "row_to_col", out[0], B, nmax, dev), _int_out("linear_assignment", "col_to_row", out[1], B, mmax, dev)
+    desc = torch.tensor([[c.data_ptr(), c.shape[0], c.shape[1], c.stride(0) if c.shape[0] > 1 and c.numel() else max(int(c.shape[1]), 1)] for c in costs], dtype=torch.int64).to(dev)
+    tht = torch.tensor(th, dtype=torch.float32).to(dev)
+    nb = int(L.lib().ey_linear_assignment_workspace_bytes(B, nmax, mmax))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    with _tr("linear_assignment_kernel", _nb(*costs, r2c, c2r), note=f"{B} x <= {nmax}x{mmax}"):
+        L.check(L.lib().ey_linear_assignment(B, desc.data_ptr(), tht.data_ptr(), nmax, mmax, r2c.data_ptr(), int(r2c.shape[1]), c2r.data_ptr(), int(c2r.shape[1]),
+                                             ws.data_ptr(), nb, L.stream()), "ey_linear_assignment")
+    return r2c, c2r
+
+
+def bytetrack_state(streams, max_tracks, device):
+    """the device state ey_bytetrack_update advances: all zero = fresh trackers."""
+    B, T = int(streams), int(max_tracks)
+    return {"kf": torch.zeros((B, T, 72), dtype=torch.float64, device=device), "slot_i": torch.zeros((B, T, 8), dtype=torch.int32, device=device),
+            "slot_f": torch.zeros((B, T, 2), dtype=torch.float32, device=device), "hdr": torch.zeros((B, 4), dtype=torch.int32, device=device)}
+
+
+def bytetrack_update(rows, count, state, settings, out=None, workspace=None):
+    """One ByteTrack frame for B streams in one launch (ey_bytetrack_update).  rows float32 (B, cap, 6) x1,y1,x2,y2,score,cls; count int32 (B,);
+    state: the dict of bytetrack_state(), advanced in place; settings: track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
+    track_buffer, fuse_score.  -> (out_rows float32 (B, cap, 8) = x1,y1,x2,y2,id,score,cls,idx, ids int32 (B, cap), counts int32 (B,)); only
+    the first counts[b] rows of stream b are written.  out=: that triple, to write instead."""
+    L.require_device(rows, "bytetrack_update")
+    _no_block("bytetrack_update")
+    dev = rows.device
+    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not rows.is_contiguous() or rows.shape[1] < 1:
+        raise ValueError(f"bytetrack_update: rows must be a contiguous float32 (B, cap >= 1, 6) tensor, got {rows.dtype} {tuple(rows.shape)}")
+    B, cap = int(rows.shape[0]), int(rows.shape[1])
+    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous() or count.device != dev:
+        raise ValueError(f"bytetrack_update: count must be a contiguous int32 ({B},) tensor on {dev}")
+    T = int(state["kf"].shape[1])
+    for k, (shape, dt) in {"kf": ((B, T, 72), torch.float64), "slot_i": ((B, T, 8), torch.int32), "slot_f": ((B, T, 2), torch.float32), "hdr": ((B, 4), torch.int32)}.items():
+        t = state[k]
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"bytetrack_update: state['{k}'] must be a contiguous {dt} {shape} tensor on {dev}")
+    want = (((B, cap, 8), torch.float32), ((B, cap), torch.int32), ((B,), torch.int32))
+    if out is None:
+        out = tuple(torch.zeros(s, dtype=dt, device=dev) for s, dt in want)
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or t.device != dev for t, (s, dt) in zip(out, want)):
+            raise ValueError(f"bytetrack_update: out= must be contiguous tensors {want} on {dev}")
+    nb = int(L.lib().ey_bytetrack_workspace_bytes(B, cap, T))
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < nb or not workspace.is_contiguous() or workspace.device != dev or workspace.data_ptr() % 16:
+        raise ValueError(f"bytetrack_update: workspace must be a contiguous, 16-byte aligned uint8 tensor of >= {nb} bytes on {dev}")
+    s = settings
+    with _tr("bytetrack_update_kernel", _nb(rows, *out), note=f"{B} streams x {cap} rows, {T} slots"):
+        L.check(L.lib().ey_bytetrack_update(B, cap, T, float(s["track_high_thresh"]), float(s["track_low_thresh"]), float(s["new_track_thresh"]), float(s["match_thresh"]),
+                                            int(30 / 30.0 * s["track_buffer"]), int(bool(s["fuse_score"])), rows.data_ptr(), count.data_ptr(), state["kf"].data_ptr(),
+                                            state["slot_i"].data_ptr(), state["slot_f"].data_ptr(), state["hdr"].data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                            out[2].data_ptr(), workspace.data_ptr(), workspace.numel(), L.stream()), "ey_bytetrack_update")
+    return out

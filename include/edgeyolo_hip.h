@@ -535,6 +535,39 @@ int ey_mask_prompt(int B, int mh, int mw, const uint8_t* masks, const int* mask_
 enum { EY_MASK_U8 = 2 };
 int ey_scale_masks(int in_dtype, long planes, int H, int W, int top, int bottom, int left, int right, int H0, int W0, const void* x, void* y, ey_stream_t stream);
 
+/* ---- Object tracking (reference trackers/byte_tracker.py BYTETracker.update, trackers/utils/kalman_filter.py KalmanFilterXYAH,
+ * trackers/utils/matching.py).  Definition, phases, resources and bounds: DESIGN.md section 7r; the text of both kernels is
+ * csrc/track_core.inc.h, which also compiles for the host with one lane.
+ *
+ * ey_linear_assignment: B independent thresholded assignments in one launch, one workgroup each.  Problem b has an n x m fp32 cost matrix
+ * with row stride ld (elements) and finds the partial matching M that minimises sum over M of (c_ij - thresh[b]); pairs with c_ij > thresh[b]
+ * and NaN / Inf costs are never matched (what lap.lapjv(cost, extend_cost=True, cost_limit=thresh) computes).  Shortest augmenting paths with
+ * fp64 duals; equal costs go to the lower column, a tie between matching and not matching to not matching; the same bits run to run.
+ * desc: DEVICE int64 [B][4] = cost pointer, n, m, ld; n and m are clamped to 0 .. nmax / mmax.  thresh: DEVICE fp32 [B].
+ * row_to_col: DEVICE int32 [B][ldr], entries 0 .. n-1 of row b are written (-1 = unmatched), nothing else; col_to_row: [B][ldc], entries
+ * 0 .. m-1.  workspace: DEVICE, 16-byte aligned, ey_linear_assignment_workspace_bytes(B, nmax, mmax) bytes.  Loops: n augmentations of at most
+ * n + 1 path steps, each one pass over the m columns. */
+size_t ey_linear_assignment_workspace_bytes(int B, int nmax, int mmax);
+int ey_linear_assignment(int B, const long* desc, const float* thresh, int nmax, int mmax, int* row_to_col, int ldr, int* col_to_row, int ldc,
+                         void* workspace, size_t workspace_bytes, ey_stream_t stream);
+
+/* ey_bytetrack_update: one ByteTrack frame for B independent streams in ONE launch, one workgroup per stream; the tracks live on the device.
+ * rows: DEVICE fp32 [B][cap][6] = x1,y1,x2,y2,score,cls in image pixels; count: DEVICE int32 [B], clamped to 0 .. cap.  A stream whose count
+ * is 0 is left alone bit for bit (only out_count[b] = 0 is written).  A row with a NaN / Inf coordinate or score is not a detection.
+ * State, read and written in place (all zero = a fresh tracker): kf fp64 [B][max_tracks][72] = mean[8], covariance[8][8]; slot_i int32
+ * [B][max_tracks][8] = state (0 free, 1 tracked, 2 lost), activated, id, idx, frame, start frame, tracklet_len, 0; slot_f fp32
+ * [B][max_tracks][2] = score, cls; hdr int32 [B][4] = frame_id, last id given, overflow count, 0.  A new track takes the lowest free slot; a
+ * slot freed by the unconfirmed round of a frame is free for the new tracks of the same frame, one freed by expiry or as a duplicate from
+ * the next frame on.  With no free slot a new track is not started and hdr[2] counts it.
+ * Outputs: out_rows fp32 [B][cap][8] = x1,y1,x2,y2 (fp32 of the fp64 posterior), id, score, cls, idx -- rows 0 .. out_count[b]-1, ascending
+ * id, nothing else is written; out_ids int32 [B][cap]; out_count int32 [B].
+ * workspace: DEVICE, 16-byte aligned, ey_bytetrack_workspace_bytes(B, cap, max_tracks) bytes, nothing in it survives the call.
+ * EY_EUNSUPPORTED (nothing launched): 16 * max_tracks + 24 * cap > 65536 (the boxes of a stream are held in LDS). */
+size_t ey_bytetrack_workspace_bytes(int B, int cap, int max_tracks);
+int ey_bytetrack_update(int B, int cap, int max_tracks, float track_high_thresh, float track_low_thresh, float new_track_thresh, float match_thresh,
+                        int max_time_lost, int fuse_score, const float* rows, const int* count, double* kf, int* slot_i, float* slot_f, int* hdr,
+                        float* out_rows, int* out_ids, int* out_count, void* workspace, size_t workspace_bytes, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
