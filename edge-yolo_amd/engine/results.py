@@ -62,7 +62,8 @@ class Boxes:
 class Masks:
     """(n,h,w) instance masks: at the network-input resolution (retina_masks=False, ey_process_mask), or at the image's original resolution
     (retina_masks=True, ey_process_mask_native: h, w = orig_shape).  `data` is torch.bool -- a view of the uint8 bytes the kernel wrote (the
-    reference keeps the same 0 / 1 values as fp32).  Polygon extraction (`xy`, `xyn`) needs cv2.findContours and is not built."""
+    reference keeps the same 0 / 1 values as fp32).  `xy` / `xyn`: one polygon per mask from ey_mask_contours (utils.ops.masks2segments), for
+    masks on the device; a Masks moved to the host (`cpu()`, `numpy()`) raises there."""
 
     def __init__(self, masks, orig_shape):
         if masks.ndim == 2:
@@ -76,13 +77,22 @@ class Masks:
     def shape(self):
         return self.data.shape
 
+    def _segments(self, normalize):
+        if not torch.is_tensor(self.data) or not self.data.is_cuda:
+            raise NotImplementedError("Masks.xy / xyn: these masks are on the host; polygon extraction runs on the device only (ey_mask_contours, no "
+                                      "CPU path): read xy / xyn before cpu() / numpy()")
+        from ..utils import ops
+        return [ops.scale_coords(self.data.shape[1:], x, self.orig_shape, normalize=normalize) for x in ops.masks2segments(self.data)]
+
     @property
     def xy(self):
-        raise NotImplementedError("Masks.xy: polygon extraction (cv2.findContours) is not built; use Masks.data")
+        """one float32 (k, 2) polygon per mask in pixels of the original image (reference engine/results.py:1227-1251)."""
+        return self._segments(False)
 
     @property
     def xyn(self):
-        raise NotImplementedError("Masks.xyn: polygon extraction (cv2.findContours) is not built; use Masks.data")
+        """the same polygons divided by the original image's width and height (reference :1202-1225)."""
+        return self._segments(True)
 
     def cpu(self):
         return Masks(self.data.cpu(), self.orig_shape)

@@ -2004,3 +2004,80 @@ def bytetrack_update(rows, count, state, settings, out=None, workspace=None):
                                             state["slot_i"].data_ptr(), state["slot_f"].data_ptr(), state["hdr"].data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
                                             out[2].data_ptr(), workspace.data_ptr(), workspace.numel(), L.stream()), "ey_bytetrack_update")
     return out
+
+
+def mask_contours_launch(masks, windows, contour_cap, vertex_cap, out=None):
+    """One ey_mask_contours launch: masks uint8 (n >= 1, h, w), windows int32 (n, 4) or None -> (lens int32 (n, contour_cap), verts int32
+    (n, vertex_cap, 2), info int32 (n, 4) = contours found, vertices found, flags, 0), see include/edgeyolo_hip.h.  out=: that triple, to
+    write instead."""
+    n, h, w = (int(v) for v in masks.shape)
+    dev = masks.device
+    want = (((n, contour_cap), torch.int32), ((n, vertex_cap, 2), torch.int32), ((n, 4), torch.int32))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=dt, device=dev) for s, dt in want)
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(not torch.is_tensor(t) or tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or t.device != dev for t, (s, dt) in zip(out, want)):
+            raise ValueError(f"mask_contours: out= must be contiguous tensors {want} on {dev}")
+    nb = int(L.lib().ey_mask_contours_workspace_bytes(n, h, w))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    with _tr("mask_contours_kernel", _nb(masks, *out), note=f"{n} masks {h}x{w}, room for {contour_cap} contours / {vertex_cap} vertices each"):
+        L.check(L.lib().ey_mask_contours(n, h, w, masks.data_ptr(), windows.data_ptr() if windows is not None else None, contour_cap, vertex_cap,
+                                         out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), nb, L.stream()), "ey_mask_contours")
+    return out
+
+
+def mask_contours(masks, boxes=None, out=None, _contour_capacity=64, _vertex_capacity=4096):
+    """External contours of binary masks on the device (ey_mask_contours: what cv2.findContours(m, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0]
+    gives per mask).  masks: contiguous uint8 or bool (n, h, w) device tensor, non-zero = set, left untouched.  boxes: optional
+    (n, >= 4) xyxy in mask pixels, the boxes process_mask cropped the masks to: mask i is scanned inside floor / ceil of box i only (every
+    set pixel must lie inside it; the result is then the same).  -> a list of n lists of (k, 2) int32 numpy arrays of x, y, in OpenCV's
+    order (last found first).  Only the counts and the vertices cross to the host.  The launch writes into fixed-size buffers; when a mask
+    needs more room than they have, they grow to what the kernel counted and the launch is repeated, so nothing is ever cut short.
+    out=: the (lens, verts, info) tensors of mask_contours_launch for the first launch."""
+    if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool) or not masks.is_contiguous():
+        raise ValueError(f"mask_contours: masks must be a contiguous uint8 or bool (n, h, w) tensor, got {getattr(masks, 'dtype', type(masks))} "
+                         f"{tuple(getattr(masks, 'shape', ()))}")
+    L.require_device(masks, "mask_contours")
+    _no_block("mask_contours")
+    n, h, w = (int(v) for v in masks.shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"mask_contours: masks of {h} x {w} pixels")
+    dev = masks.device
+    windows = None
+    if boxes is not None:
+        if not torch.is_tensor(boxes) or boxes.dim() != 2 or boxes.shape[0] != n or boxes.shape[1] < 4 or boxes.device != dev:
+            raise ValueError(f"mask_contours: boxes must be a ({n}, >= 4) xyxy tensor on {dev}")
+        b = torch.nan_to_num(boxes[:, :4].float(), nan=0.0).clamp(0, max(h, w))
+        windows = torch.cat([b[:, :2].floor(), b[:, 2:].ceil()], 1).to(torch.int32).contiguous()
+    if n == 0:
+        return []
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    import numpy as np
+    ccap, vcap = max(int(_contour_capacity), 1), max(int(_vertex_capacity), 1)
+    if out is not None:  # (their sizes are the first launch's capacities)
+        out = tuple(out)
+        if len(out) != 3 or not all(torch.is_tensor(t) for t in out) or out[0].dim() != 2 or out[1].dim() != 3 or out[0].shape[1] < 1 or out[1].shape[1] < 1:
+            raise ValueError("mask_contours: out= must be the (lens, verts, info) tensors of mask_contours_launch")
+        ccap, vcap = int(out[0].shape[1]), int(out[1].shape[1])
+    for attempt in range(2):  # the second launch has the room the first one asked for
+        lens, verts, info = mask_contours_launch(masks, windows, ccap, vcap, out if attempt == 0 else None)
+        counts = info.cpu().numpy()
+        if (counts[:, 2] & 2).any():
+            raise L.HipLibraryError(f"mask_contours: a border walk passed its step bound in mask {int(np.nonzero(counts[:, 2] & 2)[0][0])}")
+        if int(counts[:, 0].max()) <= ccap and int(counts[:, 1].max()) <= vcap:
+            break
+        ccap, vcap = max(ccap, int(counts[:, 0].max())), max(vcap, int(counts[:, 1].max()))
+    else:
+        raise L.HipLibraryError("mask_contours: the second launch asked for more room than the first one counted")
+    nc, nv = info[:, 0:1], info[:, 1:2]
+    lens = lens[torch.arange(ccap, device=dev)[None, :] < nc].cpu().numpy()
+    verts = verts[torch.arange(vcap, device=dev)[None, :] < nv].cpu().numpy()
+    ends = np.cumsum(lens)
+    res, k = [], 0
+    for i in range(n):
+        c = int(counts[i, 0])
+        res.append([verts[ends[j] - lens[j]:ends[j]] for j in range(k + c - 1, k - 1, -1)])
+        k += c
+    return res

@@ -1,7 +1,7 @@
 """Post-processing of the detection path, mirroring the reference's ultralytics/utils/ops.py:
 `make_divisible` (:130-143), `non_max_suppression` (:167-316), `xywh2xyxy` (:416-433), `scale_boxes` (:92-127),
 `clip_boxes` (:319-338), `crop_mask` (:644-660), `process_mask` (:663-693), `process_mask_native` (:696-713), `nms_rotated` (:146-164), `xywhr2xyxyxyxy` (:556-584),
-`regularize_rboxes` (:775-790).  NMS and mask assembly run in the HIP library (ey_nms, ey_nms_rotated, ey_process_mask, ey_process_mask_native); there is no
+`regularize_rboxes` (:775-790), `masks2segments` (:793-821).  NMS and mask assembly run in the HIP library (ey_nms, ey_nms_rotated, ey_process_mask, ey_process_mask_native, ey_mask_contours); there is no
 torch/torchvision fallback."""
 import math
 
@@ -302,6 +302,38 @@ def process_mask_native(protos, masks_in, bboxes, shape):
         coef = masks_in.contiguous().view(1, n, 1, nm).permute(0, 3, 1, 2)  # one level, one row per "anchor"
         rows = torch.stack([torch.zeros(n, dtype=torch.int32, device=protos.device), torch.arange(n, dtype=torch.int32, device=protos.device)], 1).contiguous()
         return _ops.process_mask_native(L.as_nhwc(protos[None]), [coef], rows, bboxes[:, :4].float().contiguous(), [0, n], [(h, w)])[1][0]
+
+
+def _contours2segment(c, strategy="all"):
+    """what masks2segments makes of one mask's contours (reference :809-820): c = a list of (k, 2) integer arrays in cv2.findContours' order."""
+    import numpy as np
+    if strategy not in ("all", "largest"):
+        raise ValueError(f"masks2segments: strategy '{strategy}' (the reference knows 'all' and 'largest')")
+    if not len(c):
+        return np.zeros((0, 2), dtype=np.float32)  # no segments found
+    if strategy == "all":  # merge and concatenate all segments
+        from ..data.converter import merge_multi_segment
+        seg = np.concatenate(merge_multi_segment([x.reshape(-1, 2) for x in c])) if len(c) > 1 else c[0].reshape(-1, 2)
+    else:  # the first contour with the most vertices
+        seg = np.array(c[np.array([len(x) for x in c]).argmax()]).reshape(-1, 2)
+    return seg.astype("float32")
+
+
+def masks2segments(masks, strategy="all"):
+    """Reference signature (:793-821): masks (n, h, w) on the device -> a list of n float32 (k, 2) segments of x, y in mask pixels.  The
+    contours are cv2.findContours(m, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) per mask, here ey_mask_contours for all masks in one launch; only
+    the vertices come to the host.  'all' joins several contours with merge_multi_segment, 'largest' takes the first one with the most
+    vertices, no contour gives zeros((0, 2)).  Masks on the host raise: contour extraction has no CPU path."""
+    from ..nn import _ops
+    if not torch.is_tensor(masks) or not masks.is_cuda:
+        raise NotImplementedError("masks2segments: the masks are on the host; polygon extraction runs on the device only (ey_mask_contours), "
+                                  "call it before .cpu() / .numpy()")
+    if strategy not in ("all", "largest"):
+        raise ValueError(f"masks2segments: strategy '{strategy}' (the reference knows 'all' and 'largest')")
+    if masks.dtype not in (torch.uint8, torch.bool):
+        masks = masks.int() != 0  # (the reference's .int(): a fraction below 1 is not set)
+    with torch.cuda.device(masks.device):
+        return [_contours2segment(c, strategy) for c in _ops.mask_contours(masks.contiguous())]
 
 
 def scale_masks(masks, shape, padding=True):

@@ -568,6 +568,25 @@ int ey_bytetrack_update(int B, int cap, int max_tracks, float track_high_thresh,
                         int max_time_lost, int fuse_score, const float* rows, const int* count, double* kf, int* slot_i, float* slot_f, int* hdr,
                         float* out_rows, int* out_ids, int* out_count, void* workspace, size_t workspace_bytes, ey_stream_t stream);
 
+/* ---- Mask polygons (reference utils/ops.py:793-821 masks2segments: cv2.findContours(x, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) per mask).
+ * ey_mask_contours: the external contours of n binary masks in ONE launch, one workgroup per mask: OpenCV's border following (Suzuki & Abe
+ * 1985, algorithm 1), the raster scan for the next border start spread over the workgroup, each border followed by one lane in the
+ * sequential order.  Definition, phases and bounds: DESIGN.md section 7s; the kernel's text is csrc/contours_core.inc.h, which also compiles for
+ * the host with one lane.
+ * masks: DEVICE uint8 [n][h][w], contiguous, non-zero = set; never written.  windows: DEVICE int32 [n][4] = x0, y0, x1, y1 or NULL: mask b is
+ * scanned in columns x0 .. x1-1 and rows y0 .. y1-1 only (clamped to the mask) and everything outside counts as 0; with every set pixel
+ * inside its window the result is that of the whole mask.
+ * Outputs, per mask b: info int32 [n][4] = contours found, vertices found, flags (1: a capacity was too small, 2: a border walk passed its
+ * step bound of 8 (h + 2)(w + 2) + 8), 0; lens int32 [n][contour_cap]: the vertex count of contour k in the order of discovery (OpenCV lists
+ * them last found first); verts int32 [n][vertex_cap][2]: x, y of the vertices, contour after contour.  The counts in info are complete even
+ * when a capacity was too small: nothing is written past lens[b][contour_cap) and verts[b][vertex_cap), flag 1 is set, and a second call with
+ * the capacities info asks for gives the whole result.
+ * workspace: DEVICE, 16-byte aligned, ey_mask_contours_workspace_bytes(n, h, w) bytes (one label per pixel and a frame), nothing in it
+ * survives the call.  n == 0 launches nothing.  (h + 2)(w + 2) <= 2^30. */
+size_t ey_mask_contours_workspace_bytes(int n, int h, int w);
+int ey_mask_contours(int n, int h, int w, const uint8_t* masks, const int* windows, int contour_cap, int vertex_cap, int* lens, int* verts, int* info,
+                     void* workspace, size_t workspace_bytes, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
