@@ -56,6 +56,29 @@ def _pcs(t):
     return (None, 0) if t is None else (t.data_ptr(), L.cstride(t))
 
 
+def _carray(ctype, values):
+    """ctypes array of `values`; an array handed to C never has zero elements (an empty input gives one zero element)."""
+    values = list(values)
+    return (ctype * max(len(values), 1))(*values)
+
+
+def _ia(values):
+    return _carray(ctypes.c_int, values)
+
+
+def _la(values):
+    return _carray(ctypes.c_long, values)
+
+
+def _fa(values):
+    return _carray(ctypes.c_float, values)
+
+
+def _pa(tensors):
+    """void* array of the tensors' pointers (NULL for None)."""
+    return _carray(ctypes.c_void_p, [_p(t) for t in tensors])
+
+
 def _aligned16(t, channels=True, width=16):
     """True when the NHWC view `t` starts on a `width`-byte boundary and its pixel stride is a multiple of `width` bytes (what the kernels' vector
     accesses need); channels: and its channel count is a multiple of 8."""
@@ -76,6 +99,77 @@ def _out(what, out, shape, dtype, device, slot=False):
     """The output of the op `what` (names the argument too, "conv2d: out="): a new NHWC tensor when `out` is None, else `out` after _nhwc_view's
     check -- the kernels trust the pointer and the pixel stride they are given, a wrong view would be written past its end."""
     return L.empty_nhwc(*shape, dtype, device) if out is None else _nhwc_view(out, what, shape, dtype, slot)
+
+
+class _AtLeast(int):
+    """An extent of a _dense shape pattern that is a lower bound, not an exact size."""
+
+    def __repr__(self):
+        return f">={int(self)}"
+
+
+_ANY = _AtLeast(0)
+
+
+def _dense(t, what, dtype, shape, device):
+    """`t` (`what` names the op and the argument, "mask_iou: pred") must be a contiguous tensor of `dtype` (or of one of a tuple of dtypes) on
+    `device` whose shape matches `shape`: a plain int is an exact extent, _AtLeast(n) a lower bound, _ANY any extent.  device: a torch.device
+    without an index takes every device of its type; None takes the tensor wherever it lives (the caller's require_device follows)."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    ok = torch.is_tensor(t) and t.dtype in dtypes and t.dim() == len(shape) and t.is_contiguous() and all(
+        g >= w if isinstance(w, _AtLeast) else g == w for g, w in zip(t.shape, shape))
+    if ok and device is not None:
+        ok = t.device.type == device.type and device.index in (None, t.device.index)
+    if not ok:
+        given = f"{t.dtype} {tuple(t.shape)}{'' if t.is_contiguous() else ' (not contiguous)'} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what} must be a contiguous {' or '.join(str(d).replace('torch.', '') for d in dtypes)} tensor of shape {tuple(shape)}"
+                         f"{'' if device is None else f' on {device}'}, got {given}")
+    return t
+
+
+def _dense_out(what, out, dtype, shape, device, fill=None):
+    """The dense output of the op `what` ("scale_masks: out="): `out` after _dense's check, or, when it is None, a new tensor of `shape` (a lower
+    bound allocates exactly the bound) holding `fill` everywhere when one is given."""
+    if out is not None:
+        return _dense(out, what, dtype, shape, device)
+    shape = tuple(int(v) for v in shape)
+    return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
+
+
+def _workspace(what, ws, nbytes, device, align=16):
+    """The scratch buffer of the op `what`: a new uint8 buffer of max(nbytes, 16) bytes when `ws` is None, else `ws` after checking that it is a
+    contiguous uint8 buffer of at least `nbytes` bytes on `device` that starts on an `align`-byte boundary, as the entry points document."""
+    if ws is None:
+        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+    _dense(ws, f"{what}: workspace", torch.uint8, (_AtLeast(nbytes),), device)
+    if ws.data_ptr() % align:
+        raise ValueError(f"{what}: workspace must start on a {align}-byte boundary")
+    return ws
+
+
+def _pair_offsets(what, pred_off, gt_off, out_off=None):
+    """The host lists of an op that writes one [M_b][N_b] matrix per image into a flat buffer: pred_off / gt_off (B+1 entries from 0) group the
+    rows by image, out_off[b] is where image b's matrix starts (default: packed one after the other).  -> (pred_off, gt_off, out_off) as int
+    lists, the matrices' sizes and the end of the flat buffer (images without a matrix do not count: their out_off is ignored)."""
+    pred_off, gt_off = [int(v) for v in pred_off], [int(v) for v in gt_off]
+    B = len(pred_off) - 1
+    if B < 0 or len(gt_off) != B + 1 or pred_off[0] != 0 or gt_off[0] != 0:
+        raise ValueError(f"{what}: pred_off and gt_off must have B+1 entries starting at 0")
+    sizes = [(gt_off[b + 1] - gt_off[b]) * (pred_off[b + 1] - pred_off[b]) for b in range(B)]
+    if out_off is None:
+        out_off = [0] * B
+        for b in range(1, B):
+            out_off[b] = out_off[b - 1] + sizes[b - 1]
+    out_off = [int(v) for v in out_off]
+    if len(out_off) != B or any(o < 0 for o, s in zip(out_off, sizes) if s):
+        raise ValueError(f"{what}: out_off must have B = {B} entries, none of them negative where the image has a matrix")
+    return pred_off, gt_off, out_off, sizes, max([o + s for o, s in zip(out_off, sizes) if s] + [0])
+
+
+def _nms_out(B, max_det, width, device):
+    """The outputs every NMS entry point fills: rows fp32 (B, max_det, width), count int32 (B,), index int32 (B, max_det)."""
+    return (torch.empty((B, max_det, width), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.int32, device=device),
+            torch.empty((B, max_det), dtype=torch.int32, device=device))
 
 
 def _try_launch(rec, what, fn, *args, kernel=None):
@@ -1102,33 +1196,33 @@ def deconv2x2(mod, x, deconv, out=None):
     return out
 
 
+def _mask_assembly(what, proto, coefs, rows, boxes, N):
+    """What process_mask and process_mask_native check and build alike: proto and every coefficient map are NHWC views, the maps have proto's
+    batch and channel counts and one dtype, rows is a dense int32 (>= N, 2) and boxes a dense fp32 (>= N, 4) tensor on proto's device.
+    -> the leading arguments of both entry points, up to the boxes' pointer."""
+    _nhwc_view(proto, f"{what}: proto", proto.shape, proto.dtype)
+    B, nm, mh, mw = proto.shape
+    for i, c in enumerate(coefs):
+        _nhwc_view(c, f"{what}: coefs[{i}]", (B, nm, *c.shape[2:]), coefs[0].dtype)
+    _dense(rows, f"{what}: rows", torch.int32, (_AtLeast(N), 2), proto.device)
+    _dense(boxes, f"{what}: boxes", torch.float32, (_AtLeast(N), 4), proto.device)
+    return (L.dtype_code(proto.dtype), B, mh, mw, nm, proto.data_ptr(), L.cstride(proto), len(coefs), _pa(coefs), L.dtype_code(coefs[0].dtype) if coefs else L.F32,
+            _ia(L.cstride(c) for c in coefs), _ia(c.shape[2] for c in coefs), _ia(c.shape[3] for c in coefs), N, rows.data_ptr(), boxes.data_ptr())
+
+
 def process_mask(proto, coefs, rows, boxes, s, n=None, out=None):
     """Mask assembly (ey_process_mask): proto logical (B,nm,mh,mw) NHWC view; coefs: list (<= 4) of logical (B,nm,H_l,W_l) NHWC views in
     concatenated-anchor order; rows int32 (N,2) = (image, anchor); boxes fp32 (N,4) xyxy in network-input pixels; s = input / proto ratio.
     -> uint8 (N, s*mh, s*mw), values 0 / 1.  n: number of leading rows to use (default all); out=: a contiguous uint8 buffer to fill."""
     L.require_device(proto, "process_mask")
     _no_block("process_mask")
-    if not L.is_nhwc_view(proto) or any(not L.is_nhwc_view(c) for c in coefs):
-        raise ValueError("process_mask: proto and the coefficient maps must be NHWC views")
-    B, nm, mh, mw = proto.shape
     N = int(rows.shape[0]) if n is None else int(n)
-    if rows.dtype != torch.int32 or boxes.dtype != torch.float32 or not rows.is_contiguous() or not boxes.is_contiguous() or rows.shape[0] < N or boxes.shape[0] < N:
-        raise ValueError("process_mask: rows must be contiguous int32 (N,2) and boxes contiguous fp32 (N,4)")
-    if any(c.shape[0] != B or c.shape[1] != nm or c.dtype != coefs[0].dtype for c in coefs):
-        raise ValueError(f"process_mask: coefficient maps {[tuple(c.shape) for c in coefs]} do not match proto {tuple(proto.shape)}")
-    nl = len(coefs)
+    head = _mask_assembly("process_mask", proto, coefs, rows, boxes, N)
+    _, nm, mh, mw = proto.shape
     s = int(s)
-    if out is None:
-        out = torch.empty((N, s * mh, s * mw), dtype=torch.uint8, device=proto.device)
-    elif out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != (N, s * mh, s * mw):
-        raise ValueError(f"process_mask: out= must be a contiguous uint8 tensor of shape {(N, s * mh, s * mw)}")
-    IA, PA = ctypes.c_int * max(nl, 1), ctypes.c_void_p * max(nl, 1)
-    cp, cs = PA(*[c.data_ptr() for c in coefs]), IA(*[L.cstride(c) for c in coefs])
-    Hs, Ws = IA(*[c.shape[2] for c in coefs]), IA(*[c.shape[3] for c in coefs])
+    out = _dense_out("process_mask: out=", out, torch.uint8, (N, s * mh, s * mw), proto.device)
     with _tr("process_mask_kernel", out.numel() + N * 24 + _nb(proto), 2.0 * N * mh * mw * nm, note=f"N{N} {mh}x{mw} s{s}"):
-        L.check(L.lib().ey_process_mask(L.dtype_code(proto.dtype), B, mh, mw, nm, proto.data_ptr(), L.cstride(proto), nl, cp,
-                                        L.dtype_code(coefs[0].dtype) if nl else L.F32, cs, Hs, Ws, N, rows.data_ptr(), boxes.data_ptr(), s, out.data_ptr(),
-                                        L.stream()), "ey_process_mask")
+        L.check(L.lib().ey_process_mask(*head, s, out.data_ptr(), L.stream()), "ey_process_mask")
     return out
 
 
@@ -1140,42 +1234,20 @@ def mask_iou(pred, pred_off, gt, gt_off, index=False, out_off=None, iou=None, in
     -> (iou, out_off, inter or None); the matrices: iou[out_off[b]: out_off[b] + M_b * N_b].view(M_b, N_b)."""
     L.require_device(pred, "mask_iou")
     _no_block("mask_iou")
-    pred_off, gt_off = [int(v) for v in pred_off], [int(v) for v in gt_off]
-    B = len(pred_off) - 1
-    if B < 0 or len(gt_off) != B + 1 or pred_off[0] != 0 or gt_off[0] != 0:
-        raise ValueError("mask_iou: pred_off and gt_off must have B+1 entries starting at 0")
-    if pred.dim() != 3 or pred.dtype != torch.uint8 or not pred.is_contiguous() or pred.shape[0] < pred_off[-1]:
-        raise ValueError(f"mask_iou: pred must be a contiguous uint8 (N,H,W) tensor with N >= {pred_off[-1]}, got {pred.dtype} {tuple(pred.shape)}")
+    pred_off, gt_off, out_off, sizes, end = _pair_offsets("mask_iou", pred_off, gt_off, out_off)
+    B, dev = len(out_off), pred.device
+    _dense(pred, "mask_iou: pred", torch.uint8, (_AtLeast(pred_off[-1]), _ANY, _ANY), dev)
     H, W = int(pred.shape[1]), int(pred.shape[2])
-    want = (torch.int32, B) if index else (torch.uint8, gt_off[-1])
-    if gt.dim() != 3 or gt.dtype != want[0] or not gt.is_contiguous() or gt.device != pred.device or gt.shape[0] < want[1] or tuple(gt.shape[1:]) != (H, W):
-        raise ValueError(f"mask_iou: gt must be a contiguous {want[0]} ({want[1]},{H},{W}) tensor on {pred.device}, got {gt.dtype} {tuple(gt.shape)}")
-    sizes = [(gt_off[b + 1] - gt_off[b]) * (pred_off[b + 1] - pred_off[b]) for b in range(B)]
-    if out_off is None:
-        out_off = [0] * B
-        for b in range(1, B):
-            out_off[b] = out_off[b - 1] + sizes[b - 1]
-    out_off = [int(v) for v in out_off]
-    end = max([o + s for o, s in zip(out_off, sizes) if s] + [0])
-    if iou is None:
-        iou = torch.empty(end, dtype=torch.float32, device=pred.device)
-    if inter is True:
-        inter = torch.empty(iou.numel(), dtype=torch.int32, device=pred.device)
-    for name, t, dt in (("iou", iou, torch.float32), ("inter", inter, torch.int32)):
-        if t is not None and (t.dim() != 1 or t.dtype != dt or not t.is_contiguous() or t.device != pred.device or t.numel() < end or len(out_off) != B
-                              or any(o < 0 for o, s in zip(out_off, sizes) if s)):
-            raise ValueError(f"mask_iou: {name} must be a flat contiguous {dt} buffer of at least {end} elements on {pred.device}")
-    nbytes = L.lib().ey_mask_iou_workspace_bytes(H, W, pred_off[-1], gt_off[-1])
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=pred.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes or workspace.device != pred.device:
-        raise ValueError(f"mask_iou: workspace must be a contiguous uint8 buffer of at least {nbytes} bytes on {pred.device}")
-    IA, LA = ctypes.c_int * (B + 1), ctypes.c_long * max(B, 1)
+    _dense(gt, "mask_iou: gt", torch.int32 if index else torch.uint8, (_AtLeast(B if index else gt_off[-1]), H, W), dev)
+    iou = _dense_out("mask_iou: iou", iou, torch.float32, (_AtLeast(end),), dev)
+    if inter is not None:
+        inter = _dense_out("mask_iou: inter", None, torch.int32, (iou.numel(),), dev) if inter is True else _dense(inter, "mask_iou: inter", torch.int32, (_AtLeast(end),), dev)
+    workspace = _workspace("mask_iou", workspace, L.lib().ey_mask_iou_workspace_bytes(H, W, pred_off[-1], gt_off[-1]), dev)
     words = (H * W + 63) // 64
     with _tr("mask_iou_kernels", pred_off[-1] * H * W + gt.numel() * gt.element_size() + 8 * end, 2.0 * sum(sizes) * words,
              note=f"B{B} N{pred_off[-1]} M{gt_off[-1]} {H}x{W}", kernels=3):
-        L.check(L.lib().ey_mask_iou(L.MASK_GT_INDEX if index else L.MASK_GT_STACK, B, H, W, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off),
-                                    LA(*out_off), iou.data_ptr(), _p(inter), workspace.data_ptr(), workspace.numel(),
+        L.check(L.lib().ey_mask_iou(L.MASK_GT_INDEX if index else L.MASK_GT_STACK, B, H, W, pred.data_ptr(), _ia(pred_off), gt.data_ptr(), _ia(gt_off),
+                                    _la(out_off), iou.data_ptr(), _p(inter), workspace.data_ptr(), workspace.numel(),
                                     L.stream()), "ey_mask_iou")
     return iou, out_off, inter
 
@@ -1203,18 +1275,12 @@ def process_mask_native(proto, coefs, rows, boxes, mask_off, shapes, out=None):
     fill (its first sum n_b H0_b W0_b bytes are written)."""
     L.require_device(proto, "process_mask_native")
     _no_block("process_mask_native")
-    if not L.is_nhwc_view(proto) or any(not L.is_nhwc_view(c) for c in coefs):
-        raise ValueError("process_mask_native: proto and the coefficient maps must be NHWC views")
     B, nm, mh, mw = proto.shape
     mask_off = [int(v) for v in mask_off]
     if len(mask_off) != B + 1 or len(shapes) != B or mask_off[0] != 0:
         raise ValueError(f"process_mask_native: mask_off must have B+1 = {B + 1} entries starting at 0 and shapes B entries")
     N = mask_off[-1]
-    if rows.dtype != torch.int32 or boxes.dtype != torch.float32 or not rows.is_contiguous() or not boxes.is_contiguous() or rows.shape[0] < N or boxes.shape[0] < N:
-        raise ValueError("process_mask_native: rows must be contiguous int32 (N,2) and boxes contiguous fp32 (N,4)")
-    if any(c.shape[0] != B or c.shape[1] != nm or c.dtype != coefs[0].dtype for c in coefs):
-        raise ValueError(f"process_mask_native: coefficient maps {[tuple(c.shape) for c in coefs]} do not match proto {tuple(proto.shape)}")
-    nl = len(coefs)
+    head = _mask_assembly("process_mask_native", proto, coefs, rows, boxes, N)
     if any(int(s[0]) < 1 or int(s[1]) < 1 for s in shapes):
         raise ValueError(f"process_mask_native: original shapes {[tuple(s) for s in shapes]} must be at least 1 x 1")
     geo = [mask_geometry((mh, mw), s) for s in shapes]
@@ -1223,18 +1289,9 @@ def process_mask_native(proto, coefs, rows, boxes, mask_off, shapes, out=None):
     for k, g in zip(counts, geo):
         out_off.append(total)
         total += max(k, 0) * max(g[4], 0) * max(g[5], 0)
-    if out is None:
-        out = torch.empty(total, dtype=torch.uint8, device=proto.device)
-    elif out.dim() != 1 or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < total or out.device != proto.device:
-        raise ValueError(f"process_mask_native: out= must be a flat contiguous uint8 buffer of at least {total} bytes on {proto.device}")
-    IA, PA, LA = ctypes.c_int * max(nl, 1), ctypes.c_void_p * max(nl, 1), ctypes.c_long * max(B, 1)
-    cp, cs = PA(*[c.data_ptr() for c in coefs]), IA(*[L.cstride(c) for c in coefs])
-    Hs, Ws = IA(*[c.shape[2] for c in coefs]), IA(*[c.shape[3] for c in coefs])
+    out = _dense_out("process_mask_native: out=", out, torch.uint8, (_AtLeast(total),), proto.device)
     with _tr("process_mask_native_kernel", total + N * 24 + _nb(proto), 2.0 * N * mh * mw * nm, note=f"B{B} N{N} {mh}x{mw} -> {sorted(set(map(tuple, shapes)))}"):
-        rc = L.lib().ey_process_mask_native(L.dtype_code(proto.dtype), B, mh, mw, nm, proto.data_ptr(), L.cstride(proto), nl, cp,
-                                            L.dtype_code(coefs[0].dtype) if nl else L.F32, cs, Hs, Ws, N, rows.data_ptr(), boxes.data_ptr(),
-                                            (ctypes.c_int * (B + 1))(*mask_off), (ctypes.c_int * (6 * max(B, 1)))(*[v for g in geo for v in g]), LA(*out_off),
-                                            out.data_ptr(), L.stream())
+        rc = L.lib().ey_process_mask_native(*head, _ia(mask_off), _ia(v for g in geo for v in g), _la(out_off), out.data_ptr(), L.stream())
         if rc == -1:  # EY_EINVAL: a bad argument of the caller's (an empty crop, offsets that do not group the rows)
             raise ValueError("ey_process_mask_native: " + L.lib().ey_last_error().decode(errors="replace"))
         L.check(rc, "ey_process_mask_native")
@@ -1255,8 +1312,8 @@ def mask_prompt(masks, mask_off, shapes, bboxes=None, points=None, labels=None, 
     if B < 0 or mask_off[0] != 0 or len(shapes) != B:
         raise ValueError("mask_prompt: mask_off must have B+1 entries starting at 0 and shapes B entries")
     N = mask_off[-1]
-    if masks.dim() != 3 or masks.dtype != torch.uint8 or not masks.is_contiguous() or masks.shape[0] < N:
-        raise ValueError(f"mask_prompt: masks must be a contiguous uint8 (N,mh,mw) tensor with N >= {N}, got {masks.dtype} {tuple(masks.shape)}")
+    dev = masks.device
+    _dense(masks, "mask_prompt: masks", torch.uint8, (_AtLeast(N), _ANY, _ANY), dev)
     mh, mw = int(masks.shape[1]), int(masks.shape[2])
     boxes = [[int(v) for v in r] for r in ([] if bboxes is None else bboxes)]
     pts = [[int(v) for v in r] for r in ([] if points is None else points)]
@@ -1264,34 +1321,24 @@ def mask_prompt(masks, mask_off, shapes, bboxes=None, points=None, labels=None, 
     if any(len(r) != 4 for r in boxes) or any(len(r) != 2 for r in pts) or len(labs) != len(pts):
         raise ValueError(f"mask_prompt: boxes must be (P,4), points (Q,2) and labels (Q,); got {len(pts)} points and {len(labs)} labels")
     P, Q = len(boxes), len(pts)
-    dev = masks.device
     want = {"full": ((N,), torch.float32), "keep": ((N,), torch.uint8)}
     if P:
         want.update(inter=((P, N), torch.float32), iou=((P, N), torch.float32), best=((B, P), torch.int32))
     if Q:
         want["hit"] = ((Q, N), torch.uint8)
+    ld = N
     if out is None:
         out = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in want.items()}
-    ld = N
-    for k in ("inter", "hit"):
-        if k in want:
-            ld = int(out[k].shape[1]) if out[k].dim() == 2 else -1
-            break
-    for k, (s, dt) in want.items():
-        t = out.get(k)
-        s = (s[0], ld) if k in ("inter", "iou", "hit") else s
-        if t is None or t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != s or ld < N:
-            raise ValueError(f"mask_prompt: out['{k}'] must be a contiguous {dt} tensor of shape {s} on {dev}")
-    nbytes = L.lib().ey_mask_prompt_workspace_bytes(B, mh, mw, min(P, 32))
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes or workspace.device != dev:
-        raise ValueError(f"mask_prompt: workspace must be a contiguous uint8 buffer of at least {nbytes} bytes on {dev}")
+    else:  # inter, iou and hit share the row stride of the first of them; one that is narrower than N or not 2-D fails its check below
+        lead = out.get("inter" if P else "hit")
+        ld = max(int(lead.shape[1]), N) if torch.is_tensor(lead) and lead.dim() == 2 else N
+        for k, (s, dt) in want.items():
+            _dense(out.get(k), f"mask_prompt: out['{k}']", dt, (s[0], ld) if k in ("inter", "iou", "hit") else s, dev)
+    workspace = _workspace("mask_prompt", workspace, L.lib().ey_mask_prompt_workspace_bytes(B, mh, mw, min(P, 32)), dev)
     geo = [v for s in shapes for v in mask_geometry((mh, mw), s)]
-    IA = lambda vals: (ctypes.c_int * max(len(vals), 1))(*vals)  # noqa: E731
     with _tr("mask_prompt_kernels", N * mh * mw + 4 * N * (2 * P + 1) + N * (Q + 1), 2.0 * N * mh * mw * (P + 1), note=f"B{B} N{N} P{P} Q{Q} {mh}x{mw}", kernels=3):
-        L.check(L.lib().ey_mask_prompt(B, mh, mw, masks.data_ptr(), IA(mask_off), IA(geo), P, IA([v for r in boxes for v in r]), Q, IA([v for r in pts for v in r]),
-                                       IA(labs), max(ld, 0), out["full"].data_ptr(), _p(out.get("inter") if P else None), _p(out.get("iou") if P else None),
+        L.check(L.lib().ey_mask_prompt(B, mh, mw, masks.data_ptr(), _ia(mask_off), _ia(geo), P, _ia(v for r in boxes for v in r), Q, _ia(v for r in pts for v in r),
+                                       _ia(labs), ld, out["full"].data_ptr(), _p(out.get("inter") if P else None), _p(out.get("iou") if P else None),
                                        _p(out.get("best") if P else None), _p(out.get("hit") if Q else None), out["keep"].data_ptr(), workspace.data_ptr(),
                                        workspace.numel(), L.stream()), "ey_mask_prompt")
     return out
@@ -1310,10 +1357,7 @@ def scale_masks(masks, shape, padding=True, out=None):
     h0, w0 = int(shape[0]), int(shape[1])
     top, bottom, left, right = mask_geometry((h, w), shape, padding)[:4]
     odt = torch.float32 if masks.dtype == torch.uint8 else masks.dtype
-    if out is None:
-        out = torch.empty((n, c, h0, w0), dtype=odt, device=masks.device)
-    elif out.dtype != odt or not out.is_contiguous() or tuple(out.shape) != (n, c, h0, w0) or out.device != masks.device:
-        raise ValueError(f"scale_masks: out= must be a contiguous {odt} tensor of shape {(n, c, h0, w0)} on {masks.device}")
+    out = _dense_out("scale_masks: out=", out, odt, (n, c, h0, w0), masks.device)
     code = L.MASK_U8 if masks.dtype == torch.uint8 else L.dtype_code(masks.dtype)
     with _tr("scale_masks_kernel", _nb(masks, out), 7.0 * out.numel(), note=f"{n * c} x {h}x{w}->{h0}x{w0}"):
         L.check(L.lib().ey_scale_masks(code, n * c, h, w, top, bottom, left, right, h0, w0, masks.data_ptr(), out.data_ptr(), L.stream()), "ey_scale_masks")
@@ -1529,10 +1573,7 @@ class Candidates:
 
 def nms_candidates(cand, iou_thres, max_det, max_nms, max_wh, agnostic):
     """Selection + greedy suppression on a Candidates buffer -> (boxes (B,max_det,6), count (B,), index (B,max_det))."""
-    dev = cand.device
-    boxes = torch.empty((cand.B, max_det, 6), dtype=torch.float32, device=dev)
-    count = torch.empty((cand.B,), dtype=torch.int32, device=dev)
-    index = torch.empty((cand.B, max_det), dtype=torch.int32, device=dev)
+    boxes, count, index = _nms_out(cand.B, max_det, 6, cand.device)
     # predict mode = the three-kernel fast path (csrc/nms_fast.inc.h), bracketed as one operator
     alg = cand.B * ((cand.A + 255) // 256 * 256 * 12 + cand.A * 16)  # keys + class ids + boxes (the tail of the buffer is scratch)
     with _tr("nms_fast(nf_select+nf_mask+nf_resolve)", alg + _nb(boxes), kernels=3):
@@ -1541,23 +1582,11 @@ def nms_candidates(cand, iou_thres, max_det, max_nms, max_wh, agnostic):
     return boxes, count, index
 
 
-def _ia(values):
-    values = list(values)
-    return (ctypes.c_int * len(values))(*values)
-
-
-def _pa(tensors):
-    """void* array of the tensors' pointers (NULL for None)."""
-    ptrs = [_p(t) for t in tensors]
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
-
-
 def _level_arrays(levels, nmaps, stride_i, off_i):
     """The ctypes arrays a per-level launch takes.  levels: one tuple per pyramid level that starts with `nmaps` NHWC views and holds the level's
     stride at index `stride_i` and its anchor offset at `off_i` -> (Hs, Ws, strides, offsets) with the sizes of map 0, [pointers of map j],
     [pixel strides of map j]."""
-    strides = (ctypes.c_float * len(levels))(*[float(lv[stride_i]) for lv in levels])
-    grid = _ia(lv[0].shape[2] for lv in levels), _ia(lv[0].shape[3] for lv in levels), strides, _ia(int(lv[off_i]) for lv in levels)
+    grid = _ia(lv[0].shape[2] for lv in levels), _ia(lv[0].shape[3] for lv in levels), _fa(float(lv[stride_i]) for lv in levels), _ia(int(lv[off_i]) for lv in levels)
     return grid, [_pa(lv[j] for lv in levels) for j in range(nmaps)], [_ia(L.cstride(lv[j]) for lv in levels) for j in range(nmaps)]
 
 
@@ -1679,16 +1708,14 @@ def e2e_topk(pred, k, want_index=False):
     """Detect.postprocess (reference head.py:167-189): pred fp32 (B,4+nc,A) with x1y1x2y2 rows -> (B,k,6) fp32 rows
     [x1,y1,x2,y2,score,class], the k best (anchor, class) pairs per image in descending score order."""
     L.require_device(pred, "e2e_topk")
-    if pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise ValueError("e2e_topk: pred must be a contiguous float32 (B,4+nc,A) tensor")
-    B, no, A = pred.shape
+    B, no, A = _dense(pred, "e2e_topk: pred (B,4+nc,A)", torch.float32, (_ANY, _ANY, _ANY), pred.device).shape
     nc = no - 4
     if not 0 < k <= A:
         raise ValueError(f"e2e_topk: k={k} must be in 1..A={A}")
     out = torch.empty((B, k, 6), dtype=torch.float32, device=pred.device)
     index = torch.empty((B, k), dtype=torch.int32, device=pred.device) if want_index else None
     nb = L.lib().ey_e2e_topk_workspace_bytes(B, nc, A)
-    ws = torch.empty(nb, dtype=torch.uint8, device=pred.device)
+    ws = _workspace("e2e_topk", None, nb, pred.device)
     with _tr("e2e_topk(score+select)", pred.numel() * 4 + out.numel() * 4):
         L.check(L.lib().ey_e2e_topk(B, nc, A, pred.data_ptr(), k, out.data_ptr(), _p(index), ws.data_ptr(), nb, L.stream()), "ey_e2e_topk")
     return (out, index) if want_index else out
@@ -1698,16 +1725,12 @@ def nms(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, class_m
     """pred fp32 (B,4+nc,A) contiguous -> (boxes (B,max_det,6) fp32, count (B,) int32, index (B,max_det) int32).
     return_workspace (tests): also the workspace tensor (keys, class ids, the fast path's per-image scratch with its n_sel / n_total / done words)."""
     L.require_device(pred, "nms")
-    if pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise ValueError("nms: pred must be a contiguous float32 (B,4+nc,A) tensor")
-    B, no, A = pred.shape
+    B, no, A = _dense(pred, "nms: pred (B,4+nc,A)", torch.float32, (_ANY, _ANY, _ANY), pred.device).shape
     dev = pred.device
     multi_label = bool(multi_label) and no - 4 > 1  # reference ops.py:240
-    boxes = torch.empty((B, max_det, 6), dtype=torch.float32, device=dev)
-    count = torch.empty((B,), dtype=torch.int32, device=dev)
-    index = torch.empty((B, max_det), dtype=torch.int32, device=dev)
+    boxes, count, index = _nms_out(B, max_det, 6, dev)
     nbytes = L.lib().ey_nms_workspace_bytes_ml(B, no - 4, A) if multi_label else L.lib().ey_nms_workspace_bytes(B, A)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("nms", None, nbytes, dev)
     with _tr("nms(score+sort_greedy)", _nb(pred, boxes)):
         L.check(L.lib().ey_nms(B, no - 4, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh), int(bool(agnostic)), int(bool(multi_label)),
                                _p(class_mask), boxes.data_ptr(), count.data_ptr(), index.data_ptr(),
@@ -1723,8 +1746,7 @@ def obb_decode_levels(levels, pred):
     L.require_device(box0, "obb_decode")
     _no_block("obb decode")
     B, nc = box0.shape[0], cls0.shape[1]
-    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[0] != B or pred.shape[1] != 4 + nc + 1:
-        raise ValueError(f"obb_decode: pred must be a contiguous float32 (B, 4+nc+1, A) tensor, got {tuple(pred.shape)} {pred.dtype}")
+    _dense(pred, "obb_decode: pred (B, 4+nc+1, A)", torch.float32, (B, 4 + nc + 1, _ANY), box0.device)
     (Hs, Ws, st, offs), ptr, cs = _level_arrays(levels, 3, 3, 4)
     nbytes = sum(_nb(lv[0], lv[1], lv[2]) for lv in levels) + _nb(pred)
     with _tr("obb_decode_kernel", nbytes, sum(2.0 * B * lv[0].shape[2] * lv[0].shape[3] * 220 for lv in levels), note=f"{n} levels"):
@@ -1737,8 +1759,8 @@ def probiou(obb1, obb2):
     """(N,5), (M,5) xywhr fp32 device tensors -> the (N,M) fp32 ProbIoU matrix (ey_probiou)."""
     L.require_device(obb1, "probiou")
     o1, o2 = obb1.float().contiguous(), obb2.float().contiguous()
-    if o1.dim() != 2 or o2.dim() != 2 or o1.shape[1] != 5 or o2.shape[1] != 5:
-        raise ValueError(f"probiou: expected (N,5) and (M,5) xywhr tensors, got {tuple(obb1.shape)} and {tuple(obb2.shape)}")
+    for name, o in (("obb1", o1), ("obb2", o2)):
+        _dense(o, f"probiou: {name} (xywhr rows)", torch.float32, (_ANY, 5), o1.device)
     out = torch.empty((o1.shape[0], o2.shape[0]), dtype=torch.float32, device=o1.device)
     with _tr("obb_probiou_kernel", _nb(o1, o2, out), 60.0 * out.numel()):
         L.check(L.lib().ey_probiou(o1.shape[0], o2.shape[0], o1.data_ptr(), o2.data_ptr(), out.data_ptr(), L.stream()), "ey_probiou")
@@ -1749,15 +1771,10 @@ def nms_rotated(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic,
     """pred fp32 (B,4+nc+1,A) contiguous (xywh, scores, angle) -> (rows (B,max_det,7) fp32 = x,y,w,h,conf,cls,angle, count (B,) int32,
     index (B,max_det) int32): fast-NMS on ProbIoU (ey_nms_rotated), single label."""
     L.require_device(pred, "nms_rotated")
-    if pred.dtype != torch.float32 or not pred.is_contiguous():
-        raise ValueError("nms_rotated: pred must be a contiguous float32 (B,4+nc+1,A) tensor")
-    B, no, A = pred.shape
-    dev = pred.device
-    rows = torch.empty((B, max_det, 7), dtype=torch.float32, device=dev)
-    count = torch.empty((B,), dtype=torch.int32, device=dev)
-    index = torch.empty((B, max_det), dtype=torch.int32, device=dev)
+    B, no, A = _dense(pred, "nms_rotated: pred (B,4+nc+1,A)", torch.float32, (_ANY, _ANY, _ANY), pred.device).shape
+    rows, count, index = _nms_out(B, max_det, 7, pred.device)
     nbytes = L.lib().ey_nms_rotated_workspace_bytes(B, A, int(max_nms))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace("nms_rotated", None, nbytes, pred.device)
     with _tr("nms_rotated(init+score+rank+pair+resolve)", _nb(pred, rows), kernels=5):
         L.check(L.lib().ey_nms_rotated(B, no - 5, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh), int(bool(agnostic)),
                                        _p(class_mask), rows.data_ptr(), count.data_ptr(), index.data_ptr(),
@@ -1800,16 +1817,12 @@ def kpts_decode_rows(levels, kpt_shape, index, count, A=None, out=None):
     head, offs = _kpt_levels(levels, kpt_shape, "kpts_decode_rows")
     B, nkpt, ndim = head[1], head[8], head[9]
     dev = levels[0][0].device
-    if index.dtype != torch.int32 or count.dtype != torch.int32 or index.dim() != 2 or index.shape[0] != B or tuple(count.shape) != (B,) or not index.is_contiguous() \
-            or not count.is_contiguous() or index.device != dev or count.device != dev or index.shape[1] < 1:
-        raise ValueError(f"kpts_decode_rows: index must be a contiguous int32 (B, max_det) tensor and count int32 (B,) on {dev}")
+    _dense(index, "kpts_decode_rows: index (B, max_det)", torch.int32, (B, _AtLeast(1)), dev)
+    _dense(count, "kpts_decode_rows: count", torch.int32, (B,), dev)
     if A is None:
         A = max(int(lv[2]) + lv[0].shape[2] * lv[0].shape[3] for lv in levels)
     max_det = index.shape[1]
-    if out is None:
-        out = torch.empty((B, max_det, nkpt, ndim), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, max_det, nkpt, ndim) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"kpts_decode_rows: out must be a contiguous float32 {(B, max_det, nkpt, ndim)} tensor on {dev}")
+    out = _dense_out("kpts_decode_rows: out=", out, torch.float32, (B, max_det, nkpt, ndim), dev)
     with _tr("kpts_decode_rows_kernel", _nb(index, out), 3.0 * out.numel()):
         L.check(L.lib().ey_kpts_decode_rows(*head, int(A), offs, max_det, index.data_ptr(), count.data_ptr(), out.data_ptr(), L.stream()), "ey_kpts_decode_rows")
     return out
@@ -1821,32 +1834,16 @@ def kpt_iou(pred, pred_off, gt, gt_off, area, sigma, out_off=None, out=None):
     the flat fp32 buffer `out` (packed one after the other by default).  -> (out, out_off)."""
     L.require_device(pred, "kpt_iou")
     _no_block("kpt_iou")
-    pred_off, gt_off = [int(v) for v in pred_off], [int(v) for v in gt_off]
-    B = len(pred_off) - 1
-    if B < 0 or len(gt_off) != B + 1 or pred_off[0] != 0 or gt_off[0] != 0:
-        raise ValueError("kpt_iou: pred_off and gt_off must have B+1 entries starting at 0")
-    dev = pred.device
-    if pred.dim() != 3 or gt.dim() != 3 or gt.shape[2] != 3 or pred.shape[1] != gt.shape[1] or pred.shape[0] < pred_off[-1] or gt.shape[0] < gt_off[-1]:
-        raise ValueError(f"kpt_iou: expected pred (N,K,ndim) and gt (M,K,3) with N >= {pred_off[-1]}, M >= {gt_off[-1]}, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    pred_off, gt_off, out_off, sizes, end = _pair_offsets("kpt_iou", pred_off, gt_off, out_off)
+    B, dev = len(out_off), pred.device
+    _dense(pred, "kpt_iou: pred (N,K,ndim)", torch.float32, (_AtLeast(pred_off[-1]), _ANY, _ANY), dev)
     K, ndim = int(pred.shape[1]), int(pred.shape[2])
-    for name, t, n in (("pred", pred, None), ("gt", gt, None), ("area", area, gt_off[-1]), ("sigma", sigma, K)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or (n is not None and (t.dim() != 1 or t.shape[0] < n)):
-            raise ValueError(f"kpt_iou: {name} must be a contiguous float32 tensor on {dev}" + (f" with {n} entries" if n is not None else ""))
-    sizes = [(gt_off[b + 1] - gt_off[b]) * (pred_off[b + 1] - pred_off[b]) for b in range(B)]
-    if out_off is None:
-        out_off = [0] * B
-        for b in range(1, B):
-            out_off[b] = out_off[b - 1] + sizes[b - 1]
-    out_off = [int(v) for v in out_off]
-    end = max([o + s for o, s in zip(out_off, sizes) if s] + [0])
-    if out is None:
-        out = torch.empty(end, dtype=torch.float32, device=dev)
-    if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < end or len(out_off) != B \
-            or any(o < 0 for o, s in zip(out_off, sizes) if s):
-        raise ValueError(f"kpt_iou: out must be a flat contiguous float32 buffer of at least {end} elements on {dev}")
-    IA, LA = ctypes.c_int * (B + 1), ctypes.c_long * max(B, 1)
+    _dense(gt, "kpt_iou: gt (M,K,3)", torch.float32, (_AtLeast(gt_off[-1]), K, 3), dev)
+    _dense(area, "kpt_iou: area", torch.float32, (_AtLeast(gt_off[-1]),), dev)
+    _dense(sigma, "kpt_iou: sigma", torch.float32, (_AtLeast(K),), dev)
+    out = _dense_out("kpt_iou: out=", out, torch.float32, (_AtLeast(end),), dev)
     with _tr("kpt_iou_kernel", _nb(pred, gt) + 4 * sum(sizes), 12.0 * K * sum(sizes), note=f"B{B} N{pred_off[-1]} M{gt_off[-1]} K{K}"):
-        L.check(L.lib().ey_kpt_iou(B, K, ndim, pred.data_ptr(), IA(*pred_off), gt.data_ptr(), IA(*gt_off), area.data_ptr(), sigma.data_ptr(), LA(*out_off),
+        L.check(L.lib().ey_kpt_iou(B, K, ndim, pred.data_ptr(), _ia(pred_off), gt.data_ptr(), _ia(gt_off), area.data_ptr(), sigma.data_ptr(), _la(out_off),
                                    out.data_ptr(), L.stream()), "ey_kpt_iou")
     return out, out_off
 
@@ -1858,15 +1855,9 @@ def classify_pool(x, w, bias, act, out=None):
     L.require_device(x, "classify_pool")
     _no_block("classify_pool")
     B, C1, H, W = x.shape
-    Cout = int(w.shape[0])
-    if w.dim() != 2 or w.shape[1] != C1 or w.dtype != x.dtype or not w.is_contiguous() or w.device != x.device:
-        raise ValueError(f"classify_pool: w must be a contiguous {x.dtype} (Cout, {C1}) tensor on {x.device}, got {w.dtype} {tuple(w.shape)}")
-    if bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.device != x.device:
-        raise ValueError(f"classify_pool: bias must be a contiguous float32 ({Cout},) tensor on {x.device}")
-    if out is None:
-        out = torch.empty((B, Cout), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Cout) or not out.is_contiguous() or out.device != x.device:
-        raise ValueError(f"classify_pool: out must be a contiguous float32 {(B, Cout)} tensor on {x.device}")
+    Cout = int(_dense(w, "classify_pool: w (Cout, C1)", x.dtype, (_ANY, C1), x.device).shape[0])
+    _dense(bias, "classify_pool: bias", torch.float32, (Cout,), x.device)
+    out = _dense_out("classify_pool: out=", out, torch.float32, (B, Cout), x.device)
     with _tr("classify_pool_kernel", _nb(x, w, bias, out), 2.0 * B * H * W * C1 * Cout):
         L.check(L.lib().ey_classify_pool(L.dtype_code(x.dtype), B, H * W, C1, Cout, int(act), x.data_ptr(), L.cstride(x), w.data_ptr(), bias.data_ptr(), out.data_ptr(),
                                          L.stream()), "ey_classify_pool")
@@ -1879,15 +1870,10 @@ def classify_linear_softmax(pooled, w, bias):
     probabilities rank the lower class index first."""
     L.require_device(pooled, "classify_linear_softmax")
     _no_block("classify_linear_softmax")
-    if pooled.dim() != 2 or pooled.dtype != torch.float32 or not pooled.is_contiguous():
-        raise ValueError(f"classify_linear_softmax: pooled must be a contiguous float32 (B, K) tensor, got {pooled.dtype} {tuple(pooled.shape)}")
-    B, K = pooled.shape
-    nc = int(w.shape[0])
     dev = pooled.device
-    if w.dim() != 2 or w.shape[1] != K or not w.is_contiguous() or w.device != dev:
-        raise ValueError(f"classify_linear_softmax: w must be a contiguous (nc, {K}) tensor on {dev}, got {tuple(w.shape)}")
-    if bias.dtype != torch.float32 or tuple(bias.shape) != (nc,) or not bias.is_contiguous() or bias.device != dev:
-        raise ValueError(f"classify_linear_softmax: bias must be a contiguous float32 ({nc},) tensor on {dev}")
+    B, K = _dense(pooled, "classify_linear_softmax: pooled (B, K)", torch.float32, (_ANY, _ANY), dev).shape
+    nc = int(_dense(w, "classify_linear_softmax: w (nc, K)", w.dtype, (_ANY, K), dev).shape[0])  # (its dtype is the entry point's to refuse)
+    _dense(bias, "classify_linear_softmax: bias", torch.float32, (nc,), dev)
     k5 = min(nc, 5)
     logits = torch.empty((B, nc), dtype=torch.float32, device=dev)
     probs = torch.empty((B, nc), dtype=torch.float32, device=dev)
@@ -1902,27 +1888,16 @@ def classify_linear_softmax(pooled, w, bias):
 def classify_transform(images, size, dtype, out=None, swap_rb=True):
     """classify_transforms(size) on the device (ey_classify_transform): images = contiguous uint8 (B, h, w, 3) device tensor (BGR like cv2)
     -> (B, 3, size, size) `dtype` RGB in [0, 1]: Resize(size) (Pillow's antialiased bilinear) + CenterCrop(size) + ToTensor in one launch."""
-    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous()):
-        raise ValueError("classify_transform: expected a contiguous uint8 device tensor of shape (B, h, w, 3)")
+    _dense(images, "classify_transform: images (B, h, w, 3)", torch.uint8, (_ANY, _ANY, _ANY, 3), torch.device("cuda"))
     L.require_device(images, "classify_transform")
     _no_block("classify_transform")
     B, h, w, _ = images.shape
     S = int(size)
-    if out is None:
-        out = torch.empty((B, 3, S, S), dtype=dtype, device=images.device)
-    elif tuple(out.shape) != (B, 3, S, S) or out.dtype != dtype or not out.is_contiguous() or out.device != images.device:
-        raise ValueError(f"classify_transform: out must be a contiguous {dtype} tensor of shape {(B, 3, S, S)} on {images.device}")
+    out = _dense_out("classify_transform: out=", out, dtype, (B, 3, S, S), images.device)
     with _tr("classify_transform_kernel", _nb(images, out)):
         L.check(L.lib().ey_classify_transform(L.dtype_code(dtype), images.data_ptr(), B, h, w, 3 * w, 3 * w * h, out.data_ptr(), S, int(swap_rb), L.stream()),
                 "ey_classify_transform")
     return out
-
-
-def _int_out(what, name, t, rows, cols, dev):
-    """an int32 output of `what` handed in through out=: contiguous, on `dev`, (rows, >= cols)."""
-    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or not t.is_contiguous() or t.device != dev:
-        raise ValueError(f"{what}: out= {name} must be a contiguous int32 ({rows}, >= {cols}) tensor on {dev}")
-    return t
 
 
 def linear_assignment(costs, thresh, out=None):
@@ -1946,14 +1921,13 @@ def linear_assignment(costs, thresh, out=None):
         raise ValueError(f"linear_assignment: {len(th)} thresholds for {B} problems")
     nmax, mmax = max(int(c.shape[0]) for c in costs), max(int(c.shape[1]) for c in costs)
     if out is None:
-        r2c = torch.full((B, max(nmax, 1)), -1, dtype=torch.int32, device=dev)
-        c2r = torch.full((B, max(mmax, 1)), -1, dtype=torch.int32, device=dev)
+        r2c, c2r = (_dense_out("linear_assignment: out=", None, torch.int32, (B, max(n, 1)), dev, fill=-1) for n in (nmax, mmax))
     else:
-        r2c, c2r = _int_out("linear_assignment", "row_to_col", out[0], B, nmax, dev), _int_out("linear_assignment", "col_to_row", out[1], B, mmax, dev)
+        r2c, c2r = (_dense(t, f"linear_assignment: out= {name}", torch.int32, (B, _AtLeast(n)), dev) for t, name, n in ((out[0], "row_to_col", nmax), (out[1], "col_to_row", mmax)))
     desc = torch.tensor([[c.data_ptr(), c.shape[0], c.shape[1], c.stride(0) if c.shape[0] > 1 and c.numel() else max(int(c.shape[1]), 1)] for c in costs], dtype=torch.int64).to(dev)
     tht = torch.tensor(th, dtype=torch.float32).to(dev)
     nb = int(L.lib().ey_linear_assignment_workspace_bytes(B, nmax, mmax))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    ws = _workspace("linear_assignment", None, nb, dev)
     with _tr("linear_assignment_kernel", _nb(*costs, r2c, c2r), note=f"{B} x <= {nmax}x{mmax}"):
         L.check(L.lib().ey_linear_assignment(B, desc.data_ptr(), tht.data_ptr(), nmax, mmax, r2c.data_ptr(), int(r2c.shape[1]), c2r.data_ptr(), int(c2r.shape[1]),
                                              ws.data_ptr(), nb, L.stream()), "ey_linear_assignment")
@@ -1975,28 +1949,16 @@ def bytetrack_update(rows, count, state, settings, out=None, workspace=None):
     L.require_device(rows, "bytetrack_update")
     _no_block("bytetrack_update")
     dev = rows.device
-    if rows.dim() != 3 or rows.shape[2] != 6 or rows.dtype != torch.float32 or not rows.is_contiguous() or rows.shape[1] < 1:
-        raise ValueError(f"bytetrack_update: rows must be a contiguous float32 (B, cap >= 1, 6) tensor, got {rows.dtype} {tuple(rows.shape)}")
-    B, cap = int(rows.shape[0]), int(rows.shape[1])
-    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous() or count.device != dev:
-        raise ValueError(f"bytetrack_update: count must be a contiguous int32 ({B},) tensor on {dev}")
+    B, cap = (int(v) for v in _dense(rows, "bytetrack_update: rows (B, cap, 6)", torch.float32, (_ANY, _AtLeast(1), 6), dev).shape[:2])
+    _dense(count, "bytetrack_update: count", torch.int32, (B,), dev)
     T = int(state["kf"].shape[1])
     for k, (shape, dt) in {"kf": ((B, T, 72), torch.float64), "slot_i": ((B, T, 8), torch.int32), "slot_f": ((B, T, 2), torch.float32), "hdr": ((B, 4), torch.int32)}.items():
-        t = state[k]
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"bytetrack_update: state['{k}'] must be a contiguous {dt} {shape} tensor on {dev}")
-    want = (((B, cap, 8), torch.float32), ((B, cap), torch.int32), ((B,), torch.int32))
-    if out is None:
-        out = tuple(torch.zeros(s, dtype=dt, device=dev) for s, dt in want)
-    else:
-        out = tuple(out)
-        if len(out) != 3 or any(tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or t.device != dev for t, (s, dt) in zip(out, want)):
-            raise ValueError(f"bytetrack_update: out= must be contiguous tensors {want} on {dev}")
-    nb = int(L.lib().ey_bytetrack_workspace_bytes(B, cap, T))
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < nb or not workspace.is_contiguous() or workspace.device != dev or workspace.data_ptr() % 16:
-        raise ValueError(f"bytetrack_update: workspace must be a contiguous, 16-byte aligned uint8 tensor of >= {nb} bytes on {dev}")
+        _dense(state[k], f"bytetrack_update: state['{k}']", dt, shape, dev)
+    if out is not None and (len(out := tuple(out)) != 3 or any(t is None for t in out)):
+        raise ValueError("bytetrack_update: out= must be the (out_rows, ids, counts) tensors")
+    out = tuple(_dense_out(f"bytetrack_update: out= {name}", out and out[i], dt, shape, dev, fill=0)
+                for i, (name, shape, dt) in enumerate((("out_rows", (B, cap, 8), torch.float32), ("ids", (B, cap), torch.int32), ("counts", (B,), torch.int32))))
+    workspace = _workspace("bytetrack_update", workspace, int(L.lib().ey_bytetrack_workspace_bytes(B, cap, T)), dev)
     s = settings
     with _tr("bytetrack_update_kernel", _nb(rows, *out), note=f"{B} streams x {cap} rows, {T} slots"):
         L.check(L.lib().ey_bytetrack_update(B, cap, T, float(s["track_high_thresh"]), float(s["track_low_thresh"]), float(s["new_track_thresh"]), float(s["match_thresh"]),
@@ -2012,17 +1974,14 @@ def mask_contours_launch(masks, windows, contour_cap, vertex_cap, out=None):
     write instead."""
     n, h, w = (int(v) for v in masks.shape)
     dev = masks.device
-    want = (((n, contour_cap), torch.int32), ((n, vertex_cap, 2), torch.int32), ((n, 4), torch.int32))
-    if out is None:
-        out = tuple(torch.empty(s, dtype=dt, device=dev) for s, dt in want)
-    else:
-        out = tuple(out)
-        if len(out) != 3 or any(not torch.is_tensor(t) or tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or t.device != dev for t, (s, dt) in zip(out, want)):
-            raise ValueError(f"mask_contours: out= must be contiguous tensors {want} on {dev}")
+    if out is not None and (len(out := tuple(out)) != 3 or any(t is None for t in out)):
+        raise ValueError("mask_contours: out= must be the (lens, verts, info) tensors")
+    out = tuple(_dense_out(f"mask_contours: out= {name}", out and out[i], torch.int32, shape, dev)
+                for i, (name, shape) in enumerate((("lens", (n, contour_cap)), ("verts", (n, vertex_cap, 2)), ("info", (n, 4)))))
     nb = int(L.lib().ey_mask_contours_workspace_bytes(n, h, w))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    ws = _workspace("mask_contours", None, nb, dev)
     with _tr("mask_contours_kernel", _nb(masks, *out), note=f"{n} masks {h}x{w}, room for {contour_cap} contours / {vertex_cap} vertices each"):
-        L.check(L.lib().ey_mask_contours(n, h, w, masks.data_ptr(), windows.data_ptr() if windows is not None else None, contour_cap, vertex_cap,
+        L.check(L.lib().ey_mask_contours(n, h, w, masks.data_ptr(), _p(windows), contour_cap, vertex_cap,
                                          out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), nb, L.stream()), "ey_mask_contours")
     return out
 
@@ -2035,9 +1994,7 @@ def mask_contours(masks, boxes=None, out=None, _contour_capacity=64, _vertex_cap
     order (last found first).  Only the counts and the vertices cross to the host.  The launch writes into fixed-size buffers; when a mask
     needs more room than they have, they grow to what the kernel counted and the launch is repeated, so nothing is ever cut short.
     out=: the (lens, verts, info) tensors of mask_contours_launch for the first launch."""
-    if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool) or not masks.is_contiguous():
-        raise ValueError(f"mask_contours: masks must be a contiguous uint8 or bool (n, h, w) tensor, got {getattr(masks, 'dtype', type(masks))} "
-                         f"{tuple(getattr(masks, 'shape', ()))}")
+    _dense(masks, "mask_contours: masks (n, h, w)", (torch.uint8, torch.bool), (_ANY, _ANY, _ANY), None)
     L.require_device(masks, "mask_contours")
     _no_block("mask_contours")
     n, h, w = (int(v) for v in masks.shape)

@@ -1,4 +1,5 @@
-"""-m gpu: every wrapper of nn/_ops.py that takes out= checks it before anything is launched.  Each op runs on the smallest legal input
+"""-m gpu: every wrapper of nn/_ops.py that takes out= checks it before anything is launched.  The post-processing wrappers (dense buffers,
+workspace=, tracker state) have their own table at the end of the file.  Each network op runs on the smallest legal input
 (B = 1, 8 channels or the op's minimum width, a 4x4 map, f16).  A wrong spatial shape, a wrong dtype and an NCHW-contiguous tensor of the
 right logical shape raise ValueError and record no launch; a good channel slot of a wider buffer gives the bits of the freshly allocated
 output and leaves its neighbours alone.  The ops that require 16-byte slots refuse a window starting at element 4; the fused ops that fall
@@ -359,3 +360,137 @@ def test_out_is_checked(name):
         assert y1 is not None and y1.data_ptr() == slot.data_ptr() and tuple(y1.shape) == (B, C, H, W)
         assert torch.equal(y1, y0), "a channel slot must receive the bits of the freshly allocated output"
         assert bool((buf[:, :8] == SENTINEL).all()) and bool((buf[:, 8 + C:] == SENTINEL).all()), "the neighbouring channels were written"
+
+
+# ---- the post-processing wrappers: dense (non-NHWC) out= buffers, workspace= and one tracker state entry, checked by _dense / _workspace.
+# One builder per op -> (call, spec): call(bufs) runs the op on its smallest legal input with the caller's buffers of `bufs` (label -> tensor; a
+# label that is missing is left to the wrapper) and returns the outputs as a list; spec: label -> (shape, dtype) of the buffer that is right.
+def _dev():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _rand(*shape, seed=1):
+    return torch.rand(*shape, generator=torch.Generator().manual_seed(seed)).cuda()
+
+
+def _bits(n, h, w, seed=2):
+    return (torch.rand(n, h, w, generator=torch.Generator().manual_seed(seed)) > 0.4).to(torch.uint8).cuda()
+
+
+def _post_process_mask():
+    from edge_yolo_amd.nn import _ops
+    proto, coef = _rand(1, 4, 4, 8).sub(0.5).permute(0, 3, 1, 2), _rand(1, 2, 2, 8, seed=3).sub(0.5).permute(0, 3, 1, 2)
+    rows = torch.tensor([[0, 0], [0, 3]], dtype=torch.int32).cuda()
+    boxes = torch.tensor([[0.0, 0.0, 8.0, 8.0], [1.0, 2.0, 7.0, 6.0]]).cuda()
+    return (lambda b: [_ops.process_mask(proto, [coef], rows, boxes, 2, out=b.get("out"))]), {"out": ((2, 8, 8), torch.uint8)}
+
+
+def _post_scale_masks():
+    from edge_yolo_amd.nn import _ops
+    masks = _bits(2, 8, 8)[:, None]
+    return (lambda b: [_ops.scale_masks(masks, (12, 10), out=b.get("out"))]), {"out": ((2, 1, 12, 10), torch.float32)}
+
+
+def _post_kpt_iou():
+    from edge_yolo_amd.nn import _ops
+    pred, gt = _rand(2, 2, 3).mul(8), _rand(2, 2, 3, seed=4).mul(8)
+    gt[:, :, 2] = 1.0
+    area, sigma = torch.tensor([30.0, 50.0]).cuda(), torch.tensor([0.05, 0.1]).cuda()
+    return (lambda b: [_ops.kpt_iou(pred, [0, 2], gt, [0, 2], area, sigma, out=b.get("out"))[0]]), {"out": ((4,), torch.float32)}
+
+
+def _post_kpts_decode_rows():
+    from edge_yolo_amd.nn import _ops
+    levels = [(_x(6), 8.0, 0)]  # K = 2 keypoints of (x, y, visibility) on a 4x4 map
+    index, count = torch.tensor([[5, 11]], dtype=torch.int32).cuda(), torch.tensor([2], dtype=torch.int32).cuda()
+    return (lambda b: [_ops.kpts_decode_rows(levels, (2, 3), index, count, out=b.get("out"))]), {"out": ((1, 2, 2, 3), torch.float32)}
+
+
+def _post_classify_pool():
+    from edge_yolo_amd import _lib as L
+    from edge_yolo_amd.nn import _ops
+    x, w, bias = _x(), _rand(16, 8).sub(0.5).half(), _rand(16, seed=5)  # f16 takes Cout in multiples of 16
+    return (lambda b: [_ops.classify_pool(x, w, bias, L.ACT_SILU, out=b.get("out"))]), {"out": ((1, 16), torch.float32)}
+
+
+def _post_classify_transform():
+    from edge_yolo_amd.nn import _ops
+    images = (_rand(1, 8, 8, 3) * 255).to(torch.uint8)
+    return (lambda b: [_ops.classify_transform(images, 4, F16, out=b.get("out"))]), {"out": ((1, 3, 4, 4), F16)}
+
+
+def _some_or_all(b, spec, labels, make=tuple):
+    """None when `b` names none of `labels`, else all of them: the caller's where given, a right one (zeros) elsewhere."""
+    if not any(k in b for k in labels):
+        return None
+    return make((k, b[k] if k in b else torch.zeros(spec[k][0], dtype=spec[k][1], device=_dev())) for k in labels)
+
+
+def _post_mask_prompt():
+    from edge_yolo_amd import _lib as L
+    from edge_yolo_amd.nn import _ops
+    masks = _bits(2, 8, 8)
+    spec = {"full": ((2,), torch.float32), "keep": ((2,), torch.uint8), "inter": ((1, 2), torch.float32), "iou": ((1, 2), torch.float32),
+            "best": ((1, 1), torch.int32), "hit": ((1, 2), torch.uint8)}
+    outs = list(spec)
+    spec["workspace"] = ((int(L.lib().ey_mask_prompt_workspace_bytes(1, 8, 8, 1)),), torch.uint8)  # exactly what the entry point asks for
+
+    def call(b):
+        got = _ops.mask_prompt(masks, [0, 2], [(8, 8)], bboxes=[[1, 1, 6, 6]], points=[[3, 4]], labels=[1], out=_some_or_all(b, spec, outs, dict), workspace=b.get("workspace"))
+        return [got[k] for k in outs]
+
+    return call, spec
+
+
+def _post_bytetrack_update():
+    import fp64_track_ref as ref
+    from edge_yolo_amd import _lib as L
+    from edge_yolo_amd.nn import _ops
+    rows = torch.zeros((1, 4, 6)).cuda()  # one stream, room for 4 detections, 8 track slots
+    rows[0, :2] = torch.tensor([[10.0, 12.0, 30.0, 40.0, 0.9, 0.0], [50.0, 20.0, 80.0, 70.0, 0.8, 1.0]]).cuda()
+    count = torch.tensor([2], dtype=torch.int32).cuda()
+    spec = {"out_rows": ((1, 4, 8), torch.float32), "ids": ((1, 4), torch.int32), "counts": ((1,), torch.int32), "state_kf": ((1, 8, 72), torch.float64),
+            "workspace": ((int(L.lib().ey_bytetrack_workspace_bytes(1, 4, 8)),), torch.uint8)}
+
+    def call(b):
+        state = _ops.bytetrack_state(1, 8, _dev())  # a fresh tracker each time: the call advances it
+        if "state_kf" in b:
+            state["kf"] = b["state_kf"]
+        out = _some_or_all(b, spec, ("out_rows", "ids", "counts"), lambda kv: tuple(t for _, t in kv))
+        return list(_ops.bytetrack_update(rows, count, state, ref.DEFAULTS, out=out, workspace=b.get("workspace"))) + [state[k] for k in sorted(state)]
+
+    return call, spec
+
+
+POST_OPS = {"process_mask": _post_process_mask, "scale_masks": _post_scale_masks, "kpt_iou": _post_kpt_iou, "kpts_decode_rows": _post_kpts_decode_rows,
+            "classify_pool": _post_classify_pool, "classify_transform": _post_classify_transform, "mask_prompt": _post_mask_prompt,
+            "bytetrack_update": _post_bytetrack_update}
+OTHER_DTYPE = {torch.float32: torch.int32, torch.int32: torch.float32, torch.uint8: torch.int8, torch.float64: torch.float32, F16: torch.float32}
+
+
+@pytest.mark.parametrize("name", sorted(POST_OPS))
+def test_dense_buffers_are_checked(name):
+    from edge_yolo_amd import profiling
+    with torch.no_grad():
+        call, spec = POST_OPS[name]()
+        y0 = [t.clone() for t in call({})]
+        torch.cuda.synchronize()
+        for label, (shape, dt) in spec.items():
+            bad = {"dtype": torch.zeros(shape, dtype=OTHER_DTYPE[dt], device=_dev()),
+                   "shape": torch.zeros(shape + (1,), dtype=dt, device=_dev()),  # the same elements under one more axis
+                   "too small": torch.zeros((shape[0] - 1,) + shape[1:], dtype=dt, device=_dev())}
+            for why, t in bad.items():
+                with profiling.trace() as rec:
+                    with pytest.raises(ValueError, match=label.replace("state_", "")):
+                        call({label: t})
+                assert rec.records == [], (label, why, [r[0] for r in rec.records])
+        mine = {label: torch.zeros(shape, dtype=dt, device=_dev()) for label, (shape, dt) in spec.items()}
+        y1 = call(mine)
+        torch.cuda.synchronize()
+        for label in spec:
+            if not label.startswith(("state", "workspace")):
+                assert any(t.data_ptr() == mine[label].data_ptr() for t in y1), f"{label}: the caller's buffer was not the one written"
+        assert len(y1) == len(y0)
+        for a, b in zip(y0, y1):
+            assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), \
+                "the caller's buffers must receive the bits of the call that allocates its own"

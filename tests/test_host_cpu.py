@@ -21,6 +21,33 @@ import synthdata as synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+C_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+
+
+def _header_prototypes(hdr):
+    """{name: (return type, [parameter types])} of every function the (comment-free) header declares, each type as C text without the parameter's name."""
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)  # preprocessor lines
+    hdr = re.sub(r'extern\s+"C"\s*\{', "", hdr)
+    hdr = re.sub(r"\btypedef\s+struct\b[^{;]*\{.*?\}[^;]*;", "", hdr, flags=re.S)  # struct bodies
+    hdr = re.sub(r"\benum\b[^{;]*\{.*?\}\s*;", "", hdr, flags=re.S)
+    hdr = re.sub(r"\btypedef\b[^;{]*;", "", hdr)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s*]*?)\b(ey_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr):
+        params = [] if params.strip() == "void" else [re.sub(r"\b\w+\s*$", "", p) for p in params.split(",")]  # (drop each parameter's name)
+        assert name not in protos, f"{name} declared twice"
+        protos[name] = tuple(" ".join(t.replace("*", " * ").split()) for t in [ret] + params)
+    return {k: (v[0], list(v[1:])) for k, v in protos.items()}
+
+
+def _binds(ctype, text):
+    """True when the ctypes type `ctype` of the binding table passes what the C type `text` takes."""
+    if text == "const char *":
+        return ctype is ctypes.c_char_p
+    if "*" in text or text == "ey_stream_t":  # every other pointer, and the stream handle
+        return ctype is ctypes.c_void_p or (isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+    return text in C_SCALARS and ctype is C_SCALARS[text]
+
+
 def test_cabi_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "edgeyolo_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -31,8 +58,18 @@ def test_cabi_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in include/edgeyolo_hip.h but not exported"
     assert declared == set(L.SIGNATURES), "ctypes binding table and header disagree"
     assert L.lib().ey_version() >= 1
+    # every prototype, type by type: a scalar of the wrong width would shift or truncate each argument behind it
+    protos = _header_prototypes(hdr)
+    assert set(protos) == declared, sorted(declared ^ set(protos))
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = L.SIGNATURES[name]
+        assert _binds(res, ret), f"{name}: returns '{ret}', bound as {res}"
+        assert len(args) == len(params), f"{name}: {len(params)} parameters declared, {len(args)} bound"
+        for i, (a, p) in enumerate(zip(args, params)):
+            assert _binds(a, p), f"{name}: parameter {i} is '{p}', bound as {a}"
     # struct layouts must match the header (sizes as the C compiler lays them out)
     assert L.lib().ey_abi_sizeof(0) == ctypes.sizeof(L.ConvDesc) and L.lib().ey_abi_sizeof(1) == ctypes.sizeof(L.ConvDirectDesc)
+    assert L.lib().ey_block_stage_sizeof() == ctypes.sizeof(L.BlockStage)
 
 
 @pytest.fixture(scope="module")
