@@ -176,6 +176,9 @@ SIGNATURES = {
     "ey_probiou": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "ey_nms_rotated_workspace_bytes": (_sz, [_i, _i, _i]),
     "ey_nms_rotated": (_i, [_i, _i, _i, _vp, _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_nms_rotated_ml_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ey_nms_rotated_ml": (_i, [_i, _i, _i, _vp, _f, _f, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_probiou_batch": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ey_kpts_decode_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_long, _i, _vp, _vp]),
     "ey_kpts_decode_rows": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ey_kpt_iou": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,9 @@
 // The reference takes max_i iou(i, j); iou is a non-increasing function of the clamped distance (exp, the subtraction, sqrt and the
 // final subtraction are each monotone in fp32), so max_i iou(i, j) = iou(min_i bd(i, j)) bit for bit and the exp / sqrt tail runs once
 // per column instead of once per pair.  The minimum is order independent: the result is the same run to run.
+// ey_nms_rotated_ml: the validation regime (every (anchor, class) score above conf is a candidate): a radix select cuts them to max_nms, the
+//   survivors go through obb_pair and obb_resolve as above; see the section at the end of the file.
+// ey_probiou_batch: ey_probiou's tile body for every image of a batch in one launch, through per-image offset tables.
 //
 // Arithmetic: this file is compiled without FMA contraction and follows the reference's fp32 expressions operation by operation
 // (division and sqrt are IEEE here).  exp / log / sin / cos are evaluated in double and rounded to fp32, i.e. correctly rounded but for
@@ -73,10 +76,10 @@ __device__ __forceinline__ float obb_pair_bd(const ObbGauss& p, const ObbGauss& 
 __device__ __forceinline__ float obb_bd_iou(float bd) { return 1.f - sqrtf(1.f - obb_expf(-bd) + OBB_EPS); }
 __device__ __forceinline__ float obb_pair_iou(const ObbGauss& p, const ObbGauss& q) { return obb_bd_iou(obb_pair_bd(p, q)); }
 
-__global__ __launch_bounds__(OBB_TILE) void obb_probiou_kernel(int N, int M, const float* __restrict__ o1, const float* __restrict__ o2, float* __restrict__ out) {
-  __shared__ ObbGauss rows[OBB_PROWS];
+// one workgroup's share of an (N, M) matrix: column tile bx, row chunk by (both inside the matrix); rows = the LDS stage of the chunk's Gaussians
+__device__ __forceinline__ void obb_probiou_tile(int N, int M, const float* __restrict__ o1, const float* __restrict__ o2, float* __restrict__ out, int bx, int by, ObbGauss* rows) {
   const int tid = threadIdx.x;
-  const int i0 = blockIdx.y * OBB_PROWS, j = blockIdx.x * OBB_TILE + tid;
+  const int i0 = by * OBB_PROWS, j = bx * OBB_TILE + tid;
   const int nr = min(OBB_PROWS, N - i0);
   if (tid < nr) {
     const float* p = o1 + (long)(i0 + tid) * 5;
@@ -87,6 +90,59 @@ __global__ __launch_bounds__(OBB_TILE) void obb_probiou_kernel(int N, int M, con
   const float* p = o2 + (long)j * 5;
   const ObbGauss q = obb_gauss(p[0], p[1], p[2], p[3], p[4]);
   for (int i = 0; i < nr; ++i) out[(long)(i0 + i) * M + j] = obb_pair_iou(rows[i], q);
+}
+
+__global__ __launch_bounds__(OBB_TILE) void obb_probiou_kernel(int N, int M, const float* __restrict__ o1, const float* __restrict__ o2, float* __restrict__ out) {
+  __shared__ ObbGauss rows[OBB_PROWS];
+  obb_probiou_tile(N, M, o1, o2, out, blockIdx.x, blockIdx.y, rows);
+}
+
+// every image's [ground truth x prediction] matrix in one launch: grid.y = image, grid.x = the image's tiles (column tile fastest)
+#define OBB_PB_MAXB 128
+struct ObbPairTab {
+  int pred_off[OBB_PB_MAXB + 1];
+  int gt_off[OBB_PB_MAXB + 1];
+  long out_off[OBB_PB_MAXB];
+};
+__global__ __launch_bounds__(OBB_TILE) void obb_probiou_batch_kernel(ObbPairTab tab, const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ out) {
+  __shared__ ObbGauss rows[OBB_PROWS];
+  const int b = blockIdx.y;
+  const int N = tab.pred_off[b + 1] - tab.pred_off[b], M = tab.gt_off[b + 1] - tab.gt_off[b];
+  if (N <= 0 || M <= 0) return;  // (workgroup-uniform)
+  const int ntx = (N + OBB_TILE - 1) / OBB_TILE, nty = (M + OBB_PROWS - 1) / OBB_PROWS;
+  if ((int)blockIdx.x >= ntx * nty) return;  // (workgroup-uniform)
+  const int by = blockIdx.x / ntx, bx = blockIdx.x - by * ntx;
+  obb_probiou_tile(M, N, gt + (long)tab.gt_off[b] * 5, pred + (long)tab.pred_off[b] * 5, out + tab.out_off[b], bx, by, rows);
+}
+
+extern "C" int ey_probiou_batch(int B, const float* pred, const int* pred_off, const float* gt, const int* gt_off, float* out, const long* out_off, ey_stream_t stream) {
+  EY_CHECK(B >= 0, "probiou_batch: B=%d", B);
+  if (B > OBB_PB_MAXB) return ey_set_error(EY_EUNSUPPORTED, "probiou_batch: B=%d (up to %d images are built)", B, OBB_PB_MAXB);
+  if (B == 0) return EY_OK;
+  EY_CHECK(pred_off && gt_off && out_off, "probiou_batch: null offset table");
+  EY_CHECK(pred_off[0] == 0 && gt_off[0] == 0, "probiou_batch: pred_off[0]=%d gt_off[0]=%d must be 0", pred_off[0], gt_off[0]);
+  ObbPairTab tab;
+  tab.pred_off[0] = tab.gt_off[0] = 0;
+  long tiles = 0;
+  for (int b = 0; b < OBB_PB_MAXB; ++b) {
+    const bool on = b < B;
+    const long nb = on ? (long)pred_off[b + 1] - pred_off[b] : 0, mb = on ? (long)gt_off[b + 1] - gt_off[b] : 0;
+    EY_CHECK(nb >= 0 && mb >= 0, "probiou_batch: offsets of image %d decrease", b);
+    EY_CHECK(!(nb && mb) || out_off[b] >= 0, "probiou_batch: out_off[%d]=%ld", b, on ? out_off[b] : 0L);
+    tab.pred_off[b + 1] = on ? pred_off[b + 1] : tab.pred_off[b];
+    tab.gt_off[b + 1] = on ? gt_off[b + 1] : tab.gt_off[b];
+    tab.out_off[b] = on ? out_off[b] : 0;
+    if (nb && mb) {
+      const long t = (long)ey_cdiv(nb, OBB_TILE) * ey_cdiv(mb, OBB_PROWS);
+      tiles = t > tiles ? t : tiles;
+    }
+  }
+  if (tiles == 0) return EY_OK;
+  if (tiles >= (1L << 31)) return ey_set_error(EY_EUNSUPPORTED, "probiou_batch: %ld tiles in one image", tiles);
+  EY_CHECK(pred && gt && out, "probiou_batch: null pointer");
+  hipLaunchKernelGGL(obb_probiou_batch_kernel, dim3((unsigned)tiles, B), dim3(OBB_TILE), 0, (hipStream_t)stream, tab, pred, gt, out);
+  EY_LAUNCH_CHECK("ey_probiou_batch");
+  return EY_OK;
 }
 
 extern "C" int ey_probiou(int N, int M, const float* obb1, const float* obb2, float* out, ey_stream_t stream) {
@@ -264,14 +320,8 @@ __global__ __launch_bounds__(256) void obb_score_kernel(int nc, int A, const flo
   }
 }
 
-__global__ __launch_bounds__(256) void obb_rank_kernel(int nc, int A, const float* __restrict__ pred, int max_nms, float cls_off, ObbWs ws) {
-  __shared__ unsigned long long tile[256];
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int n = ws.cnt[b];
-  if ((int)blockIdx.x * 256 >= n) return;  // (workgroup-uniform)
-  const unsigned long long* keys = ws.keys + (long)b * A;
-  const int j = blockIdx.x * 256 + tid;
-  const unsigned long long key = j < n ? keys[j] : ~0ull;
+// number of the n keys that are larger than `key` (the whole workgroup of 256 calls it; keys are unique, so that is the key's position)
+__device__ __forceinline__ int obb_rank_of(const unsigned long long* __restrict__ keys, int n, unsigned long long key, unsigned long long* tile, int tid) {
   int rank = 0;
   for (int t0 = 0; t0 < n; t0 += 256) {
     __syncthreads();
@@ -280,16 +330,32 @@ __global__ __launch_bounds__(256) void obb_rank_kernel(int nc, int A, const floa
 #pragma unroll 8
     for (int k = 0; k < 256; ++k) rank += tile[k] > key ? 1 : 0;
   }
-  if (j >= n || rank >= max_nms) return;
-  const int a = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-  const int cls = ws.ccls[(long)b * A + j];
+  return rank;
+}
+
+// the record of the candidate (anchor a, class cls, score bits) at position `rank` of image b
+__device__ __forceinline__ void obb_write_record(int b, int nc, int A, const float* __restrict__ pred, float cls_off, const ObbWs& ws, int rank, int a, int cls, unsigned score_bits) {
   const float* pp = pred + (long)b * (4 + nc + 1) * A + a;
   const float c = (float)cls * cls_off;  // x[:, 5:6] * (0 if agnostic else max_wh), added in fp32 (ops.py:289-292)
   const ObbGauss g = obb_gauss(pp[0] + c, pp[(long)A] + c, pp[2L * A], pp[3L * A], pp[(long)(4 + nc) * A]);
   float* r = ws.rec + ((long)b * ws.maxn + rank) * 8;
   *reinterpret_cast<f32x4*>(r) = f32x4{g.x, g.y, g.a, g.b};
-  *reinterpret_cast<f32x4*>(r + 4) = f32x4{g.c, g.d, __int_as_float(a), __uint_as_float((unsigned)(key >> 32))};
+  *reinterpret_cast<f32x4*>(r + 4) = f32x4{g.c, g.d, __int_as_float(a), __uint_as_float(score_bits)};
   ws.scls[(long)b * ws.maxn + rank] = cls;
+}
+
+__global__ __launch_bounds__(256) void obb_rank_kernel(int nc, int A, const float* __restrict__ pred, int max_nms, float cls_off, ObbWs ws) {
+  __shared__ unsigned long long tile[256];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int n = ws.cnt[b];
+  if ((int)blockIdx.x * 256 >= n) return;  // (workgroup-uniform)
+  const unsigned long long* keys = ws.keys + (long)b * A;
+  const int j = blockIdx.x * 256 + tid;
+  const unsigned long long key = j < n ? keys[j] : ~0ull;
+  const int rank = obb_rank_of(keys, n, key, tile, tid);
+  if (j >= n || rank >= max_nms) return;
+  const int a = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+  obb_write_record(b, nc, A, pred, cls_off, ws, rank, a, ws.ccls[(long)b * A + j], (unsigned)(key >> 32));
 }
 
 __global__ __launch_bounds__(OBB_TILE) void obb_pair_kernel(int max_nms, ObbWs ws) {
@@ -394,5 +460,176 @@ extern "C" int ey_nms_rotated(int B, int nc, int A, const float* pred, float con
   hipLaunchKernelGGL(obb_pair_kernel, dim3(tiles, chunks, B), dim3(OBB_TILE), 0, st, max_nms, ws);
   hipLaunchKernelGGL(obb_resolve_kernel, dim3(B), dim3(1024), 0, st, nc, A, pred, iou_thres, max_det, max_nms, ws, out_rows, out_count, out_index);
   EY_LAUNCH_CHECK("ey_nms_rotated");
+  return EY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rotated NMS, multi label
+// The validation regime (ops.py:270-297 with multi_label): every (anchor a, class c) with score > conf is a candidate, up to NK = A nc per
+// image, cut to the max_nms best.  Six launches, no host synchronisation:
+//   obb_init        (the kernel above) candidate counters = 0, column minima = +inf
+//   obb_ml_score    thread = one (anchor, class) score, read coalesced; candidates are compacted with one atomic per wave:
+//                   key = score_bits << 32 | ~(a nc + c), unique per image, so the slot order does not matter
+//   obb_ml_select   one workgroup per image: with more than max_nms candidates, the max_nms-th largest key by an 8-bit radix select over
+//                   the 64 key bits (LDS histogram of integer counts, 8 passes over the image's keys, no ranking of all candidates); then
+//                   the keys >= that key, exactly min(n, max_nms) of them, are compacted into the survivor list
+//   obb_ml_rank     obb_rank_of over the survivors (all pairs of at most max_nms keys) -> the Gaussian record at the key's position
+//   obb_pair, obb_resolve   the kernels above, unchanged: the records, the class list and the counter have the single-label layout
+// workspace, every part 256-byte aligned: counters [B] | candidate counters [B] | keys [B][NK] u64 | survivor keys [B][maxn] u64 |
+// records [B][maxn][8] | sorted class ids [B][maxn] | column minima [B][maxn], maxn = min(NK, max_nms).
+struct ObbMl {
+  int* ncand;
+  unsigned long long* keys;
+  unsigned long long* skeys;
+  long NK;
+};
+static size_t obb_ml_layout(int B, long NK, int max_nms, char* base, ObbWs* ws, ObbMl* ml) {
+  const size_t maxn = (size_t)(NK < max_nms ? NK : max_nms);
+  size_t off = 0;
+  const size_t o_cnt = off; off += obb_al((size_t)B * 4);
+  const size_t o_ncand = off; off += obb_al((size_t)B * 4);
+  const size_t o_keys = off; off += obb_al((size_t)B * NK * 8);
+  const size_t o_skeys = off; off += obb_al((size_t)B * maxn * 8);
+  const size_t o_rec = off; off += obb_al((size_t)B * maxn * 32);
+  const size_t o_scls = off; off += obb_al((size_t)B * maxn * 4);
+  const size_t o_min = off; off += obb_al((size_t)B * maxn * 4);
+  if (ws) {
+    ws->cnt = (int*)(base + o_cnt);
+    ws->keys = (unsigned long long*)(base + o_skeys);
+    ws->ccls = nullptr;
+    ws->rec = (float*)(base + o_rec);
+    ws->scls = (int*)(base + o_scls);
+    ws->colmin = (unsigned*)(base + o_min);
+    ws->maxn = (int)maxn;
+    ml->ncand = (int*)(base + o_ncand);
+    ml->keys = (unsigned long long*)(base + o_keys);
+    ml->skeys = ws->keys;
+    ml->NK = NK;
+  }
+  return off;
+}
+extern "C" size_t ey_nms_rotated_ml_workspace_bytes(int B, int nc, int A, int max_nms) {
+  if (B <= 0 || nc <= 0 || A <= 0 || max_nms <= 0 || (long)A * nc >= (1L << 31)) return 0;
+  return obb_ml_layout(B, (long)A * nc, max_nms, nullptr, nullptr, nullptr);
+}
+
+// slots for the lanes of a wave that hold a candidate: one atomic on `counter` per wave, the lanes in lane order behind it
+__device__ __forceinline__ int obb_wave_slot(bool on, int* counter, int lane) {
+  const unsigned long long bal = __ballot(on);
+  int base = 0;
+  if (lane == 0 && bal) base = atomicAdd(counter, __popcll(bal));
+  base = __shfl(base, 0);
+  return base + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(256) void obb_ml_score_kernel(int nc, int A, const float* __restrict__ pred, float conf, const uint8_t* __restrict__ mask, ObbMl ml) {
+  const int b = blockIdx.z, c = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
+  float s = 0.f;
+  bool on = false;
+  if (a < A && (!mask || mask[c])) {
+    s = pred[(long)b * (4 + nc + 1) * A + (long)(4 + c) * A + a];
+    on = s > conf;  // (strict; a NaN score is no candidate)
+  }
+  const int slot = obb_wave_slot(on, &ml.ncand[b], threadIdx.x & 63);
+  if (on) ml.keys[(long)b * ml.NK + slot] = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(a * nc + c));
+}
+
+__global__ __launch_bounds__(1024) void obb_ml_select_kernel(int max_nms, ObbWs ws, ObbMl ml) {
+  __shared__ int hist[256];
+  __shared__ int s_digit, s_k, s_cnt;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int n = ml.ncand[b];
+  const unsigned long long* keys = ml.keys + (long)b * ml.NK;
+  unsigned long long thr = 0ull;  // the smallest surviving key
+  if (n > max_nms) {  // (workgroup-uniform)
+    // invariant: at least k keys agree with `thr` on the bits above `shift`, and the k-th largest of them is the max_nms-th largest of all
+    int k = max_nms;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for (int i0 = 0; i0 < n; i0 += 1024) {  // (every lane of a wave runs the same number of rounds)
+        const int i = i0 + tid;
+        const unsigned long long key = i < n ? keys[i] : 0ull;
+        bool on = i < n && (shift == 56 || (key >> (shift + 8)) == (thr >> (shift + 8)));
+        const int digit = (int)((key >> shift) & 255ull);
+        // scores share their leading bits: up to four digit values are counted by one atomic per wave each, the rest lane by lane
+        for (int it = 0; it < 4; ++it) {
+          const unsigned long long bal = __ballot(on);
+          if (!bal) break;  // (wave-uniform)
+          const int leader = __ffsll((long long)bal) - 1;
+          const int d = __shfl(digit, leader);
+          const unsigned long long same = __ballot(on && digit == d);
+          if (lane == leader) atomicAdd(&hist[d], __popcll(same));
+          if (digit == d) on = false;
+        }
+        if (on) atomicAdd(&hist[digit], 1);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int above = 0, d = 255;
+        for (; d > 0; --d) {
+          if (above + hist[d] >= k) break;
+          above += hist[d];
+        }
+        s_digit = d;
+        s_k = k - above;
+      }
+      __syncthreads();
+      thr |= (unsigned long long)s_digit << shift;
+      k = s_k;
+    }
+  }
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  unsigned long long* skeys = ml.skeys + (long)b * ws.maxn;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + tid;
+    const unsigned long long key = i < n ? keys[i] : 0ull;
+    const bool on = i < n && key >= thr;
+    const int slot = obb_wave_slot(on, &s_cnt, lane);
+    if (on && slot < ws.maxn) skeys[slot] = key;  // (keys are unique: exactly min(n, max_nms) <= maxn of them pass)
+  }
+  if (tid == 0) ws.cnt[b] = min(n, max_nms);
+}
+
+__global__ __launch_bounds__(256) void obb_ml_rank_kernel(int nc, int A, const float* __restrict__ pred, float cls_off, ObbWs ws) {
+  __shared__ unsigned long long tile[256];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int n = ws.cnt[b];
+  if ((int)blockIdx.x * 256 >= n) return;  // (workgroup-uniform)
+  const unsigned long long* keys = ws.keys + (long)b * ws.maxn;
+  const int j = blockIdx.x * 256 + tid;
+  const unsigned long long key = j < n ? keys[j] : ~0ull;
+  const int rank = obb_rank_of(keys, n, key, tile, tid);
+  if (j >= n) return;
+  const int flat = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+  const int a = flat / nc;
+  obb_write_record(b, nc, A, pred, cls_off, ws, rank, a, flat - a * nc, (unsigned)(key >> 32));
+}
+
+extern "C" int ey_nms_rotated_ml(int B, int nc, int A, const float* pred, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
+                                 const uint8_t* class_mask, float* out_rows, int32_t* out_count, int32_t* out_index, void* workspace, size_t workspace_bytes,
+                                 ey_stream_t stream) {
+  EY_CHECK(B > 0 && nc > 0 && A > 0 && max_det > 0 && max_nms > 0, "nms_rotated_ml: B=%d nc=%d A=%d max_det=%d max_nms=%d", B, nc, A, max_det, max_nms);
+  EY_CHECK(pred && out_rows && out_count && workspace, "nms_rotated_ml: null pointer");
+  EY_CHECK(conf_thres >= 0.f, "nms_rotated_ml: conf_thres=%g (the sort key orders non-negative scores by their bits)", (double)conf_thres);
+  EY_CHECK(ey_aligned(workspace, 256), "nms_rotated_ml: the workspace must be 256-byte aligned");
+  if (B > 65535 || nc > 65535 || (long)A * nc >= (1L << 31) || (long)B * (4 + nc + 1) * A >= (1L << 40) || (long)B * max_det * 7 >= (1L << 40))
+    return ey_set_error(EY_EUNSUPPORTED, "nms_rotated_ml: tensor too large");
+  ObbWs ws;
+  ObbMl ml;
+  const size_t need = obb_ml_layout(B, (long)A * nc, max_nms, (char*)workspace, &ws, &ml);
+  EY_CHECK(workspace_bytes >= need, "nms_rotated_ml: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  const int tiles = ey_cdiv(ws.maxn, OBB_TILE), chunks = ey_cdiv(ws.maxn, OBB_ROWS);
+  if (chunks > 65535) return ey_set_error(EY_EUNSUPPORTED, "nms_rotated_ml: %d candidates per image", ws.maxn);
+  hipStream_t st = (hipStream_t)stream;
+  ObbWs wi = ws;
+  wi.cnt = ml.ncand;  // obb_init zeroes the counters it is given: the candidate counters (obb_ml_select writes ws.cnt itself)
+  hipLaunchKernelGGL(obb_init_kernel, dim3(ey_cdiv((long)B * ws.maxn, 256)), dim3(256), 0, st, B, wi);
+  hipLaunchKernelGGL(obb_ml_score_kernel, dim3(ey_cdiv(A, 256), nc, B), dim3(256), 0, st, nc, A, pred, conf_thres, class_mask, ml);
+  hipLaunchKernelGGL(obb_ml_select_kernel, dim3(B), dim3(1024), 0, st, max_nms, ws, ml);
+  hipLaunchKernelGGL(obb_ml_rank_kernel, dim3(ey_cdiv(ws.maxn, 256), B), dim3(256), 0, st, nc, A, pred, agnostic ? 0.f : max_wh, ws);
+  hipLaunchKernelGGL(obb_pair_kernel, dim3(tiles, chunks, B), dim3(OBB_TILE), 0, st, max_nms, ws);
+  hipLaunchKernelGGL(obb_resolve_kernel, dim3(B), dim3(1024), 0, st, nc, A, pred, iou_thres, max_det, max_nms, ws, out_rows, out_count, out_index);
+  EY_LAUNCH_CHECK("ey_nms_rotated_ml");
   return EY_OK;
 }

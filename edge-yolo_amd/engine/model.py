@@ -5,7 +5,7 @@ from pathlib import Path
 import torch
 
 from .predictor import ClassificationPredictor, DetectionPredictor, FastSAMPredictor, OBBPredictor, PosePredictor, SegmentationPredictor
-from .validator import ClassificationValidator, DetectionValidator, FastSAMValidator, PoseValidator, SegmentationValidator
+from .validator import ClassificationValidator, DetectionValidator, FastSAMValidator, OBBValidator, PoseValidator, SegmentationValidator  # noqa: F401 (OBBValidator: re-exported)
 from ..nn.tasks import ClassificationModel, DetectionModel, OBBModel, PoseModel, SegmentationModel, WorldModel, guess_model_task, torch_safe_load_state, yaml_model_load
 
 
@@ -23,7 +23,8 @@ def _plain(o):
 _TASK_MAP = {"detect": {"model": DetectionModel, "predictor": DetectionPredictor, "validator": DetectionValidator},
              "segment": {"model": SegmentationModel, "predictor": SegmentationPredictor, "validator": SegmentationValidator}}
 # tasks outside `task_map` (whose key set is pinned to the two tasks above): `_task_entry()` falls back to this table.  A row without a
-# "validator" is served by predict() only and val() refuses it (obb: rotated mAP on ey_probiou and multi-label rotated NMS are not built)
+# "validator" has none that val() picks by itself: the obb row stays that way because the plain `val(loader)` refusal is pinned, and its
+# validator is handed in by name, `val(loader, validator=OBBValidator)` (rotated mAP on ey_nms_rotated_ml and ey_probiou_batch)
 _PREDICT_TASKS = {"obb": {"model": OBBModel, "predictor": OBBPredictor},
                   "pose": {"model": PoseModel, "predictor": PosePredictor, "validator": PoseValidator},
                   "classify": {"model": ClassificationModel, "predictor": ClassificationPredictor, "validator": ClassificationValidator}}
@@ -233,9 +234,11 @@ class Model(torch.nn.Module):
         engine/model.py:599-655 returns validator.metrics; datasets and dataloaders are the caller's).  kwargs (reference cfg/default.yaml
         names): conf (default 0.001), iou, max_det, half, single_cls, agnostic_nms, device, and what the validator class adds in its
         `val_options` (segment: overlap_mask -- True: one index map per image --; save_json / save_txt / plots, which are not built and raise
-        when set).  validator: a validator CLASS to use instead of the task's."""
+        when set).  validator: a validator CLASS to use instead of the task's; the obb task has no default one and takes
+        `validator=OBBValidator` (engine.validator: rotated mAP, batches with (N, 5) "bboxes" = normalised xywh + angle)."""
         if validator is None and "validator" not in self._task_entry():
-            raise NotImplementedError(f"val(): validation of the '{self.task}' task is not built (obb: rotated mAP and multi-label rotated NMS)")
+            raise NotImplementedError(f"val(): the '{self.task}' task has no default validator (obb: pass the class, "
+                                      "val(loader, validator=OBBValidator) from engine.validator, for rotated mAP)")
         if dataloader is None:
             raise ValueError("val() needs an iterable of batch dicts (see DetectionValidator); datasets are not part of this build")
         vcls = validator or self._task_entry()["validator"]

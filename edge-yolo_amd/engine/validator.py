@@ -156,14 +156,23 @@ class DetectionValidator(BaseValidator):
             if self.single_cls:
                 pred = pred.copy()
                 pred[:, 5] = 0
-            predn = DetectionValidator._prepare_pred(self, pred[:, :6], pbatch)  # (the boxes; what rides behind column 6 is the task's)
+            predn = self._box_rows(pred, pbatch)
             stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
             if len(cls):
-                stat["tp"] = self._process_batch(predn, bbox, cls)
+                stat["tp"] = self._box_tp(si, predn, pbatch)
                 for k, f in more_tp.items():
                     stat[k] = f(si, predn, pbatch)
             for k in self.stats:
                 self.stats[k].append(stat[k])
+
+    def _box_rows(self, pred, pbatch):
+        """The box part of an image's kept rows in original-image pixels: xyxy boxes take the first six columns (what rides behind column 6
+        is the task's); a task whose boxes have another format (obb) overrides this."""
+        return DetectionValidator._prepare_pred(self, pred[:, :6], pbatch)
+
+    def _box_tp(self, si, predn, pbatch):
+        """The box true positives of image si, which has predictions and labels."""
+        return self._process_batch(predn, pbatch["bbox"], pbatch["cls"])
 
     def _gather_stats(self):
         """The accumulated statistics as one array per key, with the label counts per class / per image set aside; None while no prediction
@@ -540,6 +549,112 @@ class PoseValidator(TwoMetricValidator):
 
     def update(self, images, labels):
         raise NotImplementedError("PoseValidator: the (images, labels) convenience of the detect task carries no keypoints; call it with batches")
+
+
+class OBBValidator(DetectionValidator):
+    """Validation loop for the obb task, mirroring the reference's models/yolo/obb/val.py (`postprocess` :39-51, `_process_batch` :53-80,
+    `_prepare_batch` :82-93, `_prepare_pred` :95-101) with OBBMetrics.  The facade has no default validator for the task (the plain
+    `val(loader)` refusal is pinned): it is handed in by name, `model.val(loader, validator=OBBValidator)`.
+
+    Device work per batch: the forward, validation-mode rotated NMS (`ey_nms_rotated_ml`: every (anchor, class) score above conf is a
+    candidate, fast-NMS on ProbIoU) and the ProbIoU of ALL images' labels against their kept rows in one `ey_probiou_batch` call.  The host
+    gets the kept rows (n, 7) = x, y, w, h, conf, cls, angle and the [gt x pred] matrices in one copy per batch; scaling to the original
+    images, matching and AP run on the host like the detect task.
+
+    batch["bboxes"]: (N, 5) = xywh normalised to the network input plus the angle in radians.  Host predictions (`update_metrics(rows,
+    batch)` with a validator on the CPU) go through the numpy restatement metrics.probiou_host: the route the CPU tests take.  save_json
+    (the DOTA export), save_txt and plots are not built."""
+
+    val_options = {"save_json": False, "save_txt": False, "plots": False}
+
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, save_json=False, save_txt=False,
+                 plots=False):
+        refuse_options("OBBValidator", "DOTA json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+
+    def init_metrics(self):
+        super().init_metrics()
+        self.metrics = metrics.OBBMetrics()
+        self.results_dict = dict.fromkeys(self.metrics.keys + ["fitness"], 0.0)
+        self._ious = None
+
+    # ---- reference obb/val.py:39-51: rows (n_i, 7) per image
+    def postprocess(self, preds):
+        rows, count, _ = ops.nms_rotated_multi_label(preds, self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc)
+        n = count.tolist()  # the one D2H sync of the NMS
+        return [rows[i, :n[i]] for i in range(len(n))]
+
+    # ---- reference obb/val.py:82-93: labels of image si -> native (original-image) pixel space, xywh + angle
+    def _prepare_batch(self, si, batch):
+        idx = _np(batch["batch_idx"]).reshape(-1) == si
+        cls = _np(batch["cls"]).reshape(-1)[idx].astype(np.float32)
+        bbox = _np(batch["bboxes"]).reshape(-1, 5)[idx].astype(np.float32)
+        ori_shape = tuple(int(v) for v in batch["ori_shape"][si])
+        imgsz = tuple(int(v) for v in batch["img"].shape[2:])
+        ratio_pad = batch["ratio_pad"][si] if batch.get("ratio_pad") is not None else None
+        if len(cls):
+            b = torch.from_numpy(bbox.copy())
+            b[..., :4] *= torch.tensor(imgsz, dtype=torch.float32)[[1, 0, 1, 0]]
+            bbox = ops.scale_boxes(imgsz, b, ori_shape, ratio_pad=ratio_pad, xywh=True).numpy()
+        return {"cls": cls, "bbox": bbox.reshape(-1, 5), "ori_shape": ori_shape, "imgsz": imgsz, "ratio_pad": ratio_pad}
+
+    # ---- reference obb/val.py:95-101
+    def _prepare_pred(self, pred, pbatch):
+        predn = torch.as_tensor(_np(pred), dtype=torch.float32).clone()
+        ops.scale_boxes(pbatch["imgsz"], predn[:, :4], pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"], xywh=True)
+        return predn.numpy()
+
+    def _box_rows(self, pred, pbatch):
+        return self._prepare_pred(pred[:, :7], pbatch)
+
+    # ---- reference obb/val.py:53-80
+    def _process_batch(self, detections, gt_bboxes, gt_cls, iou=None):
+        """iou: the image's [gt x pred] ProbIoU matrix where the caller computed the batch's in one launch already."""
+        if iou is None:
+            iou = metrics.probiou_host(gt_bboxes, np.concatenate([detections[:, :4], detections[:, -1:]], 1))
+        return metrics.match_predictions(detections[:, 5], gt_cls, iou, self.iouv)
+
+    def _box_tp(self, si, predn, pbatch):
+        return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], iou=None if self._ious is None else self._ious[si])
+
+    # ---- reference detect/val.py:125-172 with the ProbIoU of the whole batch in one launch
+    def update_metrics(self, preds, batch):
+        """preds: postprocess's rows per image; device tensors take the one-launch route, host arrays the numpy one."""
+        from ..nn import _ops
+        B = len(preds)
+        pbatches = [self._prepare_batch(si, batch) for si in range(B)]
+        self._ious = None
+        if B and all(torch.is_tensor(r) and r.is_cuda for r in preds):
+            n, nl = [int(r.shape[0]) for r in preds], [len(pb["cls"]) for pb in pbatches]
+            if any(a and b for a, b in zip(n, nl)):
+                dev = preds[0].device
+                host = torch.cat([r.float() for r in preds], 0).cpu().numpy()  # the one D2H copy of the batch's rows
+                off = batch_offsets(n)
+                preds = [host[off[i]:off[i + 1]] for i in range(B)]
+                scaled = [self._prepare_pred(preds[i], pbatches[i])[:, [0, 1, 2, 3, 6]] for i in range(B)]
+                pk = torch.from_numpy(np.ascontiguousarray(np.concatenate(scaled, 0), np.float32)).to(dev)
+                gk = torch.from_numpy(np.ascontiguousarray(np.concatenate([pb["bbox"] for pb in pbatches], 0), np.float32)).to(dev)
+                with torch.cuda.device(dev):
+                    self._ious = pair_matrices(lambda pred_off, gt_off: _ops.probiou_batch(pk, pred_off, gk, gt_off), n, nl)
+        try:
+            self._image_stats(preds, batch, pbatches)
+        finally:
+            self._ious = None
+
+    # ---- reference detect/val.py:179-188 + OBBMetrics.process / results_dict (metrics.py:1252-1298)
+    def get_stats(self):
+        stats = self._gather_stats()
+        if stats is not None:
+            self.metrics.process(**stats)
+            self.box = self.metrics.box
+        self.results_dict = self.metrics.results_dict
+        return self.results_dict
+
+    def update(self, images, labels):
+        raise NotImplementedError("OBBValidator: the (images, labels) convenience of the detect task carries no angles; call it with batches")
+
+    def results(self):
+        raise NotImplementedError("OBBValidator: results() is the detect task's summary; read get_stats() / results_dict")
 
 
 class ClassificationValidator(BaseValidator):

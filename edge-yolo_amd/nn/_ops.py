@@ -1782,6 +1782,39 @@ def nms_rotated(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic,
     return rows, count, index
 
 
+def nms_rotated_ml(pred, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, class_mask=None):
+    """nms_rotated in the validation regime (ey_nms_rotated_ml): every (anchor, class) score above conf is a candidate, the max_nms best go
+    through fast-NMS on ProbIoU.  Same operands and outputs as nms_rotated; index is the anchor of each row."""
+    L.require_device(pred, "nms_rotated_ml")
+    B, no, A = _dense(pred, "nms_rotated_ml: pred (B,4+nc+1,A)", torch.float32, (_ANY, _AtLeast(6), _ANY), pred.device).shape
+    if class_mask is not None:
+        _dense(class_mask, "nms_rotated_ml: class_mask", torch.uint8, (no - 5,), pred.device)
+    rows, count, index = _nms_out(B, max_det, 7, pred.device)
+    nbytes = L.lib().ey_nms_rotated_ml_workspace_bytes(B, no - 5, A, int(max_nms))
+    ws = _workspace("nms_rotated_ml", None, nbytes, pred.device)
+    with _tr("nms_rotated_ml(init+score+select+rank+pair+resolve)", _nb(pred, rows), kernels=6):
+        L.check(L.lib().ey_nms_rotated_ml(B, no - 5, A, pred.data_ptr(), float(conf_thres), float(iou_thres), int(max_det), int(max_nms), float(max_wh),
+                                          int(bool(agnostic)), _p(class_mask), rows.data_ptr(), count.data_ptr(), index.data_ptr(),
+                                          ws.data_ptr(), nbytes, L.stream()), "ey_nms_rotated_ml")
+    return rows, count, index
+
+
+def probiou_batch(pred, pred_off, gt, gt_off, out_off=None, out=None):
+    """ProbIoU of a batch (ey_probiou_batch): pred fp32 (N_total,5) and gt fp32 (M_total,5) xywhr rows grouped by image through the host
+    lists pred_off / gt_off (B+1 entries from 0).  Image b's row-major [M_b][N_b] matrix batch_probiou(gt_b, pred_b) lands at element
+    out_off[b] of the flat fp32 buffer `out` (packed one after the other by default).  -> (out, out_off)."""
+    L.require_device(pred, "probiou_batch")
+    _no_block("probiou_batch")
+    pred_off, gt_off, out_off, sizes, end = _pair_offsets("probiou_batch", pred_off, gt_off, out_off)
+    B, dev = len(out_off), pred.device
+    _dense(pred, "probiou_batch: pred (N,5)", torch.float32, (_AtLeast(pred_off[-1]), 5), dev)
+    _dense(gt, "probiou_batch: gt (M,5)", torch.float32, (_AtLeast(gt_off[-1]), 5), dev)
+    out = _dense_out("probiou_batch: out=", out, torch.float32, (_AtLeast(end),), dev)
+    with _tr("obb_probiou_batch_kernel", _nb(pred, gt) + 4 * sum(sizes), 60.0 * sum(sizes), note=f"B{B} N{pred_off[-1]} M{gt_off[-1]}"):
+        L.check(L.lib().ey_probiou_batch(B, pred.data_ptr(), _ia(pred_off), gt.data_ptr(), _ia(gt_off), out.data_ptr(), _la(out_off), L.stream()), "ey_probiou_batch")
+    return out, out_off
+
+
 def _kpt_levels(levels, kpt_shape, what):
     """levels: list of (kpt map (B,nk,H,W) NHWC view, stride, a_off) -> the ctypes arrays both keypoint decode kernels take."""
     n = len(levels)

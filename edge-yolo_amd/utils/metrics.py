@@ -7,7 +7,8 @@ multi_label, models/yolo/detect/val.py:92-102) is device work and goes through `
 Segment validation adds `mask_iou` (utils/metrics.py:137-153; device tensors run on `ey_mask_iou`, host arrays on a numpy restatement with
 the same bits), the host form of the overlap_mask expansion (models/yolo/segment/val.py:206-209) and `SegmentMetrics` (:909-1029).
 
-`batch_probiou` (utils/metrics.py:244-275) is the pairwise ProbIoU of oriented boxes on `ey_probiou` (device tensors only).
+`batch_probiou` (utils/metrics.py:244-275) is the pairwise ProbIoU of oriented boxes on `ey_probiou` (device tensors only); `probiou_host` is its
+numpy restatement for host operands and `OBBMetrics` (:1240-1308) the obb task's metrics.
 
 Pose validation adds `OKS_SIGMA` (:17-20), `kpt_iou` (:156-175; device tensors on `ey_kpt_iou`, host operands on a numpy restatement) and
 `PoseMetrics` (:1051-1176)."""
@@ -173,6 +174,29 @@ def batch_probiou(obb1, obb2, eps=1e-7):
     return out if o1.is_cuda else out.to(o1.device)
 
 
+def probiou_host(obb1, obb2, eps=1e-7):
+    """batch_probiou for host operands: (N,5) x (M,5) xywhr arrays / CPU tensors -> (N,M) fp32 ndarray, the numpy restatement of the
+    reference's fp32 expression (metrics.py:178-195,244-275), operation by operation.  The route of a validator without a device."""
+    f = np.float32
+    o1, o2 = np.asarray(_host(obb1), f).reshape(-1, 5), np.asarray(_host(obb2), f).reshape(-1, 5)
+
+    def cov(b):
+        a, c = b[:, 2] ** 2 / f(12), b[:, 3] ** 2 / f(12)
+        cs, sn = np.cos(b[:, 4]), np.sin(b[:, 4])
+        return a * cs ** 2 + c * sn ** 2, a * sn ** 2 + c * cs ** 2, (a - c) * cs * sn
+
+    x1, y1, x2, y2 = o1[:, 0, None], o1[:, 1, None], o2[None, :, 0], o2[None, :, 1]
+    a1, b1, c1 = (t[:, None] for t in cov(o1))
+    a2, b2, c2 = (t[None, :] for t in cov(o2))
+    e = f(eps)
+    det = (a1 + a2) * (b1 + b2) - (c1 + c2) ** 2
+    t1 = (((a1 + a2) * (y1 - y2) ** 2 + (b1 + b2) * (x1 - x2) ** 2) / (det + e)) * f(0.25)
+    t2 = (((c1 + c2) * (x2 - x1) * (y1 - y2)) / (det + e)) * f(0.5)
+    t3 = np.log(det / (f(4) * np.sqrt(np.maximum(a1 * b1 - c1 ** 2, f(0)) * np.maximum(a2 * b2 - c2 ** 2, f(0))) + e) + e) * f(0.5)
+    bd = np.clip(t1 + t2 + t3, e, f(100))
+    return (f(1) - np.sqrt(f(1) - np.exp(-bd) + e)).astype(f)
+
+
 # per-keypoint falloff constants of the COCO keypoint evaluation (reference utils/metrics.py:17-20)
 OKS_SIGMA = np.array([0.26, 0.25, 0.25, 0.35, 0.35, 0.79, 0.79, 0.72, 0.72, 0.62, 0.62, 1.07, 1.07, 0.87, 0.87, 0.89, 0.89]) / 10.0
 
@@ -284,6 +308,39 @@ class PoseMetrics(SegmentMetrics):
     @property
     def keys(self):
         return list(POSE_KEYS)
+
+
+OBB_KEYS = ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)"]  # reference metrics.py:1268-1270
+
+
+class OBBMetrics:
+    """Rotated-box metrics (reference OBBMetrics, metrics.py:1240-1308): one Metric, `box`, fed with true positives matched on ProbIoU.
+    The reference zips its four keys (+ fitness) with the fork's five means (+ fitness), which files mAP75 under "metrics/mAP50-95(B)" and
+    mAP50-95 under "fitness"; here every key holds what it names: mAP50-95 is column 4 of `mean_results()`, and fitness (the fork weights
+    only mAP50-95) is the same number as the reference's."""
+
+    def __init__(self):
+        self.box = Metric()
+
+    def process(self, tp, conf, pred_cls, target_cls):
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls))
+
+    @property
+    def keys(self):
+        return list(OBB_KEYS)
+
+    def mean_results(self):
+        """[precision, recall, mAP50, mAP75, mAP50-95], as Metric.mean_results."""
+        return self.box.mean_results()
+
+    @property
+    def fitness(self):
+        return self.box.fitness()
+
+    @property
+    def results_dict(self):
+        m = self.mean_results()
+        return dict(zip(self.keys + ["fitness"], [m[0], m[1], m[2], m[4], self.fitness]))
 
 
 class ClassifyMetrics:

@@ -153,11 +153,31 @@ def _nms_device_rotated(prediction, conf_thres, iou_thres, classes, agnostic, ma
     if prediction.shape[1] - nc - 4 != 1:
         raise ValueError(f"nms_device(rotated=True): nc={nc} but the prediction has {prediction.shape[1]} channels (4 + nc + 1 angle expected)")
     if multi_label and nc > 1:
-        raise NotImplementedError("rotated NMS with multi_label=True (the validation regime, one candidate per (anchor, class)) is not built; "
-                                  "single-label (predict) mode is")
+        raise NotImplementedError("rotated NMS with multi_label=True (the validation regime, one candidate per (anchor, class)) is not served by this "
+                                  "entry point, whose single-label (predict) form is pinned; call ops.nms_rotated_multi_label (ey_nms_rotated_ml)")
     with torch.cuda.device(prediction.device):  # launches go to the current device's stream (_lib.stream)
         p = prediction.float().contiguous()
         return _ops.nms_rotated(p, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, _class_mask(classes, nc, p.device))
+
+
+def nms_rotated_multi_label(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, max_det=300, nc=0, max_nms=30000, max_wh=7680):
+    """The reference's non_max_suppression(..., multi_label=True, rotated=True) (ops.py:270-297; what its OBBValidator runs, obb/val.py:39-51)
+    on ey_nms_rotated_ml: (B,4+nc+1,A) predictions of an OBB head -> (rows (B,max_det,7) = x,y,w,h,conf,cls,angle, count (B,), index
+    (B,max_det) = anchor of each row), fixed sizes, no host synchronisation.  Every (anchor, class) score above conf_thres is a candidate, so
+    an anchor can give several rows; order is descending score, equal scores by ascending anchor * nc + class (the reference's argsort leaves
+    ties unspecified); the max_nms best go through fast-NMS on ProbIoU.  nc is required, as for nms_device(rotated=True)."""
+    from ..nn import _ops
+    assert 0 <= conf_thres <= 1, f"Invalid Confidence threshold {conf_thres}, valid values are between 0.0 and 1.0"
+    assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
+    if isinstance(prediction, (list, tuple)):
+        prediction = prediction[0]
+    if not nc:
+        raise NotImplementedError("rotated NMS needs nc= (the number of classes: the prediction is 4 + nc + 1 angle channels)")
+    if prediction.dim() != 3 or prediction.shape[1] - nc - 4 != 1:
+        raise ValueError(f"nms_rotated_multi_label: nc={nc} but the prediction has shape {tuple(prediction.shape)} ((B, 4 + nc + 1 angle, A) expected)")
+    with torch.cuda.device(prediction.device):  # launches go to the current device's stream (_lib.stream)
+        p = prediction.float().contiguous()
+        return _ops.nms_rotated_ml(p, conf_thres, iou_thres, max_det, max_nms, max_wh, agnostic, _class_mask(classes, nc, p.device))
 
 
 def nms_rotated(boxes, scores, threshold=0.45):

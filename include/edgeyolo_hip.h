@@ -830,7 +830,20 @@ int ey_nms(int B, int nc, int A, const float* pred, float conf_thres, float iou_
  *   max(0, max_{i before j} probiou(i, j)) < iou_thres.  out_rows fp32 [B,max_det,7] = x,y,w,h,conf,cls,angle copied from pred, the first
  *   max_det kept columns in score order (zeros beyond the count); out_count int32 [B]; out_index int32 [B,max_det] = anchor of each row, -1
  *   beyond the count (may be NULL).  workspace: ey_nms_rotated_workspace_bytes(B, A, max_nms) bytes, 256-byte aligned.  No host
- *   synchronisation, no allocation: graph-capturable.  Exact at every candidate count up to max_nms. */
+ *   synchronisation, no allocation: graph-capturable.  Exact at every candidate count up to max_nms.
+ * ey_nms_rotated_ml: the same call in the validation regime, non_max_suppression(multi_label=True, rotated=True) (utils/ops.py:270-297):
+ *   a candidate is every (anchor a, class c) with pred[4+c][a] > conf_thres (strict) and class_mask[c], up to A*nc per image (A*nc < 2^31),
+ *   so one anchor can give several rows that share the box and the angle.  Order: descending score, equal scores by ascending a*nc + c
+ *   (a stable sort of the reference's torch.where order; the reference's own argsort leaves ties unspecified).  The max_nms best go
+ *   through the pair and keep stages of ey_nms_rotated, with the same fp32 expressions.  The max_nms-th score is found by a radix select
+ *   over the key bits: no step ranks all A*nc candidates against each other.  Outputs as for ey_nms_rotated (out_index = anchor; the class
+ *   is in column 5 of the row).  workspace: ey_nms_rotated_ml_workspace_bytes(B, nc, A, max_nms) bytes (0 for arguments the call refuses),
+ *   256-byte aligned.  No host synchronisation, no float atomics: graph-capturable, the same bytes run to run.  nc == 1 is ey_nms_rotated's
+ *   result.
+ * ey_probiou_batch: batch_probiou(gt_b, pred_b) for every image of a batch in ONE launch.  pred fp32 [pred_off[B]][5], gt fp32
+ *   [gt_off[B]][5] xywhr; pred_off / gt_off (B+1 entries from 0) and out_off (B entries, in elements) are HOST arrays as for ey_kpt_iou.
+ *   Image b's row-major [M_b][N_b] matrix (ground truth x prediction) goes to out + out_off[b], bit-identical to ey_probiou(M_b, N_b, gt_b,
+ *   pred_b); images with M_b == 0 or N_b == 0 have none; B == 0 is valid; B <= 128, otherwise EY_EUNSUPPORTED. */
 int ey_obb_decode_levels(int dtype, int B, int nlevels, const int* H, const int* W, const float* stride, const void* const* box, const int* box_cstride,
                          const void* const* cls, const int* cls_cstride, const void* const* angle, const int* angle_cstride, int nc, float* pred,
                          int A_total, const int* a_off, ey_stream_t stream);
@@ -839,6 +852,11 @@ size_t ey_nms_rotated_workspace_bytes(int B, int A, int max_nms);
 int ey_nms_rotated(int B, int nc, int A, const float* pred, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
                    const uint8_t* class_mask, float* out_rows, int32_t* out_count, int32_t* out_index, void* workspace, size_t workspace_bytes,
                    ey_stream_t stream);
+size_t ey_nms_rotated_ml_workspace_bytes(int B, int nc, int A, int max_nms);
+int ey_nms_rotated_ml(int B, int nc, int A, const float* pred, float conf_thres, float iou_thres, int max_det, int max_nms, float max_wh, int agnostic,
+                      const uint8_t* class_mask, float* out_rows, int32_t* out_count, int32_t* out_index, void* workspace, size_t workspace_bytes,
+                      ey_stream_t stream);
+int ey_probiou_batch(int B, const float* pred, const int* pred_off, const float* gt, const int* gt_off, float* out, const long* out_off, ey_stream_t stream);
 
 /* ---- Pose estimation (csrc/pose.hip).  Levels are described as for ey_obb_decode_levels: per level an NHWC map kpt [B,H,W,nkpt*ndim] of
  *   `dtype` (logits of the cv4 towers) with its pixel stride, the level's stride and its first anchor a_off.  ndim is 2 (x, y) or 3
