@@ -193,6 +193,7 @@ SIGNATURES = {
     "ey_bytetrack_update": (_i, [_i, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ey_mask_contours_workspace_bytes": (_sz, [_i, _i, _i]),
     "ey_mask_contours": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ey_match_batch": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp]),
     "ey_classify_transform": (_i, [_i, _vp, _i, _i, _i, _i, C.c_long, _vp, _i, _i, _vp]),
 }
 

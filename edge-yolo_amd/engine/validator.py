@@ -81,12 +81,22 @@ class BaseValidator:
 class DetectionValidator(BaseValidator):
     """Batches: {"img", "cls" (N,1), "bboxes" (N,4 normalised xywh in the network input frame), "batch_idx" (N,), "ori_shape" [B x (h,w)],
     "ratio_pad" [B x ((gain,gain),(padw,padh))] or absent} (the reference's dataset collate format, data/dataset.py); the results dict is the
-    reference's DetMetrics.results_dict."""
+    reference's DetMetrics.results_dict.
 
-    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None):
+    Two keywords, both off by default, shared by every task with boxes (with both off nothing differs: same launches, copies, results):
+    confusion_matrix=True: `self.confusion_matrix` (metrics.ConfusionMatrix, conf 0.25, IoU 0.45 like the reference's) is made by
+      init_metrics and fed once per batch: device rows in one ey_match_batch launch, host-array rows image by image in numpy.
+    device_match=True: the batch's true positives come from that kernel too (with both keywords it is ONE launch) and the host gets the kept
+      rows and their TP bytes in one copy; host-array rows raise ValueError.  `stats` hold the same arrays in the same order either way."""
+
+    val_options = {"confusion_matrix": False, "device_match": False}
+
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, confusion_matrix=False,
+                 device_match=False):
         """model: a DetectionModel on its device (fused / dtype set by the caller or by __call__), or a YOLO facade.
         conf None -> 0.001 like the reference (engine/validator.py:100-101)."""
         super().__init__(model, half, device)
+        self._cm_on, self.device_match, self._stash = bool(confusion_matrix), bool(device_match), None
         self.conf = 0.001 if conf is None else conf
         self.iou, self.max_det, self.single_cls, self.agnostic_nms = iou, max_det, single_cls, agnostic_nms
         self.iouv = metrics.IOUV
@@ -100,10 +110,81 @@ class DetectionValidator(BaseValidator):
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[], target_img=[])
         self.results_dict = dict(zip(KEYS + ["fitness"], [0.0] * 6))
         self.box = None
+        self.confusion_matrix = metrics.ConfusionMatrix(self.nc, conf=self.conf) if self._cm_on else None  # (reference val.py:77)
 
     # ---- reference val.py:92-102
     def postprocess(self, preds):
-        return ops.non_max_suppression(preds, self.conf, self.iou, multi_label=True, agnostic=self.single_cls or self.agnostic_nms, max_det=self.max_det)
+        if not (self._cm_on or self.device_match):
+            return ops.non_max_suppression(preds, self.conf, self.iou, multi_label=True, agnostic=self.single_cls or self.agnostic_nms, max_det=self.max_det)
+        boxes, count, _ = ops.nms_device(preds, self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, multi_label=True)
+        return self._kept(boxes, count)  # (what non_max_suppression returns, with the fixed-size pair kept for the matching kernel)
+
+    def _kept(self, boxes, count):
+        """NMS's fixed-size (boxes, count) -> the per-image kept rows (one D2H sync for the counts); with a keyword on, the pair is stashed
+        for update_metrics."""
+        n = count.tolist()
+        rows = [boxes[i, :n[i]] for i in range(len(n))]
+        if self._cm_on or self.device_match:
+            self._stash = (boxes, count, n, rows)
+        return rows
+
+    def _device_batch(self, rows):
+        """(rows (B, max_det, W) fp32, count (B,) int32, n) on the device for the per-image device rows `rows` -- the pair postprocess stashed
+        when they are its rows, else the rows padded -- or None when they are host arrays."""
+        if not (len(rows) and all(torch.is_tensor(r) and r.is_cuda for r in rows)):
+            return None
+        st, self._stash = self._stash, None
+        if st is not None and st[3] is rows:
+            return st[:3]
+        n = [int(r.shape[0]) for r in rows]
+        pad = torch.zeros((len(rows), max(max(n), 1), int(rows[0].shape[1])), dtype=torch.float32, device=rows[0].device)
+        for i, r in enumerate(rows):
+            pad[i, :n[i]] = r
+        return pad, torch.tensor(n, dtype=torch.int32, device=pad.device), n
+
+    @staticmethod
+    def _xform(pb):
+        """padx, pady, gain, w0, h0 of ops.scale_boxes for the image of `_prepare_batch`'s dict pb (ey_match_batch's xform row)."""
+        (h1, w1), (h0, w0) = pb["imgsz"], pb["ori_shape"]
+        if pb["ratio_pad"] is None:
+            gain = min(h1 / h0, w1 / w0)
+            pad = (round((w1 - w0 * gain) / 2 - 0.1), round((h1 - h0 * gain) / 2 - 0.1))
+        else:
+            gain, pad = pb["ratio_pad"][0][0], pb["ratio_pad"][1]
+        return [pad[0], pad[1], gain, w0, h0]
+
+    def _match_device(self, dev_batch, pbatches, iou=None, iou_off=None, want_cm=False, want_tp=True):
+        """ONE ey_match_batch launch over the batch: the true positives (uint8 (B, max_det, niou) on the device) when want_tp, the confusion
+        matrix's increments when want_cm.  iou / iou_off: the flat [gt x pred] matrices of a pair-matrix launch in the place of the boxes."""
+        boxes, count, n = dev_batch
+        if self.single_cls:
+            boxes = boxes.clone()
+            boxes[..., 5] = 0
+        gt_off = batch_offsets([len(pb["cls"]) for pb in pbatches])
+        cls = np.concatenate([pb["cls"] for pb in pbatches]) if pbatches else np.zeros(0, np.float32)
+        gt = xform = None
+        if iou is None:
+            gt = np.concatenate([pb["bbox"].reshape(-1, 4) for pb in pbatches]).astype(np.float32)
+            xform = np.asarray([self._xform(pb) for pb in pbatches], np.float32)
+        if want_cm:
+            return self.confusion_matrix.process_device_batch(boxes, count, gt, cls, gt_off, xform=xform, iou=iou, iou_off=iou_off, iou_n=n,
+                                                              iouv=self.iouv if want_tp else None)
+        return metrics.match_batch(boxes, gt, cls, self.iouv, iou=iou, count=count, gt_off=gt_off, nc=self.nc, xform=xform, iou_off=iou_off, iou_n=n)
+
+    def _fetch_matched(self, dev_batch, tps, width=6):
+        """The kept rows (first `width` columns) and their TP bytes in ONE copy to the host -> (rows per image, per tps entry the per-image
+        (n_i, niou) bool arrays)."""
+        boxes, count, n = dev_batch
+        keep = ops.kept_rows(count, boxes.shape[1])
+        host = torch.cat([boxes[keep][:, :width].float()] + [t[keep].float() for t in tps], 1).cpu().numpy()
+        off, T = batch_offsets(n), self.niou
+        rows = [host[off[i]:off[i + 1], :width] for i in range(len(n))]
+        return rows, [[host[off[i]:off[i + 1], width + k * T: width + (k + 1) * T] != 0 for i in range(len(n))] for k in range(len(tps))]
+
+    def _host_rows_only(self, rows):
+        """device_match with rows that are host arrays: refused."""
+        if self.device_match:
+            raise ValueError(f"{type(self).__name__}: device_match=True matches on the device; these rows are host arrays (use the default host route)")
 
     # ---- reference val.py:104-115: labels of image si -> native (original-image) pixel space
     def _prepare_batch(self, si, batch):
@@ -131,19 +212,33 @@ class DetectionValidator(BaseValidator):
 
     # ---- reference val.py:125-172 (plots / json / txt saving are out of scope)
     def update_metrics(self, preds, batch):
-        self._image_stats(preds, batch)
+        if not (self._cm_on or self.device_match):
+            return self._image_stats(preds, batch)
+        dev_batch = self._device_batch(preds)
+        if dev_batch is None:
+            self._host_rows_only(preds)
+            return self._image_stats(preds, batch, host_cm=True)
+        pbatches = [self._prepare_batch(si, batch) for si in range(len(preds))]
+        tp = self._match_device(dev_batch, pbatches, want_cm=self._cm_on, want_tp=self.device_match)
+        if not self.device_match:
+            return self._image_stats(preds, batch, pbatches)
+        rows, (tps,) = self._fetch_matched(dev_batch, [tp])
+        self._image_stats(rows, batch, pbatches, tps={"tp": tps})
 
-    def _image_stats(self, rows, batch, pbatches=None, **more_tp):
+    def _image_stats(self, rows, batch, pbatches=None, tps=None, host_cm=False, **more_tp):
         """The per-image statistics loop of every task with boxes.  rows: per image the kept (n_i, 6+) rows [xyxy, conf, cls, ...] in
         network-input pixels.  pbatches: the images' `_prepare_batch` dicts where the task's batch-wide work made them already.
         more_tp: the task's further true-positive arrays by their `stats` key, each a `f(si, predn, pbatch) -> (n_i, niou) bool` that is
-        called for the images that have both predictions and labels."""
+        called for the images that have both predictions and labels.  tps: the true-positive arrays by their `stats` key where the device
+        matched the batch already: per key the per-image (n_i, niou) bool arrays (the rows' boxes are then not scaled on the host: `stats`
+        take only their conf and cls).  host_cm: feed the confusion matrix image by image, in numpy (reference val.py:146-147,165-166)."""
+        keys = ("tp", *more_tp) if tps is None else tuple(tps)
         for si, pred in enumerate(rows):
             self.seen += 1
             pred = _np(pred).astype(np.float32)
             pred = pred.reshape(-1, pred.shape[-1] if pred.ndim == 2 else 6)
             npr = pred.shape[0]
-            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), **{k: np.zeros((npr, self.niou), bool) for k in ("tp", *more_tp)})
+            stat = dict(conf=np.zeros(0, np.float32), pred_cls=np.zeros(0, np.float32), **{k: np.zeros((npr, self.niou), bool) for k in keys})
             pbatch = self._prepare_batch(si, batch) if pbatches is None else pbatches[si]
             cls, bbox = pbatch["cls"], pbatch["bbox"]
             stat["target_cls"] = cls
@@ -152,16 +247,23 @@ class DetectionValidator(BaseValidator):
                 if len(cls):
                     for k in self.stats:
                         self.stats[k].append(stat[k])
+                    if host_cm:
+                        self.confusion_matrix.process_batch(None, bbox, cls)
                 continue
             if self.single_cls:
                 pred = pred.copy()
                 pred[:, 5] = 0
-            predn = self._box_rows(pred, pbatch)
+            predn = self._box_rows(pred, pbatch) if tps is None else pred
             stat["conf"], stat["pred_cls"] = predn[:, 4], predn[:, 5]
-            if len(cls):
+            if tps is not None:
+                for k in keys:
+                    stat[k] = np.asarray(tps[k][si], bool).reshape(npr, self.niou)
+            elif len(cls):
                 stat["tp"] = self._box_tp(si, predn, pbatch)
                 for k, f in more_tp.items():
                     stat[k] = f(si, predn, pbatch)
+            if host_cm:
+                self.confusion_matrix.process_batch(predn, bbox, cls)
             for k in self.stats:
                 self.stats[k].append(stat[k])
 
@@ -269,15 +371,15 @@ class SegmentationValidator(TwoMetricValidator):
     a validator on the device: on the CPU, where only ready masks are scored, it raises.  save_json, save_txt and plots are not built."""
 
     metrics_cls, second, tp_second = metrics.SegmentMetrics, "seg", "tp_m"  # (reference segment/val.py:45-53)
-    val_options = {"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False, "process_mask_native": False}
+    val_options = {"overlap_mask": True, "save_json": False, "save_txt": False, "plots": False, "process_mask_native": False, **DetectionValidator.val_options}
 
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, overlap_mask=True,
-                 save_json=False, save_txt=False, plots=False, process_mask_native=False):
+                 save_json=False, save_txt=False, plots=False, process_mask_native=False, confusion_matrix=False, device_match=False):
         refuse_options("SegmentationValidator", "COCO json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
         self.process_mask_native = bool(process_mask_native)
         self.overlap_mask = bool(overlap_mask)
         self.keep_outputs = False  # True: update_metrics appends (rows (n,6+nm), mask bits (n,mh,mw)) per image to self.kept, on the host
-        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device, confusion_matrix, device_match)
         if self.process_mask_native and self.device.type != "cuda":  # (the host route takes ready masks; the native assembly is the kernel alone)
             raise NotImplementedError(f"SegmentationValidator: process_mask_native=True is built on ey_process_mask_native and this validator is on '{self.device}': "
                                       "there is no CPU path; put the model on the device first (YOLO.val does) or pass device=")
@@ -294,8 +396,7 @@ class SegmentationValidator(TwoMetricValidator):
     def postprocess(self, preds):
         boxes, count, _ = ops.nms_device(preds[0], self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc, multi_label=True)
         proto = preds[1][-1] if len(preds[1]) == 3 else preds[1]
-        n = count.tolist()  # the one D2H sync of the NMS
-        return [boxes[i, :n[i]] for i in range(len(n))], proto
+        return self._kept(boxes, count), proto  # (the one D2H sync of the NMS)
 
     # ---- reference segment/val.py:86-91
     def _prepare_batch(self, si, batch):
@@ -374,9 +475,16 @@ class SegmentationValidator(TwoMetricValidator):
         either side is empty).  pred_masks: (sum n, mh, mw) uint8 on the device."""
         from ..nn import _ops
         B = len(n)
+        launch = self._mask_iou_launch(pred_masks, n, batch, nl)
+        return [None] * B if launch is None else pair_matrices(launch, n, nl)
+
+    def _mask_iou_launch(self, pred_masks, n, batch, nl):
+        """The `launch(pred_off, gt_off) -> (flat, out_off)` of the batch's ey_mask_iou call, None when no image has both sides."""
+        from ..nn import _ops
+        B = len(n)
         gt = batch["masks"]
         if not any(a and b for a, b in zip(n, nl)):
-            return [None] * B
+            return None
         index = self.overlap_mask
         if not index:  # one mask per label, image after image (the collate order); anything else is gathered into that order
             bi = _np(batch["batch_idx"]).reshape(-1)
@@ -388,7 +496,7 @@ class SegmentationValidator(TwoMetricValidator):
                 gt = torch.cat([(gt[i:i + 1] == torch.arange(1, nl[i] + 1, device=gt.device).view(-1, 1, 1)) for i in range(B)], 0)
                 index = False
             gt = self._resize_gt(gt, pred_masks.shape[1:])
-        return pair_matrices(lambda pred_off, gt_off: _ops.mask_iou(pred_masks, pred_off, gt.contiguous(), gt_off, index=index)[:2], n, nl)
+        return lambda pred_off, gt_off: _ops.mask_iou(pred_masks, pred_off, gt.contiguous(), gt_off, index=index)[:2]
 
     # ---- reference segment/val.py:99-166
     def update_metrics(self, preds, batch, pred_masks=None):
@@ -404,16 +512,30 @@ class SegmentationValidator(TwoMetricValidator):
             nl = [int((bi == si).sum()) for si in range(B)]
             imgsz = tuple(int(v) for v in batch["img"].shape[2:])
             all_masks = self._batch_pred_masks(rows, proto, imgsz)
-            ious = self._batch_mask_ious(all_masks, n, batch, nl)
             if self.keep_outputs:
                 host, off = all_masks.cpu().numpy(), batch_offsets(n)
                 self.kept += [(_np(rows[i]).copy(), host[off[i]:off[i + 1]]) for i in range(B)]
+            dev_batch = self._device_batch(rows) if self._cm_on or self.device_match else None
+            if dev_batch is not None:  # boxes: one launch for the true positives and the confusion matrix; masks: matrix mode on ey_mask_iou's buffer
+                pbatches = [self._prepare_batch(si, batch) for si in range(B)]
+                tp = self._match_device(dev_batch, pbatches, want_cm=self._cm_on, want_tp=self.device_match)
+                if self.device_match:
+                    launch = self._mask_iou_launch(all_masks, n, batch, nl)
+                    tp_m = torch.zeros_like(tp)
+                    if launch is not None:
+                        flat, off = launch(batch_offsets(n), batch_offsets(nl))
+                        tp_m = self._match_device(dev_batch, pbatches, iou=flat, iou_off=off)
+                    host_rows, (tps, tps_m) = self._fetch_matched(dev_batch, [tp, tp_m])
+                    return self._image_stats(host_rows, batch, pbatches, tps={"tp": tps, "tp_m": tps_m})
+            ious = self._batch_mask_ious(all_masks, n, batch, nl)
+        elif self._cm_on or self.device_match:
+            self._host_rows_only(rows)
 
         def tp_m(si, predn, pbatch):
             return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], None if on_device else pred_masks[si], pbatch["masks"], self.overlap_mask,
                                        masks=True, iou=ious[si])
 
-        self._image_stats(rows, batch, tp_m=tp_m)
+        self._image_stats(rows, batch, host_cm=self._cm_on and not on_device, tp_m=tp_m)
 
     def update(self, images, labels):
         raise NotImplementedError("SegmentationValidator: the (images, labels) convenience of the detect task carries no masks; call it with batches")
@@ -434,13 +556,13 @@ class PoseValidator(TwoMetricValidator):
     tests take.  save_json, save_txt and plots are not built."""
 
     metrics_cls, second, tp_second = metrics.PoseMetrics, "pose", "tp_p"
-    val_options = {"save_json": False, "save_txt": False, "plots": False}
+    val_options = {"save_json": False, "save_txt": False, "plots": False, **DetectionValidator.val_options}
 
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, save_json=False, save_txt=False,
-                 plots=False):
+                 plots=False, confusion_matrix=False, device_match=False):
         refuse_options("PoseValidator", "COCO json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
         self.keep_outputs = False  # True: update_metrics appends (rows (n,6), keypoints (n,K,ndim) in input pixels) per image to self.kept, on the host
-        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device, confusion_matrix, device_match)
 
     # ---- reference pose/val.py:77-84
     def init_metrics(self):
@@ -456,8 +578,7 @@ class PoseValidator(TwoMetricValidator):
         head = self.model.model[-1]
         boxes, count, index = ops.nms_device(y, self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc, multi_label=True)
         kpts = _ops.kpts_decode_rows(head.kpt_levels(maps), head.kpt_shape, index, count)
-        n = count.tolist()  # the one D2H sync of the NMS
-        return [boxes[i, :n[i]] for i in range(len(n))], kpts
+        return self._kept(boxes, count), kpts  # (the one D2H sync of the NMS)
 
     def _forward(self, img):
         head = self.model.model[-1]
@@ -524,7 +645,11 @@ class PoseValidator(TwoMetricValidator):
         K = self.kpt_shape[0]
         on_device = torch.is_tensor(kpts) and kpts.is_cuda
         ious = [None] * B
+        flags = self._cm_on or self.device_match
+        if flags and not on_device:
+            self._host_rows_only(rows)
         if on_device:
+            launch = None
             n, nl = [int(r.shape[0]) for r in rows], [len(pb["cls"]) for pb in pbatches]
             scaled = self._scale_pred_kpts(kpts, pbatches)
             if self.keep_outputs:
@@ -536,7 +661,19 @@ class PoseValidator(TwoMetricValidator):
                 gk = torch.from_numpy(np.concatenate([pb["kpts"].reshape(-1, K, 3) for pb in pbatches], 0)).to(dev)
                 ar = torch.from_numpy(np.concatenate([self._gt_area(pb["bbox"]) for pb in pbatches]).astype(np.float32)).to(dev)
                 sg = torch.from_numpy(np.asarray(self.sigma, np.float32)).to(dev)
-                ious = pair_matrices(lambda pred_off, gt_off: _ops.kpt_iou(pk, pred_off, gk, gt_off, ar, sg), n, nl)
+                launch = lambda pred_off, gt_off: _ops.kpt_iou(pk, pred_off, gk, gt_off, ar, sg)  # noqa: E731
+            dev_batch = self._device_batch(rows) if flags else None
+            if dev_batch is not None:  # boxes: one launch for the true positives and the confusion matrix; keypoints: matrix mode on ey_kpt_iou's buffer
+                tp = self._match_device(dev_batch, pbatches, want_cm=self._cm_on, want_tp=self.device_match)
+                if self.device_match:
+                    tp_p = torch.zeros_like(tp)
+                    if launch is not None:
+                        flat, off = launch(batch_offsets(n), batch_offsets(nl))
+                        tp_p = self._match_device(dev_batch, pbatches, iou=flat, iou_off=off)
+                    host_rows, (tps, tps_p) = self._fetch_matched(dev_batch, [tp, tp_p])
+                    return self._image_stats(host_rows, batch, pbatches, tps={"tp": tps, "tp_p": tps_p})
+            if launch is not None:
+                ious = pair_matrices(launch, n, nl)
 
         def tp_p(si, predn, pbatch):
             if on_device:
@@ -545,7 +682,7 @@ class PoseValidator(TwoMetricValidator):
             ops.scale_coords(pbatch["imgsz"], pk, pbatch["ori_shape"], ratio_pad=pbatch["ratio_pad"])
             return self._process_batch(predn, pbatch["bbox"], pbatch["cls"], pk.numpy(), pbatch["kpts"])
 
-        self._image_stats(rows, batch, pbatches, tp_p=tp_p)
+        self._image_stats(rows, batch, pbatches, host_cm=self._cm_on and not on_device, tp_p=tp_p)
 
     def update(self, images, labels):
         raise NotImplementedError("PoseValidator: the (images, labels) convenience of the detect task carries no keypoints; call it with batches")
@@ -565,12 +702,12 @@ class OBBValidator(DetectionValidator):
     batch)` with a validator on the CPU) go through the numpy restatement metrics.probiou_host: the route the CPU tests take.  save_json
     (the DOTA export), save_txt and plots are not built."""
 
-    val_options = {"save_json": False, "save_txt": False, "plots": False}
+    val_options = {"save_json": False, "save_txt": False, "plots": False, **DetectionValidator.val_options}
 
     def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, save_json=False, save_txt=False,
-                 plots=False):
+                 plots=False, confusion_matrix=False, device_match=False):
         refuse_options("OBBValidator", "DOTA json / txt export and plots", save_json=save_json, save_txt=save_txt, plots=plots)
-        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device)
+        super().__init__(model, conf, iou, max_det, half, single_cls, agnostic_nms, device, confusion_matrix, device_match)
 
     def init_metrics(self):
         super().init_metrics()
@@ -581,8 +718,7 @@ class OBBValidator(DetectionValidator):
     # ---- reference obb/val.py:39-51: rows (n_i, 7) per image
     def postprocess(self, preds):
         rows, count, _ = ops.nms_rotated_multi_label(preds, self.conf, self.iou, None, self.single_cls or self.agnostic_nms, self.max_det, nc=self.nc)
-        n = count.tolist()  # the one D2H sync of the NMS
-        return [rows[i, :n[i]] for i in range(len(n))]
+        return self._kept(rows, count)  # (the one D2H sync of the NMS)
 
     # ---- reference obb/val.py:82-93: labels of image si -> native (original-image) pixel space, xywh + angle
     def _prepare_batch(self, si, batch):
@@ -624,20 +760,37 @@ class OBBValidator(DetectionValidator):
         B = len(preds)
         pbatches = [self._prepare_batch(si, batch) for si in range(B)]
         self._ious = None
+        flags = self._cm_on or self.device_match
+        dev_batch = self._device_batch(preds) if flags else None
+        if flags and dev_batch is None:
+            self._host_rows_only(preds)
+        host_cm, tps = self._cm_on and dev_batch is None, None
         if B and all(torch.is_tensor(r) and r.is_cuda for r in preds):
             n, nl = [int(r.shape[0]) for r in preds], [len(pb["cls"]) for pb in pbatches]
+            launch, dev = None, preds[0].device
             if any(a and b for a, b in zip(n, nl)):
-                dev = preds[0].device
                 host = torch.cat([r.float() for r in preds], 0).cpu().numpy()  # the one D2H copy of the batch's rows
                 off = batch_offsets(n)
                 preds = [host[off[i]:off[i + 1]] for i in range(B)]
                 scaled = [self._prepare_pred(preds[i], pbatches[i])[:, [0, 1, 2, 3, 6]] for i in range(B)]
                 pk = torch.from_numpy(np.ascontiguousarray(np.concatenate(scaled, 0), np.float32)).to(dev)
                 gk = torch.from_numpy(np.ascontiguousarray(np.concatenate([pb["bbox"] for pb in pbatches], 0), np.float32)).to(dev)
-                with torch.cuda.device(dev):
-                    self._ious = pair_matrices(lambda pred_off, gt_off: _ops.probiou_batch(pk, pred_off, gk, gt_off), n, nl)
+                launch = lambda pred_off, gt_off: _ops.probiou_batch(pk, pred_off, gk, gt_off)  # noqa: E731
+            with torch.cuda.device(dev):
+                if dev_batch is not None:  # true positives and confusion matrix from ONE launch in matrix mode, on the ProbIoU buffer
+                    flat, off = launch(batch_offsets(n), batch_offsets(nl)) if launch is not None else (torch.zeros(1, dtype=torch.float32, device=dev), [0] * B)
+                    tp = self._match_device(dev_batch, pbatches, iou=flat, iou_off=off, want_cm=self._cm_on, want_tp=self.device_match)
+                    if self.device_match:
+                        host = torch.cat([tp[i, :n[i]] for i in range(B)], 0).cpu().numpy()  # (the rows came to the host above, for their scaling)
+                        o = batch_offsets(n)
+                        tps = {"tp": [host[o[i]:o[i + 1]] != 0 for i in range(B)]}
+                        if launch is None:  # (the rows did not come to the host above: one copy of them here)
+                            hr = torch.cat([r.float() for r in preds], 0).cpu().numpy()
+                            preds = [hr[o[i]:o[i + 1]] for i in range(B)]
+                elif launch is not None:
+                    self._ious = pair_matrices(launch, n, nl)
         try:
-            self._image_stats(preds, batch, pbatches)
+            self._image_stats(preds, batch, pbatches, tps=tps, host_cm=host_cm)
         finally:
             self._ious = None
 
@@ -665,12 +818,15 @@ class ClassificationValidator(BaseValidator):
     min(nc, 5) classes come from the head's kernel (ey_classify_linear_softmax; equal probabilities rank the lower class first, where the
     reference's argsort is unspecified) and reach the host as ONE copy of a (B, 5) int32 tensor.  Host predictions (`update_metrics(probs,
     batch)` with a numpy array / CPU tensor of probabilities) are ranked by the same rule on the host: the route the CPU tests take.
-    plots=True raises; the confusion matrix is not built."""
+    plots=True raises.  confusion_matrix=True: `self.confusion_matrix` (metrics.ConfusionMatrix, task "classify": (nc, nc), row = predicted,
+    column = true) is fed with the top-1 class of every sample from the copy the batch makes anyway (reference classify/val.py:44,83)."""
 
-    val_options = {"plots": False}
+    val_options = {"plots": False, "confusion_matrix": False}
 
-    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, plots=False):
-        refuse_options("ClassificationValidator", "confusion matrix and sample plots", plots=plots)
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, half=False, single_cls=False, agnostic_nms=False, device=None, plots=False,
+                 confusion_matrix=False):
+        refuse_options("ClassificationValidator", "sample plots", plots=plots)
+        self._cm_on = bool(confusion_matrix)
         super().__init__(model, half, device)
         self.metrics = metrics.ClassifyMetrics()
         self.init_metrics()
@@ -679,6 +835,7 @@ class ClassificationValidator(BaseValidator):
         self.names = self.model.names
         self.nc = len(self.names)
         self.pred, self.targets = [], []
+        self.confusion_matrix = metrics.ConfusionMatrix(self.nc, task="classify") if self._cm_on else None
         self.results_dict = dict(zip(self.metrics.keys + ["fitness"], [0.0] * 3))
 
     def postprocess(self, preds):
@@ -699,6 +856,8 @@ class ClassificationValidator(BaseValidator):
             top = self.rank(preds[0] if isinstance(preds, (list, tuple)) else preds, n5)
         self.pred.append(top)
         self.targets.append(_np(batch["cls"]).reshape(-1).astype(np.int32))
+        if self.confusion_matrix is not None:
+            self.confusion_matrix.process_cls_preds(self.pred[-1:], self.targets[-1:])
 
     def get_stats(self):
         self.metrics.process(self.targets, self.pred)

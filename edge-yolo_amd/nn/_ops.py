@@ -2071,3 +2071,58 @@ def mask_contours(masks, boxes=None, out=None, _contour_capacity=64, _vertex_cap
         res.append([verts[ends[j] - lens[j]:ends[j]] for j in range(k + c - 1, k - 1, -1)])
         k += c
     return res
+
+
+MATCH_MAX_T = 16  # mtc::MAX_T: the most IoU thresholds ey_match_batch takes
+
+
+def match_batch(rows, count, gt_cls, gt_off, iouv, nc, gt=None, xform=None, iou=None, iou_off=None, iou_n=None, cm_conf=0.25, cm_iou=0.45, tp=None,
+                matrix=None):
+    """Validation matching of a batch in one launch (ey_match_batch, include/edgeyolo_hip.h).  rows fp32 (B, max_det, >= 6) x1,y1,x2,y2,conf,cls
+    (a channel window of a wider row buffer is fine) and count int32 (B,), as nms_device returns them; gt fp32 (M, 4) xyxy, gt_cls int32 (M,)
+    device tensors grouped by image through the host list gt_off (B+1 entries from 0); xform fp32 (B, 5) padx, pady, gain, w0, h0 or None.
+    iou / iou_off / iou_n: matrix mode, the flat [gt x pred] buffer and the host offsets a pair-matrix op returned plus the images' kept counts
+    as the host knows them (the matrices' row lengths), in the place of the boxes.
+    iouv: host sequence of 1..16 thresholds.  tp: uint8 (B, max_det, T) to fill below each image's count, or None for no true positives;
+    matrix: int32 ((nc+1)^2,) to add to, or None for no confusion matrix.  -> (tp, matrix) as given."""
+    L.require_device(rows, "match_batch")
+    _no_block("match_batch")
+    dev = rows.device
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] < 6 or rows.shape[1] < 1 or rows.stride(2) != 1 or rows.stride(1) < rows.shape[2] or (
+            rows.shape[0] > 1 and rows.stride(0) != rows.shape[1] * rows.stride(1)):
+        raise ValueError(f"match_batch: rows must be a float32 (B, max_det, >= 6) tensor whose rows are dense windows of one buffer, got {tuple(rows.shape)} "
+                         f"{rows.dtype} strides {rows.stride()}")
+    B, max_det, stride = int(rows.shape[0]), int(rows.shape[1]), int(rows.stride(1))
+    _dense(count, "match_batch: count", torch.int32, (B,), dev)
+    gt_off = [int(v) for v in gt_off]
+    if len(gt_off) != B + 1 or gt_off[0] != 0 or any(b < a for a, b in zip(gt_off, gt_off[1:])):
+        raise ValueError("match_batch: gt_off must have B+1 non-decreasing entries starting at 0")
+    M = gt_off[-1]
+    thr = [float(v) for v in iouv]
+    T = len(thr)
+    if not 1 <= T <= MATCH_MAX_T:
+        raise ValueError(f"match_batch: {T} thresholds (1..{MATCH_MAX_T} are built)")
+    _dense(gt_cls, "match_batch: gt_cls", torch.int32, (_AtLeast(M),), dev)
+    if iou is None:
+        _dense(gt, "match_batch: gt (M,4)", torch.float32, (_AtLeast(M), 4), dev)
+        if xform is not None:
+            _dense(xform, "match_batch: xform (B,5)", torch.float32, (B, 5), dev)
+        off = None
+    else:
+        if iou_off is None or len(iou_off) != B or iou_n is None or len(iou_n) != B:
+            raise ValueError("match_batch: matrix mode needs iou_off and iou_n with B entries")
+        off, ld = [int(v) for v in iou_off], [int(v) for v in iou_n]
+        if any(n < 0 or n > max_det for n in ld) or any(o < 0 for b, o in enumerate(off) if gt_off[b + 1] > gt_off[b]):
+            raise ValueError(f"match_batch: iou_n must lie in [0, {max_det}] and iou_off must not be negative where the image has labels")
+        need = max([off[b] + (gt_off[b + 1] - gt_off[b]) * ld[b] for b in range(B) if gt_off[b + 1] > gt_off[b]] + [0])
+        _dense(iou, "match_batch: iou", torch.float32, (_AtLeast(need),), dev)
+        xform = None
+    if tp is not None:
+        _dense(tp, "match_batch: tp=", torch.uint8, (B, max_det, T), dev)
+    if matrix is not None:
+        _dense(matrix, "match_batch: matrix=", torch.int32, ((int(nc) + 1) ** 2,), dev)
+    with _tr("match_batch_kernel", 24 * B * max_det + 20 * M + (B * max_det * T if tp is not None else 0), 12.0 * max_det * M, note=f"B{B} max_det{max_det} M{M} T{T}"):
+        L.check(L.lib().ey_match_batch(B, max_det, stride, rows.data_ptr(), count.data_ptr(), _p(xform), _p(gt) if iou is None else None, gt_cls.data_ptr(),
+                                       _ia(gt_off), _p(iou), None if off is None else _la(off), None if off is None else _ia(ld), T, _fa(thr), int(nc), float(cm_conf), float(cm_iou),
+                                       _p(tp), _p(matrix), L.stream()), "ey_match_batch")
+    return tp, matrix

@@ -47,6 +47,216 @@ def match_predictions(pred_classes, true_classes, iou, iouv=IOUV):
     return correct
 
 
+def _closed_tp(iou, gt_cls, det_cls, iouv):
+    """match_predictions as the closed form the kernel runs (csrc/match_core.inc.h): iou (G, D) fp32 -> (D, T) bool.  Best label per detection
+    (of equal ones the higher index), then every label goes to the lowest detection that wants it at the threshold."""
+    iou = np.asarray(iou, np.float32)
+    G, D = iou.shape
+    thr = np.asarray(iouv, np.float32)
+    tp = np.zeros((D, len(thr)), bool)
+    if G == 0 or D == 0:
+        return tp
+    q = iou * (np.asarray(gt_cls, np.float32)[:, None] == np.asarray(det_cls, np.float32)[None, :])
+    gs = G - 1 - np.argmax(q[::-1], axis=0)
+    b = q[gs, np.arange(D)]
+    for t in range(len(thr)):
+        d = np.nonzero(b >= thr[t])[0]
+        taker = np.full(G, D, np.int64)
+        np.minimum.at(taker, gs[d], d)
+        tp[d, t] = taker[gs[d]] == d
+    return tp
+
+
+def _closed_cm(matrix, iou, gt_cls, det_cls, conf, nc, cm_conf, cm_iou):
+    """ConfusionMatrix.process_batch as the closed form the kernel runs: adds one image to `matrix` ((nc+1, nc+1), row = predicted).  Among the
+    detections above cm_conf: best label per detection (valid above cm_iou), then every label takes its highest-IoU detection (of equal ones the
+    lower index); what is left on either side goes to the background row / column."""
+    iou = np.asarray(iou, np.float32)
+    gt_cls, det_cls = np.asarray(gt_cls).astype(np.int64), np.asarray(det_cls).astype(np.int64)
+    part = np.nonzero(np.asarray(conf, np.float32) > np.float32(cm_conf))[0]
+    G = len(gt_cls)
+    taken = np.full(G, -1, np.int64)
+    if G and len(part):
+        sub = iou[:, part]
+        gs = G - 1 - np.argmax(sub[::-1], axis=0)
+        b = sub[gs, np.arange(len(part))]
+        ok = b > np.float32(cm_iou)
+        for g in np.unique(gs[ok]):
+            k = np.nonzero(ok & (gs == g))[0]
+            taken[g] = part[k[np.argmax(b[k])]]  # argmax: the first of equal values
+    for g in range(G):
+        matrix[det_cls[taken[g]] if taken[g] >= 0 else nc, gt_cls[g]] += 1
+    for d in np.setdiff1d(part, taken[taken >= 0]):
+        matrix[det_cls[d], nc] += 1
+
+
+def _is_dev(t):
+    return hasattr(t, "is_cuda") and t.is_cuda
+
+
+def _check_classes(cls, nc, what):
+    c = np.asarray(_host(cls)).reshape(-1)
+    if len(c) and not ((c >= 0) & (c < nc) & (c == np.floor(c))).all():
+        raise ValueError(f"{what}: class ids must be integers in [0, {nc}), got {c[~((c >= 0) & (c < nc) & (c == np.floor(c)))][:4].tolist()}")
+    return c.astype(np.int32)
+
+
+def _labels_to(dev, gt, gt_cls, nc, what, width=4):
+    """labels for the kernel: boxes fp32 (M, width) and classes int32 (M,) on `dev`; host class ids are checked before the upload."""
+    import torch
+    if not _is_dev(gt_cls):
+        gt_cls = torch.from_numpy(_check_classes(gt_cls, nc, what)).to(dev)
+    if gt is not None and not _is_dev(gt):
+        gt = torch.from_numpy(np.ascontiguousarray(np.asarray(_host(gt), np.float32).reshape(-1, width))).to(dev)
+    return None if gt is None else gt.float().contiguous(), gt_cls.to(torch.int32).contiguous()
+
+
+def match_batch(rows, gt_bboxes, gt_cls, iouv=IOUV, iou=None, count=None, gt_off=None, nc=None, xform=None, iou_off=None, iou_n=None):
+    """The true positives of match_predictions, as the closed form of csrc/match_core.inc.h.
+    Host form (count is None): rows (n, 6+) x1,y1,x2,y2,conf,cls of ONE image and its labels gt_bboxes (m, 4) xyxy, gt_cls (m,), all in one
+      frame -> (n, len(iouv)) bool in numpy; iou: the image's (m, n) matrix in the place of the box IoU.
+    Device form: rows (B, max_det, >= 6) fp32 and count (B,) int32 on the device, as ops.nms_device returns them, the labels of the batch
+      (gt_bboxes (M, 4), gt_cls (M,), host or device) grouped by the host list gt_off, nc, and optionally xform (B, 5) padx, pady, gain, w0, h0
+      (host or device) or the flat matrices iou / iou_off / iou_n -> uint8 (B, max_det, T) on the device from one ey_match_batch launch, zero at
+      and beyond each image's count."""
+    if count is None:
+        if _is_dev(rows):
+            raise ValueError("match_batch: device rows need count= and gt_off= (the batch form)")
+        r = np.asarray(_host(rows), np.float32)
+        r = r.reshape(-1, r.shape[-1] if r.ndim == 2 else 6)
+        g = np.asarray(_host(gt_cls)).reshape(-1)
+        m = box_iou(np.asarray(_host(gt_bboxes), np.float32).reshape(-1, 4), r[:, :4]) if iou is None else np.asarray(_host(iou), np.float32).reshape(len(g), len(r))
+        return _closed_tp(m, g, r[:, 5], iouv)
+    import torch
+    from ..nn import _ops
+    if not _is_dev(rows):
+        raise ValueError("match_batch: the batch form runs on the device: rows on the host go through the per-image form (count=None)")
+    if nc is None or gt_off is None:
+        raise ValueError("match_batch: the batch form needs nc= and gt_off=")
+    dev = rows.device
+    gt, cls = _labels_to(dev, None if iou is not None else gt_bboxes, gt_cls, nc, "match_batch")
+    if xform is not None and not _is_dev(xform):
+        xform = torch.from_numpy(np.ascontiguousarray(np.asarray(_host(xform), np.float32).reshape(-1, 5))).to(dev)
+    with torch.cuda.device(dev):
+        tp = torch.zeros((rows.shape[0], rows.shape[1], len(iouv)), dtype=torch.uint8, device=dev)
+        _ops.match_batch(rows, count, cls, gt_off, iouv, nc, gt=gt, xform=xform, iou=iou, iou_off=iou_off, iou_n=iou_n, tp=tp)
+    return tp
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (utils/metrics.py:294-393): `matrix` (float64, (nc+1, nc+1) for task "detect" with the background last,
+    (nc, nc) for "classify"; row = predicted, column = true), `process_batch`, `process_cls_preds`, `tp_fp`, `print`.  Host operands take the
+    numpy closed form, device tensors ey_match_batch (integer atomics into an int32 matrix on the device, which `matrix` adds in); both give
+    the reference's counts on tie-free data, and on exact IoU ties the rule of csrc/match_core.inc.h (the reference's is numpy's unstable
+    sort).  plot() is not built."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, task="detect"):
+        self.task = task
+        self.nc = int(nc)
+        self._host_matrix = np.zeros((self.nc + 1, self.nc + 1)) if task == "detect" else np.zeros((self.nc, self.nc))
+        self._dev_matrix = None
+        self.conf = 0.25 if conf in {None, 0.001} else conf  # the reference's rule: the validation default means 0.25 here
+        self.iou_thres = iou_thres
+
+    @property
+    def matrix(self):
+        if self._dev_matrix is None:
+            return self._host_matrix
+        return self._host_matrix + self._dev_matrix.cpu().numpy().reshape(self.nc + 1, self.nc + 1)
+
+    def _device_counts(self, dev):
+        import torch
+        if self.task != "detect":
+            raise ValueError("ConfusionMatrix: process_batch is the detect task's; task='classify' takes process_cls_preds")
+        if self._dev_matrix is None or self._dev_matrix.device != dev:
+            if self._dev_matrix is not None:
+                self._host_matrix += self._dev_matrix.cpu().numpy().reshape(self.nc + 1, self.nc + 1)
+            self._dev_matrix = torch.zeros((self.nc + 1) ** 2, dtype=torch.int32, device=dev)
+        return self._dev_matrix
+
+    def process_cls_preds(self, preds, targets):
+        """preds: list of (n_i, k) top-k class arrays, best first; targets: list of (n_i,) classes.  On the host."""
+        p = np.concatenate([np.asarray(_host(x)).reshape(len(x), -1) for x in preds])[:, 0].astype(np.int64)
+        t = np.concatenate([np.asarray(_host(x)).reshape(-1) for x in targets]).astype(np.int64)
+        if len(p) != len(t) or (len(p) and not ((p >= 0) & (p < self.nc) & (t >= 0) & (t < self.nc)).all()):
+            raise ValueError(f"ConfusionMatrix.process_cls_preds: {len(p)} predictions, {len(t)} targets, classes must lie in [0, {self.nc})")
+        np.add.at(self._host_matrix, (p, t), 1)
+
+    def process_batch(self, detections, gt_bboxes, gt_cls):
+        """One image.  detections (n, 6) x1,y1,x2,y2,conf,cls or (n, 7) x,y,w,h,conf,cls,angle with (m, 5) xywhr labels, or None; gt_bboxes
+        (m, 4 | 5); gt_cls (m,).  Device detections run ey_match_batch (obb: on the ProbIoU matrix of ey_probiou), host ones numpy.  Class ids
+        outside [0, nc) raise ValueError on both routes (the device route reads the rows' class column for that; process_device_batch does not)."""
+        if self.task != "detect":
+            raise ValueError("ConfusionMatrix: process_batch is the detect task's; task='classify' takes process_cls_preds")
+        if _is_dev(detections):
+            import torch
+            from ..nn import _ops
+            dev = detections.device
+            det = detections.float()
+            if not _is_dev(gt_cls):
+                gt_cls = np.asarray(_host(gt_cls)).reshape(-1)
+            if not _is_dev(gt_bboxes):
+                gt_bboxes = np.asarray(_host(gt_bboxes), np.float32)
+            n, m = int(det.shape[0]), int(gt_cls.shape[0])
+            obb = det.dim() == 2 and det.shape[1] == 7 and gt_bboxes.shape[-1] == 5
+            _check_classes(det[:, 5], self.nc, "ConfusionMatrix.process_batch: detections")  # (as the host route; one read of the column)
+            gt, cls = _labels_to(dev, gt_bboxes, gt_cls, self.nc, "ConfusionMatrix.process_batch", 5 if obb else 4)
+            with torch.cuda.device(dev):
+                iou = off = ld = None
+                if obb and n and m:
+                    iou, off, ld = _ops.probiou(gt, det[:, [0, 1, 2, 3, 6]].contiguous()).reshape(-1), [0], [n]
+                elif obb:
+                    iou, off, ld = torch.zeros(1, dtype=torch.float32, device=dev), [0], [n]
+                rows = det[None, :, :6].contiguous() if n else torch.zeros((1, 1, 6), dtype=torch.float32, device=dev)
+                count = torch.full((1,), n, dtype=torch.int32, device=dev)
+                _ops.match_batch(rows, count, cls, [0, m], IOUV[:1], self.nc, gt=None if obb else gt, iou=iou, iou_off=off, iou_n=ld, cm_conf=self.conf,
+                                 cm_iou=self.iou_thres, matrix=self._device_counts(dev))
+            return
+        g = _check_classes(gt_cls, self.nc, "ConfusionMatrix.process_batch")
+        if detections is None:
+            det = np.zeros((0, 6), np.float32)
+        else:
+            det = np.asarray(_host(detections), np.float32)
+            det = det.reshape(-1, det.shape[-1] if det.ndim == 2 else 6)
+        _check_classes(det[:, 5], self.nc, "ConfusionMatrix.process_batch: detections")
+        gb = np.asarray(_host(gt_bboxes), np.float32)
+        if not len(g) or not len(det):
+            iou = np.zeros((len(g), len(det)), np.float32)
+        elif det.shape[1] == 7 and gb.shape[-1] == 5:
+            iou = probiou_host(gb.reshape(-1, 5), np.concatenate([det[:, :4], det[:, -1:]], 1))
+        else:
+            iou = box_iou(gb.reshape(-1, 4), det[:, :4])
+        _closed_cm(self._host_matrix, iou, g, det[:, 5], det[:, 4], self.nc, self.conf, self.iou_thres)
+
+    def process_device_batch(self, rows, count, gt_bboxes, gt_cls, gt_off, xform=None, iou=None, iou_off=None, iou_n=None, iouv=None):
+        """A whole batch in ONE ey_match_batch launch: rows (B, max_det, >= 6) / count (B,) as ops.nms_device returns them, the batch's labels
+        (host or device) grouped by the host list gt_off, xform or the flat matrices as for match_batch.  iouv given: the launch also returns
+        the true positives, uint8 (B, max_det, T), zero at and beyond each count; else None."""
+        import torch
+        from ..nn import _ops
+        if not _is_dev(rows):
+            raise ValueError("ConfusionMatrix.process_device_batch: rows on the host go image by image through process_batch")
+        dev = rows.device
+        gt, cls = _labels_to(dev, None if iou is not None else gt_bboxes, gt_cls, self.nc, "ConfusionMatrix.process_device_batch")
+        if xform is not None and not _is_dev(xform):
+            xform = torch.from_numpy(np.ascontiguousarray(np.asarray(_host(xform), np.float32).reshape(-1, 5))).to(dev)
+        with torch.cuda.device(dev):
+            tp = None if iouv is None else torch.zeros((rows.shape[0], rows.shape[1], len(iouv)), dtype=torch.uint8, device=dev)
+            _ops.match_batch(rows, count, cls, gt_off, IOUV[:1] if iouv is None else iouv, self.nc, gt=gt, xform=xform, iou=iou, iou_off=iou_off, iou_n=iou_n,
+                             cm_conf=self.conf, cm_iou=self.iou_thres, tp=tp, matrix=self._device_counts(dev))
+        return tp
+
+    def tp_fp(self):
+        m = self.matrix
+        tp = m.diagonal()
+        fp = m.sum(1) - tp
+        return (tp[:-1], fp[:-1]) if self.task == "detect" else (tp, fp)
+
+    def print(self):
+        for row in self.matrix:
+            print(" ".join(map(str, row)))
+
+
 def smooth(y, f=0.05):
     nf = round(len(y) * f * 2) // 2 + 1
     p = np.ones(nf // 2)

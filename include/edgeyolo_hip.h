@@ -587,6 +587,35 @@ size_t ey_mask_contours_workspace_bytes(int n, int h, int w);
 int ey_mask_contours(int n, int h, int w, const uint8_t* masks, const int* windows, int contour_cap, int vertex_cap, int* lens, int* verts, int* info,
                      void* workspace, size_t workspace_bytes, ey_stream_t stream);
 
+/* ---- Validation matching (csrc/match.hip; reference engine/validator.py:222-262 match_predictions and utils/metrics.py:326-382
+ * ConfusionMatrix.process_batch).  ey_match_batch: the true positives of a batch's kept rows at T IoU thresholds and the batch's increments
+ * of a confusion matrix in ONE launch, one workgroup per image, fp32, no host synchronisation (graph-capturable).  The closed forms, why
+ * they equal the reference and the tie rules: csrc/match_core.inc.h (which also compiles for the host with one lane) and DESIGN.md 7t.
+ * rows: DEVICE fp32 [B][max_det][stride >= 6] = x1,y1,x2,y2,conf,cls,... and count: DEVICE int32 [B], as the NMS entry points leave them;
+ *   only columns 0..5 of the rows below count[b] (clamped to max_det) are read.  A row whose class is not in [0, nc) is skipped: its tp bytes
+ *   are 0 and it adds nothing to the matrix.
+ * xform: DEVICE fp32 [B][5] = padx, pady, gain, w0, h0 or NULL.  Given, every row's box goes through ops.scale_boxes + clip_boxes in registers
+ *   (v - pad, IEEE division by gain, clamp to [0, w0] / [0, h0], the host path's fp32 operations in its order); NULL: the rows are in the
+ *   labels' frame already.
+ * gt: DEVICE fp32 [M][4] xyxy in original-image pixels; gt_cls: DEVICE int32 [M]; gt_off: HOST int32 [B+1] from 0, image b's labels are
+ *   gt_off[b] .. gt_off[b+1]-1.  A label whose class is not in [0, nc) is skipped.
+ * iou / iou_off / iou_ld (matrix mode): iou DEVICE fp32, iou_off HOST [B] element offsets, iou_ld HOST int32 [B]: image b's row-major
+ *   [labels][iou_ld[b]] matrix starts at iou + iou_off[b] (images without labels have none); iou_ld[b] is the image's kept count as the host
+ *   knows it, and no column at or beyond it is read whatever count[b] says.  Given, it replaces the box IoU (gt may be NULL) and xform is not used; with the
+ *   box IoUs in it the outputs are identical to boxes mode.  NULL: box IoU = inter / ((a1 + a2) - inter + 1e-7f), no FMA contraction, IEEE
+ *   division: metrics.box_iou bit for bit.
+ * iouv: HOST fp32 [T], 1 <= T <= 16, compared in fp32 (>=).  cm_conf / cm_iou: only rows with conf > cm_conf take part in the matrix; a
+ *   pair is a match when its IoU > cm_iou.
+ * Outputs, either may be NULL: tp uint8 [B][max_det][T], rows at or beyond count[b] are left untouched; matrix int32 [(nc+1)^2], row =
+ *   predicted class (nc = background), column = true class, accumulated with integer atomics (deterministic) and NOT zeroed by the call.
+ * Exact IoU ties: among labels the higher label index wins, among detections the lower detection index.
+ * The labels of an image, its takers (labels x T) and 12 bytes per row live in LDS: 1024 rows x 1024 labels x 16 thresholds fit (104 KiB of
+ * the 160 KiB); past 160 KiB, or B > 128, the call returns EY_EUNSUPPORTED before anything is launched, with the limit named.  EY_EINVAL: null
+ * required pointers, T outside 1..16, bad sizes or offsets.  A refusal leaves both outputs untouched. */
+int ey_match_batch(int B, int max_det, int stride, const float* rows, const int* count, const float* xform, const float* gt, const int* gt_cls,
+                   const int* gt_off, const float* iou, const long* iou_off, const int* iou_ld, int T, const float* iouv, int nc, float cm_conf, float cm_iou,
+                   uint8_t* tp, int* matrix, ey_stream_t stream);
+
 /* ---- K7 (module-level form): channel-slice copy with optional nearest x2 upsample — nn.Upsample / Concat
  * (conv.py:345-355) when they are not folded into the consuming conv.  dst[b,y,x,c] = src[b,y>>up,x>>up,c]. */
 int ey_copy_nhwc(int dtype, int B, int H, int W, int C, int up, const void* src, int src_cstride, void* dst,
